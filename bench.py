@@ -18,10 +18,15 @@ orientation -> RootSIFT per view, then brute-force FGINN matching of the ~24 k x
              --shard views makes that mode the headline value instead.
   --loopback W   one GPU: the view-sharded path with W in-process ranks (loopback transport: the all-gather is W
              device-to-device copies, everything else is the code the RCCL transport runs), workers / W lanes per rank
-Rank 0 prints ONE JSON line: value = pairs/s of the whole job, `roofline` = the distance kernels (all k_match_*
-launches -- pack, sweep 1, decide, resolve -- on the descriptors of this run) against the int8 MFMA peak, `roofline_describe` = the
-describe stage against HBM with SURVEY section 8(d) bytes, `cpu_baseline` = the CPU oracle (restatement of the reference's
-CPU path) on the same workload with all host cores and with one, `parity` = GPU vs that CPU path on one pair of the run.
+  --full     also run the legs beyond the headline (a plain run sets up, warms up, times the K steps and prints the line):
+             the per-step-barrier form, the upload form, configs[4]'s F verification, the ladder's parts and latencies, the
+             per-kernel and roofline legs, the short runs under `extra` (--no-extra), the CPU baseline and parity (--no-cpu-baseline)
+  --dump-outputs DIR   after the timed steps, write what the last timed step computed (rank 0's pairs) as DIR/<name>.npy
+Rank 0 prints ONE JSON line: value = pairs/s of the whole job, ms_per_step = milliseconds of one timed step.  With --full also
+`roofline` = the distance kernels (all k_match_* launches -- pack, sweep 1, decide, resolve -- on the descriptors of this run)
+against the int8 MFMA peak, `roofline_describe` = the describe stage against HBM with SURVEY section 8(d) bytes, `cpu_baseline` =
+the CPU oracle (restatement of the reference's CPU path) on the same workload with all host cores and with one, `parity` = GPU vs
+that CPU path on one pair of the run.
 """
 import argparse
 import itertools
@@ -170,6 +175,51 @@ def oracle_pair_views(O, a, b, views_o, params, threads, seed=1, query_cap=None,
     return out
 
 
+DUMP_BYTES_MAX = 60 << 20     # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: the per-pair results of the last timed step, as a caller of the path receives them (None = a pair another rank
+    verified), one .npy per array, rows in the step's pair order:
+      pair_index [P]  counts [P, 8] (regions 1, regions 2, tentatives, unique, RANSAC inliers, verified, RANSAC samples, LO count)
+      H [P, 3, 3]     tentative_ids [T, 4] (q, t0, tj, t1)   tentative_dist [T, 4] (d1, d2, d2by2ndcl, ratio)
+      tentative_pair [T] (its pair)   ransac_inlier [T], verified [T] (0 / 1)   tentative_rows [T] (its row in the full list)
+    The unique tentatives of all pairs are one list; past DUMP_BYTES_MAX a fixed, seeded sample of its rows is written.  Integers
+    travel as float32 while they are exact there (below 2^24), as float64 otherwise; distances and H as float64."""
+    import numpy as np
+
+    def exact(x):
+        x = np.asarray(x)
+        return x.astype(np.float32) if x.size == 0 or np.abs(x).max() < (1 << 24) else x.astype(np.float64)
+    idx = [i for i, r in enumerate(results) if r is not None]
+    rs = [results[i] for i in idx]
+    counts = np.array([[r["n_regions"][0], r["n_regions"][1], r["n_tentatives"], r["n_unique"], r["n_ransac_inliers"],
+                        r["n_verified"], r["ransac_samples"], r["ransac_lo"]] for r in rs], np.float64).reshape(-1, 8)
+    H = np.array([np.asarray(r["H"], np.float64).reshape(3, 3) for r in rs]).reshape(-1, 3, 3)
+    tents = [r["tentatives"] for r in rs]
+    t = np.concatenate(tents) if tents else np.zeros(0)
+    pair = np.concatenate([np.full(len(x), i, np.int64) for i, x in zip(idx, tents)]) if tents else np.zeros(0, np.int64)
+    inl = np.concatenate([r["ransac_inlier"] for r in rs]) if rs else np.zeros(0, bool)
+    ver = np.concatenate([r["verified"] for r in rs]) if rs else np.zeros(0, bool)
+    rows = np.arange(len(t))
+    row_bytes = 64 if len(t) < (1 << 24) and (not len(counts) or counts[:, :2].max() < (1 << 24)) else 88
+    cap = max(0, (DUMP_BYTES_MAX - counts.nbytes - H.nbytes - 8 * len(idx)) // row_bytes)
+    if len(t) > cap:
+        rows = np.sort(np.random.RandomState(20260).choice(len(t), cap, replace=False))
+    t = t[rows]
+    arrays = {
+        "pair_index": np.asarray(idx, np.float64), "counts": counts, "H": H,
+        "tentative_ids": exact(np.stack([t[f] for f in ("q", "t0", "tj", "t1")], 1).reshape(-1, 4) if len(t) else np.zeros((0, 4))),
+        "tentative_dist": (np.stack([t[f] for f in ("d1", "d2", "d2by2ndcl", "ratio")], 1).reshape(-1, 4) if len(t)
+                           else np.zeros((0, 4))).astype(np.float64),
+        "tentative_pair": exact(pair[rows]), "ransac_inlier": inl[rows].astype(np.float32), "verified": ver[rows].astype(np.float32),
+        "tentative_rows": exact(rows),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class ShardGroup:
     """The view-sharded mode of a step.  RCCL: this process is one rank, its contexts are the lanes of ONE communicator.
     Loopback (one GPU): W in-process ranks, each with its own contexts / lanes.  Pair i of a step runs on lane i % lanes of
@@ -272,6 +322,10 @@ def main():
     ap.add_argument("--batch-api", action="store_true", help="multi-view configs: run a step as ONE modsx_match_pairs_views call")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the short 1/8/11-view and 4000-blob runs reported under `extra`")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline: step-barrier and upload forms, wxbs F, ladder "
+                    "parts, per-kernel and roofline legs, `extra`, CPU baseline and parity (default: the headline alone)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the results of the last timed step (rank 0's pairs) as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
 
     import numpy as np
@@ -473,8 +527,10 @@ def main():
     elapsed, ndesc, results = timed(run_batch, args.warmup, args.steps, group, back_to_back=b2b)
     host_cpu_headline = host_cpu["s"]       # of the K timed steps (later legs run through timed() too)
     host_cpu_split = (host_cpu.get("ctx", 0.0), host_cpu.get("sys", 0.0))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results)
     barrier_form = None
-    if b2b:
+    if b2b and args.full:
         eb, nb_, _ = timed(run_batch, 0, args.steps, group)
         eb, nb_ = reduce_over_ranks(eb, nb_)
         barrier_form = {"value": args.steps * world * nbatch / eb, "unit": "image-pairs/s", "ms_per_step": 1e3 * eb / args.steps,
@@ -487,7 +543,7 @@ def main():
     # `value` is measured with the images resident in HBM; this is the PCIe-inclusive figure beside it.  u8 grey images, as cv::imread
     # delivers them: modsx_image_update refills the two images a context keeps (no allocation per pair), the device converts to f32.
     upload_form = None
-    if rank == 0 and group is None and lsteps is None and not os.environ.get("MODSX_BENCH_NO_UPLOAD_LEG"):
+    if args.full and rank == 0 and group is None and lsteps is None and not os.environ.get("MODSX_BENCH_NO_UPLOAD_LEG"):
         nst = max(1, min(args.steps, 3))
         n = len(imgs1)
         hostA = [pairs_host[i % len(pairs_host)][0] for i in range(n)]
@@ -537,7 +593,7 @@ def main():
         upload_form = {"value": nst * n / du, "unit": "image-pairs/s", "steps": nst, "upload_ms_per_pair": 1e3 * up_s[0] / (nst * n),
                        "bytes_per_pair": int(hostA[0].nbytes + hostB[0].nbytes), "note": note}
     wxbs_f = None
-    if wxbs and rank == 0 and group is None:
+    if args.full and wxbs and rank == 0 and group is None:
         # configs[4] with epipolar verification: measured HERE, before any leg that brackets launches with timing events -- once a
         # context has recorded such events the runtime keeps per-dispatch completion signals on its queue, which costs the context's
         # host thread ~20 ms of CPU per pair from then on (tools/wxbs_cpu_probe.py: 8.5 -> 29 ms), and this leg is the one that is
@@ -566,7 +622,7 @@ def main():
         dtFstep = time.perf_counter() - tb
         wxbs_f = (fms, fn, fth, vst, cw, ch, dtF, dtFstep, cpuF, ruF0, ruF1, rF, stF, veF)
     ladder_parts = {}
-    if ladder and rank == 0 and group is None:
+    if args.full and ladder and rank == 0 and group is None:
         # the MSER steps alone and the HessianAffine steps alone: the former are short of host CPU, so they too are measured before the
         # contexts have recorded timing events
         for name, det in (("mser_steps_only", 3), ("hessaff_steps_only", 0)):
@@ -660,7 +716,7 @@ def main():
     PROF_STEPS = 1
     stats = {}
     pctxs = ctxs
-    if views_hung:
+    if views_hung or not args.full:
         pass
     elif (rank == 0 and group is None) or (group is not None and not args.loopback):
         # the event-bracketed legs run on contexts of their own where they can (pair-sharded runs): a context that has recorded timing
@@ -681,7 +737,7 @@ def main():
     # Roofline leg: in the timed region the kernels of --workers streams time-slice the CUs, so an event pair there
     # brackets queueing as well.  The same pairs are repeated on ONE stream and the launch durations come from that pass.
     iso, niso, mroof = {}, 0, None
-    if rank == 0 and not views_hung and (group is None or views_world == 1 or args.loopback):
+    if args.full and rank == 0 and not views_hung and (group is None or views_world == 1 or args.loopback):
         # really one stream: a lone multi-view pair would otherwise run image 2 on a peer context and every image in three parts on
         # helper contexts (engine_views.hip), and the event brackets of this leg would include their queueing
         os.environ["MODSX_PAIR_SERIAL"] = "1"; os.environ["MODSX_PAIR_NOSPLIT"] = "1"
@@ -738,8 +794,9 @@ def main():
             "result": {"regions": list(res["n_regions"]), "tentatives": res["n_tentatives"], "unique": res["n_unique"],
                        "verified": res["n_verified"],
                        "H_vs_generator_max_abs": float(np.abs(res["H"] / res["H"][2, 2] - Hgt).max())},
-            "kernel_ms_per_pair_multi_stream": {k: v["ms"] / (PROF_STEPS * nbatch) for k, v in stats.items() if v["launches"]},
         }
+        if stats:
+            out["kernel_ms_per_pair_multi_stream"] = {k: v["ms"] / (PROF_STEPS * nbatch) for k, v in stats.items() if v["launches"]}
         # the same figure under a key that never changes meaning: with N > 1 `value` becomes the view-sharded one (below)
         out["value_pair_sharded"] = value
         out["steps_issue"] = ("back to back: a context goes from the last pair of step k to the first of step k + 1, no host-side barrier "
@@ -892,7 +949,7 @@ def main():
                       "host_ransac_share_of_wall": (fms / max(1, fn)) / max(1, fth) / (dtF / (stF * nbatch) * 1e3)},
                 "note": "DuplicateFiltering + LO-RANSAC run on helper threads beside the device pipeline; share = per-pair verify "
                         "time / helper threads / per-pair wall time (the fraction of the wall the helpers are busy)"}
-        if ladder:
+        if ladder and args.full:
             # where a ladder's time goes: the MSER steps alone and the HessianAffine steps alone (throughput, same contexts), and
             # one pair on an otherwise idle GPU step by step (latency)
             lad = {"steps": [{"detector": "MSER" if d == 3 else "HessianAffine", "views": len(v), "match_ratio": r} for v, r, d in lsteps]}
@@ -912,7 +969,7 @@ def main():
                            "that detector's steps")
             out["ladder"] = lad
         # ---- short runs of the other view counts (same timed-region rules, fewer steps) ---------------------------------
-        if not args.no_extra and group is None and world == 1 and not args.tilts and not wxbs and not ladder:
+        if args.full and not args.no_extra and group is None and world == 1 and not args.tilts and not wxbs and not ladder:
             extra = {}
             for name in ("views1", "views8", "views11"):
                 if name == args.config:
@@ -960,7 +1017,7 @@ def main():
                     a_.free(); b_.free()
             out["extra"] = extra
         # ---- the CPU path on the same workload: parity of one pair of the run + the baseline timing ---------------------
-        if world == 1 and not args.no_cpu_baseline and not wxbs and not ladder and group is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and not wxbs and not ladder and group is None:
             from oracle import pyoracle as O
             model, ncpu, usable = cpu_info()
             a, b = pairs_host[0][0].astype(np.float32), pairs_host[0][1].astype(np.float32)

@@ -4,5 +4,5 @@ R=$GRAFT_REPO_ROOT
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = base ]; then L=$R/mods_amd/libmodsx.so; else L=$R/mods_amd/libmodsx_$v.so; fi
-  MODSX_LIB=$L python $R/bench.py --no-cpu-baseline --no-extra 2>/dev/null | python $R/tools/bench_line.py $v
+  MODSX_LIB=$L python $R/bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | python $R/tools/bench_line.py $v
 done; done

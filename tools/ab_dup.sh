@@ -4,5 +4,5 @@
 R=$GRAFT_REPO_ROOT
 for rep in 1 2; do
 for m in "$@"; do
-  MODSX_DUP=$m MODSX_LIB=$R/mods_amd/libmodsx_dup.so python $R/bench.py --no-cpu-baseline --no-extra 2>/dev/null | python $R/tools/bench_line.py dup=$m
+  MODSX_DUP=$m MODSX_LIB=$R/mods_amd/libmodsx_dup.so python $R/bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | python $R/tools/bench_line.py dup=$m
 done; done

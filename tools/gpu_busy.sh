@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/rp_busy
-rocprofv3 --kernel-trace -d /tmp/rp_busy -o p -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /tmp/rp_busy.log 2>&1
+rocprofv3 --kernel-trace -d /tmp/rp_busy -o p -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /tmp/rp_busy.log 2>&1
 DB=$(find /tmp/rp_busy -name "*.db" | head -1)
 python - <<PY
 import sqlite3

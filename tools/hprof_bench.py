@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py under a -DMODSX_HPROF library (MODSX_LIB=mods_amd/libmodsx_hprof.so), then the host profile of the F verification
-summed over all verifying threads.  usage: hprof_bench.py <bench.py arguments>"""
+summed over all verifying threads.  usage: hprof_bench.py <bench.py arguments>, e.g. --config wxbs --full (the leg that verifies with F)"""
 import ctypes, os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/${1:-shardapi}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export MODSX_PAIR_NOSPLIT=1 MODSX_PAIR_SERIAL=1
-ONE="--steps 2 --warmup 1 --workers 1 --batch 4 --no-cpu-baseline --no-extra"
+ONE="--full --steps 2 --warmup 1 --workers 1 --batch 4 --no-cpu-baseline --no-extra"
 for mode in unsharded sharded; do
   a=""; [ $mode = sharded ] && a="--shard views"
   rm -rf /tmp/rq_$mode
