@@ -118,7 +118,8 @@ struct WarpJob {
   int pad;
 };
 
-// one non-identity view of a batched synthesis (kernels_views.hip): src -R-> rot -blur (through tmp)-> rot -W-> dst
+// one non-identity view of a batched synthesis (kernels_views.hip): src -R-> rot -blur (through tmp)-> rot -W-> dst;
+// a view of the one-launch form (fused == 2) goes src -> dst and has no rot / tmp
 struct ViewJob {
   const float *src;
   float *rot, *tmp, *dst;
@@ -126,7 +127,9 @@ struct ViewJob {
   int kx, ky, tapOfs, doBlur;
   int tileA, tileB;   // first 64 x 4 tile of this view in the rotated-image / output-image tile lists
   int tileF, fused;   // fused rotate + blur: first VF_TW x VF_TH tile of this view (views with a blur whose halo fits)
+  int tileG, pad;     // rotate + blur + tilt in one launch (fused == 2: W is diagonal as well): first VF_TW x VF_TH tile of the ROTATED image
   double R[6], W[6];  // inverse maps of the two cv::warpAffine calls (f64, inverted on the host)
+  double invW[2];     // 1 / W[0], 1 / W[4]: where a fused tile starts looking for its first output column / row (a hint, never the answer)
 };
 
 // matching
@@ -249,6 +252,7 @@ void launch_views_warp(hipStream_t s, const ViewJob *jobs, int n, int tiles, int
 void launch_views_blur(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int pass);
 constexpr int VF_TW = 128, VF_TH = 16, VF_RX = 32, VF_RY = 2;   // tile of the fused rotate + blur kernel and the largest halo it takes
 void launch_views_rotblur(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int maxRx, int maxRy);
+void launch_views_fused(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int maxRx, int maxRy);
 size_t match_workspace_bytes(int n1, int n2);
 void launch_match(hipStream_t s, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2,
                   double sqminratio, double contrDistSq, int nn, MatchRow *rows, void *workspace);

@@ -171,16 +171,20 @@ static int plan_view(const modsx_image *gray, const modsx_view &v, ViewPlan &P) 
   return MODSX_OK;
 }
 
-// Synthesises n views of `gray` in four launches (rotate all, blur rows all, blur columns all, tilt/zoom all).  Outputs go to
-// dst[i] (device, P[i].ow x P[i].oh floats; ignored for identity views).  No host wait: the job table and the taps travel
-// through pinned staging that is only rewritten after the caller's next synchronisation of the stream.
+// Synthesises n views of `gray`: one launch for all views whose blur fits the fused kernel's tile and whose tilt / zoom map is
+// diagonal (every view plan_view makes with a blur of up to 2 VF_RX + 1 by 2 VF_RY + 1 taps), the separate launches (rotate,
+// blur rows, blur columns -- or rotate + blur --, tilt / zoom) for the rest.  Outputs go to dst[i] (device, P[i].ow x P[i].oh
+// floats; ignored for identity views).  No host wait: the job table and the taps travel through pinned staging that is only
+// rewritten after the caller's next synchronisation of the stream.  MODSX_VIEWS_SEPARATE=1 keeps every view on the separate
+// launches (measurements: the values are the same either way).
 static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, const ViewPlan *P, float *const *dst, int n) {
+  static const bool separate = getenv("MODSX_VIEWS_SEPARATE") && atoi(getenv("MODSX_VIEWS_SEPARATE"));
   hipStream_t s = c->stream;
   std::vector<ViewJob> jobs;
   std::vector<float> taps;
-  size_t rotFloats = 0;
-  int tilesA = 0, tilesB = 0, tilesF = 0, maxRx = 0, maxRy = 0;
-  double wpx = 0, rpx = 0;
+  size_t rotFloats = 0, tmpFloats = 0;
+  int tilesA = 0, tilesB = 0, tilesF = 0, tilesG = 0, maxRx = 0, maxRy = 0, maxRxG = 0, maxRyG = 0;
+  double pxRot = 0, pxBlur = 0, pxFused = 0, pxTilt = 0;   // pixels moved through HBM by the four kinds of launch
   for (int i = 0; i < n; i++) {
     if (P[i].identity) continue;
     ViewJob j;
@@ -192,30 +196,47 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
     j.doBlur = P[i].doBlur; j.kx = P[i].kx; j.ky = P[i].ky; j.tapOfs = (int)taps.size();
     taps.insert(taps.end(), P[i].taps.begin(), P[i].taps.end());
     for (int q = 0; q < 6; q++) { j.R[q] = P[i].Rinv[q]; j.W[q] = P[i].Winv[q]; }
-    j.tileA = tilesA; j.tileB = tilesB; j.tileF = tilesF;
-    // rotate + blur in one launch when the halo of the two filters fits the fused kernel's tile (every default view does)
+    j.tileA = tilesA; j.tileB = tilesB; j.tileF = tilesF; j.tileG = tilesG;
+    const double srcPx = (double)gray->rows * gray->cols, rotPx = (double)j.rrows * j.rcols, dstPx = (double)j.drows * j.dcols;
+    // rotate + blur in LDS when the halo of the two filters fits the fused kernels' tile (every default view does); the tilt
+    // as well when its inverse map is diagonal with positive scales: tap origins monotone in x and y, independent of the other
     j.fused = j.doBlur && (j.kx >> 1) <= VF_RX && (j.ky >> 1) <= VF_RY;
-    if (j.fused) {
-      tilesF += ((j.rcols + VF_TW - 1) / VF_TW) * ((j.rrows + VF_TH - 1) / VF_TH);
-      maxRx = std::max(maxRx, j.kx >> 1); maxRy = std::max(maxRy, j.ky >> 1);
-    } else
-      tilesA += ((j.rcols + 63) / 64) * ((j.rrows + 3) / 4);
-    tilesB += ((j.dcols + 63) / 64) * ((j.drows + 3) / 4);
-    j.rot = (float *)(uintptr_t)rotFloats;            // offsets first; the bases are added once the buffers exist
-    rotFloats += (size_t)j.rrows * j.rcols;
-    wpx += (double)gray->rows * gray->cols + 2.0 * j.rrows * j.rcols + (double)j.drows * j.dcols;
-    rpx += (double)j.rrows * j.rcols;
+    if (j.fused && !separate && j.W[1] == 0 && j.W[3] == 0 && j.W[0] > 0 && j.W[4] > 0) j.fused = 2;
+    const int tilesV = ((j.rcols + VF_TW - 1) / VF_TW) * ((j.rrows + VF_TH - 1) / VF_TH);
+    if (j.fused == 2) {
+      tilesG += tilesV;
+      maxRxG = std::max(maxRxG, j.kx >> 1); maxRyG = std::max(maxRyG, j.ky >> 1);
+      j.invW[0] = 1.0 / j.W[0]; j.invW[1] = 1.0 / j.W[4];
+      pxFused += srcPx + dstPx;
+    } else {
+      if (j.fused) {
+        tilesF += tilesV;
+        maxRx = std::max(maxRx, j.kx >> 1); maxRy = std::max(maxRy, j.ky >> 1);
+        pxBlur += srcPx + rotPx;
+      } else {
+        tilesA += ((j.rcols + 63) / 64) * ((j.rrows + 3) / 4);
+        pxRot += srcPx + rotPx;
+        if (j.doBlur) pxBlur += 4 * rotPx;
+        j.tmp = (float *)(uintptr_t)tmpFloats;
+        tmpFloats += (size_t)j.rrows * j.rcols;
+      }
+      tilesB += ((j.dcols + 63) / 64) * ((j.drows + 3) / 4);
+      pxTilt += rotPx + dstPx;
+      j.rot = (float *)(uintptr_t)rotFloats;          // offsets first; the bases are added once the buffers exist
+      rotFloats += (size_t)j.rrows * j.rcols;
+    }
     jobs.push_back(j);
   }
   if (jobs.empty()) return MODSX_OK;
   const size_t jobB = jobs.size() * sizeof(ViewJob), tapB = std::max<size_t>(1, taps.size()) * 4;
-  if (!c->viewTmp[0].ensure(rotFloats * 4) || !c->viewTmp[1].ensure(rotFloats * 4) || !c->viewJobs.ensure(jobB + tapB + 64) ||
+  // the rotated planes of the views that are not fused end to end, the row-filtered planes of those that are not fused at all
+  if (!c->viewTmp[0].ensure(rotFloats * 4) || !c->viewTmp[1].ensure(tmpFloats * 4) || !c->viewJobs.ensure(jobB + tapB + 64) ||
       !c->hViewJobs.ensure(jobB + tapB + 64))
     return MODSX_ERR_NOMEM;
   for (ViewJob &j : jobs) {
-    const size_t o = (size_t)(uintptr_t)j.rot;
-    j.rot = (float *)c->viewTmp[0].p + o;
-    j.tmp = (float *)c->viewTmp[1].p + o;
+    if (j.fused == 2) continue;
+    j.rot = (float *)c->viewTmp[0].p + (size_t)(uintptr_t)j.rot;
+    j.tmp = j.fused ? nullptr : (float *)c->viewTmp[1].p + (size_t)(uintptr_t)j.tmp;
   }
   char *hb = (char *)c->hViewJobs.p;
   memcpy(hb, jobs.data(), jobB);
@@ -223,18 +244,31 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
   MX_HIP(ctx_copy(c, c->viewJobs.p, hb, jobB + tapB, hipMemcpyHostToDevice));
   const ViewJob *dj = (const ViewJob *)c->viewJobs.p;
   const float *dt = (const float *)((char *)c->viewJobs.p + jobB);
+  const int nj = (int)jobs.size();
   size_t pslot;
-  prof_begin(c, K_WARP, wpx * 4, &pslot);
-  launch_views_warp(s, dj, (int)jobs.size(), tilesA, 0);
-  prof_end(c, pslot);
-  prof_begin(c, K_VIEW_BLUR, rpx * 16, &pslot);
-  launch_views_rotblur(s, dj, (int)jobs.size(), tilesF, dt, maxRx, maxRy);
-  launch_views_blur(s, dj, (int)jobs.size(), tilesA, dt, 0);
-  launch_views_blur(s, dj, (int)jobs.size(), tilesA, dt, 1);
-  prof_end(c, pslot);
-  prof_begin(c, K_WARP, 0, &pslot);
-  launch_views_warp(s, dj, (int)jobs.size(), tilesB, 1);
-  prof_end(c, pslot);
+  // a profiling bracket only around launches that have tiles
+  if (tilesG > 0) {
+    prof_begin(c, K_VIEW_BLUR, pxFused * 4, &pslot);
+    launch_views_fused(s, dj, nj, tilesG, dt, maxRxG, maxRyG);
+    prof_end(c, pslot);
+  }
+  if (tilesA > 0) {
+    prof_begin(c, K_WARP, pxRot * 4, &pslot);
+    launch_views_warp(s, dj, nj, tilesA, 0);
+    prof_end(c, pslot);
+  }
+  if (tilesF > 0 || tilesA > 0) {
+    prof_begin(c, K_VIEW_BLUR, pxBlur * 4, &pslot);
+    launch_views_rotblur(s, dj, nj, tilesF, dt, maxRx, maxRy);
+    launch_views_blur(s, dj, nj, tilesA, dt, 0);
+    launch_views_blur(s, dj, nj, tilesA, dt, 1);
+    prof_end(c, pslot);
+  }
+  if (tilesB > 0) {
+    prof_begin(c, K_WARP, pxTilt * 4, &pslot);
+    launch_views_warp(s, dj, nj, tilesB, 1);
+    prof_end(c, pslot);
+  }
   MX_HIP(hipGetLastError());
   return MODSX_OK;
 }

@@ -29,8 +29,12 @@ MX_D float warp_fetch(const float *src, int sh, int sw, float cval, int adelta, 
   const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;
   float out;
   if (sx >= 0 && sx < sw - 1 && sy >= 0 && sy < sh - 1) {
+    // the two taps of a row as ONE 8-byte load (4-byte aligned): the gathers of the rotation are bound by load instructions
     const float *S = src + (size_t)sy * sw + sx;
-    out = S[0] * w0 + S[1] * w1 + S[sw] * w2 + S[sw + 1] * w3;
+    float2 a, b;
+    __builtin_memcpy(&a, S, 8);
+    __builtin_memcpy(&b, S + sw, 8);
+    out = a.x * w0 + a.y * w1 + b.x * w2 + b.y * w3;
   } else if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
     out = cval;
   } else {
@@ -127,13 +131,24 @@ __global__ __launch_bounds__(256) void k_harris_combine(const float *bxx, const 
   o[i] = (a - b) - c;
 }
 
-// ---- batched form: all views of a launch set in four launches (warp, blur rows, blur columns, warp) ---------------------------
+// ---- batched form: all views of a launch set in a few launches -----------------------------------------------------------------
 // A view of tilt t is 1/t of the image, 31 to 61 of them per image: launched one by one they are ~250 launches of 2-10 us
-// per pair.  Every block takes one 64 x 4 tile of one view; the view is found from the tile prefix carried by the jobs.
+// per pair.  Every block takes one tile of one view; the view is found from the tile prefix carried by the jobs.  A set is at
+// most four tile lists: 64 x 4 tiles of the rotated images (rotate, blur rows, blur columns as separate launches: views whose
+// filters outgrow the LDS tiles, or without a blur), 64 x 4 tiles of the outputs (tilt / zoom of those and of the next list),
+// VF_TW x VF_TH tiles of k_views_rotblur (rotate + blur in one launch: a tilt that is not diagonal) and the VF_TW x VF_TH
+// tiles of k_views_fused (source image to tilted view in ONE launch: every view of the shipped view sets).
+// The last view whose first tile is <= `tile` (views without tiles in a list share their successor's prefix), by bisection: the
+// loads depend on each other, and a walk over 30 views cost every workgroup microseconds before its first pixel.
 MX_D int find_view(const ViewJob *jobs, int n, int tile, int stage) {
-  int j = 0;
-  while (j + 1 < n && tile >= (stage == 2 ? jobs[j + 1].tileF : (stage ? jobs[j + 1].tileB : jobs[j + 1].tileA))) j++;
-  return j;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    const ViewJob &m = jobs[mid];
+    const int first = stage == 3 ? m.tileG : (stage == 2 ? m.tileF : (stage ? m.tileB : m.tileA));
+    if (tile >= first) lo = mid; else hi = mid - 1;
+  }
+  return lo;
 }
 __global__ __launch_bounds__(256) void k_views_warp(const ViewJob *jobs, int n, int stage) {
   const int j = find_view(jobs, n, blockIdx.x, stage);
@@ -158,7 +173,50 @@ __global__ __launch_bounds__(256) void k_views_blur(const ViewJob *jobs, int n, 
             (t / tx) * 4 + (threadIdx.x >> 6));
 }
 
-// the two filter passes of k_views_rotblur over its LDS tiles; N = compile-time tap count (0: runtime nx / ny)
+// One output of the row filter / the column filter over an LDS tile; N = compile-time tap count (0: runtime nx / ny), k = the
+// taps in registers (N > 0), `row` / `col` = the line of the output pixel.  Terms and order are blur_body's.
+template <int N>
+MX_D float vf_row_value(const float *row, int lx, const float *k, const float *kxT, int Rx, int nx) {
+  float r;
+  if (N == 1) r = row[lx];
+  else if (N == 3 || N == 5) {
+    constexpr int R = N >> 1;
+    r = row[lx] * k[R];
+#pragma unroll
+    for (int q = 1; q <= R; q++) r = r + (row[lx - q] + row[lx + q]) * k[R + q];
+  } else if (N > 5) {
+    constexpr int R = N >> 1;
+    r = 0.f;
+#pragma unroll
+    for (int q = 0; q < N; q++) r = r + row[lx + q - R] * k[q];
+  } else {
+    if (nx <= 5) {
+      r = row[lx] * kxT[Rx];
+      for (int q = 1; q <= Rx; q++) r = r + (row[lx - q] + row[lx + q]) * kxT[Rx + q];
+    } else {
+      r = 0.f;
+      for (int q = 0; q < nx; q++) r = r + row[lx + q - Rx] * kxT[q];
+    }
+  }
+  return r;
+}
+template <int N>
+MX_D float vf_col_value(const float *col, int lx, int stride, const float *k, const float *kyT, int Ry) {
+  float r;
+  if (N == 1) r = col[lx];
+  else if (N > 1) {
+    constexpr int R = N >> 1;
+    r = k[R] * col[lx] + 0.f;
+#pragma unroll
+    for (int q = 1; q <= R; q++) r = r + k[R + q] * (col[lx + q * stride] + col[lx - q * stride]);
+  } else {
+    r = kyT[Ry] * col[lx] + 0.f;
+    for (int q = 1; q <= Ry; q++) r = r + kyT[Ry + q] * (col[lx + q * stride] + col[lx - q * stride]);
+  }
+  return r;
+}
+
+// the two filter passes of k_views_rotblur over its LDS tiles
 template <int N>
 MX_D void vf_rows(const float *Wt, float *Tt, const float *kxT, int WW, int Rx, int lane, int ty, int xOut, int yEnd, int nxRt) {
   constexpr int NK = N ? N : 1;
@@ -167,31 +225,7 @@ MX_D void vf_rows(const float *Wt, float *Tt, const float *kxT, int WW, int Rx, 
   for (int q = 0; q < NK; q++) k[q] = N ? kxT[q] : 0.f;
   for (int ly = ty; ly < yEnd; ly += 4) {
     const float *row = Wt + ly * WW + Rx;
-    for (int lx = lane; lx < xOut; lx += 64) {
-      float r;
-      if (N == 1) r = row[lx];
-      else if (N == 3 || N == 5) {
-        constexpr int R = N >> 1;
-        r = row[lx] * k[R];
-#pragma unroll
-        for (int q = 1; q <= R; q++) r = r + (row[lx - q] + row[lx + q]) * k[R + q];
-      } else if (N > 5) {
-        constexpr int R = N >> 1;
-        r = 0.f;
-#pragma unroll
-        for (int q = 0; q < N; q++) r = r + row[lx + q - R] * k[q];
-      } else {
-        const int nx = nxRt;
-        if (nx <= 5) {
-          r = row[lx] * kxT[Rx];
-          for (int q = 1; q <= Rx; q++) r = r + (row[lx - q] + row[lx + q]) * kxT[Rx + q];
-        } else {
-          r = 0.f;
-          for (int q = 0; q < nx; q++) r = r + row[lx + q - Rx] * kxT[q];
-        }
-      }
-      Tt[ly * VF_TW + lx] = r;
-    }
+    for (int lx = lane; lx < xOut; lx += 64) Tt[ly * VF_TW + lx] = vf_row_value<N>(row, lx, k, kxT, Rx, nxRt);
   }
 }
 template <int N>
@@ -200,24 +234,11 @@ MX_D void vf_cols(const float *Tt, float *outBase, const float *kyT, int rcols, 
   float k[NK];
 #pragma unroll
   for (int q = 0; q < NK; q++) k[q] = N ? kyT[q] : 0.f;
+  (void)nyRt;
   for (int ly = ty; ly < yOut; ly += 4) {
     const float *col = Tt + (ly + Ry) * VF_TW;
     float *out = outBase + (size_t)ly * rcols;
-    for (int lx = lane; lx < xOut; lx += 64) {
-      float r;
-      if (N == 1) r = col[lx];
-      else if (N > 1) {
-        constexpr int R = N >> 1;
-        r = k[R] * col[lx] + 0.f;
-#pragma unroll
-        for (int q = 1; q <= R; q++) r = r + k[R + q] * (col[lx + q * VF_TW] + col[lx - q * VF_TW]);
-      } else {
-        (void)nyRt;
-        r = kyT[Ry] * col[lx] + 0.f;
-        for (int q = 1; q <= Ry; q++) r = r + kyT[Ry + q] * (col[lx + q * VF_TW] + col[lx - q * VF_TW]);
-      }
-      out[lx] = r;
-    }
+    for (int lx = lane; lx < xOut; lx += 64) out[lx] = vf_col_value<N>(col, lx, VF_TW, k, kyT, Ry);
   }
 }
 
@@ -280,6 +301,177 @@ __global__ __launch_bounds__(256) void k_views_rotblur(const ViewJob *jobs, int 
   }
 }
 
+// ---- source image to tilted view in ONE launch ---------------------------------------------------------------------------------
+// The second cv::warpAffine of a view (tilt / zoom) has a diagonal inverse map: output column x taps the blurred columns sx(x)
+// and sx(x) + 1 whatever the row, output row y the rows sy(y) and sy(y) + 1, and sx, sy are monotone.  At tilt t only 2 / t of
+// the blurred columns are ever read.  k_views_rotblur + k_views_warp filter all of them, write the blurred plane (4 - 5 x the
+// size of the output) and read it back; here a workgroup keeps its VF_TW x VF_TH tile of the blurred rotated image in LDS,
+// filters only the columns and rows some output pixel of the tile taps, and emits the output pixels whose (clamped) tap origin
+// lies in the tile.  Every value is the f32 the separate launches pass through memory: the rotation is warp_fetch, the filter
+// terms are vf_row_value / vf_col_value, the output is warp_fetch's expression read from the tile (warp_fetch_tile).
+constexpr int VG_TS = VF_TW + 1;          // row stride of the row-filtered tile: the tile's columns and the one the taps sx + 1 reach
+constexpr int VG_HR = VF_TH + 2 * VF_RY + 1;   // most rows of the rotated tile
+constexpr int VG_TABS = VF_TW + 4 + VF_TH + 4;   // bytes of the tapped-column and tapped-row lists
+
+// tap origin of output column p (axis 0) / row p (axis 1) under a diagonal inverse map: warp_fetch's sx / sy
+MX_D int warp_tap0(const double *M, int axis, int p) {
+  int ad, bd, X0, Y0;
+  warp_xterm(M, axis ? 0 : p, ad, bd);
+  warp_yterm(M, axis ? p : 0, X0, Y0);
+  const int s = ((axis ? Y0 + bd : X0 + ad) >> 5) >> 5;
+  return s < -32768 ? -32768 : (s > 32767 ? 32767 : s);
+}
+// first p of [0, n] whose tap origin, clamped into [0, lim), reaches `target`.  The origin is monotone in p (M[0], M[4] > 0);
+// `inv` only says where to start looking, the answer comes from the fixed-point map itself.
+MX_D int first_reaching(const double *M, int axis, int target, int n, int lim, double inv) {
+  if (target <= 0) return 0;
+  if (target >= lim) return n;
+  const double h = ((double)target - M[axis ? 5 : 2]) * inv;
+  int p = h > 0. ? (h < (double)n ? (int)h : n) : 0;
+  while (p > 0 && warp_tap0(M, axis, p - 1) >= target) p--;      // 0 < target < lim: clamping changes neither comparison
+  while (p < n && warp_tap0(M, axis, p) < target) p++;
+  return p;
+}
+// warp_fetch on the blurred tile Bt (stride WW, origin (x0, y0) of the sh x sw rotated image): the same four products in the
+// same order and the same three branches; a tap inside the image is in the tile for every pixel the tile owns
+MX_D float warp_fetch_tile(const float *Bt, int WW, int x0, int y0, int sh, int sw, float cval, int adelta, int bdelta, int X0, int Y0) {
+  const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+  int sx = X >> 5, sy = Y >> 5;
+  sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
+  sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
+  const float fx = (float)(X & 31) * (1.f / 32), fy = (float)(Y & 31) * (1.f / 32);
+  const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;
+  float out;
+  if (sx >= 0 && sx < sw - 1 && sy >= 0 && sy < sh - 1) {
+    const float *S = Bt + (sy - y0) * WW + (sx - x0);
+    out = S[0] * w0 + S[1] * w1 + S[WW] * w2 + S[WW + 1] * w3;
+  } else if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
+    out = cval;
+  } else {
+    const bool bx0 = sx >= 0 && sx < sw, bx1 = sx + 1 >= 0 && sx + 1 < sw, by0 = sy >= 0 && sy < sh, by1 = sy + 1 >= 0 && sy + 1 < sh;
+    const float v0 = (bx0 && by0) ? Bt[(sy - y0) * WW + (sx - x0)] : cval;
+    const float v1 = (bx1 && by0) ? Bt[(sy - y0) * WW + (sx + 1 - x0)] : cval;
+    const float v2 = (bx0 && by1) ? Bt[(sy + 1 - y0) * WW + (sx - x0)] : cval;
+    const float v3 = (bx1 && by1) ? Bt[(sy + 1 - y0) * WW + (sx + 1 - x0)] : cval;
+    out = v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3;
+  }
+  return out;
+}
+// The workgroup's 256 threads walk an (outer x inner) index space row-major: a tile of tilt 8 owns 16 output columns and taps
+// 32 blurred ones, so lanes mapped to columns would idle.  One division per thread and pass.
+struct FlatWalk {
+  int o, i, dq, dr, n;
+  MX_D FlatWalk(int tid, int inner) : o(tid / inner), i(tid - (tid / inner) * inner), dq(256 / inner), dr(256 - (256 / inner) * inner), n(inner) {}
+  MX_D void next() { o += dq; i += dr; if (i >= n) { i -= n; o++; } }
+};
+template <int N>
+MX_D void vg_rows(const float *Wt, float *Tt, const unsigned char *colTab, const float *kxT, int WW, int Rx, int tid, int nix, int yEnd, int nxRt) {
+  constexpr int NK = N ? N : 1;
+  float k[NK];
+#pragma unroll
+  for (int q = 0; q < NK; q++) k[q] = N ? kxT[q] : 0.f;
+  for (FlatWalk w(tid, nix); w.o < yEnd; w.next()) {
+    const int lc = colTab[w.i];
+    if (lc != 255) Tt[w.o * VG_TS + lc] = vf_row_value<N>(Wt + w.o * WW + Rx, lc, k, kxT, Rx, nxRt);
+  }
+}
+template <int N>
+MX_D void vg_cols(const float *Tt, float *Bt, const unsigned char *colTab, const unsigned char *rowTab, const float *kyT, int WW, int Ry, int tid,
+                  int nix, int niy) {
+  constexpr int NK = N ? N : 1;
+  float k[NK];
+#pragma unroll
+  for (int q = 0; q < NK; q++) k[q] = N ? kyT[q] : 0.f;
+  for (FlatWalk w(tid, nix); w.o < niy; w.next()) {
+    const int lc = colTab[w.i], lr = rowTab[w.o];
+    if (lc != 255 && lr != 255) Bt[lr * WW + lc] = vf_col_value<N>(Tt + (lr + Ry) * VG_TS, lc, VG_TS, k, kyT, Ry);
+  }
+}
+__global__ __launch_bounds__(256) void k_views_fused(const ViewJob *jobs, int n, const float *taps, int wFloats, int tFloats) {
+  extern __shared__ float smem[];
+  const int j = find_view(jobs, n, blockIdx.x, 3);
+  const ViewJob &v = jobs[j];
+  const int Rx = v.kx >> 1, Ry = v.ky >> 1;
+  const int t = blockIdx.x - v.tileG, tx = (v.rcols + VF_TW - 1) / VF_TW;
+  const int x0 = (t % tx) * VF_TW, y0 = (t / tx) * VF_TH;
+  const int x1 = min(x0 + VF_TW, v.rcols), y1 = min(y0 + VF_TH, v.rrows);
+  // Ownership: output pixel (x, y) belongs to the tile that holds (clamp(sx, 0, rcols - 1), clamp(sy, 0, rrows - 1)), so pixels
+  // whose taps fall outside the rotated image are written exactly once too.  Columns [xa, xb) x rows [ya, yb).
+  // (each of the four waves finds one of the four bounds)
+  __shared__ int own[4];
+  {
+    const int axis = threadIdx.x >> 7, upper = (threadIdx.x >> 6) & 1;
+    const int r = first_reaching(v.W, axis, axis ? (upper ? y1 : y0) : (upper ? x1 : x0), axis ? v.drows : v.dcols, axis ? v.rrows : v.rcols, v.invW[axis]);
+    if ((threadIdx.x & 63) == 0) own[threadIdx.x >> 6] = r;
+  }
+  __syncthreads();
+  const int xa = own[0], xb = own[1], ya = own[2], yb = own[3];
+  const int nox = xb - xa, noy = yb - ya;
+  if (nox <= 0 || noy <= 0) return;
+  // blurred pixels the taps of owned pixels can read: the tile and, inside the image, the column and row behind it
+  const int colsB = x1 - x0 + (x1 < v.rcols ? 1 : 0), rowsB = y1 - y0 + (y1 < v.rrows ? 1 : 0);
+  const int xEnd = colsB + 2 * Rx, yEnd = rowsB + 2 * Ry;      // ... and what the two filters reach of the rotated image
+  const int WW = VF_TW + 2 * Rx + 1;
+  float *const Wt = smem, *const Tt = smem + wFloats;          // rotated tile (later the blurred one), row-filtered tile
+  unsigned char *const colTab = (unsigned char *)(smem + wFloats + tFloats), *const rowTab = colTab + VF_TW + 4;
+  const int tid = threadIdx.x;
+  // The columns to filter: every one of the tile when the owned pixels tap at least that many (a tilt below 2), else the two
+  // taps of each owned column; rows likewise.  255 = a tap outside the image (it reads cval, not a blurred value).
+  const bool denseX = 2 * nox >= colsB, denseY = 2 * noy >= rowsB;
+  const int nix = denseX ? colsB : 2 * nox, niy = denseY ? rowsB : 2 * noy;
+  {
+    // cv::warpAffine's per-column and per-row terms of the rotation, tabulated once (they live where the row-filtered tile
+    // goes afterwards); halo pixels outside the rotated image mirror it (BORDER_REFLECT_101 of the blur)
+    int *const colAd = (int *)Tt, *const colBd = colAd + WW, *const rowX0 = colBd + WW, *const rowY0 = rowX0 + VG_HR;
+    for (int i = tid; i < xEnd + yEnd; i += 256) {
+      if (i < xEnd) warp_xterm(v.R, reflect101(x0 - Rx + i, v.rcols), colAd[i], colBd[i]);
+      else warp_yterm(v.R, reflect101(y0 - Ry + i - xEnd, v.rrows), rowX0[i - xEnd], rowY0[i - xEnd]);
+    }
+    for (int i = tid; i < nix + niy; i += 256) {
+      if (i < nix) {
+        const int lc = denseX ? i : warp_tap0(v.W, 0, xa + (i >> 1)) + (i & 1) - x0;
+        colTab[i] = (unsigned char)(lc >= 0 && lc < colsB ? lc : 255);
+      } else {
+        const int q = i - nix, lr = denseY ? q : warp_tap0(v.W, 1, ya + (q >> 1)) + (q & 1) - y0;
+        rowTab[q] = (unsigned char)(lr >= 0 && lr < rowsB ? lr : 255);
+      }
+    }
+    __syncthreads();
+    for (FlatWalk w(tid, xEnd); w.o < yEnd; w.next())
+      Wt[w.o * WW + w.i] = warp_fetch(v.src, v.srows, v.scols, 128.f, colAd[w.i], colBd[w.i], rowX0[w.o], rowY0[w.o]);
+  }
+  __syncthreads();
+  const float *kxT = taps + v.tapOfs, *kyT = kxT + v.kx;
+  const int nx = v.kx, ny = v.ky;
+  // wave-uniform tap counts: one switch per pass picks a fully unrolled body with the taps in registers (as k_views_rotblur)
+  switch (nx) {
+    case 1: vg_rows<1>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 3: vg_rows<3>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 5: vg_rows<5>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 7: vg_rows<7>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 9: vg_rows<9>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 11: vg_rows<11>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    case 13: vg_rows<13>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+    default: vg_rows<0>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
+  }
+  __syncthreads();
+  // the blurred tile takes the place of the rotated one, which nothing reads any more
+  switch (ny) {
+    case 1: vg_cols<1>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
+    case 3: vg_cols<3>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
+    case 5: vg_cols<5>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
+    default: vg_cols<0>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
+  }
+  __syncthreads();
+  for (FlatWalk w(tid, nox); w.o < noy; w.next()) {
+    const int x = xa + w.i, y = ya + w.o;
+    int ad, bd, X0, Y0;
+    warp_xterm(v.W, x, ad, bd);
+    warp_yterm(v.W, y, X0, Y0);
+    v.dst[(size_t)y * v.dcols + x] = warp_fetch_tile(Wt, WW, x0, y0, v.rrows, v.rcols, 128.f, ad, bd, X0, Y0);
+  }
+}
+
 void launch_warp_affine(hipStream_t s, const WarpJob &jb) {
   dim3 grid((jb.dcols + 63) / 64, (jb.drows + 3) / 4);
   hipLaunchKernelGGL(k_warp_affine, grid, dim3(256), 0, s, jb);
@@ -307,6 +499,14 @@ void launch_views_rotblur(hipStream_t s, const ViewJob *jobs, int n, int tiles, 
   if (tiles <= 0) return;
   const int wFloats = (VF_TH + 2 * maxRy) * (VF_TW + 2 * maxRx), tFloats = (VF_TH + 2 * maxRy) * VF_TW;
   MX_DUP(K_VIEW_BLUR) hipLaunchKernelGGL(k_views_rotblur, dim3(tiles), dim3(256), (size_t)(wFloats + tFloats) * 4, s, jobs, n, taps, wFloats);
+}
+void launch_views_fused(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int maxRx, int maxRy) {
+  if (tiles <= 0) return;
+  const int wFloats = (VF_TH + 2 * maxRy + 1) * (VF_TW + 2 * maxRx + 1), tFloats = (VF_TH + 2 * maxRy + 1) * VG_TS;
+  static_assert(2 * (VF_TW + 2 * VF_RX + 1) + 2 * VG_HR <= (VF_TH + 1) * VG_TS, "the rotation's column / row terms fit the row-filtered tile");
+  static_assert(VF_TW + 1 < 255 && VF_TH + 1 < 255, "tapped columns / rows are listed as bytes");
+  MX_DUP(K_VIEW_BLUR) hipLaunchKernelGGL(k_views_fused, dim3(tiles), dim3(256), (size_t)(wFloats + tFloats) * 4 + ((VG_TABS + 3) & ~3), s, jobs, n, taps,
+                                         wFloats, tFloats);
 }
 
 }  // namespace mx
