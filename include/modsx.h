@@ -401,6 +401,38 @@ int modsx_detect_describe_views(modsx_ctx *ctx, const modsx_image *img, const mo
 int modsx_match_fginn_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2,
                              const double *pos2, double ratio, double contradDist, int nn, modsx_tentative **out);
 
+/* FGINN matching against a descriptor database: MatchFlannFGINNPlusDB (matching/matching.hpp:270-271, .cpp:462-572), the WxBS
+ * strategy.  The squared distance dDB of a query to its nearest database descriptor is one more "second nearest": a record
+ * is kept iff max(d1/d2, d1/dDB) <= ratio^2 (f32 quotients widened, std::max: a NaN d1/dDB -- the query equals its nearest train
+ * AND a database row -- is ignored), its `ratio` is the square root of that maximum, and d2byDB = dDB.  With ratio >= 1 the
+ * records are those of modsx_match_fginn plus d2byDB.  The search is exact (the reference asks a kd-tree).
+ * modsx_db: cv::Mat descDB of mods.cpp:207-216 / CorrespondenceBank::DB, packed once into HBM: n rows of 128 values holding
+ * the integers 0..255, dtype 0 = u8, 1 = f32 (anything else -- fractions, values out of range, NaN, n < 1, more than
+ * MODSX_DB_MAX_ROWS rows -- gives NULL and a message).  Read-only after creation: every context of its device may use it, also
+ * at the same time.  Parsing OpenCV FileStorage files is the caller's business: hand over the array. */
+#define MODSX_DB_MAX_ROWS 16777216L   /* 2^24 rows (2 GiB of HBM) */
+typedef struct modsx_db modsx_db;
+modsx_db *modsx_db_create(modsx_ctx *ctx, const void *rows, long n, int dtype);
+/* A database must outlive its attachments (modsx_set_fginn_db); freeing one that is attached to `ctx` detaches it there. */
+void modsx_db_free(modsx_ctx *ctx, modsx_db *db);
+long modsx_db_rows(const modsx_db *db);
+/* stage tap: dmin[i] = squared L2 distance of query i ([n][128] f32 holding integers 0..255) to its nearest database row */
+int modsx_db_nearest(modsx_ctx *ctx, const modsx_db *db, const float *desc, int n, float *dmin);
+/* As modsx_match_fginn / modsx_match_fginn_device, plus the database (NULL, or one of another device: MODSX_ERR_ARG).
+ * d2byDB (optional): malloc'd, one value per returned record (modsx_free). */
+int modsx_match_fginn_db(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
+                         double ratio, double contradDist, int nn, const modsx_db *db, modsx_tentative **out, double **d2byDB);
+int modsx_match_fginn_db_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2,
+                                const double *pos2, double ratio, double contradDist, int nn, const modsx_db *db,
+                                modsx_tentative **out, double **d2byDB);
+/* MatchPars::useDBforFGINN for the fused callers of this context (modsx_match_pair, _pairs, _pair_views, _pairs_views,
+ * _ladder): every match and re-match of a class whose descriptor is MODSX_DESC_ROOT_SIFT, of either detector, goes against
+ * the database, and no other class does (correspondencebank.cpp:333-341).  NULL detaches.  All contexts of one
+ * modsx_match_pairs / modsx_match_pairs_views call must have the same database attached, or none (MODSX_ERR_ARG before any
+ * work).  The sharded calls refuse a context with a database attached (MODSX_ERR_ARG at entry, before any collective): the
+ * attachment must therefore be alike on all ranks. */
+int modsx_set_fginn_db(modsx_ctx *ctx, const modsx_db *db);
+
 /* One step of mods.cpp:229-415 with a ladder of synthesised views per image (same views for both images,
  * as in iters_mods_cviu.ini). */
 int modsx_match_pair_views(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,
@@ -590,7 +622,8 @@ int modsx_load_regions(const char *path, const char *det_name, const char *desc_
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:
  * blur_hess, hessian, resize, nms_localize (scan + refine), baumberg, orientation, patch_sample, blur_rows, describe,
  * match_fginn, gray, warp_affine, view_blur, blur_cols, match_sweep1 (the one k_match launch that carries the 2 N M 128
- * contraction; also part of match_fginn).  modsx_kernel_stats returns the number of classes.
+ * contraction; also part of match_fginn), match_db (k_dbnn_min, the database pass of the _db matchers: 2 x selected queries x
+ * database rows x 128; not part of match_fginn).  modsx_kernel_stats returns the number of classes.
  * Cost: with ROCm 7 a stream that has recorded timing events keeps per-dispatch completion signals on its queue -- every later
  * launch of that context costs its host thread more CPU (measured: 8.5 -> 29 ms per 1920x1080 pair of ~220 launches), also after
  * modsx_profile(ctx, 0).  Profile on contexts made for it, or after the throughput measurement (bench.py orders its legs so). */

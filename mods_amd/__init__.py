@@ -99,7 +99,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_comm_attach", "modsx_comm_lane_done", "modsx_comm_reset_lanes", "modsx_comm_set_timeout", "modsx_comm_stats",
            "modsx_shard_block_bytes", "modsx_shard_block_pack", "modsx_shard_blocks_unpack", "modsx_shard_device_pack",
            "modsx_shard_device_unpack", "modsx_verify_device_stats", "modsx_verify_device_timing", "modsx_comm_set_exchange",
-           "modsx_shard_owner_plan"]
+           "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
+           "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -109,7 +110,7 @@ SHARD_ROW_REGION, SHARD_ROW_KP = 0, 1     # include/modsx.h: what of a region tr
 EXCHANGE_ALL_GATHER, EXCHANGE_OWNER = 0, 1   # include/modsx.h: modsx_comm_set_exchange
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
-                  "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1"]
+                  "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
 
 
 def build(force=False):
@@ -155,6 +156,14 @@ def lib():
         L.modsx_image_wrap_device.restype = C.c_void_p
         L.modsx_image_wrap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.modsx_image_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_db_create.restype = C.c_void_p
+        L.modsx_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int]
+        L.modsx_db_free.restype = None
+        L.modsx_db_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_db_rows.restype = C.c_long
+        L.modsx_db_rows.argtypes = [C.c_void_p]
+        L.modsx_db_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_set_fginn_db.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -402,6 +411,22 @@ class Image(object):
         return out
 
 
+class Db(object):
+    """A descriptor database resident in HBM (modsx_db): the background set of MatchFlannFGINNPlusDB."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def rows(self):
+        return int(lib().modsx_db_rows(self.h)) if self.h else 0
+
+    def free(self):
+        if self.h:
+            lib().modsx_db_free(self.ctx.h, self.h)
+            self.h = None
+
+
 class Context(object):
     """One modsx_ctx (one HIP stream).  Raises if no gfx950 device is available."""
 
@@ -509,6 +534,48 @@ class Context(object):
         n = _check(lib().modsx_match_fginn(self._c(), _p(d1), len(d1), _p(d2), len(d2), _p(pos2), C.c_double(ratio),
                                            C.c_double(contrad_dist), nn, C.byref(out)), "match_fginn")
         return _take(out, n, TENT)
+
+    def db_create(self, rows):
+        """modsx_db_create: [n][128] descriptors holding the integers 0..255 (uint8, or anything convertible to float32)."""
+        a = np.ascontiguousarray(rows)
+        if a.dtype != np.uint8:
+            a = np.ascontiguousarray(a, np.float32)
+        if a.ndim != 2 or a.shape[1] != 128:
+            raise ValueError("db_create: an [n][128] array is expected")
+        h = lib().modsx_db_create(self._c(), _p(a), a.shape[0], 0 if a.dtype == np.uint8 else 1)
+        if not h:
+            raise RuntimeError("modsx_db_create failed: " + _err())
+        return Db(self, h)
+
+    def db_nearest(self, db, desc):
+        """Squared L2 distance of every descriptor to its nearest database row (float32, exact integers)."""
+        d = np.ascontiguousarray(desc, np.float32)
+        out = np.empty(len(d), np.float32)
+        _check(lib().modsx_db_nearest(self._c(), C.c_void_p(db.h), _p(d), len(d), _p(out)), "db_nearest")
+        return out
+
+    def match_fginn_db(self, d1, d2, pos2, db, ratio=0.8, contrad_dist=30.0, nn=50):
+        """MatchFlannFGINNPlusDB: (tentatives, d2byDB)."""
+        d1 = np.ascontiguousarray(d1, np.float32)
+        d2 = np.ascontiguousarray(d2, np.float32)
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out, dd = C.c_void_p(), C.c_void_p()
+        n = _check(lib().modsx_match_fginn_db(self._c(), _p(d1), len(d1), _p(d2), len(d2), _p(pos2), C.c_double(ratio),
+                                              C.c_double(contrad_dist), nn, C.c_void_p(db.h if db is not None else None),
+                                              C.byref(out), C.byref(dd)), "match_fginn_db")
+        return _take(out, n, TENT), _take(dd, n, np.dtype("f8"))
+
+    def match_fginn_db_device(self, d1_ptr, n1, d2_ptr, n2, pos2, db, ratio=0.8, contrad_dist=30.0, nn=50):
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out, dd = C.c_void_p(), C.c_void_p()
+        n = _check(lib().modsx_match_fginn_db_device(self._c(), C.c_void_p(d1_ptr), int(n1), C.c_void_p(d2_ptr), int(n2),
+                                                     _p(pos2), C.c_double(ratio), C.c_double(contrad_dist), nn,
+                                                     C.c_void_p(db.h), C.byref(out), C.byref(dd)), "match_fginn_db_device")
+        return _take(out, n, TENT), _take(dd, n, np.dtype("f8"))
+
+    def set_fginn_db(self, db):
+        """MatchPars::useDBforFGINN for the fused callers of this context; None detaches."""
+        _check(lib().modsx_set_fginn_db(self._c(), C.c_void_p(db.h) if db is not None else None), "set_fginn_db")
 
     def synth_view(self, img, view):
         H = np.zeros(9)

@@ -473,6 +473,8 @@ int modsx_match_pairs(modsx_ctx *const *ctxs, int n_ctx, const modsx_image *cons
   NEED(ctxs); NEED(par); NEED(results);
   if (n_ctx <= 0 || n_pairs < 0 || (n_pairs > 0 && (!imgs1 || !imgs2))) { mx::set_error("modsx_match_pairs: bad argument"); return MODSX_ERR_ARG; }
   for (int i = 0; i < n_ctx; i++) NEED(ctxs[i]);
+  for (int i = 1; i < n_ctx; i++)
+    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error("modsx_match_pairs: all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
   for (int i = 0; i < n_pairs; i++) memset(&results[i], 0, sizeof results[i]);   // no result owns arrays before its group ran
   std::atomic<int> next(0), failed(0);
   std::string firstErr;
@@ -578,6 +580,8 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
     return MODSX_ERR_ARG;
   }
   for (int i = 0; i < n_ctx; i++) NEED(ctxs[i]);
+  for (int i = 1; i < n_ctx; i++)
+    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error("modsx_match_pairs_views: all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
   for (int i = 0; i < n_pairs; i++) memset(&results[i], 0, sizeof results[i]);
   std::atomic<int> next(0), failed(0);
   std::string firstErr;
@@ -758,6 +762,73 @@ int modsx_match_fginn_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, c
   if (rc) return rc;
   *out = to_malloc(t);
   return (int)t.size();
+}
+
+// ---- the descriptor database of MatchFlannFGINNPlusDB --------------------------------------------------------------------------
+modsx_db *modsx_db_create(modsx_ctx *ctx, const void *rows, long n, int dtype) {
+  if (!ctx) { mx::set_error("modsx_db_create: null context"); return nullptr; }
+  hipSetDevice(ctx->dev);
+  mx::DbSet *s = db_create(ctx, rows, n, dtype);
+  return reinterpret_cast<modsx_db *>(s);     // modsx_db holds exactly one DbSet
+}
+void modsx_db_free(modsx_ctx *ctx, modsx_db *db) {
+  if (!db) return;
+  if (ctx) {
+    hipSetDevice(ctx->dev);
+    if (ctx->fginnDb == &db->set) ctx->fginnDb = nullptr;     // freeing a database that is attached to the freeing context detaches it
+  }
+  db_free(&db->set);
+}
+long modsx_db_rows(const modsx_db *db) { return db ? db->set.rows : 0; }
+int modsx_db_nearest(modsx_ctx *ctx, const modsx_db *db, const float *desc, int n, float *dmin) {
+  NEED(ctx); NEED(db);
+  if (n < 0 || (n > 0 && (!desc || !dmin))) { mx::set_error("modsx_db_nearest: bad argument"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  return db_nearest(ctx, db->set, desc, n, dmin);
+}
+static double *d2_to_malloc(const std::vector<double> &v) {
+  double *p = (double *)malloc(sizeof(double) * std::max<size_t>(1, v.size()));
+  if (!v.empty()) memcpy(p, v.data(), sizeof(double) * v.size());
+  return p;
+}
+int modsx_match_fginn_db(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
+                         double ratio, double contradDist, int nn, const modsx_db *db, modsx_tentative **out, double **d2byDB) {
+  NEED(ctx); NEED(out);
+  if (!db) { mx::set_error("modsx_match_fginn_db: null database"); return MODSX_ERR_ARG; }
+  if (n1 < 0 || n2 < 0 || (n1 > 0 && !desc1) || (n2 > 0 && (!desc2 || !pos2))) { mx::set_error("modsx_match_fginn_db: bad argument"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  std::vector<double> d2;
+  int rc = match_host_desc(ctx, desc1, n1, desc2, n2, pos2, ratio, contradDist, nn, t, &db->set, &d2);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  if (d2byDB) *d2byDB = d2_to_malloc(d2);
+  return (int)t.size();
+}
+int modsx_match_fginn_db_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2,
+                                const double *pos2, double ratio, double contradDist, int nn, const modsx_db *db,
+                                modsx_tentative **out, double **d2byDB) {
+  NEED(ctx); NEED(out);
+  if (!db) { mx::set_error("modsx_match_fginn_db_device: null database"); return MODSX_ERR_ARG; }
+  if (n1 < 0 || n2 < 0 || (n1 > 0 && !dev_desc1_u8) || (n2 > 0 && (!dev_desc2_u8 || !pos2))) {
+    mx::set_error("modsx_match_fginn_db_device: bad argument");
+    return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  std::vector<double> d2;
+  int rc = match_device(ctx, (const uint8_t *)dev_desc1_u8, n1, (const uint8_t *)dev_desc2_u8, n2, pos2, ratio, contradDist, nn, t,
+                        &db->set, &d2);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  if (d2byDB) *d2byDB = d2_to_malloc(d2);
+  return (int)t.size();
+}
+int modsx_set_fginn_db(modsx_ctx *ctx, const modsx_db *db) {
+  NEED(ctx);
+  if (db && db->set.dev != ctx->dev) { mx::set_error("modsx_set_fginn_db: the descriptor database lives on another device"); return MODSX_ERR_ARG; }
+  ctx->fginnDb = db ? &db->set : nullptr;
+  return MODSX_OK;
 }
 
 int modsx_match_ladder(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,

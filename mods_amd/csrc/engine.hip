@@ -428,7 +428,7 @@ void ctx_destroy(modsx_ctx *c) {
   for (int i = 0; i < MAXB; i++) c->pyr[i].store.release();
   DevBuf *bufs[] = {&c->nmsJobs, &c->cand, &c->counter, &c->affJobs, &c->affOut, &c->oriJobs, &c->oriOut, &c->descJobs, &c->tilePrefix,
                     &c->taps, &c->imgRefs, &c->scratchA, &c->scratchB, &c->descAllF[0], &c->descAllF[1], &c->descAllU8[0],
-                    &c->descAllU8[1], &c->descAllU8b[0], &c->descAllU8b[1], &c->shardLocal, &c->pos2, &c->matchRows, &c->matchWork, &c->misc, &c->scratchC, &c->needTab, &c->coordTab, &c->tileJob, &c->blurTiles, &c->nmsQueue, &c->rowStarts, &c->viewTmp[0], &c->viewTmp[1], &c->viewTaps, &c->viewJobs};
+                    &c->descAllU8[1], &c->descAllU8b[0], &c->descAllU8b[1], &c->shardLocal, &c->pos2, &c->matchRows, &c->matchWork, &c->dbSel, &c->misc, &c->scratchC, &c->needTab, &c->coordTab, &c->tileJob, &c->blurTiles, &c->nmsQueue, &c->rowStarts, &c->viewTmp[0], &c->viewTmp[1], &c->viewTaps, &c->viewJobs};
   for (DevBuf *b : bufs) b->release();
   for (int i = 0; i < MAXB; i++) { c->descF[i].release(); c->descU8[i].release(); c->viewImg[i].release(); for (int k = 0; k < 3; k++) c->descU8x[k][i].release(); }
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) for (int sd = 0; sd < 2; sd++) c->descCls[d][t][sd].release();
@@ -1576,8 +1576,15 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
 }
 
 // the host half of the matcher: per-query result rows -> TentativeCorrespExt records (matching.cpp:435-457)
-void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_tentative> &o) {
+// ddb (optional): the squared distance of every query to its nearest database descriptor (BIG where no record can arise) turns
+// the records into MatchFlannFGINNPlusDB's (matching.cpp:462-572).  ratioDB = d0 / dDB does not depend on j, so the database
+// variant yields the plain records filtered and relabelled: with `max` = std::max, max(r_j, rDB) is rDB iff r_j < rDB (a NaN
+// rDB -- the query sits ON its nearest train and ON a database row -- leaves r_j), and a record survives iff that maximum
+// is <= ratio^2.  In the "all points" branch (ratio >= 1, :505-536) the records are the plain ones plus d2byDB.
+void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_tentative> &o, const int *ddb, double sqminratio,
+                        std::vector<double> *d2byDB) {
   o.reserve(n1 / 4 + 16);
+  if (d2byDB) d2byDB->clear();
   for (int q = 0; q < n1; q++) {
     const MatchRow &r = rows[q];
     // rank of the first ratio-passing neighbour is nless+1; it must be <= nn-1 and every neighbour
@@ -1588,6 +1595,15 @@ void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_
     t.t1 = r.t1;
     t.d1 = r.d0; t.d2 = r.dj; t.d2by2ndcl = r.d1;
     double ratio = r.d0 / r.dj;  // f32 / f32, then widened (matching.cpp:437)
+    if (ddb) {
+      const float dDB = (float)ddb[q];                 // an integer below 2^24: exact
+      if (sqminratio < 1.0) {
+        const double ratioDB = r.d0 / dDB;             // f32 / f32, then widened (:544)
+        if (ratio < ratioDB) ratio = ratioDB;          // std::max(ratio, ratioDB) (:548)
+        if (!(ratio <= sqminratio)) continue;          // (:549)
+      }
+      if (d2byDB) d2byDB->push_back((double)dDB);
+    }
     t.ratio = sqrt(ratio);
     o.push_back(t);
   }
@@ -1597,8 +1613,11 @@ void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_
 // independent (query set, train set) problems that share the kernel launches (blockIdx.z) and one synchronisation
 int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                        const double *const *pos2Host, double ratioT, double contradDist, int nn,
-                       std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev) {
+                       std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev, const DbSet *db,
+                       std::vector<double> *d2byDB) {
   // pos2Dev (optional, unsharded branch): the positions already live on the device; pos2Host is then not read
+  // db (optional, unsharded branch): MatchFlannFGINNPlusDB -- behind the matcher's launches, on the same stream, the queries that
+  // give a record are selected and swept against the database (kernels_dbnn.hip); their dDB words travel down with the rows
   CtxBusy busy(c);
   if (nb < 1 || nb > MATCH_MAXB) { set_error("match_device_batch: batch size"); return MODSX_ERR_ARG; }
   hipStream_t s = c->stream;
@@ -1613,6 +1632,7 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     // view-sharded run (engine_shard.hip): this rank matches the query rows [lo, lo + per) of ONE problem; the result rows
     // of all ranks are all-gathered on the device and every rank builds the full tentative list
     if (nb != 1) { set_error("match_device_batch: a sharded match takes one problem"); return MODSX_ERR_ARG; }
+    if (db) { set_error("match_device_batch: a sharded match takes no descriptor database"); return MODSX_ERR_ARG; }
     out[0].clear();
     const int N1 = shard->n1_total, M = n2[0], per = shard->per;
     const int lo = shard->lo, nloc = std::max(0, std::min(N1, lo + per) - lo);
@@ -1645,10 +1665,12 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     rows_to_tentatives(rows.data(), N1, nn, out[0]);
     return MODSX_OK;
   }
+  if (db && db->dev != c->dev) { set_error("match: the descriptor database lives on another device"); return MODSX_ERR_ARG; }
   size_t posOfs[MATCH_MAXB], rowOfs[MATCH_MAXB], workOfs[MATCH_MAXB], posB = 0, rowB = 0, workB = 0;
   int live[MATCH_MAXB], nl = 0;
   for (int i = 0; i < nb; i++) {
     out[i].clear();
+    if (d2byDB) d2byDB[i].clear();
     if (n1[i] <= 0 || n2[i] <= 0) continue;
     posOfs[nl] = posB; posB += up((size_t)n2[i] * 16);
     rowOfs[nl] = rowB; rowB += up((size_t)n1[i] * sizeof(MatchRow));
@@ -1656,7 +1678,15 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     live[nl++] = i;
   }
   if (!nl) return MODSX_OK;
-  if (!c->pos2.ensure(posB) || !c->matchRows.ensure(rowB) || !c->matchWork.ensure(workB) || !c->hMatch.ensure(posB + rowB))
+  // with a database: dDB per query behind the rows (one download), the selected-query lists and their counts in a buffer of their own
+  size_t ddbOfs[MATCH_MAXB], selOfs[MATCH_MAXB], selB = 256;
+  if (db)
+    for (int k = 0; k < nl; k++) {
+      ddbOfs[k] = rowB; rowB += up((size_t)n1[live[k]] * 4);
+      selOfs[k] = selB; selB += up((size_t)n1[live[k]] * 4);
+    }
+  if (!c->pos2.ensure(posB) || !c->matchRows.ensure(rowB) || !c->matchWork.ensure(workB) || !c->hMatch.ensure(posB + rowB) ||
+      (db && !c->dbSel.ensure(selB)))
     return MODSX_ERR_NOMEM;
   char *hpos = (char *)c->hMatch.p, *hrow = hpos + posB;   // pinned staging: positions up, rows down
   const uint8_t *pd1[MATCH_MAXB], *pd2[MATCH_MAXB];
@@ -1682,16 +1712,31 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     ProfScope ps(c, K_MATCH, work);
     launch_match_batch(s, nl, pd1, pn1, pd2, pn2, ppos, sqminratio, contrDistSq, nn, prow, pwork, tS1 ? evS1 : nullptr);
   }
+  if (db) {
+    int *psel[MATCH_MAXB], *pddb[MATCH_MAXB];
+    for (int k = 0; k < nl; k++) { psel[k] = (int *)((char *)c->dbSel.p + selOfs[k]); pddb[k] = (int *)((char *)c->matchRows.p + ddbOfs[k]); }
+    launch_db_select(s, nl, prow, pn1, nn, sqminratio >= 1.0, psel, (int *)c->dbSel.p, pddb);
+    ProfScope ps(c, K_MATCH_DB, 0);      // its work, 2 x selected x rows x 128, is known once the rows are down
+    launch_dbnn_min(s, nl, pd1, pn1, psel, (int *)c->dbSel.p, pddb, *db);
+  }
   MX_HIP(ctx_copy(c, hrow, c->matchRows.p, rowB, hipMemcpyDeviceToHost));
   MX_HIP(ctx_sync(c));
   MX_HIP(hipGetLastError());
-  for (int k = 0; k < nl; k++) rows_to_tentatives((const MatchRow *)(hrow + rowOfs[k]), pn1[k], nn, out[live[k]]);
+  for (int k = 0; k < nl; k++) {
+    const int *ddb = db ? (const int *)(hrow + ddbOfs[k]) : nullptr;
+    rows_to_tentatives((const MatchRow *)(hrow + rowOfs[k]), pn1[k], nn, out[live[k]], ddb, sqminratio, d2byDB ? &d2byDB[live[k]] : nullptr);
+    if (db && c->prof.enabled) {
+      long sel = 0;
+      for (int q = 0; q < pn1[k]; q++) sel += ddb[q] != 0x7fffffff;
+      c->prof.work[K_MATCH_DB] += 2.0 * (double)sel * (double)db->rows * 128;
+    }
+  }
   return MODSX_OK;
 }
 
 int match_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2Host,
-                 double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out) {
-  return match_device_batch(c, 1, &d1, &n1, &d2, &n2, &pos2Host, ratioT, contradDist, nn, &out, nullptr);
+                 double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db, std::vector<double> *d2byDB) {
+  return match_device_batch(c, 1, &d1, &n1, &d2, &n2, &pos2Host, ratioT, contradDist, nn, &out, nullptr, nullptr, db, d2byDB);
 }
 
 // The matcher computes on u8: the reference's SIFT-family descriptors hold the integers 0..255
@@ -1709,8 +1754,9 @@ static bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u) {
 }
 
 int match_host_desc(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
-                    double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out) {
+                    double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db, std::vector<double> *d2byDB) {
   out.clear();
+  if (d2byDB) d2byDB->clear();
   if (n1 == 0 || n2 == 0) return MODSX_OK;
   std::vector<uint8_t> u1((size_t)n1 * 128), u2((size_t)n2 * 128);
   if (!desc_f32_to_u8(desc1, u1.size(), u1.data()) || !desc_f32_to_u8(desc2, u2.size(), u2.data())) {
@@ -1721,7 +1767,93 @@ int match_host_desc(modsx_ctx *c, const float *desc1, int n1, const float *desc2
   MX_HIP(hipMemcpyAsync(c->descU8[0].p, u1.data(), u1.size(), hipMemcpyHostToDevice, c->stream));
   MX_HIP(hipMemcpyAsync(c->descU8[1].p, u2.data(), u2.size(), hipMemcpyHostToDevice, c->stream));
   MX_HIP(hipStreamSynchronize(c->stream));
-  return match_device(c, (uint8_t *)c->descU8[0].p, n1, (uint8_t *)c->descU8[1].p, n2, pos2, ratioT, contradDist, nn, out);
+  return match_device(c, (uint8_t *)c->descU8[0].p, n1, (uint8_t *)c->descU8[1].p, n2, pos2, ratioT, contradDist, nn, out, db, d2byDB);
+}
+
+// ---- the descriptor database of MatchFlannFGINNPlusDB (cv::Mat descDB of mods.cpp:207-216) ---------------------------------------
+// rows: n x 128 values, u8 (dtype 0) or f32 holding the integers 0..255 (dtype 1).  The host validates, finds the parity class of
+// every row (c = |b'|^2 + 2 sum b' is odd iff sum b is) and hands k_db_pack the first slot of every 256-row workgroup in each class.
+DbSet *db_create(modsx_ctx *c, const void *rows, long n, int dtype) {
+  if (!rows || n < 1 || (dtype != 0 && dtype != 1)) { set_error("modsx_db_create: bad argument (n >= 1 rows of 128 values, dtype 0 = u8 / 1 = f32)"); return nullptr; }
+  if (n > MODSX_DB_MAX_ROWS) { set_error("modsx_db_create: more than MODSX_DB_MAX_ROWS rows"); return nullptr; }
+  CtxBusy busy(c);
+  std::vector<uint8_t> conv;
+  const uint8_t *u8 = (const uint8_t *)rows;
+  if (dtype == 1) {
+    conv.resize((size_t)n * 128);
+    if (!desc_f32_to_u8((const float *)rows, conv.size(), conv.data())) {
+      set_error("modsx_db_create: descriptors must hold the integers 0..255 (SIFT-family quantisation)");
+      return nullptr;
+    }
+    u8 = conv.data();
+  }
+  const int nblk = db_pack_blocks(n);
+  std::vector<int2> base((size_t)nblk);
+  std::vector<unsigned char> odd((size_t)n);
+  long nOdd = 0;
+  for (long i = 0; i < n; i++) {
+    unsigned sum = 0;
+    for (int k = 0; k < 128; k++) sum += u8[(size_t)i * 128 + k];
+    odd[i] = sum & 1; nOdd += sum & 1;
+  }
+  const DbGeo geo = db_geo(n, nOdd);
+  int e = 0, o = geo.TEp * 32;
+  for (int b = 0; b < nblk; b++) {
+    base[b] = make_int2(e, o);
+    const long hi = std::min(n, (long)(b + 1) * 256);
+    for (long i = (long)b * 256; i < hi; i++) { if (odd[i]) o++; else e++; }
+  }
+  DbSet *db = new DbSet();
+  db->dev = c->dev; db->rows = n; db->geo = geo;
+  const size_t tilesB = db_tiles_bytes(geo), hrowB = db_hrow_bytes(geo);
+  DevBuf raw, dbase;
+  bool ok = db->store.ensure(tilesB + hrowB) && raw.ensure((size_t)n * 128) && dbase.ensure((size_t)nblk * sizeof(int2));
+  if (ok) {
+    db->tiles = (const unsigned char *)db->store.p; db->hrow = (const int *)((char *)db->store.p + tilesB);
+    ok = hipMemcpyAsync(raw.p, u8, (size_t)n * 128, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+         hipMemcpyAsync(dbase.p, base.data(), (size_t)nblk * sizeof(int2), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    if (ok) {
+      launch_db_pack(c->stream, (const uint8_t *)raw.p, n, (const int2 *)dbase.p, nOdd, geo, (unsigned char *)db->store.p, (int *)((char *)db->store.p + tilesB));
+      ok = hipStreamSynchronize(c->stream) == hipSuccess && hipGetLastError() == hipSuccess;
+    }
+    if (!ok) set_error("modsx_db_create: upload or packing failed");
+  }
+  raw.release(); dbase.release();
+  if (!ok) { db->store.release(); delete db; return nullptr; }
+  return db;
+}
+void db_free(DbSet *db) {
+  if (!db) return;
+  db->store.release();
+  delete db;
+}
+// stage tap: squared L2 distance of every query to its nearest database row (every query is "selected")
+int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *dmin) {
+  CtxBusy busy(c);
+  if (db.dev != c->dev) { set_error("modsx_db_nearest: the descriptor database lives on another device"); return MODSX_ERR_ARG; }
+  if (n == 0) return MODSX_OK;
+  std::vector<uint8_t> u((size_t)n * 128);
+  if (!desc_f32_to_u8(desc, u.size(), u.data())) {
+    set_error("modsx_db_nearest: descriptors must hold the integers 0..255 (SIFT-family quantisation)");
+    return MODSX_ERR_ARG;
+  }
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nB = up((size_t)n * 4);
+  if (!c->descU8[0].ensure(u.size()) || !c->dbSel.ensure(256 + nB) || !c->matchRows.ensure(nB)) return MODSX_ERR_NOMEM;
+  MX_HIP(hipMemcpyAsync(c->descU8[0].p, u.data(), u.size(), hipMemcpyHostToDevice, c->stream));
+  const uint8_t *d1 = (const uint8_t *)c->descU8[0].p;
+  int *sel = (int *)((char *)c->dbSel.p + 256), *cnt = (int *)c->dbSel.p, *dd = (int *)c->matchRows.p;
+  launch_db_select(c->stream, 1, nullptr, &n, 2, true, &sel, cnt, &dd);
+  {
+    ProfScope ps(c, K_MATCH_DB, 2.0 * n * (double)db.rows * 128);
+    launch_dbnn_min(c->stream, 1, &d1, &n, &sel, cnt, &dd, db);
+  }
+  std::vector<int> h((size_t)n);
+  MX_HIP(hipMemcpyAsync(h.data(), dd, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));
+  MX_HIP(hipGetLastError());
+  for (int i = 0; i < n; i++) dmin[i] = (float)h[i];
+  return MODSX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1871,7 +2003,7 @@ int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_
     for (int g0 = 0; g0 < G; g0 += MATCH_MAXB) {
       const int nbm = std::min(MATCH_MAXB, G - g0);
       rc = match_device_batch(c, nbm, pd1 + g0, pn1 + g0, pd2 + g0, pn2 + g0, ppos + g0, ds.ratio[k], pp.contradDist, pp.nn,
-                              part + g0, nullptr);
+                              part + g0, nullptr, nullptr, fginn_db_for(c, ds.type[k]));
       if (rc) return rc;
     }
     for (int g = 0; g < G; g++) {

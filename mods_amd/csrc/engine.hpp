@@ -278,6 +278,27 @@ constexpr int MATCH_MAXB = 4;   // independent matching problems per launch set 
 void launch_match_batch(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                         const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
                         void *const *workspace, hipEvent_t *evSweep1 = nullptr);   // evSweep1: two events recorded around sweep 1
+// A descriptor database resident in HBM (kernels_dbnn.hip): the rows packed once into the matcher's operand form.  Read-only
+// after creation, so every context of its device may use it at the same time.
+struct DbGeo { int TEp, TOp; };     // tiles of the even / odd parity class (multiples of 4)
+struct DbSet {
+  DevBuf store;                     // tiles, then the row constants
+  const unsigned char *tiles = nullptr;
+  const int *hrow = nullptr;
+  DbGeo geo = {0, 0};
+  long rows = 0;
+  int dev = 0;
+};
+DbGeo db_geo(long n, long nOdd);
+size_t db_tiles_bytes(const DbGeo &g);
+size_t db_hrow_bytes(const DbGeo &g);
+int db_pack_blocks(long n);         // workgroups of k_db_pack (256 rows each): the host hands it one pair of slot bases per workgroup
+void launch_db_pack(hipStream_t s, const uint8_t *raw, long n, const int2 *base, long nOdd, const DbGeo &geo, unsigned char *tiles,
+                    int *hrow);
+void launch_db_select(hipStream_t s, int nb, const MatchRow *const *rows, const int *n1, int nn, bool allPoints, int *const *sel, int *cnt,
+                      int *const *dmin);
+void launch_dbnn_min(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, int *const *sel, int *cnt, int *const *dmin,
+                     const DbSet &db);
 
 }  // namespace mx
 
@@ -291,7 +312,7 @@ int dup_count(int cls);
 #define MX_DUP(cls)
 #endif
 enum KClass { K_BLUR_HESS = 0, K_HESSIAN, K_RESIZE, K_NMS, K_BAUMBERG, K_ORIENT, K_PATCH_SAMPLE, K_BLUR_ROWS, K_DESCRIBE,
-              K_MATCH, K_GRAY, K_WARP, K_VIEW_BLUR, K_BLUR_COLS, K_MATCH_SWEEP1, K_NCLASS };
+              K_MATCH, K_GRAY, K_WARP, K_VIEW_BLUR, K_BLUR_COLS, K_MATCH_SWEEP1, K_MATCH_DB, K_NCLASS };
 struct Profiler {
   bool enabled = false;
   std::vector<hipEvent_t> evA, evB;
@@ -302,6 +323,8 @@ struct Profiler {
   long launches[K_NCLASS] = {0};
 };
 }  // namespace mx
+
+struct modsx_db { mx::DbSet set; };
 
 struct modsx_image {
   float *d;
@@ -316,7 +339,7 @@ struct modsx_ctx {
   mx::DevBuf candSort, candOut;   // device-side detection order: keys / indices / hash table / temp storage, and the ordered survivors
   size_t lastSurvivors = 0;
   mx::DevBuf nmsJobs, cand, counter, affJobs, affOut, oriJobs, oriOut, descJobs, tilePrefix, taps, imgRefs, scratchA, scratchB,
-      descF[mx::MAXB], descU8[mx::MAXB], descAllF[2], descAllU8[2], descAllU8b[2], descCls[2][4][2], descU8x[3][mx::MAXB], shardLocal, pos2, matchRows, matchWork, misc, viewTmp[2], viewTaps, viewJobs, viewImg[mx::MAXB], scratchC, needTab, coordTab, tileJob, blurTiles, nmsQueue, rowStarts;
+      descF[mx::MAXB], descU8[mx::MAXB], descAllF[2], descAllU8[2], descAllU8b[2], descCls[2][4][2], descU8x[3][mx::MAXB], shardLocal, pos2, matchRows, matchWork, dbSel, misc, viewTmp[2], viewTaps, viewJobs, viewImg[mx::MAXB], scratchC, needTab, coordTab, tileJob, blurTiles, nmsQueue, rowStarts;
   mx::ImgRef imgRefsHost[mx::MAXB];   // what imgRefs holds on the device
   mx::PinBuf hDescB;           // second staging blob of describe_batch: chunk k + 1 is prepared while chunk k runs
   hipEvent_t descEv[2];
@@ -345,6 +368,7 @@ struct modsx_ctx {
   double timings[6];
   mx::Profiler prof;
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
+  const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

@@ -86,7 +86,8 @@ int detect_describe_items_sharded(modsx_ctx *c, modsx_comm *cm, const modsx_imag
                                   DevBuf *const *descAcc, const size_t *base, int *itemCounts, const unsigned char *wantImg = nullptr,
                                   std::vector<size_t> *regStart = nullptr, double **devPos = nullptr, std::vector<double> *kpRows = nullptr,
                                   const int *ownerImg = nullptr);   // ownerImg[j]: the one rank that reads image j's rows (owner-only exchange)
-void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_tentative> &o);
+void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_tentative> &o, const int *ddb = nullptr,
+                        double sqminratio = 0, std::vector<double> *d2byDB = nullptr);
 int comm_rank(const modsx_comm *cm);
 int comm_world(const modsx_comm *cm);
 int comm_same_value(modsx_ctx *c, modsx_comm *cm, int value, const char *what);   // one 4-byte all-gather; an error on every rank when they differ
@@ -94,11 +95,19 @@ int match_sharded(modsx_ctx *c, modsx_comm *cm, const uint8_t *d1, int n1, const
                   double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out);
 int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                        const double *const *pos2Host, double ratioT, double contradDist, int nn,
-                       std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev = nullptr);
+                       std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev = nullptr,
+                       const DbSet *db = nullptr, std::vector<double> *d2byDB = nullptr);   // db: MatchFlannFGINNPlusDB; d2byDB[i] aligned with out[i]
 int match_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2Host,
-                 double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out);
+                 double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db = nullptr,
+                 std::vector<double> *d2byDB = nullptr);
 int match_host_desc(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
-                    double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out);
+                    double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db = nullptr,
+                    std::vector<double> *d2byDB = nullptr);
+DbSet *db_create(modsx_ctx *c, const void *rows, long n, int dtype);
+void db_free(DbSet *db);
+int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *dmin);
+// MatchImgReps (correspondencebank.cpp:333-341): with useDBforFGINN the RootSIFT classes, and no other, are matched against the database
+inline const DbSet *fginn_db_for(const modsx_ctx *c, int descType) { return descType == MODSX_DESC_ROOT_SIFT ? c->fginnDb : nullptr; }
 // The region list a tentative's indices refer to: the per-class lists of one image in the order GetCorresponcesVector walks
 // the classes (descriptor name, then detector name), as segments -- two descriptor classes of one detector share their
 // regions, so the concatenation is never materialised.

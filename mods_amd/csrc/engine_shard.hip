@@ -1531,9 +1531,18 @@ int modsx_view_block_order(const int *counts, int world, int nviews, int *src, i
   return n;
 }
 
+// Sharded calls take no descriptor database yet (sharding it over the ranks is a later change): refused at entry, before any
+// collective, so the attachment must be alike -- none -- on all ranks or the others wait for a rank that has left.
+static bool shard_refuses_db(const modsx_ctx *ctx, const char *fn) {
+  if (!ctx->fginnDb) return false;
+  mx::set_error(std::string(fn) + ": the context has a descriptor database attached (modsx_set_fginn_db); sharded calls do not take one");
+  return true;
+}
+
 int modsx_detect_describe_views_sharded(modsx_ctx *ctx, modsx_comm *comm, const modsx_image *img, const modsx_view *views, int nviews,
                                         const modsx_pair_params *par, modsx_region **regs, void **dev_desc_u8, int *view_counts) {
   if (!ctx || !comm || !img || !views || !par || !regs || nviews <= 0) { mx::set_error("modsx_detect_describe_views_sharded: bad argument"); return MODSX_ERR_ARG; }
+  if (shard_refuses_db(ctx, "modsx_detect_describe_views_sharded")) return MODSX_ERR_ARG;
   hipSetDevice(ctx->dev);
   std::vector<modsx_region> r;
   // the first descriptor class of par's list is the one returned (the orientation mode follows the whole list)
@@ -1562,6 +1571,7 @@ int modsx_match_fginn_sharded(modsx_ctx *ctx, modsx_comm *comm, const void *dev_
     mx::set_error("modsx_match_fginn_sharded: bad argument");
     return MODSX_ERR_ARG;
   }
+  if (shard_refuses_db(ctx, "modsx_match_fginn_sharded")) return MODSX_ERR_ARG;
   hipSetDevice(ctx->dev);
   std::vector<modsx_tentative> t;
   int rc = match_sharded(ctx, comm, (const uint8_t *)dev_desc1_u8, n1, (const uint8_t *)dev_desc2_u8, n2, pos2, ratio, contradDist, nn, t);
@@ -1575,6 +1585,7 @@ int modsx_match_fginn_sharded(modsx_ctx *ctx, modsx_comm *comm, const void *dev_
 int modsx_match_pair_views_sharded(modsx_ctx *ctx, modsx_comm *comm, const modsx_image *img1, const modsx_image *img2,
                                    const modsx_view *views, int nviews, const modsx_pair_params *par, int owner, modsx_pair_result *res) {
   if (!ctx || !comm || !img1 || !img2 || !views || !par || !res || nviews <= 0) { mx::set_error("modsx_match_pair_views_sharded: bad argument"); return MODSX_ERR_ARG; }
+  if (shard_refuses_db(ctx, "modsx_match_pair_views_sharded")) return MODSX_ERR_ARG;
   hipSetDevice(ctx->dev);
   return match_pair_views_sharded(ctx, comm, img1, img2, views, nviews, *par, owner, res);
 }
@@ -1587,6 +1598,7 @@ int modsx_match_pairs_views_sharded(modsx_ctx *ctx, modsx_comm *comm, const mods
     return MODSX_ERR_ARG;
   }
   for (int g = 0; g < n_pairs; g++) if (!imgs1[g] || !imgs2[g]) { mx::set_error("modsx_match_pairs_views_sharded: null image"); return MODSX_ERR_ARG; }
+  if (shard_refuses_db(ctx, "modsx_match_pairs_views_sharded")) return MODSX_ERR_ARG;
   hipSetDevice(ctx->dev);
   const int rc = match_pairs_views_sharded(ctx, comm, imgs1, imgs2, n_pairs, views, nviews, *par, owner_base, results);
   if (rc) for (int g = 0; g < n_pairs; g++) modsx_pair_result_release(&results[g]);
@@ -1599,6 +1611,7 @@ int modsx_match_ladder_sharded(modsx_ctx *ctx, modsx_comm *comm, const modsx_ima
   if (!ctx || !comm || !img1 || !img2 || !steps || nsteps < 1 || !par || !res) { mx::set_error("modsx_match_ladder_sharded: bad argument"); return MODSX_ERR_ARG; }
   for (int i = 0; i < nsteps; i++)
     if (!steps[i].views || steps[i].nviews < 1) { mx::set_error("modsx_match_ladder_sharded: a step without views"); return MODSX_ERR_ARG; }
+  if (shard_refuses_db(ctx, "modsx_match_ladder_sharded")) return MODSX_ERR_ARG;
   hipSetDevice(ctx->dev);
   // every rank verifies (owner -1): same tentatives, same seed, same result -- the early exit needs no collective
   return match_ladder(ctx, img1, img2, steps, nsteps, min_matches, *par, res, steps_done, nullptr, comm, -1);

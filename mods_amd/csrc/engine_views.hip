@@ -811,7 +811,7 @@ int match_ladder(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2,
       int rc = cm ? match_sharded(c, cm, (uint8_t *)k.buf[0]->p, (int)k.regs[0].size(), (uint8_t *)k.buf[1]->p, (int)k.regs[1].size(),
                                   pos2.data(), ds.ratio[j], pp.contradDist, pp.nn, k.tents)
                   : match_device(c, (uint8_t *)k.buf[0]->p, (int)k.regs[0].size(), (uint8_t *)k.buf[1]->p, (int)k.regs[1].size(),
-                                 pos2.data(), ds.ratio[j], pp.contradDist, pp.nn, k.tents);
+                                 pos2.data(), ds.ratio[j], pp.contradDist, pp.nn, k.tents, fginn_db_for(c, ds.type[j]));
       if (rc) { release_result_arrays(res); return rc; }
     }
     const double tL2 = tnowL();
