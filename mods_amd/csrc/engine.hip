@@ -1,4 +1,6 @@
-// engine.hip -- host orchestration of the device path (C++ above HIP, below the C ABI).
+// engine.hip -- host orchestration of the device path (C++ above HIP, below the C ABI): context, waits, copies, profiler,
+// then orientation, description, matching and verification.  The detection front end (pyramid, extrema, detection order, affine
+// adaptation) is in engine_detect.hip.
 //
 // Mirrors, stage by stage, what the reference does per synthesised view in
 // ImageRepresentation::SynthDetectDescribeKeypoints (imagerepresentation.cpp:603-2047) and per pair
@@ -13,7 +15,6 @@
 #include <map>
 #include <unordered_set>
 #include <mutex>
-#include <dlfcn.h>
 #include <string>
 #include "engine_api.hpp"
 
@@ -203,46 +204,8 @@ hipError_t ctx_sync(modsx_ctx *c) {
 }
 
 // ---- per-kernel-class GPU timing with HIP events on the launch stream ------------------------------
-struct ProfScope {
-  modsx_ctx *c;
-  bool on;
-  size_t slot = 0;
-  ProfScope(modsx_ctx *c_, int cls, double work) : c(c_), on(c_->prof.enabled) {
-    if (!on) return;
-    Profiler &p = c->prof;
-    if (p.used == p.evA.size()) {
-      hipEvent_t a, b;
-      hipEventCreate(&a); hipEventCreate(&b);
-      p.evA.push_back(a); p.evB.push_back(b); p.cls.push_back(0);
-    }
-    slot = p.used++;
-    p.cls[slot] = cls;
-    p.work[cls] += work;
-    p.launches[cls]++;
-    hipEventRecord(p.evA[slot], c->stream);
-  }
-  ~ProfScope() { if (on) hipEventRecord(c->prof.evB[slot], c->stream); }
-};
-void prof_begin(modsx_ctx *c, int cls, double work, size_t *slot) {
-  *slot = (size_t)-1;
-  Profiler &p = c->prof;
-  if (!p.enabled) return;
-  if (p.used == p.evA.size()) {
-    hipEvent_t a, b;
-    hipEventCreate(&a); hipEventCreate(&b);
-    p.evA.push_back(a); p.evB.push_back(b); p.cls.push_back(0);
-  }
-  *slot = p.used++;
-  p.cls[*slot] = cls;
-  p.work[cls] += work;
-  p.launches[cls]++;
-  hipEventRecord(p.evA[*slot], c->stream);
-}
-void prof_end(modsx_ctx *c, size_t slot) { if (slot != (size_t)-1) hipEventRecord(c->prof.evB[slot], c->stream); }
-// a slot whose two events the caller records itself (around one launch inside a launch helper); false when profiling is off
-bool prof_reserve(modsx_ctx *c, int cls, double work, hipEvent_t *ev2) {
-  Profiler &p = c->prof;
-  if (!p.enabled) return false;
+// the next slot of the profiler, its two events created on first use
+static size_t prof_take_slot(Profiler &p, int cls, double work) {
   if (p.used == p.evA.size()) {
     hipEvent_t a, b;
     hipEventCreate(&a); hipEventCreate(&b);
@@ -252,7 +215,20 @@ bool prof_reserve(modsx_ctx *c, int cls, double work, hipEvent_t *ev2) {
   p.cls[slot] = cls;
   p.work[cls] += work;
   p.launches[cls]++;
-  ev2[0] = p.evA[slot]; ev2[1] = p.evB[slot];
+  return slot;
+}
+void prof_begin(modsx_ctx *c, int cls, double work, size_t *slot) {
+  *slot = (size_t)-1;
+  if (!c->prof.enabled) return;
+  *slot = prof_take_slot(c->prof, cls, work);
+  hipEventRecord(c->prof.evA[*slot], c->stream);
+}
+void prof_end(modsx_ctx *c, size_t slot) { if (slot != (size_t)-1) hipEventRecord(c->prof.evB[slot], c->stream); }
+// a slot whose two events the caller records itself (around one launch inside a launch helper); false when profiling is off
+bool prof_reserve(modsx_ctx *c, int cls, double work, hipEvent_t *ev2) {
+  if (!c->prof.enabled) return false;
+  const size_t slot = prof_take_slot(c->prof, cls, work);
+  ev2[0] = c->prof.evA[slot]; ev2[1] = c->prof.evB[slot];
   return true;
 }
 void prof_collect(modsx_ctx *c) {
@@ -269,17 +245,6 @@ void prof_reset(modsx_ctx *c, bool enable) {
   Profiler &p = c->prof;
   p.enabled = enable; p.used = 0;
   for (int i = 0; i < K_NCLASS; i++) { p.ms[i] = 0; p.work[i] = 0; p.launches[i] = 0; }
-}
-
-// MODSX_HOST_TIMING=2: wall time of the host phases between the launches of a set (stderr)
-struct HostMark {
-  bool on; double t;
-  HostMark() : on(getenv("MODSX_HOST_TIMING") && atoi(getenv("MODSX_HOST_TIMING")) >= 2), t(0) { if (on) t = now(); }
-  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-  void mark(const char *what) { if (!on) return; const double n = now(); fprintf(stderr, "  host %-28s %.3f ms\n", what, n - t); t = n; }
-};
-static double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,626 +408,6 @@ void ctx_destroy(modsx_ctx *c) {
   hipStreamDestroy(c->stream);
   if (c->hFlag) hipHostFree(c->hFlag);
   delete c;
-}
-
-// ------------------------------------------------------------------------------------------------
-// pyramid
-// ------------------------------------------------------------------------------------------------
-static int cv_round(double v) { return (int)lrint(v); }  // cvRound: round half to even
-
-struct SigmaPlan {
-  int levels;
-  float sigmaStep;
-  float curSigma[8];   // sigma of level i (pyramid.cpp:458-459, 532)
-  float incSigma[8];   // blur applied to level i-1 to get level i (:483)
-};
-
-static SigmaPlan make_sigma_plan(const modsx_hessaff_params &p) {
-  SigmaPlan s;
-  s.levels = p.numberOfScales + 2;
-  s.sigmaStep = powf(2.0f, 1.0f / (float)p.numberOfScales);
-  float cur = p.initialSigma;
-  s.curSigma[0] = cur; s.incSigma[0] = 0;
-  for (int i = 1; i < s.levels; i++) {
-    s.incSigma[i] = cur * sqrtf(s.sigmaStep * s.sigmaStep - 1.0f);
-    cur *= s.sigmaStep;
-    s.curSigma[i] = cur;
-  }
-  return s;
-}
-
-static int fill_taps(BlurBatch &b, float sigma) {
-  int n = blur_ksize(sigma);
-  if (n > MAX_TAPS) { set_error("pyramid blur kernel larger than 17 taps is not supported"); return MODSX_ERR_ARG; }
-  std::vector<float> k = gaussian_kernel(n, sigma);
-  b.n = n;
-  for (int i = 0; i < n; i++) b.k[i] = k[i];
-  return MODSX_OK;
-}
-
-// ScaleSpaceDetector::detectPyramidKeypoints / detectOctaveKeypoints (pyramid.cpp:455-573) for a batch
-// of images: builds every blur and response level in HBM.  firstLevelGiven: the image IS the first level
-// of a single octave (stage tap used by modsx_octave_levels).
-int build_pyramids(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &p,
-                   bool singleOctaveFromFirstLevel) {
-  if (n <= 0 || n > MAXB) { set_error("batch size"); return MODSX_ERR_ARG; }
-  if (p.numberOfScales < 1 || p.numberOfScales > 6) { set_error("numberOfScales"); return MODSX_ERR_ARG; }
-  if (p.detectorType != MODSX_DET_HESSIAN && p.detectorType != MODSX_DET_DOG && p.detectorType != MODSX_DET_HARRIS) {
-    set_error("detectorType must be Hessian (0), DoG (1) or Harris (2)");
-    return MODSX_ERR_ARG;
-  }
-  const bool hess = p.detectorType == MODSX_DET_HESSIAN;    // its response is fused into the blur / resize kernels; the others follow below
-  const SigmaPlan sp = make_sigma_plan(p);
-  const int L = sp.levels;
-  const int minSize = 2 * p.border + 2;
-  int maxOct = 0;
-  for (int i = 0; i < n; i++) {
-    Pyramid &py = c->pyr[i];
-    py.nOct = 0;
-    int rows = imgs[i]->rows, cols = imgs[i]->cols;
-    float pd = 1.0f;
-    size_t total = 0;
-    while (rows > minSize && cols > minSize && py.nOct < 24) {
-      Octave &o = py.oct[py.nOct++];
-      o.rows = rows; o.cols = cols; o.pixelDistance = pd;
-      total += (size_t)2 * L * rows * cols;
-      pd *= 2.0;
-      rows = cv_round(rows * 0.5); cols = cv_round(cols * 0.5);
-      if (singleOctaveFromFirstLevel) break;
-    }
-    if (!py.store.ensure(total * sizeof(float) + 64)) return MODSX_ERR_NOMEM;
-    float *ptr = (float *)py.store.p;
-    for (int o = 0; o < py.nOct; o++) {
-      size_t npx = (size_t)py.oct[o].rows * py.oct[o].cols;
-      for (int l = 0; l < L; l++) { py.oct[o].blur[l] = ptr; ptr += npx; }
-      for (int l = 0; l < L; l++) { py.oct[o].resp[l] = ptr; ptr += npx; }
-    }
-    maxOct = std::max(maxOct, py.nOct);
-  }
-  hipStream_t s = c->stream;
-  for (int o = 0; o < maxOct; o++) {
-    // first level of the octave
-    BlurBatch bb;
-    memset(&bb, 0, sizeof bb);
-    int nj = 0, mr = 0, mc = 0;
-    if (o == 0) {
-      const float curSigma0 = 0.5f;
-      const bool preBlur = !singleOctaveFromFirstLevel && p.initialSigma > curSigma0;
-      if (preBlur) {
-        float sigma = sqrtf(p.initialSigma * p.initialSigma - curSigma0 * curSigma0);
-        int rc = fill_taps(bb, sigma);
-        if (rc) return rc;
-      }
-      for (int i = 0; i < n; i++) {
-        if (c->pyr[i].nOct <= 0) continue;
-        Octave &oc = c->pyr[i].oct[0];
-        BlurJob &j = bb.j[nj++];
-        j.src = imgs[i]->d; j.blur = oc.blur[0]; j.resp = hess ? oc.resp[0] : nullptr; j.rows = oc.rows; j.cols = oc.cols;
-        j.norm = sp.curSigma[0] * sp.curSigma[0];
-        mr = std::max(mr, oc.rows); mc = std::max(mc, oc.cols);
-        if (!preBlur) {
-          MX_HIP(hipMemcpyAsync(oc.blur[0], imgs[i]->d, (size_t)oc.rows * oc.cols * 4, hipMemcpyDeviceToDevice, s));
-          j.src = oc.blur[0];
-        }
-      }
-      double px = 0;
-      for (int q = 0; q < nj; q++) px += (double)bb.j[q].rows * bb.j[q].cols;
-      if (nj) {
-        if (preBlur) { ProfScope ps(c, K_BLUR_HESS, px * 12); launch_blur_hess(s, bb, nj, mr, mc); }
-        else if (hess) { ProfScope ps(c, K_HESSIAN, px * 8); launch_hessian(s, bb, nj, mr, mc); }
-      }
-    } else {
-      ResizeBatch rb;
-      memset(&rb, 0, sizeof rb);
-      for (int i = 0; i < n; i++) {
-        if (c->pyr[i].nOct <= o) continue;
-        Octave &pv = c->pyr[i].oct[o - 1], &oc = c->pyr[i].oct[o];
-        ResizeJob &r = rb.j[nj];
-        r.src = pv.blur[p.numberOfScales]; r.dst = oc.blur[0];
-        r.srows = pv.rows; r.scols = pv.cols; r.drows = oc.rows; r.dcols = oc.cols;
-        r.resp = hess ? oc.resp[0] : nullptr; r.norm = sp.curSigma[0] * sp.curSigma[0];   // resize + Hessian of the new level in one launch
-        BlurJob &j = bb.j[nj++];
-        j.src = oc.blur[0]; j.blur = nullptr; j.resp = oc.resp[0]; j.rows = oc.rows; j.cols = oc.cols;
-        j.norm = sp.curSigma[0] * sp.curSigma[0];
-        mr = std::max(mr, oc.rows); mc = std::max(mc, oc.cols);
-      }
-      if (nj) {
-        double spx = 0, dpx = 0;
-        for (int q = 0; q < nj; q++) { spx += (double)rb.j[q].srows * rb.j[q].scols; dpx += (double)rb.j[q].drows * rb.j[q].dcols; }
-        { ProfScope ps(c, K_RESIZE, (spx + dpx) * 4 + dpx * 4); launch_resize_half(s, rb, nj, mr, mc); }
-      }
-    }
-    if (!nj) continue;
-    for (int l = 1; l < L; l++) {
-      BlurBatch b2;
-      memset(&b2, 0, sizeof b2);
-      int rc = fill_taps(b2, sp.incSigma[l]);
-      if (rc) return rc;
-      int k = 0;
-      for (int i = 0; i < n; i++) {
-        if (c->pyr[i].nOct <= o) continue;
-        Octave &oc = c->pyr[i].oct[o];
-        BlurJob &j = b2.j[k++];
-        j.src = oc.blur[l - 1]; j.blur = oc.blur[l]; j.resp = hess ? oc.resp[l] : nullptr; j.rows = oc.rows; j.cols = oc.cols;
-        j.norm = sp.curSigma[l] * sp.curSigma[l];
-      }
-      double px = 0;
-      for (int q = 0; q < k; q++) px += (double)b2.j[q].rows * b2.j[q].cols;
-      ProfScope ps(c, K_BLUR_HESS, px * 12);
-      launch_blur_hess(s, b2, k, mr, mc);
-    }
-    if (!hess) {
-      // DoG / Harris (ScaleSpaceDetector::dogResponse :176-181, HarrisResponse :283-305; norm = sigma^2 of the level, :475,490):
-      // the response of every level from its blur, with the generic any-sigma filter passes (the DoG of a level is the level minus
-      // its blur with sigma = norm; Harris blurs three gradient products with sqrt(0.6 norm)) -- separate launches per image and
-      // level: these detectors are on no shipped configuration's path, the Hessian's fused kernels are untouched
-      for (int l = 0; l < L; l++) {
-        const float norm = sp.curSigma[l] * sp.curSigma[l];
-        const float sigma = p.detectorType == MODSX_DET_DOG ? norm : sqrtf((float)(0.6 * norm));
-        const int nt = blur_ksize(sigma);
-        if (2 * nt > 2 * 4096) { set_error("response blur kernel too large"); return MODSX_ERR_ARG; }
-        if (!c->viewTaps.ensure((size_t)L * 2 * 4100 * 4) || !c->hViewTaps.ensure((size_t)L * 2 * 4100 * 4)) return MODSX_ERR_NOMEM;
-        // one slice of the staging buffers per level, so that no upload overwrites taps a queued launch still reads
-        float *dT = (float *)c->viewTaps.p + (size_t)l * 2 * 4100, *hT = (float *)c->hViewTaps.p + (size_t)l * 2 * 4100;
-        bool tapsUp = false;
-        for (int i = 0; i < n; i++) {
-          if (c->pyr[i].nOct <= o) continue;
-          Octave &oc = c->pyr[i].oct[o];
-          const int rows = oc.rows, cols = oc.cols;
-          const size_t npx = (size_t)rows * cols;
-          if (!c->scratchA.ensure(npx * 4 * 8)) return MODSX_ERR_NOMEM;
-          float *buf = (float *)c->scratchA.p, *tmp = buf, *a = buf + npx, *b = buf + 2 * npx, *cc = buf + 3 * npx;
-          float *ba = buf + 4 * npx, *bb2 = buf + 5 * npx, *bc = buf + 6 * npx;
-          const int nx = cols == 1 ? 1 : nt, ny = rows == 1 ? 1 : nt;
-          if (!tapsUp || nx != nt || ny != nt) {
-            std::vector<float> kx = gaussian_kernel(nx, sigma), ky = gaussian_kernel(ny, sigma);
-            if (tapsUp) MX_HIP(ctx_sync(c));      // a degenerate (one-row / one-column) level re-uses the slice
-            memcpy(hT, kx.data(), nx * 4); memcpy(hT + nx, ky.data(), ny * 4);
-            MX_HIP(ctx_copy(c, dT, hT, (size_t)(nx + ny) * 4, hipMemcpyHostToDevice));
-            tapsUp = nx == nt && ny == nt;
-          }
-          auto blur = [&](const float *src, float *dst) {
-            if (nt == 1) { MX_HIP(hipMemcpyAsync(dst, src, npx * 4, hipMemcpyDeviceToDevice, s)); return MODSX_OK; }
-            launch_blur_pass(s, src, tmp, rows, cols, dT, nx, 0, 1);
-            launch_blur_pass(s, tmp, dst, rows, cols, dT + nx, ny, 1, 1);
-            return MODSX_OK;
-          };
-          if (p.detectorType == MODSX_DET_DOG) {
-            int rc = blur(oc.blur[l], a);
-            if (rc) return rc;
-            launch_sub(s, oc.blur[l], a, oc.resp[l], npx);
-          } else {
-            launch_grad_products(s, oc.blur[l], rows, cols, a, b, cc);
-            int rc = blur(a, ba);
-            if (!rc) rc = blur(b, bb2);
-            if (!rc) rc = blur(cc, bc);
-            if (rc) return rc;
-            launch_harris_combine(s, ba, bb2, bc, (float)(0.6 * norm), oc.resp[l], npx);
-          }
-        }
-      }
-    }
-  }
-  MX_HIP(hipGetLastError());
-  return MODSX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// detection: extrema + localisation on device, detection order + octaveMap + scale on host
-// ------------------------------------------------------------------------------------------------
-static const unsigned CAND_CAP = 1u << 21;
-
-int detect_scalespace_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &p,
-                            std::vector<modsx_sskp> *out) {
-  int rc = build_pyramids(c, imgs, n, p, false);
-  if (rc) return rc;
-  hipStream_t s = c->stream;
-  if (!c->cand.ensure((size_t)CAND_CAP * sizeof(Candidate)) || !c->nmsQueue.ensure((size_t)CAND_CAP * 16)) return MODSX_ERR_NOMEM;
-  if (!c->counter.ensure((NMS_QUEUES + 1) * 128)) return MODSX_ERR_NOMEM;
-  // [0] accepted candidates, [1] extremum-queue overflow flag, from word 32 on the sub-queue counters: one fill for the lot
-  MX_HIP(hipMemsetAsync(c->counter.p, 0, 128 + NMS_QUEUES * 128, s));
-  bool queuesClean = true;   // the sub-queue counters are zero (no scan has run since the fill)
-  // thresholds, affinedetectors/pyramid.h:47-67 (DET_HESSIAN)
-  NmsBatch nb;
-  memset(&nb, 0, sizeof nb);
-  nb.edgeScoreThreshold = (p.edgeEigenValueRatio + 1.0f) * (p.edgeEigenValueRatio + 1.0f) / p.edgeEigenValueRatio;
-  float finalTh = p.threshold;
-  float posTh = (float)(0.8 * finalTh);
-  float negTh = -posTh;
-  if (p.detectorType == MODSX_DET_HESSIAN) finalTh = p.threshold * p.threshold;     // pyramid.h:56-57: squared for DET_HESSIAN only
-  if (p.mode != MODSX_FIXED_TH) finalTh = posTh = negTh = 0.0f;
-  nb.posTh = posTh; nb.negTh = negTh; nb.finalTh = finalTh; nb.border = p.border; nb.detType = p.detectorType;
-  int maxOct = 0;
-  for (int i = 0; i < n; i++) maxOct = std::max(maxOct, c->pyr[i].nOct);
-  // all (image, octave, level) scans of the batch in one launch (NMS_MAXJ jobs at most per launch).  With the shipped
-  // numberOfScales = 3 the tiles number OCTAVES and a tile scans the three levels of its octave in one pass over the five
-  // response planes (k_nms_localize_oct); otherwise a tile belongs to one level
-  const bool perOctave = p.numberOfScales == 3 && !getenv("MODSX_NMS_PER_LEVEL");
-  std::vector<NmsJob> hjobs;
-  std::vector<int> hpfx(1, 0), hfirst;
-  double px = 0;
-  auto flush = [&](bool last) -> int {
-    const int nj = (int)hjobs.size();
-    if (!nj) return MODSX_OK;
-    const int np = (int)hpfx.size() - 1;     // tile groups: octaves or levels
-    const size_t jobBytes = (size_t)nj * sizeof(NmsJob), pfxBytes = (size_t)(np + 1) * 4, firstBytes = (size_t)std::max<size_t>(1, hfirst.size()) * 4;
-    if (!c->nmsJobs.ensure(jobBytes + pfxBytes + firstBytes + 64)) return MODSX_ERR_NOMEM;
-    if (!c->hNms.ensure(jobBytes + pfxBytes + firstBytes)) return MODSX_ERR_NOMEM;   // jobs + prefix (+ first level job of every octave): one pinned blob, one copy
-    memcpy(c->hNms.p, hjobs.data(), jobBytes);
-    memcpy((char *)c->hNms.p + jobBytes, hpfx.data(), pfxBytes);
-    if (!hfirst.empty()) memcpy((char *)c->hNms.p + jobBytes + pfxBytes, hfirst.data(), hfirst.size() * 4);
-    MX_HIP(ctx_copy(c, c->nmsJobs.p, c->hNms.p, jobBytes + pfxBytes + firstBytes, hipMemcpyHostToDevice));
-    if (!c->tileJob.ensure((size_t)hpfx.back() * 4 + 4)) return MODSX_ERR_NOMEM;
-    const int *dPfx = (const int *)((char *)c->nmsJobs.p + jobBytes);
-    launch_expand_tiles(s, dPfx, np, (int *)c->tileJob.p);
-    {
-      ProfScope ps(c, K_NMS, px * 12);
-      if (!queuesClean) MX_HIP(hipMemsetAsync((unsigned *)c->counter.p + 32, 0, NMS_QUEUES * 128, s));
-      queuesClean = false;
-      launch_nms(s, nb, (const NmsJob *)c->nmsJobs.p, dPfx, (const int *)c->tileJob.p, nj,
-                 hpfx.back(), (int4 *)c->nmsQueue.p, (unsigned *)c->counter.p + 32, CAND_CAP, (Candidate *)c->cand.p,
-                 (unsigned *)c->counter.p, CAND_CAP, perOctave ? (const int *)((char *)c->nmsJobs.p + jobBytes + pfxBytes) : nullptr,
-                 p.numberOfScales);
-    }
-    // the host tables are reused by the next flush; after the last one the counter read-back below waits for the launch
-    if (!last) MX_HIP(ctx_sync(c));
-    hjobs.clear(); hpfx.assign(1, 0); hfirst.clear(); px = 0;
-    return MODSX_OK;
-  };
-  for (int o = 0; o < maxOct; o++)
-    for (int i = 0; i < n; i++) {
-      if (c->pyr[i].nOct <= o) continue;
-      Octave &oc = c->pyr[i].oct[o];
-      const int w = oc.cols - 2 * p.border, h = oc.rows - 2 * p.border;
-      if (w <= 0 || h <= 0) continue;
-      if ((int)hjobs.size() + p.numberOfScales > NMS_MAXJ) { int rcf = flush(false); if (rcf) return rcf; }
-      const int tiles = ((w + 63) / 64) * ((h + NMS_TILE_ROWS - 1) / NMS_TILE_ROWS);
-      if (perOctave) { hfirst.push_back((int)hjobs.size()); hpfx.push_back(hpfx.back() + tiles); }
-      for (int l = 1; l <= p.numberOfScales; l++) {
-        NmsJob j;
-        j.low = oc.resp[l - 1]; j.cur = oc.resp[l]; j.high = oc.resp[l + 1]; j.blur = oc.blur[l];
-        j.rows = oc.rows; j.cols = oc.cols; j.img = i; j.octave = o; j.level = l; j.pad = 0;
-        hjobs.push_back(j);
-        if (!perOctave) hpfx.push_back(hpfx.back() + tiles);
-        px += (double)oc.rows * oc.cols;
-      }
-    }
-  { int rcf = flush(true); if (rcf) return rcf; }
-  // MODSX_DEVICE_ORDER=1: detection order and the octaveMap claim on the device (kernels_cand.hip) -- the host receives the
-  // SURVIVING candidates in the reference's visiting order and only forms the scale (glibc powf) and the keypoint records.
-  // Built and bit-exact (tests/test_gpu_parity.py), but NOT the default: measured in round 4 it costs the 31-view bench 9 %
-  // (167 against 183.5 pairs/s) and a lone pair 0.5 ms (13.05 against 12.55 ms) -- key build, radix sort, two table fills, claim
-  // and compaction are six more small launches on every launch set's stream, while the host's radix sort + hash claim run on
-  // host cores that are otherwise idle and overlap the other contexts' device work.
-  static const bool deviceOrder = getenv("MODSX_DEVICE_ORDER") != nullptr && atoi(getenv("MODSX_DEVICE_ORDER")) != 0;
-  if (deviceOrder) {
-    // the opt-in path lives in libmodsx_cand.so beside this library (kernels_cand.hip), loaded on first use
-    typedef size_t (*temp_fn)(unsigned);
-    typedef int (*order_fn)(hipStream_t, const Candidate *, const unsigned *, unsigned, unsigned long long *, unsigned long long *, unsigned *, unsigned *,
-                            void *, size_t, unsigned long long *, unsigned *, unsigned, unsigned *, Candidate *, unsigned *);
-    static temp_fn cand_sort_temp_bytes = nullptr;
-    static order_fn launch_cand_order = nullptr;
-    static std::once_flag candOnce;
-    std::call_once(candOnce, [] {
-      Dl_info di;
-      std::string path = "libmodsx_cand.so";
-      if (dladdr((const void *)&modsx_create, &di) && di.dli_fname) {
-        const std::string self(di.dli_fname);
-        const size_t sl = self.rfind('/');
-        if (sl != std::string::npos) path = self.substr(0, sl + 1) + "libmodsx_cand.so";
-      }
-      if (void *h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL)) {
-        cand_sort_temp_bytes = (temp_fn)dlsym(h, "modsx_cand_sort_temp_bytes");
-        launch_cand_order = (order_fn)dlsym(h, "modsx_cand_order");
-      }
-    });
-    if (!cand_sort_temp_bytes || !launch_cand_order) {
-      set_error("MODSX_DEVICE_ORDER=1, but libmodsx_cand.so (make -C mods_amd/csrc cand) is not beside libmodsx.so");
-      return MODSX_ERR_DEVICE;
-    }
-    if (!c->hMisc.ensure(64)) return MODSX_ERR_NOMEM;
-    for (int attempt = 0;; attempt++) {
-      // the sort runs over a host-chosen capacity (the device-side count is not known here): what the context's last set had
-      // (+ 1/4); a set that holds more is ordered again with its real count -- one more wait, as for the old download
-      const unsigned nsort = (unsigned)std::min<size_t>(CAND_CAP, attempt ? c->lastCandCount + 64 : c->lastCandCount + c->lastCandCount / 4 + 1024);
-      unsigned tabSize = 1024;
-      while (tabSize < 2 * nsort + 16) tabSize <<= 1;
-      auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-      const size_t tempB = cand_sort_temp_bytes(nsort);
-      const size_t oKeys = 0, oKeys2 = oKeys + up((size_t)nsort * 8), oIdx = oKeys2 + up((size_t)nsort * 8), oIdx2 = oIdx + up((size_t)nsort * 4),
-                   oSlot = oIdx2 + up((size_t)nsort * 4), oTabK = oSlot + up((size_t)nsort * 4), oTabR = oTabK + up((size_t)tabSize * 8),
-                   oTemp = oTabR + up((size_t)tabSize * 4), total = oTemp + up(tempB) + 256;
-      if (!c->candSort.ensure(total) || !c->candOut.ensure((size_t)nsort * sizeof(Candidate) + 64)) return MODSX_ERR_NOMEM;
-      char *w = (char *)c->candSort.p;
-      unsigned *survivors = (unsigned *)c->counter.p + 2;     // word 2 of the counter block (zeroed with it)
-      if (launch_cand_order(s, (const Candidate *)c->cand.p, (const unsigned *)c->counter.p, nsort, (unsigned long long *)(w + oKeys),
-                            (unsigned long long *)(w + oKeys2), (unsigned *)(w + oIdx), (unsigned *)(w + oIdx2), w + oTemp, tempB,
-                            (unsigned long long *)(w + oTabK), (unsigned *)(w + oTabR), tabSize, (unsigned *)(w + oSlot),
-                            (Candidate *)c->candOut.p, survivors)) { set_error("device-side detection order failed"); return MODSX_ERR_DEVICE; }
-      const size_t spec = std::min<size_t>(nsort, c->lastSurvivors + c->lastSurvivors / 4 + 1024);
-      if (!c->hCand.ensure(std::max<size_t>(spec, 1) * sizeof(Candidate))) return MODSX_ERR_NOMEM;
-      MX_HIP(ctx_copy(c, c->hMisc.p, c->counter.p, 12, hipMemcpyDeviceToHost));
-      MX_HIP(ctx_copy(c, c->hCand.p, c->candOut.p, spec * sizeof(Candidate), hipMemcpyDeviceToHost));
-      MX_HIP(ctx_sync(c));
-      const unsigned cnt = ((unsigned *)c->hMisc.p)[0], nsurv = ((unsigned *)c->hMisc.p)[2];
-      if (cnt > CAND_CAP || ((unsigned *)c->hMisc.p)[1]) { set_error("candidate buffer overflow"); return MODSX_ERR_NOMEM; }
-      c->lastCandCount = cnt;
-      if (cnt > nsort) {                       // the capacity was a guess and too small: once more with the count
-        if (attempt) { set_error("device-side detection order: capacity does not converge"); return MODSX_ERR_INTERNAL; }
-        continue;
-      }
-      c->lastSurvivors = nsurv;
-      if (nsurv > spec) {
-        if (!c->hCand.ensure((size_t)nsurv * sizeof(Candidate))) return MODSX_ERR_NOMEM;   // (re-allocation loses the first part: copy all)
-        MX_HIP(ctx_copy(c, c->hCand.p, c->candOut.p, (size_t)nsurv * sizeof(Candidate), hipMemcpyDeviceToHost));
-        MX_HIP(ctx_sync(c));
-      }
-      HostMark hm;
-      const Candidate *cd = (const Candidate *)c->hCand.p;
-      const SigmaPlan sp = make_sigma_plan(p);
-      // image-major, then (octave, level, row, column): one linear pass
-      std::vector<uint32_t> imgStart(n + 1, 0);
-      for (unsigned k = 0; k < nsurv; k++) {
-        if ((unsigned)cd[k].img >= (unsigned)n || (unsigned)cd[k].octave >= 32u) { set_error("candidate outside the image / octave range"); return MODSX_ERR_DEVICE; }
-        imgStart[cd[k].img + 1]++;
-      }
-      for (int i = 0; i < n; i++) imgStart[i + 1] += imgStart[i];
-      host_parallel_light(n, [&](int img) {
-        std::vector<modsx_sskp> &dst = out[img];
-        dst.clear();
-        dst.reserve(imgStart[img + 1] - imgStart[img]);
-        for (uint32_t k = imgStart[img]; k < imgStart[img + 1]; k++) {
-          const Candidate &q = cd[k];
-          const float pixelDistance = c->pyr[q.img].oct[q.octave].pixelDistance;
-          const float curScale = sp.curSigma[q.level];
-          float scale = curScale * powf(2.0f, q.b2 / p.numberOfScales);
-          modsx_sskp kp;
-          kp.octave = q.octave; kp.level = q.level; kp.r0 = q.r0; kp.c0 = q.c0; kp.r = q.r; kp.c = q.c; kp.type = q.type;
-          kp.pad = 0;
-          kp.b0 = q.b0; kp.b1 = q.b1; kp.b2 = q.b2; kp.val = q.val;
-          kp.x = pixelDistance * (q.c + q.b0);
-          kp.y = pixelDistance * (q.r + q.b1);
-          kp.s = pixelDistance * scale;
-          kp.pixelDistance = pixelDistance;
-          dst.push_back(kp);
-        }
-      });
-      hm.mark("sskp from ordered survivors");
-      return MODSX_OK;
-    }
-  }
-  // the count and the candidates come down behind ONE wait: the records are copied speculatively, as many as the context's
-  // last set had (+ 1/4); a set that holds more costs a second copy for the rest
-  if (!c->hMisc.ensure(64)) return MODSX_ERR_NOMEM;
-  const size_t spec = std::min<size_t>(CAND_CAP, c->lastCandCount + c->lastCandCount / 4 + 1024);
-  if (!c->hCand.ensure(spec * sizeof(Candidate))) return MODSX_ERR_NOMEM;
-  MX_HIP(ctx_copy(c, c->hMisc.p, c->counter.p, 8, hipMemcpyDeviceToHost));
-  MX_HIP(ctx_copy(c, c->hCand.p, c->cand.p, spec * sizeof(Candidate), hipMemcpyDeviceToHost));
-  MX_HIP(ctx_sync(c));
-  unsigned cnt = *(unsigned *)c->hMisc.p;
-  if (cnt > CAND_CAP || ((unsigned *)c->hMisc.p)[1]) { set_error("candidate buffer overflow"); return MODSX_ERR_NOMEM; }
-  c->lastCandCount = cnt;
-  if (cnt > spec) {
-    if (!c->hCand.ensure((size_t)cnt * sizeof(Candidate))) return MODSX_ERR_NOMEM;   // (re-allocation loses the first part: copy all)
-    MX_HIP(ctx_copy(c, c->hCand.p, c->cand.p, (size_t)cnt * sizeof(Candidate), hipMemcpyDeviceToHost));
-    MX_HIP(ctx_sync(c));
-  }
-  HostMark hm;
-  const Candidate *cd = (const Candidate *)c->hCand.p;
-  // The reference visits (octave, level, row, col) in this order per image (pyramid.cpp:438-451, 490-498, 564-571) and the
-  // first candidate in that order that lands on a pixel of an octave claims it (octaveMap, :414-418).  Images are
-  // independent: the candidates are bucketed by image once, then every image sorts one 64-bit key per candidate, applies the
-  // claim through a small open-addressing table and builds its keypoints -- one task per image on the host pool.
-  for (unsigned k = 0; k < cnt; k++) {
-    const Candidate &q = cd[k];
-    if ((unsigned)q.img >= (unsigned)n || (unsigned)q.octave >= 32u || (unsigned)q.level >= 32u || (unsigned)q.r0 >= (1u << 14) ||
-        (unsigned)q.c0 >= (1u << 14) || (unsigned)q.r >= (1u << 24) || (unsigned)q.c >= (1u << 24)) {
-      set_error("candidate outside the sort key's range");
-      return MODSX_ERR_DEVICE;
-    }
-  }
-  std::vector<uint32_t> &byImg = c->candOrder;
-  std::vector<uint32_t> imgStart(n + 1, 0);
-  byImg.resize(cnt);
-  for (unsigned k = 0; k < cnt; k++) imgStart[cd[k].img + 1]++;
-  for (int i = 0; i < n; i++) imgStart[i + 1] += imgStart[i];
-  {
-    std::vector<uint32_t> fill(imgStart.begin(), imgStart.end() - 1);
-    for (unsigned k = 0; k < cnt; k++) byImg[fill[cd[k].img]++] = k;
-  }
-  hm.mark("cand bucket by image");
-  const SigmaPlan sp = make_sigma_plan(p);
-  host_parallel_light(n, [&](int img) {
-    std::vector<modsx_sskp> &dst = out[img];
-    dst.clear();
-    const uint32_t *idx = byImg.data() + imgStart[img];
-    const size_t m = imgStart[img + 1] - imgStart[img];
-    if (!m) return;
-    // keys are unique (one candidate per (octave, level, pixel)), so the order is the same whatever sorts them: an LSD radix
-    // sort of (key, index), 11 bits per pass, passes whose digit is the same for every key left out
-    // key and index share ONE 64-bit word (octave 5 | level 5 | row 14 | column 14 | index 21 bits: images are at most 16384 px per side,
-    // a set holds at most 2^21 candidates): half the bytes per pass of the (key, index) pairs sorted until round 6
-    static thread_local std::vector<uint64_t> order, order2;
-    static_assert(CAND_CAP <= (1u << 21), "index field of the packed sort key");
-    order.resize(m); order2.resize(m);
-    for (size_t k = 0; k < m; k++) {
-      const Candidate &q = cd[idx[k]];
-      order[k] = ((uint64_t)q.octave << 54) | ((uint64_t)q.level << 49) | ((uint64_t)(q.r0 & 0x3fff) << 35) | ((uint64_t)(q.c0 & 0x3fff) << 21) | idx[k];
-    }
-    {
-      constexpr int BITS = 11, NB = 1 << BITS;
-      uint32_t hist[NB];
-      for (int shift = 21; shift < 59; shift += BITS) {
-        memset(hist, 0, sizeof hist);
-        for (size_t k = 0; k < m; k++) hist[(order[k] >> shift) & (NB - 1)]++;
-        if (hist[(order[0] >> shift) & (NB - 1)] == m) continue;
-        uint32_t sum = 0;
-        for (int b = 0; b < NB; b++) { const uint32_t h = hist[b]; hist[b] = sum; sum += h; }
-        for (size_t k = 0; k < m; k++) order2[hist[(order[k] >> shift) & (NB - 1)]++] = order[k];
-        order.swap(order2);
-      }
-    }
-    size_t tabSize = 64;
-    while (tabSize < m * 2 + 16) tabSize <<= 1;
-    std::vector<uint64_t> claimed(tabSize, 0);  // key + 1, 0 = empty
-    dst.reserve(m);
-    for (size_t kk = 0; kk < m; kk++) {
-      const Candidate &q = cd[order[kk] & 0x1fffffu];
-      const uint64_t key = (((uint64_t)q.octave << 48) | ((uint64_t)q.r << 24) | (uint64_t)q.c) + 1;
-      size_t h = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 20) & (tabSize - 1);
-      bool taken = false;
-      while (claimed[h]) { if (claimed[h] == key) { taken = true; break; } h = (h + 1) & (tabSize - 1); }
-      if (taken) continue;
-      claimed[h] = key;
-      const float pixelDistance = c->pyr[q.img].oct[q.octave].pixelDistance;
-      const float curScale = sp.curSigma[q.level];
-      float scale = curScale * powf(2.0f, q.b2 / p.numberOfScales);
-      modsx_sskp kp;
-      kp.octave = q.octave; kp.level = q.level; kp.r0 = q.r0; kp.c0 = q.c0; kp.r = q.r; kp.c = q.c; kp.type = q.type;
-      kp.pad = 0;
-      kp.b0 = q.b0; kp.b1 = q.b1; kp.b2 = q.b2; kp.val = q.val;
-      kp.x = pixelDistance * (q.c + q.b0);
-      kp.y = pixelDistance * (q.r + q.b1);
-      kp.s = pixelDistance * scale;
-      kp.pixelDistance = pixelDistance;
-      dst.push_back(kp);
-    }
-  });
-  hm.mark("octaveMap claim + sskp");
-  return MODSX_OK;
-}
-
-static int ensure_smm_mask(modsx_ctx *c, int W) {
-  if (c->smmW == W && c->dSmmMask) return MODSX_OK;
-  if (W < 3 || W > 19 || !(W & 1)) { set_error("smmWindowSize must be odd and <= 19"); return MODSX_ERR_ARG; }
-  if (c->dSmmMask) hipFree(c->dSmmMask);
-  std::vector<float> m(W * W);
-  gauss_mask(m.data(), W);
-  MX_HIP(hipMalloc(&c->dSmmMask, W * W * 4));
-  MX_HIP(hipMemcpy(c->dSmmMask, m.data(), W * W * 4, hipMemcpyHostToDevice));
-  c->smmW = W;
-  return MODSX_OK;
-}
-
-// AffineDetector::prepareKeysForExport, scale-space-detector.hpp:118-198
-static void prepare_keys_for_export(std::vector<modsx_keypoint> &keys, const modsx_hessaff_params &p) {
-  if (keys.empty() || p.mode == MODSX_FIXED_TH) return;
-  auto cmpv = [](modsx_keypoint k1, modsx_keypoint k2) { return fabs(k1.response) > fabs(k2.response); };
-  std::sort(keys.begin(), keys.end(), cmpv);
-  double maxResponse = fabs(keys[0].response);
-  int regNumber = (int)keys.size();
-  auto cmp = [](const modsx_keypoint &k1, const modsx_keypoint &k2) { return fabs(k1.response) > fabs(k2.response); };
-  switch (p.mode) {
-    case MODSX_RELATIVE_TH: {
-      modsx_keypoint t = keys[0];
-      t.response = (float)(maxResponse * p.rel_threshold);
-      keys.resize(std::lower_bound(keys.begin(), keys.end(), t, cmp) - keys.begin());
-      break;
-    }
-    case MODSX_FIXED_REG_NUMBER: {
-      int nn = p.reg_number;
-      if (p.doBaumberg) nn = (int)floor(3.0 * (double)nn);
-      if ((nn < regNumber) && (nn >= 0)) keys.resize(nn);
-      break;
-    }
-    case MODSX_RELATIVE_REG_NUMBER: {
-      keys.resize((int)floor(p.rel_reg_number * (double)keys.size()));
-      break;
-    }
-    case MODSX_NOT_LESS_THAN_REGIONS: {
-      modsx_keypoint t = keys[0];
-      t.response = p.threshold;
-      int fix = (int)(std::lower_bound(keys.begin(), keys.end(), t, cmp) - keys.begin());
-      if (fix < p.reg_number) keys.resize(std::min(p.reg_number, regNumber));
-      else keys.resize(std::min(fix, regNumber));
-      break;
-    }
-    default: break;
-  }
-  if (p.mode == MODSX_FIXED_REG_NUMBER && (int)keys.size() > p.reg_number) keys.resize(p.reg_number);
-}
-
-// DetectAffineKeypoints (scale-space-detector.cpp:43-85) for a batch of images
-int detect_keypoints_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &par,
-                           const double *tilts, const double *zooms, std::vector<modsx_keypoint> *out) {
-  modsx_hessaff_params p = par;  // reg_number is rescaled per image just before the export step (it only matters there)
-  std::vector<modsx_sskp> ss[MAXB];
-  int rc = detect_scalespace_batch(c, imgs, n, p, ss);
-  if (rc) return rc;
-  HostMark hm;
-  rc = ensure_smm_mask(c, p.smmWindowSize);
-  if (rc) return rc;
-  size_t total = 0;
-  for (int i = 0; i < n; i++) total += ss[i].size();
-  for (int i = 0; i < n; i++) out[i].clear();
-  if (!total) return MODSX_OK;
-  hipStream_t s = c->stream;
-  if (!c->hAff.ensure(total * sizeof(AffJob) + total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
-  if (!c->affJobs.ensure(total * sizeof(AffJob)) || !c->affOut.ensure(total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
-  AffJob *hj = (AffJob *)c->hAff.p;
-  AffOut *ho = (AffOut *)((char *)c->hAff.p + total * sizeof(AffJob));
-  size_t first[MAXB + 1];   // image i's keypoints are jobs first[i] .. first[i + 1]
-  first[0] = 0;
-  for (int i = 0; i < n; i++) first[i + 1] = first[i] + ss[i].size();
-  host_parallel_light(n, [&](int i) {
-    size_t k = first[i];
-    for (const modsx_sskp &q : ss[i]) {
-      const Octave &oc = c->pyr[i].oct[q.octave];
-      AffJob &j = hj[k++];
-      j.blur = oc.blur[q.level - 1];  // prevBlur: one level below the detection level (pyramid.cpp:428-429)
-      j.rows = oc.rows; j.cols = oc.cols;
-      j.x = q.x; j.y = q.y; j.s = q.s; j.pixelDistance = q.pixelDistance;
-    }
-  });
-  hm.mark("AffJob build");
-  if (p.doBaumberg) {
-    MX_HIP(ctx_copy(c, c->affJobs.p, hj, total * sizeof(AffJob), hipMemcpyHostToDevice));
-    ProfScope ps(c, K_BAUMBERG, (double)total * 361 * 4 * 2);
-    launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, (int)total, c->dSmmMask, p.smmWindowSize,
-                    p.maxIterations, p.convergenceThreshold, p.affInitialSigma);
-    MX_HIP(ctx_copy(c, ho, c->affOut.p, total * sizeof(AffOut), hipMemcpyDeviceToHost));
-    MX_HIP(ctx_sync(c));
-  } else {
-    for (size_t i = 0; i < total; i++) { ho[i].u11 = 1; ho[i].u12 = 0; ho[i].u21 = 0; ho[i].u22 = 1; ho[i].ok = 1; ho[i].iters = 0; }
-  }
-  hm.mark("baumberg launch + wait");
-  host_parallel_light(n, [&](int i) {
-    size_t k = first[i];
-    out[i].reserve(ss[i].size());
-    for (const modsx_sskp &q : ss[i]) {
-      const AffOut &a = ho[k++];
-      if (!a.ok) continue;
-      modsx_keypoint kp;
-      memset(&kp, 0, sizeof kp);
-      kp.x = q.x; kp.y = q.y; kp.s = q.s;
-      kp.a11 = a.u11; kp.a12 = a.u12; kp.a21 = a.u21; kp.a22 = a.u22;
-      kp.response = q.val;
-      kp.sub_type = q.type;
-      out[i].push_back(kp);
-    }
-    modsx_hessaff_params pe = p;
-    const double tilt = tilts ? tilts[i] : 1.0, zoom = zooms ? zooms[i] : 1.0;
-    if ((tilt > 2.0) || (zoom < 0.5)) pe.reg_number = (int)floor(zoom * (double)pe.reg_number / tilt);
-    prepare_keys_for_export(out[i], pe);
-  });
-  hm.mark("keypoints + export");
-  return MODSX_OK;
-}
-
-// DetectAffineRegions<>, synth-detection.hpp:93-126
-void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out) {
-  for (int i = 0; i < n; i++) {
-    modsx_keypoint k = kps[i];
-    modsx_region &r = out[i];         // built in place (a 200-byte record)
-    memset(&r, 0, sizeof r);
-    r.img_id = img_id; r.img_reproj_id = 0; r.type = det_type; r.id = i;
-    r.det_kp.s = k.s * sqrt(fabs(k.a11 * k.a22 - k.a12 * k.a21));
-    rectify(k.a11, k.a12, k.a21, k.a22);
-    r.det_kp.x = k.x; r.det_kp.y = k.y;
-    r.det_kp.a11 = k.a11; r.det_kp.a12 = k.a12; r.det_kp.a21 = k.a21; r.det_kp.a22 = k.a22;
-    r.det_kp.response = k.response;
-    r.det_kp.sub_type = k.sub_type;
-  }
 }
 
 static const double K_SIGMA = 2 * 3.0 * sqrt(3.0);  // synth-detection.cpp:28
@@ -1446,8 +791,10 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
       // descriptor at its region's place, so the reference's list order is untouched.
       // (a stable LSD radix sort of one key per job: jobs are generated in (image, outIdx) order, which breaks the ties)
       {
-        std::vector<uint64_t> key(nj), key2(nj);
-        std::vector<uint32_t> ord(nj), ord2(nj);
+        // the key in the high half of a word, the job's position in the low half; sorted by the key's bits alone, the low halves
+        // are the order.  MAXB = 32 leaves room: the key needs 31 bits (image 5 | band 10 | x 16) of its 32
+        static_assert(MAXB <= 64, "describe job sort key: the image index has 6 bits at the most");
+        std::vector<uint64_t> key(nj), key2;
         for (size_t q = 0; q < nj; q++) {
           const DescJob &a = jobs[q];
           // the order only places neighbouring windows on neighbouring workgroups (no result depends on it): whole pixels
@@ -1455,25 +802,11 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
           const int xi = (int)a.x, yb = (int)a.y >> 6;
           const uint32_t x16 = (uint32_t)(xi < 0 ? 0 : (xi > 65535 ? 65535 : xi));
           const uint32_t band = (uint32_t)(yb < 0 ? 0 : (yb > 1023 ? 1023 : yb));
-          key[q] = ((uint64_t)(uint32_t)a.img << 26) | ((uint64_t)band << 16) | x16;
-          ord[q] = (uint32_t)q;
+          key[q] = ((((uint64_t)(uint32_t)a.img << 26) | ((uint64_t)band << 16) | x16) << 32) | (uint32_t)q;
         }
-        constexpr int BITS = 11, NB = 1 << BITS;
-        uint32_t hist[NB];
-        for (int shift = 0; shift < 33; shift += BITS) {
-          memset(hist, 0, sizeof hist);
-          for (size_t q = 0; q < nj; q++) hist[(key[q] >> shift) & (NB - 1)]++;
-          if (nj && hist[(key[0] >> shift) & (NB - 1)] == nj) continue;
-          uint32_t sum = 0;
-          for (int b = 0; b < NB; b++) { const uint32_t h = hist[b]; hist[b] = sum; sum += h; }
-          for (size_t q = 0; q < nj; q++) {
-            const uint32_t d = hist[(key[q] >> shift) & (NB - 1)]++;
-            key2[d] = key[q]; ord2[d] = ord[q];
-          }
-          key.swap(key2); ord.swap(ord2);
-        }
+        host_radix_sort_u64(key, key2, 32, 63);
         std::vector<DescJob> sorted(nj);
-        for (size_t q = 0; q < nj; q++) sorted[q] = jobs[ord[q]];
+        for (size_t q = 0; q < nj; q++) sorted[q] = jobs[(uint32_t)key[q]];
         jobs.swap(sorted);
       }
       hm.mark("desc job sort");
@@ -1498,10 +831,9 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
       }
       // the job table, the five tile prefixes and the three small tables travel as ONE pinned blob and one copy: nine
       // separate uploads cost nine ~6 us copy kernels per chunk on the stream
-      auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-      const size_t oJobs = 0, oPfx = up16(nj * sizeof(DescJob)), pfxB = up16((nj + 1) * 4);
-      const size_t oTaps = oPfx + 5 * pfxB, oNeed = oTaps + up16(taps.size() * 4), oCoord = oNeed + up16(needTab.size() * 4);
-      const size_t blobB = oCoord + up16(coordTab.size() * 4) + 16;
+      const size_t oJobs = 0, oPfx = align_up(nj * sizeof(DescJob), 16), pfxB = align_up((nj + 1) * 4, 16);
+      const size_t oTaps = oPfx + 5 * pfxB, oNeed = oTaps + align_up(taps.size() * 4, 16), oCoord = oNeed + align_up(needTab.size() * 4, 16);
+      const size_t blobB = oCoord + align_up(coordTab.size() * 4, 16) + 16;
       // two staging blobs in turn: the copy of chunk k may still be in flight while chunk k + 1 is being prepared
       const int slot = chunkNo & 1;
       PinBuf &hblob = slot ? c->hDescB : c->hDesc;
@@ -1627,7 +959,6 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
   if (nn < 2 || nn > MATCH_NN_MAX) { set_error("match: nn must be in [2, 256]"); return MODSX_ERR_ARG; }
   for (int i = 0; i < nb; i++)      // the matcher logs train tiles as 16-bit numbers (kernels_match.hip k_match_resolve)
     if (n2[i] > 2000000) { set_error("match: more than 2 000 000 train descriptors in one problem"); return MODSX_ERR_ARG; }
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   if (shard) {
     // view-sharded run (engine_shard.hip): this rank matches the query rows [lo, lo + per) of ONE problem; the result rows
     // of all ranks are all-gathered on the device and every rank builds the full tentative list
@@ -1642,8 +973,8 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     // from here to the all-gather nothing returns: a local failure travels in the block header
     int lrc = MODSX_OK;
     const int world = shard->world;
-    const size_t posB = up((size_t)M * 16), allB = (size_t)world * (per + 1) * sizeof(MatchRow);
-    if (!c->pos2.ensure(posB) || !c->hMatch.ensure(posB + up(allB)) || !c->matchWork.ensure(match_workspace_bytes(std::max(1, nloc), M)))
+    const size_t posB = align_up((size_t)M * 16, 256), allB = (size_t)world * (per + 1) * sizeof(MatchRow);
+    if (!c->pos2.ensure(posB) || !c->hMatch.ensure(posB + align_up(allB, 256)) || !c->matchWork.ensure(match_workspace_bytes(std::max(1, nloc), M)))
       lrc = MODSX_ERR_NOMEM;
     char *hpos = (char *)c->hMatch.p, *hrow = hpos ? hpos + posB : nullptr;
     if (!lrc) {
@@ -1672,9 +1003,9 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     out[i].clear();
     if (d2byDB) d2byDB[i].clear();
     if (n1[i] <= 0 || n2[i] <= 0) continue;
-    posOfs[nl] = posB; posB += up((size_t)n2[i] * 16);
-    rowOfs[nl] = rowB; rowB += up((size_t)n1[i] * sizeof(MatchRow));
-    workOfs[nl] = workB; workB += up(match_workspace_bytes(n1[i], n2[i]));
+    posOfs[nl] = posB; posB += align_up((size_t)n2[i] * 16, 256);
+    rowOfs[nl] = rowB; rowB += align_up((size_t)n1[i] * sizeof(MatchRow), 256);
+    workOfs[nl] = workB; workB += align_up(match_workspace_bytes(n1[i], n2[i]), 256);
     live[nl++] = i;
   }
   if (!nl) return MODSX_OK;
@@ -1682,8 +1013,8 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
   size_t ddbOfs[MATCH_MAXB], selOfs[MATCH_MAXB], selB = 256;
   if (db)
     for (int k = 0; k < nl; k++) {
-      ddbOfs[k] = rowB; rowB += up((size_t)n1[live[k]] * 4);
-      selOfs[k] = selB; selB += up((size_t)n1[live[k]] * 4);
+      ddbOfs[k] = rowB; rowB += align_up((size_t)n1[live[k]] * 4, 256);
+      selOfs[k] = selB; selB += align_up((size_t)n1[live[k]] * 4, 256);
     }
   if (!c->pos2.ensure(posB) || !c->matchRows.ensure(rowB) || !c->matchWork.ensure(workB) || !c->hMatch.ensure(posB + rowB) ||
       (db && !c->dbSel.ensure(selB)))
@@ -1837,8 +1168,7 @@ int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *d
     set_error("modsx_db_nearest: descriptors must hold the integers 0..255 (SIFT-family quantisation)");
     return MODSX_ERR_ARG;
   }
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t nB = up((size_t)n * 4);
+  const size_t nB = align_up((size_t)n * 4, 256);
   if (!c->descU8[0].ensure(u.size()) || !c->dbSel.ensure(256 + nB) || !c->matchRows.ensure(nB)) return MODSX_ERR_NOMEM;
   MX_HIP(hipMemcpyAsync(c->descU8[0].p, u.data(), u.size(), hipMemcpyHostToDevice, c->stream));
   const uint8_t *d1 = (const uint8_t *)c->descU8[0].p;

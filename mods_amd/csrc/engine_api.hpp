@@ -1,5 +1,8 @@
-// engine_api.hpp -- functions shared between engine.hip, ransac.cpp, filters.cpp and capi.hip.
+// engine_api.hpp -- functions shared between engine.hip, engine_detect.hip, engine_views.hip, engine_shard.hip, ransac.cpp,
+// filters.cpp and capi.hip.
 #pragma once
+#include <stdio.h>
+#include <chrono>
 #include <functional>
 #include <string>
 #include <vector>
@@ -44,7 +47,6 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
                    double mrSize, int patchSize, int fast, int photoNorm, int descType, double maxBin,
                    float *const *descHost, float *const *devF, uint8_t *const *devU8, const DescSet *ds = nullptr,
                    uint8_t *const *const *devU8x = nullptr);
-struct ProfScopeFwd;
 int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt, double phi_base, double InitSigma,
                 int doBlur, modsx_view *par, int cap, modsx_view *prev, int *nprev, int cap_prev);
 // slot < 0: the view is a fresh allocation owned by the returned image (public API).  slot in [0, MAXB): the view lives in
@@ -70,9 +72,45 @@ int match_ladder(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2,
                  modsx_comm *comm = nullptr, int owner = -1);
 int match_pair_views(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2, const modsx_view *views, int nv,
                      const modsx_pair_params &pp, modsx_pair_result *res, VerifyTask *defer = nullptr);
+// per-kernel-class GPU timing with HIP events on the launch stream (engine.hip); *slot = (size_t)-1 when profiling is off
 void prof_begin(modsx_ctx *c, int cls, double work, size_t *slot);
 void prof_end(modsx_ctx *c, size_t slot);
 bool prof_reserve(modsx_ctx *c, int cls, double work, hipEvent_t *ev2);
+struct ProfScope {     // prof_begin ... prof_end around the launches of a block
+  modsx_ctx *c;
+  size_t slot;
+  ProfScope(modsx_ctx *c_, int cls, double work) : c(c_) { prof_begin(c, cls, work, &slot); }
+  ~ProfScope() { prof_end(c, slot); }
+  ProfScope(const ProfScope &) = delete;
+  ProfScope &operator=(const ProfScope &) = delete;
+};
+// MODSX_HOST_TIMING=2: wall time of the host phases between the launches of a set (stderr)
+struct HostMark {
+  bool on; double t;
+  HostMark() : on(getenv("MODSX_HOST_TIMING") && atoi(getenv("MODSX_HOST_TIMING")) >= 2), t(0) { if (on) t = now(); }
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void mark(const char *what) { if (!on) return; const double n = now(); fprintf(stderr, "  host %-28s %.3f ms\n", what, n - t); t = n; }
+};
+inline double now_ms() { return HostMark::now(); }
+inline size_t align_up(size_t bytes, size_t a) { return (bytes + a - 1) & ~(a - 1); }   // a: a power of two
+// Stable LSD radix sort of w by its bits loBit..hiBit, 11 bits per pass; a pass whose digit is the same in every word is left
+// out.  tmp is the second buffer of the passes (resized here; callers keep it to keep its memory).
+inline void host_radix_sort_u64(std::vector<uint64_t> &w, std::vector<uint64_t> &tmp, int loBit, int hiBit) {
+  constexpr int BITS = 11, NB = 1 << BITS;
+  const size_t m = w.size();
+  if (!m) return;
+  tmp.resize(m);
+  uint32_t hist[NB];
+  for (int shift = loBit; shift <= hiBit; shift += BITS) {
+    memset(hist, 0, sizeof hist);
+    for (size_t k = 0; k < m; k++) hist[(w[k] >> shift) & (NB - 1)]++;
+    if (hist[(w[0] >> shift) & (NB - 1)] == m) continue;
+    uint32_t sum = 0;
+    for (int b = 0; b < NB; b++) { const uint32_t h = hist[b]; hist[b] = sum; sum += h; }
+    for (size_t k = 0; k < m; k++) tmp[hist[(w[k] >> shift) & (NB - 1)]++] = w[k];
+    w.swap(tmp);
+  }
+}
 // a sharded match (engine_shard.hip): this rank owns the query rows [lo, lo + per) of n1_total
 struct MatchShard { void *comm; int world, per, n1_total, lo; };
 // the lane's (per + 1)-row blocks (header row + result rows), grown by agreement; then header + all-gather + download + wait

@@ -1015,7 +1015,6 @@ int match_sharded_batch(modsx_ctx *c, modsx_comm *cm, int nb, const uint8_t *con
   if (nn < 2 || nn > MATCH_NN_MAX) { set_error("match: nn must be in [2, 256]"); return MODSX_ERR_ARG; }
   const int W = cm->world, R = cm->rank;
   hipStream_t s = c->stream;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // the row shares: every rank derives the same layout from the gathered counts
   std::vector<int> per(nb), lo(nb), nloc(nb), off(nb);
   int rowsTot = 0, n1Tot = 0;
@@ -1028,8 +1027,8 @@ int match_sharded_batch(modsx_ctx *c, modsx_comm *cm, int nb, const uint8_t *con
     nloc[g] = live ? std::max(0, std::min(n1[g], lo[g] + per[g]) - lo[g]) : 0;
     off[g] = 1 + rowsTot;
     rowsTot += per[g]; n1Tot += live ? n1[g] : 0;
-    posOfs[g] = posB; posB += up((size_t)std::max(0, n2[g]) * 16);
-    workOfs[g] = workB; workB += up(match_workspace_bytes(std::max(1, nloc[g]), std::max(1, n2[g])));
+    posOfs[g] = posB; posB += align_up((size_t)std::max(0, n2[g]) * 16, 256);
+    workOfs[g] = workB; workB += align_up(match_workspace_bytes(std::max(1, nloc[g]), std::max(1, n2[g])), 256);
   }
   if (rowsTot == 0) return MODSX_OK;       // the same on every rank: nobody issues a collective
   MatchShard sh;
@@ -1039,7 +1038,7 @@ int match_sharded_batch(modsx_ctx *c, modsx_comm *cm, int nb, const uint8_t *con
   if (rc) return rc;
   int lrc = MODSX_OK;
   const size_t allB = (size_t)W * (rowsTot + 1) * sizeof(MatchRow);
-  if (!c->pos2.ensure(posB + 256) || !c->hMatch.ensure(posB + up(allB) + 256) || !c->matchWork.ensure(workB + 256)) lrc = MODSX_ERR_NOMEM;
+  if (!c->pos2.ensure(posB + 256) || !c->hMatch.ensure(posB + align_up(allB, 256) + 256) || !c->matchWork.ensure(workB + 256)) lrc = MODSX_ERR_NOMEM;
   char *hpos = (char *)c->hMatch.p, *hrow = hpos ? hpos + posB : nullptr;
   if (!lrc && !pos2Dev) {
     for (int g = 0; g < nb; g++) if (n2[g] > 0) memcpy(hpos + posOfs[g], pos2Host[g], (size_t)n2[g] * 16);
@@ -1055,10 +1054,7 @@ int match_sharded_batch(modsx_ctx *c, modsx_comm *cm, int nb, const uint8_t *con
     double work = 0;
     auto flush = [&]() {
       if (!k) return;
-      size_t pslot;
-      prof_begin(c, K_MATCH, work, &pslot);
-      launch_match_batch(s, k, pd1, pn1, pd2, pn2, ppos, sqminratio, contrDistSq, nn, prow, pwork);
-      prof_end(c, pslot);
+      { ProfScope ps(c, K_MATCH, work); launch_match_batch(s, k, pd1, pn1, pd2, pn2, ppos, sqminratio, contrDistSq, nn, prow, pwork); }
       k = 0; work = 0;
     };
     for (int g = 0; g < nb; g++) {

@@ -245,29 +245,24 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
   const ViewJob *dj = (const ViewJob *)c->viewJobs.p;
   const float *dt = (const float *)((char *)c->viewJobs.p + jobB);
   const int nj = (int)jobs.size();
-  size_t pslot;
   // a profiling bracket only around launches that have tiles
   if (tilesG > 0) {
-    prof_begin(c, K_VIEW_BLUR, pxFused * 4, &pslot);
+    ProfScope ps(c, K_VIEW_BLUR, pxFused * 4);
     launch_views_fused(s, dj, nj, tilesG, dt, maxRxG, maxRyG);
-    prof_end(c, pslot);
   }
   if (tilesA > 0) {
-    prof_begin(c, K_WARP, pxRot * 4, &pslot);
+    ProfScope ps(c, K_WARP, pxRot * 4);
     launch_views_warp(s, dj, nj, tilesA, 0);
-    prof_end(c, pslot);
   }
   if (tilesF > 0 || tilesA > 0) {
-    prof_begin(c, K_VIEW_BLUR, pxBlur * 4, &pslot);
+    ProfScope ps(c, K_VIEW_BLUR, pxBlur * 4);
     launch_views_rotblur(s, dj, nj, tilesF, dt, maxRx, maxRy);
     launch_views_blur(s, dj, nj, tilesA, dt, 0);
     launch_views_blur(s, dj, nj, tilesA, dt, 1);
-    prof_end(c, pslot);
   }
   if (tilesB > 0) {
-    prof_begin(c, K_WARP, pxTilt * 4, &pslot);
+    ProfScope ps(c, K_WARP, pxTilt * 4);
     launch_views_warp(s, dj, nj, tilesB, 1);
-    prof_end(c, pslot);
   }
   MX_HIP(hipGetLastError());
   return MODSX_OK;

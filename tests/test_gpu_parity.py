@@ -103,6 +103,58 @@ def test_scalespace_keypoints_bit_exact(ctx, modsx, oracle, small_pair, mode):
         _check_sskp(got, ref)
 
 
+@pytest.mark.parametrize("k", [4, 5, 6])
+def test_scalespace_keypoints_other_scale_counts_bit_exact(ctx, modsx, oracle, small_pair, k):
+    """numberOfScales != 3: the extrema scan numbers its tiles per level instead of per octave (no first-level table) and the
+    scale of a keypoint divides by another count.  4, 5 and 6 are the counts above 3 the library takes (6 fills the level arrays)."""
+    for img in small_pair[:2]:
+        im = ctx.upload(img)
+        got = ctx.detect_scalespace(im, modsx.default_hessaff_params(numberOfScales=k))
+        im.free()
+        ref = oracle.detect_scalespace(img, oracle.default_params(numberOfScales=k))
+        assert len(ref) >= 50
+        _check_sskp(got, ref)
+
+
+def test_scalespace_too_few_scales_for_the_pyramid_taps_is_refused(ctx, modsx, small_pair):
+    """numberOfScales = 2 with the default initialSigma = 1.6: the last level's blur has sigma 3.2 sqrt(2^(2/2) - 1) = 3.2, a
+    21-tap kernel, and the pyramid kernels hold 17 (numberOfScales = 1: 35 taps)."""
+    im = ctx.upload(small_pair[0])
+    with pytest.raises(RuntimeError, match="pyramid blur kernel larger than 17 taps"):
+        ctx.detect_scalespace(im, modsx.default_hessaff_params(numberOfScales=2))
+    im.free()
+
+
+def test_scalespace_per_level_scan_opt_in_is_bit_exact(small_pair):
+    """MODSX_NMS_PER_LEVEL=1 sends the shipped numberOfScales = 3 through the per-level tile numbering as well.  Runs in a child
+    process: the test session's library must keep its default."""
+    import json, subprocess, sys
+    code = (
+        "import sys, json\n"
+        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import mods_amd\n"
+        "from mods_amd import synthetic\n"
+        "from oracle import pyoracle as O\n"
+        "from common import same_records\n"
+        "a, b, _ = synthetic.make_pair(rows=240, cols=320, nblobs=420, seed=777)\n"
+        "ctx = mods_amd.Context(0)\n"
+        "ok, n = True, []\n"
+        "for img in (a, b):\n"
+        "    im = ctx.upload(img)\n"
+        "    ss = ctx.detect_scalespace(im, mods_amd.default_hessaff_params())\n"
+        "    ref = O.detect_scalespace(img, O.default_params())\n"
+        "    ok = ok and same_records(ss, ref.view(mods_amd.SSKP))\n"
+        "    n.append(int(len(ref)))\n"
+        "    im.free()\n"
+        "print(json.dumps({'ok': bool(ok), 'n': n}))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, MODSX_NMS_PER_LEVEL="1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    assert res["ok"] and min(res["n"]) >= 50
+
+
 @pytest.mark.parametrize("det,th", [(1, 1.5), (2, 400.0)])
 def test_dog_and_harris_scale_space_detectors_bit_exact(ctx, modsx, oracle, small_pair, det, th):
     """PyramidParams::DetectorType = DET_DOG / DET_HARRIS inside the scale-space loop (ScaleSpaceDetector::Response,
