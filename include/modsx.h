@@ -367,6 +367,10 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
 /* host share of the last modsx_match_pairs / modsx_match_pairs_views call: wall time of DuplicateFiltering + LO-RANSAC summed over its pairs (ms),
  * the pairs verified and the helper threads that ran them (measurement hook) */
 int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads);
+/* shape of the process's most recent matcher launch, as used for its first problem: 32-query sets per wavefront (2 / 4), whole-CU
+ * workgroups (0 / 1), splits of the train tiles, tiles per split, upper bound of the tile count (measurement hook).  The five
+ * values are written one by one: they belong together only while a single thread launches matcher work */
+int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, int *ntiles_ub);
 /* per-stage time of the last modsx_match_pair in ms: detect, orient, describe, match, verify, total */
 int modsx_last_timings(modsx_ctx *ctx, double *ms6);
 

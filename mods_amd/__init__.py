@@ -93,7 +93,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_loransac_h", "modsx_ransac_h_errtype", "modsx_loransac_h_errtype", "modsx_ransac_f", "modsx_loransac_f", "modsx_match_pair", "modsx_match_pairs", "modsx_match_pairs_views", "modsx_pair_result_release",
            "modsx_set_vs_pars", "modsx_synth_view", "modsx_detect_describe_views", "modsx_match_fginn_device",
            "modsx_match_pair_views", "modsx_match_ladder", "modsx_save_regions", "modsx_load_regions", "modsx_default_mser_params", "modsx_detect_msers", "modsx_detect_msers_u8", "modsx_last_timings", "modsx_profile",
-           "modsx_kernel_stats", "modsx_last_batch_verify", "modsx_comm_unique_id", "modsx_comm_create", "modsx_comm_destroy", "modsx_comm_info",
+           "modsx_kernel_stats", "modsx_last_batch_verify", "modsx_last_match_geometry", "modsx_comm_unique_id", "modsx_comm_create", "modsx_comm_destroy", "modsx_comm_info",
            "modsx_view_block_order", "modsx_detect_describe_views_sharded", "modsx_match_fginn_sharded",
            "modsx_match_pair_views_sharded", "modsx_match_pairs_views_sharded", "modsx_match_ladder_sharded", "modsx_comm_loopback_id", "modsx_comm_set_lanes",
            "modsx_comm_attach", "modsx_comm_lane_done", "modsx_comm_reset_lanes", "modsx_comm_set_timeout", "modsx_comm_stats",
@@ -767,6 +767,13 @@ def last_batch_verify():
     ms, n, t = C.c_double(), C.c_int(), C.c_int()
     lib().modsx_last_batch_verify(C.byref(ms), C.byref(n), C.byref(t))
     return ms.value, n.value, t.value
+
+
+def last_match_geometry():
+    """dict(qs, fat, S, tiles_per_split, ntiles_ub): the shape the process's last matcher launch used for its first problem."""
+    v = [C.c_int() for _ in range(5)]
+    lib().modsx_last_match_geometry(*[C.byref(x) for x in v])
+    return dict(zip(("qs", "fat", "S", "tiles_per_split", "ntiles_ub"), (x.value for x in v)))
 
 
 def view_block_order(counts):

@@ -671,6 +671,11 @@ int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads) {
   return MODSX_OK;
 }
 
+int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, int *ntiles_ub) {
+  mx::last_match_geometry(qs, fat, S, tiles_per_split, ntiles_ub);
+  return MODSX_OK;
+}
+
 // verification time (DuplicateFiltering + LO-RANSAC + the LAF checks, wall of the verifying thread) of every pair of the last batch call
 extern "C" __attribute__((visibility("default"))) int modsx_debug_last_batch_verify_each(double *ms, int cap) {
   std::lock_guard<std::mutex> lk(g_verifyEachMu);

@@ -278,6 +278,7 @@ constexpr int MATCH_MAXB = 4;   // independent matching problems per launch set 
 void launch_match_batch(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                         const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
                         void *const *workspace, hipEvent_t *evSweep1 = nullptr);   // evSweep1: two events recorded around sweep 1
+void last_match_geometry(int *qs, int *fat, int *S, int *tilesPerSplit, int *ntilesUB);   // of problem 0 of the process's last launch
 // A descriptor database resident in HBM (kernels_dbnn.hip): the rows packed once into the matcher's operand form.  Read-only
 // after creation, so every context of its device may use it at the same time.
 struct DbGeo { int TEp, TOp; };     // tiles of the even / odd parity class (multiples of 4)

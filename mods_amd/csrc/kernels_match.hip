@@ -980,6 +980,16 @@ __global__ __launch_bounds__(256) void k_match_pdf(MatchBatch b, double contrDis
   A.contrDistSq = contrDistSq; A.nn = nn; A.und = P.und; A.nUndecided = P.counter; A.rows = P.rows; A.scratch = P.pdf;
   pdf_body(A);
 }
+// measurement hook (modsx_last_match_geometry): what launch_match_batch_once used for problem 0 of the process's last launch
+// (five separate words: a launch from another context's thread in between gives a reading mixed from both)
+static std::atomic<int> g_lastQs{0}, g_lastFat{0}, g_lastS{0}, g_lastTilesPerSplit{0}, g_lastNtilesUB{0};
+void last_match_geometry(int *qs, int *fat, int *S, int *tilesPerSplit, int *ntilesUB) {
+  if (qs) *qs = g_lastQs.load();
+  if (fat) *fat = g_lastFat.load();
+  if (S) *S = g_lastS.load();
+  if (tilesPerSplit) *tilesPerSplit = g_lastTilesPerSplit.load();
+  if (ntilesUB) *ntilesUB = g_lastNtilesUB.load();
+}
 // Problems with n1 == 0 or n2 == 0 must be left out by the caller.  workspace[i] holds match_workspace_bytes(n1[i], n2[i]).
 static void launch_match_batch_once(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                                     const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
@@ -1018,6 +1028,7 @@ static void launch_match_batch_once(hipStream_t s, int nb, const uint8_t *const 
     P.d1 = d1[i]; P.d2 = d2[i]; P.pos2 = pos2[i]; P.rows = rows[i];
     maxN1 = std::max(maxN1, n1[i]); maxS = std::max(maxS, L.S); maxWg = std::max(maxWg, (n2[i] + PB - 1) / PB);
   }
+  g_lastQs = qs; g_lastFat = fat ? 1 : 0; g_lastS = b.p[0].g.S; g_lastTilesPerSplit = b.p[0].g.tilesPerSplit; g_lastNtilesUB = b.p[0].g.ntilesUB;
   hipLaunchKernelGGL(k_match_pack, dim3(std::max((maxN1 + 31) / 32, maxWg), 2, nb), dim3(256), 0, s, b);
   const int QPB = qpb_of(qs), NW2 = 256 * sweep_wps(qs), QPB1 = s1_qpb(qs, fat);
   const dim3 grid((maxN1 + QPB1 - 1) / QPB1, maxS, nb), block1(64 * s1_waves(qs, fat));

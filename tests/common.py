@@ -70,6 +70,16 @@ def synth_two_view(seed, n_in=300, n_out=150, planar_frac=0.0, noise=0.5):
     return pts, laf
 
 
+def grouped_pair_hosts(a, b):
+    """The ten mixed-size pairs of test_grouped_pairs_equal_single_pairs (and of the matcher-shape children) around the session's
+    small pair (a, b): repeated and swapped pairs, cropped images, blank images that give empty problems inside a batch."""
+    from mods_amd import synthetic
+    a2, b2, _ = synthetic.make_pair(rows=200, cols=272, nblobs=260, seed=31)
+    a3, b3, _ = synthetic.make_pair(rows=256, cols=256, nblobs=300, seed=32)
+    blank = np.full((96, 128), 90, np.float32)   # no keypoints: an empty problem inside a batched match launch
+    return [(a, b), (blank, b2), (a2, b2), (a3, b3), (b, a), (a2, b3[:200, :]), (a3, blank), (a, b), (b2, a2), (blank, blank)]
+
+
 def normH(H):
     H = np.asarray(H, float).reshape(3, 3)
     return H / H[2, 2]

@@ -10,7 +10,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from common import oracle_features, oracle_pair, laf_of, normH, same_records, need_ref
+from common import oracle_features, oracle_pair, laf_of, normH, same_records, need_ref, grouped_pair_hosts
+from tests.match_cases import tie_cases, all_points_case, clustered_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -333,19 +334,14 @@ def test_match_fginn_bit_exact_on_real_descriptors(ctx, oracle, small_pair):
 
 
 def test_match_fginn_ties_ranks_and_ragged_sizes(ctx, oracle):
-    rs = np.random.RandomState(9)
-    for n1, n2 in ((1, 50), (33, 95), (70, 257), (5, 64)):
+    for d1, d2, pos2, params in (c[:4] for c in tie_cases()):
         # low-entropy descriptors: many exact distance ties, duplicates, zero distances
-        d1 = rs.randint(0, 3, (n1, 128)).astype(np.float32) * 40
-        d2 = rs.randint(0, 3, (n2, 128)).astype(np.float32) * 40
-        d2[n2 // 2:] = d2[: n2 - n2 // 2]                       # duplicated trains
-        d1[0] = d2[3]                                          # exact hit (d0 = 0)
-        pos2 = rs.uniform(0, 60, (n2, 2))                      # dense positions: long walks through consistent NNs
-        for ratio, cd in ((0.8, 30.0), (0.95, 80.0), (0.8, 5.0)):
+        for ratio, cd, _ in params:
             _check_tents(ctx.match_fginn(d1, d2, pos2, ratio, cd), oracle.match_fginn(d1, d2, pos2, ratio, cd))
     assert len(ctx.match_fginn(np.zeros((0, 128)), np.zeros((4, 128)), np.zeros((4, 2)))) == 0
     # outside the domain the int8 path is exact on (integers 0..255), and for the branches that are not built, the call
     # fails loudly instead of returning something else than the reference would
+    rs = np.random.RandomState(10)                    # any eight valid descriptors: only the refusals below are asserted
     d = rs.randint(0, 255, (8, 128)).astype(np.float32)
     p2 = rs.uniform(0, 60, (8, 2))
     for bad in (d + 0.5, d - 300.0, np.where(np.arange(128) == 3, np.nan, d)):
@@ -367,18 +363,8 @@ def test_match_fginn_all_points_mode(ctx, oracle, small_pair):
         ref = oracle.match_fginn(d1, d2, pos2, ratio, cd, nn)
         assert len(ref) == len(d1)
         _check_tents(ctx.match_fginn(d1, d2, pos2, ratio, cd, nn), ref)
-    rs = np.random.RandomState(5)
-    n1, n2 = 300, 3000
-    e2 = rs.randint(1, 90, (n2, 128)).astype(np.float32)
-    e1 = rs.randint(1, 90, (n1, 128)).astype(np.float32)
-    p2 = rs.uniform(0, 300, (n2, 2))
-    for q in range(0, n1, 2):
-        k = int(rs.randint(2, 60))
-        start = int(rs.randint(0, n2 - k))
-        e2[start:start + k] = np.clip(e1[q][None, :] + rs.randint(-2, 3, (k, 128)), 1, 255)
-        p2[start:start + k] = p2[start] + rs.uniform(-3, 3, (k, 2))
-    e2[7] = e2[8]                                                   # an exact tie
-    for ratio, cd, nn in ((1.0, 30.0, 50), (1.5, 10.0, 8), (1.0, 500.0, 100)):
+    e1, e2, p2, params = all_points_case()[:4]
+    for ratio, cd, nn in params:
         _check_tents(ctx.match_fginn(e1, e2, p2, ratio, cd, nn), oracle.match_fginn(e1, e2, p2, ratio, cd, nn))
     # fewer than nn trains: a walk that never meets a contradictive neighbour runs off the list and leaves no record
     _check_tents(ctx.match_fginn(e1[:40], e2[:30], p2[:30], 1.0, 1e6, 50), oracle.match_fginn(e1[:40], e2[:30], p2[:30], 1.0, 1e6, 50))
@@ -389,30 +375,8 @@ def test_match_fginn_clustered_near_duplicates_and_split_ranges(ctx, oracle):
     index chunks of 12 tiles, runs of up to 40 near-duplicate trains of one query packed into ONE (split, lane-half) stream
     (more than the 16 event slots of a stream with fewer than nn groups in total -> the exact rescan of that stream), exact
     distance ties across tiles and lane halves, walks that end at rank nn - 1 / nn, and a query block boundary (n1 > 256)."""
-    rs = np.random.RandomState(31)
-    for n1, n2, kmax in ((300, 2100, 40), (40, 5000, 25), (513, 1000, 12), (60, 3000, 150)):   # (the last: runs beyond 64, for nn > 64)
-        base = rs.randint(0, 90, (n2, 128)).astype(np.float32)
-        d2 = base.copy()
-        d1 = rs.randint(0, 90, (n1, 128)).astype(np.float32)
-        pos2 = rs.uniform(0, 2000, (n2, 2))
-        for q in range(0, n1, 3):
-            k = int(rs.randint(2, kmax))
-            start = int(rs.randint(0, n2 - k))
-            near = np.clip(d1[q][None, :] + rs.randint(-2, 3, (k, 128)), 0, 255)
-            d2[start:start + k] = near                     # contiguous: same tiles, same stream
-            pos2[start:start + k] = pos2[start] + rs.uniform(-3, 3, (k, 2))
-            if q % 6 == 0:
-                d2[start + k - 1] = d2[start]               # an exact tie inside the run
-        # one near-duplicate per tile, always in the same lane half, over 20 consecutive tiles of the first split: 20 event
-        # groups in ONE stream (> 16 slots) but fewer than nn in total -> the stream is rescanned exactly
-        for q in (1, 4, 7):
-            t0 = 32 * (q % 3)
-            for j in range(20):
-                t = t0 + 32 * j + 1
-                if t < n2:
-                    d2[t] = np.clip(d1[q] + rs.randint(-2, 3, 128), 0, 255)
-                    pos2[t] = pos2[t0 + 1] + rs.uniform(-3, 3, 2)
-        for ratio, cd, nn in ((0.8, 30.0, 50), (0.9, 30.0, 20), (0.8, 2.0, 50), (0.9, 30.0, 100), (0.95, 40.0, 256), (0.9, 30.0, 65)):
+    for d1, d2, pos2, params in (c[:4] for c in clustered_cases()):
+        for ratio, cd, nn in params:
             _check_tents(ctx.match_fginn(d1, d2, pos2, ratio, cd, nn), oracle.match_fginn(d1, d2, pos2, ratio, cd, nn))
 
 
@@ -607,13 +571,9 @@ def test_full_size_pair_properties(ctx, modsx, oracle):
 def test_grouped_pairs_equal_single_pairs(modsx, small_pair):
     """modsx_match_pairs runs up to four pairs (eight images, mixed sizes) as one batch per context; every result
     must be the one modsx_match_pair returns for that pair alone."""
-    from mods_amd import synthetic
     a, b, _ = small_pair
-    a2, b2, _ = synthetic.make_pair(rows=200, cols=272, nblobs=260, seed=31)
-    a3, b3, _ = synthetic.make_pair(rows=256, cols=256, nblobs=300, seed=32)
     ctxs = [modsx.Context(0), modsx.Context(0)]
-    blank = np.full((96, 128), 90, np.float32)   # no keypoints: an empty problem inside a batched match launch
-    hosts = [(a, b), (blank, b2), (a2, b2), (a3, b3), (b, a), (a2, b3[:200, :]), (a3, blank), (a, b), (b2, a2), (blank, blank)]
+    hosts = grouped_pair_hosts(a, b)
     dev = [(ctxs[0].upload(x), ctxs[0].upload(y)) for x, y in hosts]
     par = modsx.default_pair_params(ransac_seed=9)
     singles = [ctxs[0].match_pair(x, y, par) for x, y in dev]

@@ -14,19 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import mods_amd  # noqa: E402
 from oracle import pyoracle as O  # noqa: E402
-
-
-def same(a, b):
-    if len(a) != len(b):
-        return False
-    for f in a.dtype.names:
-        x, y = a[f], b[f]
-        if x.dtype.kind == "f":
-            if not np.array_equal(x, y, equal_nan=True):
-                return False
-        elif not np.array_equal(x, y):
-            return False
-    return True
+from tests.match_cases import near_duplicates, same_tentatives as same  # noqa: E402  (shared with the test suite's planted runs)
 
 
 def main(n, seed0):
@@ -60,7 +48,7 @@ def main(n, seed0):
             for q in range(0, n1, int(rs.randint(1, 4))):
                 k = int(rs.randint(2, min(n2 - 1, int(rs.choice([4, 20, 80, 300])))))
                 st = int(rs.randint(0, n2 - k))
-                d2[st:st + k] = np.clip(d1[q][None, :] + rs.randint(-2, 3, (k, 128)), 0, 255)
+                d2[st:st + k] = near_duplicates(rs, d1[q], k)
                 if rs.rand() < 0.7:
                     pos2[st:st + k] = pos2[st] + rs.uniform(-3, 3, (k, 2))
                 if rs.rand() < 0.3:
