@@ -371,6 +371,15 @@ int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads);
  * workgroups (0 / 1), splits of the train tiles, tiles per split, upper bound of the tile count (measurement hook).  The five
  * values are written one by one: they belong together only while a single thread launches matcher work */
 int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, int *ntiles_ub);
+/* orientation jobs launched by the pair and view pipelines of this process, and regions they left out of the orientation launch
+ * because modsx_debug_reproject_certain_drop flags them, since the last reset (measurement hook; MODSX_ORI_PREFILTER=0 in the
+ * environment launches them all).  modsx_detect_orientation itself never leaves a region out */
+int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long long *skipped, int reset);
+/* drop[i] = 1 when modsx_reproject_regions (boxk = 2 * 3 * sqrt 3) / modsx_reproject_regions_touch_boundary (boxk = mrSize) with
+ * the same H and size removes region i whatever rotation modsx_detect_orientation applies to its shape first, 0 when that is not
+ * certain (host only).  Returns n */
+int modsx_debug_reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk,
+                                       unsigned char *drop);
 /* per-stage time of the last modsx_match_pair in ms: detect, orient, describe, match, verify, total */
 int modsx_last_timings(modsx_ctx *ctx, double *ms6);
 

@@ -100,7 +100,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_block_bytes", "modsx_shard_block_pack", "modsx_shard_blocks_unpack", "modsx_shard_device_pack",
            "modsx_shard_device_unpack", "modsx_verify_device_stats", "modsx_verify_device_timing", "modsx_comm_set_exchange",
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
-           "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db"]
+           "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
+           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -164,6 +165,8 @@ def lib():
         L.modsx_db_rows.argtypes = [C.c_void_p]
         L.modsx_db_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_set_fginn_db.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -774,6 +777,24 @@ def last_match_geometry():
     v = [C.c_int() for _ in range(5)]
     lib().modsx_last_match_geometry(*[C.byref(x) for x in v])
     return dict(zip(("qs", "fat", "S", "tiles_per_split", "ntiles_ub"), (x.value for x in v)))
+
+
+def orientation_counts(reset=False):
+    """(launched, skipped): orientation jobs launched by the pair / view pipelines of this process and regions left out of
+    the launch because their reprojection is certain to drop them, since the last reset."""
+    a, b = C.c_ulonglong(), C.c_ulonglong()
+    lib().modsx_debug_orientation_counts(C.byref(a), C.byref(b), int(reset))
+    return a.value, b.value
+
+
+def reproject_certain_drop(regs, H, w, h, boxk=2 * 3.0 * 3.0 ** 0.5):
+    """bool per region: reproject_regions(.., H, w, h) (boxk: the box factor, default k_sigma) removes it whatever its orientation."""
+    regs = np.ascontiguousarray(regs, REGION)
+    H = np.ascontiguousarray(H, np.float64).reshape(9)
+    drop = np.zeros(max(1, len(regs)), np.uint8)
+    _check(lib().modsx_debug_reproject_certain_drop(_p(regs), len(regs), _p(H), int(w), int(h), C.c_double(boxk), _p(drop)),
+           "reproject_certain_drop")
+    return drop[:len(regs)].astype(bool)
 
 
 def view_block_order(counts):

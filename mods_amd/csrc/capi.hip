@@ -357,6 +357,18 @@ int modsx_reproject_regions_touch_boundary(modsx_region *regs, int n, const doub
   return reproject_regions_box(regs, n, H, orig_w, orig_h, mrSize);
 }
 
+int modsx_debug_reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk,
+                                       unsigned char *drop) {
+  if (n < 0 || (n > 0 && (!regs || !drop)) || !H) { mx::set_error("modsx_debug_reproject_certain_drop: bad argument"); return MODSX_ERR_ARG; }
+  reproject_certain_drop(regs, n, H, orig_w, orig_h, boxk, drop);
+  return n;
+}
+
+int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long long *skipped, int reset) {
+  mx::orientation_counts(launched, skipped, reset != 0);
+  return MODSX_OK;
+}
+
 int modsx_describe_regions(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                            int patchSize, int fast_extraction, int photoNorm, int desc_type, double maxBinValue,
                            float *desc) {

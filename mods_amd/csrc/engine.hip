@@ -450,11 +450,33 @@ static int upload_img_refs(modsx_ctx *c, const modsx_image *const *imgs, int n) 
   return MODSX_OK;
 }
 
+// ReprojectRegions' test for "H is the identity": the regions are copied, not transformed (synth-detection.cpp:549-560)
+static double eye_test(const double *H) {
+  return fabs(H[0] - 1.0) + fabs(H[1]) + fabs(H[2]) + fabs(H[3]) + fabs(H[4] - 1.0) + fabs(H[5]) + fabs(H[6]) + fabs(H[7]) +
+         fabs(H[8] - 1.0);
+}
+static bool is_eye(const double *H) { return eye_test(H) < 0.01; }
+// MODSX_ORI_PREFILTER=0: detect_orientation_batch launches every region that passes the view's border test (A/B runs, tests)
+static bool ori_prefilter_on() {
+  static const bool on = !(getenv("MODSX_ORI_PREFILTER") && atoi(getenv("MODSX_ORI_PREFILTER")) == 0);
+  return on;
+}
+// measurement hook (modsx_debug_orientation_counts): orientation jobs launched, and regions left out because their reprojection
+// is certain to drop them, by every context of the process since the last reset
+static std::atomic<unsigned long long> g_oriLaunched{0}, g_oriSkipped{0};
+void orientation_counts(unsigned long long *launched, unsigned long long *skipped, bool reset) {
+  if (launched) *launched = reset ? g_oriLaunched.exchange(0) : g_oriLaunched.load();
+  else if (reset) g_oriLaunched.store(0);
+  if (skipped) *skipped = reset ? g_oriSkipped.exchange(0) : g_oriSkipped.load();
+  else if (reset) g_oriSkipped.store(0);
+}
+
 // DetectOrientation, synth-detection.cpp:841-919, for a batch of (image, region list)
 int detect_orientation_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *in,
                              double mrSize, int patchSize, int doHalfSIFT, int maxAngNum, double th, int addUpRight,
-                             std::vector<modsx_region> *out) {
+                             std::vector<modsx_region> *out, const OriReproj *reproj) {
   if (patchSize != 41) { set_error("orientation patchSize must be 41"); return MODSX_ERR_ARG; }
+  const bool prefilter = reproj && ori_prefilter_on();
   for (int i = 0; i < n; i++) out[i].clear();
   double mrScale = (double)mrSize;
   int patchImageSize = 2 * int(mrScale) + 1;
@@ -462,16 +484,26 @@ int detect_orientation_batch(modsx_ctx *c, const modsx_image *const *imgs, int n
   HostMark hm;
   std::vector<OriJob> jobs;
   std::vector<char> passed[MAXB];
+  std::vector<unsigned char> certain[MAXB];   // reproj: the caller's reproject_regions drops the region whatever its angle turns out to be
   std::vector<OriJob> jobsOf[MAXB];     // per image, then concatenated: the images are independent (one pool task each)
   host_parallel_light(n, [&](int i) {
     passed[i].assign(in[i].size(), 0);
     jobsOf[i].clear();
     jobsOf[i].reserve(in[i].size());
+    // (the identity onto the view's own size repeats the test below on the rotated shape: a region that passes it unrotated has
+    // |a11| + |a12| >= the row norm inside the bounds and is never certain to be dropped -- nothing to compute)
+    const bool sameTest = prefilter && reproj[i].orig_w == imgs[i]->cols && reproj[i].orig_h == imgs[i]->rows && is_eye(reproj[i].H);
+    if (prefilter && !sameTest) {
+      certain[i].resize(in[i].size());
+      reproject_certain_drop(in[i].data(), (int)in[i].size(), reproj[i].H, reproj[i].orig_w, reproj[i].orig_h, K_SIGMA, certain[i].data());
+    }
+    unsigned long long nSkipped = 0;
     for (size_t r = 0; r < in[i].size(); r++) {
       const modsx_keypoint &k = in[i][r].det_kp;
       if (check_borders_host(imgs[i]->cols, imgs[i]->rows, (float)k.x, (float)k.y, (float)k.a11, (float)k.a12,
                              (float)k.a21, (float)k.a22, (int)(K_SIGMA * k.s), (int)(K_SIGMA * k.s)))
         continue;
+      if (!certain[i].empty() && certain[i][r]) { nSkipped++; continue; }   // like a region at the view's border: no job, no output
       passed[i][r] = 1;
       if (maxAngNum > 0) {
         float curr_sc = imageToPatchScale * k.s;
@@ -482,11 +514,13 @@ int detect_orientation_batch(modsx_ctx *c, const modsx_image *const *imgs, int n
         jobsOf[i].push_back(j);
       }
     }
+    if (nSkipped) g_oriSkipped.fetch_add(nSkipped, std::memory_order_relaxed);
   });
   size_t jobStart[MAXB + 1];
   jobStart[0] = 0;
   for (int i = 0; i < n; i++) jobStart[i + 1] = jobStart[i] + jobsOf[i].size();
   jobs.resize(jobStart[n]);
+  g_oriLaunched.fetch_add(jobStart[n], std::memory_order_relaxed);
   host_parallel_light(n, [&](int i) { if (!jobsOf[i].empty()) memcpy(jobs.data() + jobStart[i], jobsOf[i].data(), jobsOf[i].size() * sizeof(OriJob)); });
   hm.mark("orientation jobs");
   const float *res = nullptr;   // in the pinned staging buffer: (1 + maxA) words per job
@@ -551,8 +585,7 @@ int reproject_regions(modsx_region *regs, int n, const double *H, int orig_w, in
   return reproject_regions_box(regs, n, H, orig_w, orig_h, K_SIGMA);
 }
 int reproject_regions_box(modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk) {
-  double eyeTest = fabs(H[0] - 1.0) + fabs(H[1]) + fabs(H[2]) + fabs(H[3]) + fabs(H[4] - 1.0) + fabs(H[5]) + fabs(H[6]) +
-                   fabs(H[7]) + fabs(H[8] - 1.0);
+  double eyeTest = eye_test(H);
   double Hi[9];
   invert3(H, Hi);
   for (int i = 0; i < n; i++) {
@@ -578,6 +611,64 @@ int reproject_regions_box(modsx_region *regs, int n, const double *H, int orig_w
     }
   }
   return m;
+}
+
+// drop[i] = 1 when reproject_regions_box(..., H, orig_w, orig_h, boxk) removes region i after ANY rotation of its shape matrix
+// from the right (what detect_orientation_batch does with the dominant angles), 0 when that is not certain.
+//
+// The centre test does not read the shape: it is evaluated here by the exact path's own expressions.  For the box, with
+// M = Hinv_lin * A and a rotation R, the corners lie at x' +- hw * m11' +- hw * m12' with (m11', m12') = row 1 of M * R, and
+// |m11'| + |m12'| >= ||row 1 of M * R|| = ||row 1 of M||: the largest corner offset in x is at least dx = |hw| * ||row 1 of M||
+// whatever the angle, the same in y with row 2.  The region is certainly dropped when x' + dx > w - 3, x' - dx < 1,
+// y' + dy > h - 3 or y' - dy < 1 hold with a margin for the rounding of the exact path (u = 2^-24, T = |x'| + sqrt 2 * dx
+// bounds |x'| + |hw| * (|m11'| + |m12'|)):
+//  * cosf / sinf are within 1 ulp, taken as 2^-23 per entry: the applied matrix is R + E with ||E||_2 <= 2^-22, the row norm
+//    shrinks by at most dx * 4u;
+//  * the f64 products of the rotation and of Hinv_lin * (A * R), four roundings on sums of two products each: at most
+//    e64 = |hw| * 2^-50 * (|Hi_r0| + |Hi_r1|) * (|a11| + |a12| + |a21| + |a22|) in a corner coordinate (no cancellation assumed);
+//  * the casts of x', m11', m12' to f32, the two f32 products and the two f32 additions of check_borders: every term of the
+//    corner carries at most four factors (1 + u), at most 4u * T.
+// Together less than B = 4u * (|x'| + 3 * dx) + e64.  The margin is 32 * B (2^-17 * (|x'| + 3 * dx) + 32 * e64, 0.01 px for a
+// 1024 px image): too generous a margin only narrows the caught band by that much.  Anything not finite, a box size beyond
+// int and magnitudes near the end of the f32 range are "not certain".
+void reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk, unsigned char *drop) {
+  const bool eye = is_eye(H);
+  double Hi[9];
+  invert3(H, Hi);
+  const double lim[2] = {(double)(float)(orig_w - 3), (double)(float)(orig_h - 3)};   // check_borders: width - 1, height - 1
+  for (int i = 0; i < n; i++) {
+    drop[i] = 0;
+    const modsx_keypoint &k = regs[i].det_kp;
+    double c[2] = {k.x, k.y};
+    double m[2][2] = {{k.a11, k.a12}, {k.a21, k.a22}};
+    double hi1[2] = {1.0, 1.0};    // |Hi_r0| + |Hi_r1| of the row (the identity view copies the shape: no products, e64 over-estimates)
+    if (!eye) {
+      c[0] = (Hi[0] * k.x + Hi[1] * k.y + Hi[2]);
+      c[1] = (Hi[3] * k.x + Hi[4] * k.y + Hi[5]);
+      m[0][0] = (Hi[0] * k.a11 + Hi[1] * k.a21);
+      m[0][1] = (Hi[0] * k.a12 + Hi[1] * k.a22);
+      m[1][0] = (Hi[3] * k.a11 + Hi[4] * k.a21);
+      m[1][1] = (Hi[3] * k.a12 + Hi[4] * k.a22);
+      hi1[0] = fabs(Hi[0]) + fabs(Hi[1]);
+      hi1[1] = fabs(Hi[3]) + fabs(Hi[4]);
+    }
+    const double box = boxk * k.s;
+    const double a1 = fabs(k.a11) + fabs(k.a12) + fabs(k.a21) + fabs(k.a22);
+    if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(m[0][0] + m[0][1] + m[1][0] + m[1][1]) || !std::isfinite(a1) ||
+        !std::isfinite(hi1[0] + hi1[1]) || !(fabs(box) < 2e9))
+      continue;
+    // far inside the f32 range, or check_borders may meet inf - inf: a NaN corner compares false and keeps the region
+    if (!(fabs(c[0]) + fabs(c[1]) + fabs(m[0][0]) + fabs(m[0][1]) + fabs(m[1][0]) + fabs(m[1][1]) < 1e25)) continue;
+    if (!((c[0] < orig_w) && (c[1] < orig_h) && (c[0] > 0) && (c[1] > 0))) { drop[i] = 1; continue; }
+    const double hw = fabs((double)(float)ceil((double)(float)(int)box / 2.0));    // check_borders' hw of res_w = (int)(boxk * s)
+    for (int r = 0; r < 2; r++) {
+      const double d = hw * sqrt(m[r][0] * m[r][0] + m[r][1] * m[r][1]);
+      const double e64 = hw * 0x1p-50 * hi1[r] * a1;
+      const double margin = 0x1p-17 * (fabs(c[r]) + 3.0 * d) + 32.0 * e64;
+      if (!std::isfinite(d) || !std::isfinite(margin)) continue;
+      if (c[r] - d < 1.0 - margin || c[r] + d > lim[r] + margin) drop[i] = 1;
+    }
+  }
 }
 
 // DescribeRegions<SIFTDescriptor>, synth-detection.hpp:169-255, for a batch.  Descriptors stay in HBM
@@ -1291,10 +1382,12 @@ int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_
   DescSet ds;
   rc = resolve_descs(pp, nullptr, ds);
   if (rc) return rc;
-  rc = detect_orientation_batch(c, imgs, n, regs, pp.ori_mrSize, pp.ori_patchSize, ds.half() ? 1 : 0, pp.ori_maxAngles, pp.ori_threshold,
-                                0, oriented);
-  if (rc) return rc;
   const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  OriReproj rp[MAXB];     // the reprojection below: identity, the image's own size
+  for (int i = 0; i < n; i++) rp[i] = {eye, imgs[i]->cols, imgs[i]->rows};
+  rc = detect_orientation_batch(c, imgs, n, regs, pp.ori_mrSize, pp.ori_patchSize, ds.half() ? 1 : 0, pp.ori_maxAngles, pp.ori_threshold,
+                                0, oriented, rp);
+  if (rc) return rc;
   for (int i = 0; i < n; i++) {
     int m = reproject_regions(oriented[i].data(), (int)oriented[i].size(), eye, imgs[i]->cols, imgs[i]->rows);
     oriented[i].resize(m);

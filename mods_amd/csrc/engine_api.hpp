@@ -23,11 +23,18 @@ int detect_scalespace_batch(modsx_ctx *c, const modsx_image *const *imgs, int n,
 int detect_keypoints_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &par,
                            const double *tilts, const double *zooms, std::vector<modsx_keypoint> *out);
 void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out);
+// reproj (optional, one entry per image): what the caller's reproject_regions will be called with.  A region that
+// reproject_certain_drop flags for it is treated like one at the view's border: no orientation job and no output entry,
+// also under addUpRight (MODSX_ORI_PREFILTER=0 switches this off)
+struct OriReproj { const double *H; int orig_w, orig_h; };
 int detect_orientation_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *in,
                              double mrSize, int patchSize, int doHalfSIFT, int maxAngNum, double th, int addUpRight,
-                             std::vector<modsx_region> *out);
+                             std::vector<modsx_region> *out, const OriReproj *reproj = nullptr);
 int reproject_regions(modsx_region *regs, int n, const double *H, int orig_w, int orig_h);
 int reproject_regions_box(modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk);
+// drop[i] = 1: reproject_regions_box removes region i whatever rotation is applied to its shape first (engine.hip)
+void reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk, unsigned char *drop);
+void orientation_counts(unsigned long long *launched, unsigned long long *skipped, bool reset);
 // The descriptor classes one step carries (modsx_pair_params / modsx_ladder_step n_desc, desc_types, desc_ratios resolved):
 // `Descriptors=` and `FGINNThreshold=` of a [DetectorN] section.  half(): the step orients with doHalfSIFT = true
 // (imagerepresentation.cpp:693-706, 1259-1264).

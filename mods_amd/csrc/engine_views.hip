@@ -405,8 +405,10 @@ int detect_describe_items(modsx_ctx *c, const modsx_image *const *itemImg, const
       });
       // DetectOrientation(..., HalfSIFT_like_desc, ...): one oriented list for every descriptor of the step
       // (imagerepresentation.cpp:1254-1268, 1288-1296)
+      OriReproj rp[MAXB];     // the reprojection below
+      for (int i = 0; i < n; i++) rp[i] = {Hs[i], gimg[i]->cols, gimg[i]->rows};
       rc = detect_orientation_batch(c, cimg, n, r0, pp.ori_mrSize, pp.ori_patchSize, oriHalf, pp.ori_maxAngles, pp.ori_threshold,
-                                    0, ro);
+                                    0, ro, rp);
     }
     t3 = tnow();
     tq = t3;
