@@ -489,6 +489,62 @@ int modsx_match_ladder(modsx_ctx *ctx, const modsx_image *img1, const modsx_imag
                        const modsx_ladder_step *steps, int nsteps, int min_matches, const modsx_pair_params *par,
                        modsx_pair_result *res, int *steps_done);
 
+/* ---- stored image representations: describe once, match against many ---------------------------------------------------
+ * modsx_rep is the reference's ImageRepresentation (imagerepresentation.hpp): one region list with its descriptors per
+ * (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER}) x (descriptor type MODSX_DESC_*) class -- RegionVectorMap[det][desc].  It lives
+ * on the device of the context that made it and owns its buffers (no context's scratch), so it outlives calls.  Besides the
+ * [n][128] u8 descriptors a class keeps them in the matcher's packed train form, rebuilt whole at the end of every
+ * modsx_rep_add_views / modsx_rep_append on the adding context's stream and waited for there: a match that takes the
+ * representation as its train side never packs it again.
+ *   A representation is changed by one thread at a time.  Otherwise it is read-only: any context of its device may match
+ * against it, also at the same time (as with modsx_db).  Free it after every call that uses it has returned.
+ *   The sharded calls do not take representations. */
+typedef struct modsx_rep modsx_rep;
+modsx_rep *modsx_rep_create(modsx_ctx *ctx);
+void modsx_rep_free(modsx_ctx *ctx, modsx_rep *rep);
+/* One step of SynthDetectDescribeKeypoints + AddRegions (imagerepresentation.cpp:603-2047, :552-600) for one image: what one
+ * image side of a modsx_match_ladder step does.  The step's views are synthesised, detected with step->detector, oriented once
+ * and described with every descriptor of the step (step->n_desc, else par's list, else par->desc_type); each of those classes
+ * receives the step's regions, ids re-based onto its own list.  step->match_ratio / desc_ratios are not used.  Returns the
+ * regions added to each class of the step. */
+int modsx_rep_add_views(modsx_ctx *ctx, modsx_rep *rep, const modsx_image *img, const modsx_ladder_step *step,
+                        const modsx_pair_params *par);
+/* LoadRegions (read_pre_extracted, mods.cpp:236-241): n regions and their [n][128] descriptors from the caller, appended to one
+ * class with the ids as given.  dtype 0 = u8, 1 = f32 holding the integers 0..255 (anything else -- fractions, values out of
+ * range, NaN, another dtype -- is MODSX_ERR_ARG).  Returns n. */
+int modsx_rep_append(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const void *desc, int dtype,
+                     int n);
+/* The regions and u8 descriptors of one class as malloc'd copies (modsx_free); either pointer may be NULL.  Returns n. */
+int modsx_rep_class(modsx_ctx *ctx, const modsx_rep *rep, int detector, int desc_type, modsx_region **regs, unsigned char **desc_u8);
+/* Stage tap: the MatchFlannFGINN records of one class, rep1 the queries, rep2 (pre-packed) the trains with the positions
+ * reproj_kp.x, y of its regions -- what modsx_match_fginn_device returns for the same descriptors and positions. */
+int modsx_rep_match_fginn(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep *rep2, int detector, int desc_type, double ratio,
+                          double contradDist, int nn, modsx_tentative **out);
+/* CorrespondenceBank::MatchImgReps(ImgRep1, ImgRep2) (correspondencebank.cpp:291-347) + GetCorresponcesVector("All", "All") +
+ * DuplicateFiltering + LORANSACFiltering (H or F per par) of rep1 against each of n partners: results[i] is what
+ * modsx_match_ladder leaves for a pair whose two representations hold these classes.
+ *   classes: the classes to match and to verify, each with its FGINN ratio.  n_classes == 0: every class that is non-empty in
+ * rep1 or in the partner, with the ratio par gives its descriptor (desc_ratios of par's list; a descriptor par does not list,
+ * or a ratio that is not positive: par->match_ratio).  Classes are concatenated in map order -- descriptor types 3, 2, 1, 0,
+ * HessianAffine before MSER inside a type -- and the tentatives' indices refer to that concatenation.
+ *   The contexts take groups of up to 4 partners off a shared counter; a group costs one matcher launch set per class (problems
+ * with an empty side are left out), verification runs on helper threads as in modsx_match_pairs_views.  A database attached
+ * to the contexts applies to the RootSIFT classes (modsx_set_fginn_db; all contexts the same database, or none).  A partner
+ * without regions gives the zeroed result with H = -1 and n_regions1 set.  Returns n. */
+typedef struct { int detector, desc_type; double ratio; } modsx_rep_class_sel;
+int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
+                     const modsx_rep_class_sel *classes, int n_classes, const modsx_pair_params *par, modsx_pair_result *results);
+/* The loop of mods_multi.cpp:232-379: one image against n partners over the iteration ladder.  Per step the representation of
+ * img1 grows ONCE and every partner's grows (the images are dealt over the contexts), the classes of the step's detector are
+ * re-matched for every partner with the step's ratios -- the other classes keep their tentatives, as in modsx_match_ladder --
+ * and every partner is verified.  The loop ends after the first step in which ANY partner reached min_matches verified
+ * correspondences (GetAtLeastOneImageMatch, mods_multi.cpp:230-232, 365-367); all partners finish that step.  results[i] is what
+ * modsx_match_ladder(img1, imgs2[i], steps, *steps_done, min_matches = infinity) returns.  Restrictions are those of
+ * modsx_match_ladder.  The images must live on the device of the contexts.  Returns n. */
+int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image *img1, const modsx_image *const *imgs2, int n,
+                            const modsx_ladder_step *steps, int nsteps, int min_matches, const modsx_pair_params *par,
+                            modsx_pair_result *results, int *steps_done);
+
 /* ---- view-sharded multi-GPU path (one process per GPU, RCCL over xGMI) ------------------------------------------------
  * The reference's unit of parallelism is the synthesised view (`#pragma omp parallel for` over views,
  * imagerepresentation.cpp:612-622); views meet only in AddRegions' ordered concatenation (:2044-2045, ids re-based by

@@ -84,6 +84,10 @@ class PairResult(C.Structure):
                 ("ransac_inlier", C.c_void_p), ("verified", C.c_void_p)]
 
 
+class RepClassSel(C.Structure):
+    _fields_ = [("detector", C.c_int), ("desc_type", C.c_int), ("ratio", C.c_double)]
+
+
 EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "modsx_destroy", "modsx_synchronize",
            "modsx_default_hessaff_params", "modsx_default_pair_params", "modsx_image_upload", "modsx_image_update",
            "modsx_image_wrap_device", "modsx_image_free", "modsx_image_download", "modsx_detect_affine_keypoints",
@@ -101,7 +105,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_device_unpack", "modsx_verify_device_stats", "modsx_verify_device_timing", "modsx_comm_set_exchange",
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
-           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop"]
+           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop",
+           "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
+           "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -167,6 +173,19 @@ def lib():
         L.modsx_set_fginn_db.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_rep_create.restype = C.c_void_p
+        L.modsx_rep_create.argtypes = [C.c_void_p]
+        L.modsx_rep_free.restype = None
+        L.modsx_rep_free.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_rep_add_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_rep_append.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.modsx_rep_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.modsx_rep_match_fginn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                            C.c_void_p]
+        L.modsx_match_reps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p]
+        L.modsx_match_one_to_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -430,6 +449,69 @@ class Db(object):
             self.h = None
 
 
+def _ladder_steps(steps):
+    """(views, match_ratio[, detector[, descs]]) tuples -> (LadderStep array, the view arrays it points into)."""
+    arr = (LadderStep * len(steps))()
+    keep = []
+    for i, st in enumerate(steps):
+        va = _view_array(st[0])
+        keep.append(va)
+        arr[i].views = C.cast(va, C.c_void_p)
+        arr[i].nviews = len(st[0])
+        arr[i].match_ratio = float(st[1])
+        arr[i].detector = int(st[2]) if len(st) > 2 else 0
+        if len(st) > 3 and st[3] is not None:
+            _set_descs(arr[i], st[3])
+    return arr, keep
+
+
+class Rep(object):
+    """A stored image representation (modsx_rep): the regions and descriptors of one image per (detector, descriptor) class,
+    resident in HBM with their packed matcher form.  Describe once with add_views / append, match against many with
+    match_reps."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = lib().modsx_rep_create(ctx.h)
+        if not self.h:
+            raise RuntimeError("modsx_rep_create failed: " + _err())
+
+    def add_views(self, img, views, params, detector=0, descs=None, ctx=None):
+        """One step of SynthDetectDescribeKeypoints + AddRegions; descs = [(descriptor type, ratio), ...] as in match_ladder's
+        steps (the ratios are not used here).  Returns the regions added to each class of the step."""
+        arr, keep = _ladder_steps([(views, 0.0, detector, descs)])
+        return _check(lib().modsx_rep_add_views((ctx or self.ctx).h, self.h, img.h, arr, C.addressof(params)), "rep_add_views")
+
+    def append(self, regs, desc, detector=0, desc_type=1, ctx=None):
+        """LoadRegions: regions (REGION records) and their [n][128] descriptors (uint8, or anything convertible to float32)."""
+        regs = np.ascontiguousarray(regs, REGION)
+        d = np.ascontiguousarray(desc)
+        if d.dtype != np.uint8:
+            d = np.ascontiguousarray(d, np.float32)
+        if d.shape != (len(regs), 128):
+            raise ValueError("rep.append: [n][128] descriptors for n regions are expected")
+        return _check(lib().modsx_rep_append((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs), _p(d),
+                                             0 if d.dtype == np.uint8 else 1, len(regs)), "rep_append")
+
+    def regions(self, detector=0, desc_type=1, want_desc=True):
+        """(regions, [n][128] uint8 descriptors) of one class; want_desc=False: the regions only."""
+        regs, desc = C.c_void_p(), C.c_void_p()
+        n = _check(lib().modsx_rep_class(self.ctx.h, self.h, int(detector), int(desc_type), C.byref(regs),
+                                         C.byref(desc) if want_desc else None), "rep_class")
+        r = _take(regs, n, REGION)
+        if not want_desc:
+            return r
+        return r, _take(desc, n * 128, np.dtype(np.uint8)).reshape(n, 128)
+
+    def count(self, detector=0, desc_type=1):
+        return _check(lib().modsx_rep_class(self.ctx.h, self.h, int(detector), int(desc_type), None, None), "rep_class")
+
+    def free(self):
+        if self.h:
+            lib().modsx_rep_free(self.ctx.h, self.h)
+            self.h = None
+
+
 class Context(object):
     """One modsx_ctx (one HIP stream).  Raises if no gfx950 device is available."""
 
@@ -618,6 +700,13 @@ class Context(object):
         n = _check(lib().modsx_match_fginn_device(self._c(), C.c_void_p(d1_ptr), int(n1), C.c_void_p(d2_ptr), int(n2),
                                                   _p(pos2), C.c_double(ratio), C.c_double(contrad_dist), nn,
                                                   C.byref(out)), "match_fginn_device")
+        return _take(out, n, TENT)
+
+    def rep_match_fginn(self, rep1, rep2, detector=0, desc_type=1, ratio=0.8, contrad_dist=30.0, nn=50):
+        """MatchFlannFGINN of one class of two stored representations: rep1 the queries, rep2 (pre-packed) the trains."""
+        out = C.c_void_p()
+        n = _check(lib().modsx_rep_match_fginn(self.h, rep1.h, rep2.h, int(detector), int(desc_type), C.c_double(ratio),
+                                               C.c_double(contrad_dist), int(nn), C.byref(out)), "rep_match_fginn")
         return _take(out, n, TENT)
 
     def match_pair_views(self, img1, img2, views, params):
@@ -928,6 +1017,36 @@ def match_pairs_views(ctxs, imgs1, imgs2, views, params, arrays=True):
     res = (PairResult * n)()
     _check(lib().modsx_match_pairs_views(carr, len(ctxs), a1, a2, n, arr, len(views), C.byref(params), res), "match_pairs_views")
     return [_unpack_pair_result(res[i], arrays) for i in range(n)]
+
+
+def match_reps(ctxs, rep1, reps2, params, classes=None, arrays=True):
+    """modsx_match_reps: MatchImgReps + verification of rep1 against every representation of reps2 over several contexts.
+    classes = [(detector, descriptor type, ratio), ...]; None: every non-empty class with the ratio params gives its descriptor."""
+    n = len(reps2)
+    carr = (C.c_void_p * max(1, len(ctxs)))(*[c.h for c in ctxs])
+    rarr = (C.c_void_p * max(1, n))(*[r.h for r in reps2])
+    classes = classes or []
+    sel = (RepClassSel * max(1, len(classes)))()
+    for i, (det, typ, ratio) in enumerate(classes):
+        sel[i].detector, sel[i].desc_type, sel[i].ratio = int(det), int(typ), float(ratio)
+    res = (PairResult * max(1, n))()
+    _check(lib().modsx_match_reps(carr, len(ctxs), rep1.h, rarr, n, sel, len(classes), C.addressof(params), res), "match_reps")
+    return [_unpack_pair_result(res[i], arrays) for i in range(n)]
+
+
+def match_one_to_many(ctxs, img1, imgs2, steps, params, min_matches=10, arrays=True):
+    """modsx_match_one_to_many (the loop of mods_multi.cpp): img1 against every image of imgs2 over the ladder `steps` (as in
+    Context.match_ladder); the loop ends after the first step in which any partner reached min_matches verified.
+    Returns (list of per-partner results, steps executed)."""
+    n = len(imgs2)
+    carr = (C.c_void_p * max(1, len(ctxs)))(*[c.h for c in ctxs])
+    a2 = (C.c_void_p * max(1, n))(*[im.h for im in imgs2])
+    arr, keep = _ladder_steps(steps)
+    res = (PairResult * max(1, n))()
+    done = C.c_int(0)
+    _check(lib().modsx_match_one_to_many(carr, len(ctxs), img1.h, a2, n, arr, len(steps), int(min_matches), C.addressof(params),
+                                         res, C.byref(done)), "match_one_to_many")
+    return [_unpack_pair_result(res[i], arrays) for i in range(n)], done.value
 
 
 def _unpack_pair_result(res, arrays=True):

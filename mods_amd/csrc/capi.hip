@@ -670,6 +670,197 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
   return n_pairs;
 }
 
+// ---- stored representations: one against many (engine_reps.hip) ---------------------------------------------------------------
+// One round of MatchImgReps + verification of rep1 against n partners: the contexts take groups of up to MATCH_MAXB partners off
+// a shared counter, a group costs one matcher launch set per class of sel; every partner's tentatives (tents[i], the classes of
+// sel replaced, the others kept) are verified over the classes `present` marks, on helper threads while the contexts go on.
+// results[i] must own nothing or the arrays of an earlier round (released here).  The round is over when it returns.
+static int reps_round(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
+                      const modsx_rep_class_sel *sel, int nsel, unsigned present, const modsx_pair_params &pp, mx::RepTents *tents,
+                      modsx_pair_result *results) {
+  std::atomic<int> next(0), failed(0);
+  std::string firstErr;
+  std::mutex mu;
+  struct Queue {
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<mx::VerifyTask> q;
+    bool done = false;
+  } vq;
+  int group = (n + n_ctx - 1) / n_ctx;       // the group shrinks so that all contexts get work when there are few partners
+  if (group > mx::MATCH_MAXB) group = mx::MATCH_MAXB;
+  if (group < 1) group = 1;
+  auto take = [&](mx::VerifyTask &t, bool wait) {
+    std::unique_lock<std::mutex> lk(vq.m);
+    if (wait) vq.cv.wait(lk, [&] { return vq.done || !vq.q.empty(); });
+    if (vq.q.empty()) return false;
+    t = std::move(vq.q.front());
+    vq.q.pop_front();
+    return true;
+  };
+  auto helper = [&]() {
+    ThreadCpu cpu(g_cpuHelperUs);
+    mx::VerifyTask t;
+    while (take(t, true)) { hipSetDevice(t.dev); verify_timed(t, pp); }
+  };
+  auto worker = [&](int w) {
+    modsx_ctx *c = ctxs[w];
+    ThreadCpu cpu(g_cpuWorkerUs);
+    hipSetDevice(c->dev);
+    for (;;) {
+      if (failed.load()) break;
+      const int i = next.fetch_add(group);
+      if (i >= n) break;
+      const int g = (n - i) < group ? (n - i) : group;
+      mx::RepTents *tp[mx::MATCH_MAXB];
+      for (int k = 0; k < g; k++) tp[k] = &tents[i + k];
+      const int rc = mx::reps_match_group(c, rep1, reps2 + i, g, sel, nsel, pp, tp);
+      if (rc) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!failed.exchange(rc)) firstErr = mx::last_error();
+        continue;
+      }
+      for (int k = 0; k < g; k++) {
+        mx::VerifyTask task;
+        modsx_pair_result_release(&results[i + k]);
+        mx::reps_verify_task(rep1, reps2[i + k], present, tents[i + k], &results[i + k], c->dev, task);
+        { std::lock_guard<std::mutex> lk(vq.m); vq.q.push_back(std::move(task)); }
+        vq.cv.notify_one();
+      }
+    }
+    mx::VerifyTask t;      // out of partners: help with the verifications still queued (see modsx_match_pairs)
+    while (take(t, false)) { hipSetDevice(t.dev); verify_timed(t, pp); }
+  };
+  std::vector<std::thread> th, hth;
+  const int ngroups = (n + group - 1) / group;
+  const int nw = n_ctx < ngroups ? n_ctx : ngroups;
+  g_verifyUs = 0; g_verifyPairs = 0; g_verifyThreads = nw; g_cpuWorkerUs = 0; g_cpuHelperUs = 0;
+  { std::lock_guard<std::mutex> lk(g_verifyEachMu); g_verifyEachUs.clear(); }
+  for (int w = 0; w < verify_helpers(nw); w++) hth.emplace_back(helper);
+  for (int w = 1; w < nw; w++) th.emplace_back(worker, w);
+  if (nw > 0) worker(0);
+  for (auto &t : th) t.join();
+  { std::lock_guard<std::mutex> lk(vq.m); vq.done = true; }
+  vq.cv.notify_all();
+  for (auto &t : hth) t.join();
+  if (failed.load()) { mx::set_error(firstErr); return failed.load(); }
+  return MODSX_OK;
+}
+static int reps_contexts_ok(modsx_ctx *const *ctxs, int n_ctx, const char *who) {
+  if (!ctxs || n_ctx < 1) { mx::set_error(std::string(who) + ": at least one context is needed"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n_ctx; i++) if (!ctxs[i]) { mx::set_error(std::string(who) + ": null context"); return MODSX_ERR_ARG; }
+  for (int i = 1; i < n_ctx; i++) {
+    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error(std::string(who) + ": all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
+    if (ctxs[i]->dev != ctxs[0]->dev) { mx::set_error(std::string(who) + ": the contexts must share one device (that of the representations)"); return MODSX_ERR_ARG; }
+  }
+  return MODSX_OK;
+}
+
+int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
+                     const modsx_rep_class_sel *classes, int n_classes, const modsx_pair_params *par, modsx_pair_result *results) {
+  { const int rc = reps_contexts_ok(ctxs, n_ctx, "modsx_match_reps"); if (rc) return rc; }
+  NEED(rep1); NEED(par);
+  if (n < 0 || n_classes < 0 || n_classes > 8 || (n > 0 && (!reps2 || !results)) || (n_classes > 0 && !classes)) {
+    mx::set_error("modsx_match_reps: bad argument");
+    return MODSX_ERR_ARG;
+  }
+  for (int i = 0; i < n; i++) NEED(reps2[i]);
+  for (int i = 0; i <= n; i++)
+    if ((i ? reps2[i - 1] : rep1)->dev != ctxs[0]->dev) { mx::set_error("modsx_match_reps: a representation lives on another device than the contexts"); return MODSX_ERR_ARG; }
+  modsx_rep_class_sel sel[8];
+  int nsel = 0;
+  unsigned present = 0;
+  if (n_classes > 0) {
+    for (int k = 0; k < n_classes; k++) {
+      int det;
+      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det)) { mx::set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
+      if (present >> (det * 4 + classes[k].desc_type) & 1) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
+      present |= 1u << (det * 4 + classes[k].desc_type);
+      sel[nsel++] = classes[k];
+    }
+  } else {
+    mx::DescSet ds;
+    { const int rd = mx::resolve_descs(*par, nullptr, ds); if (rd) return rd; }
+    present = 0xff;
+    for (int t = 3; t >= 0; t--)
+      for (int d = 0; d < 2; d++) {
+        if (rep1->slot[d][t].regs.empty()) continue;       // no queries: no partner has tentatives in this class
+        double ratio = par->match_ratio;
+        for (int j = 0; j < ds.n; j++) if (ds.type[j] == t && ds.ratio[j] > 0) ratio = ds.ratio[j];
+        sel[nsel].detector = d ? MODSX_DET_MSER : MODSX_DET_HESSIAN; sel[nsel].desc_type = t; sel[nsel].ratio = ratio;
+        nsel++;
+      }
+  }
+  for (int i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
+  if (n == 0) return 0;
+  DeviceGuard restoreCallerDevice;
+  std::vector<mx::RepTents> tents((size_t)n);
+  const int rc = reps_round(ctxs, n_ctx, rep1, reps2, n, sel, nsel, present, *par, tents.data(), results);
+  if (rc) { for (int i = 0; i < n; i++) modsx_pair_result_release(&results[i]); return rc; }
+  return n;
+}
+
+int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image *img1, const modsx_image *const *imgs2, int n,
+                            const modsx_ladder_step *steps, int nsteps, int min_matches, const modsx_pair_params *par,
+                            modsx_pair_result *results, int *steps_done) {
+  { const int rc = reps_contexts_ok(ctxs, n_ctx, "modsx_match_one_to_many"); if (rc) return rc; }
+  NEED(img1); NEED(steps); NEED(par);
+  if (n < 0 || nsteps <= 0 || (n > 0 && (!imgs2 || !results))) { mx::set_error("modsx_match_one_to_many: bad argument"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) NEED(imgs2[i]);
+  for (int s = 0; s < nsteps; s++)
+    if (!steps[s].views || steps[s].nviews <= 0) { mx::set_error("modsx_match_one_to_many: empty step"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
+  if (steps_done) *steps_done = 0;
+  if (n == 0) return 0;
+  DeviceGuard restoreCallerDevice;
+  // image 0 of the call is img1, image i + 1 partner i: one representation each, freed before the call returns
+  std::vector<modsx_rep *> reps((size_t)n + 1, nullptr);
+  for (auto &r : reps) r = modsx_rep_create(ctxs[0]);
+  std::vector<mx::RepTents> tents((size_t)n);
+  int rc = MODSX_OK, step = 0;
+  bool reached = false;
+  for (; step < nsteps && !reached && !rc; step++) {
+    // SynthDetectDescribeKeypoints + AddRegions of the step: the n + 1 images come off a shared counter
+    std::atomic<int> next(0), failed(0);
+    std::string firstErr;
+    std::mutex mu;
+    auto grow = [&](int w) {
+      hipSetDevice(ctxs[w]->dev);
+      for (;;) {
+        if (failed.load()) break;
+        const int i = next.fetch_add(1);
+        if (i > n) break;
+        const int ra = mx::rep_add_views(ctxs[w], reps[i], i ? imgs2[i - 1] : img1, steps[step], *par);
+        if (ra < 0) {
+          std::lock_guard<std::mutex> lk(mu);
+          if (!failed.exchange(ra)) firstErr = mx::last_error();
+        }
+      }
+    };
+    {
+      std::vector<std::thread> th;
+      const int nw = n_ctx < n + 1 ? n_ctx : n + 1;
+      for (int w = 1; w < nw; w++) th.emplace_back(grow, w);
+      grow(0);
+      for (auto &t : th) t.join();
+    }
+    if (failed.load()) { rc = failed.load(); mx::set_error(firstErr); break; }
+    // MatchImgReps re-matches the classes of the step's detector with the step's ratios; the verified set comes from all classes
+    mx::DescSet ds;
+    rc = mx::resolve_descs(*par, &steps[step], ds);
+    if (rc) break;
+    modsx_rep_class_sel sel[MODSX_MAX_DESC];
+    for (int j = 0; j < ds.n; j++) { sel[j].detector = steps[step].detector == MODSX_DET_MSER ? MODSX_DET_MSER : MODSX_DET_HESSIAN; sel[j].desc_type = ds.type[j]; sel[j].ratio = ds.ratio[j]; }
+    rc = reps_round(ctxs, n_ctx, reps[0], reps.data() + 1, n, sel, ds.n, 0xff, *par, tents.data(), results);
+    if (rc) break;
+    for (int i = 0; i < n; i++) reached = reached || results[i].n_verified >= min_matches;
+  }
+  for (auto &r : reps) modsx_rep_free(ctxs[0], r);
+  if (rc) { for (int i = 0; i < n; i++) modsx_pair_result_release(&results[i]); return rc; }
+  if (steps_done) *steps_done = step;
+  return n;
+}
+
 void modsx_pair_result_release(modsx_pair_result *res) {
   if (!res) return;
   free(res->tentatives); free(res->ransac_inlier); free(res->verified);

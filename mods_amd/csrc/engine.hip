@@ -1037,8 +1037,10 @@ void rows_to_tentatives(const MatchRow *rows, int n1, int nn, std::vector<modsx_
 int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                        const double *const *pos2Host, double ratioT, double contradDist, int nn,
                        std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev, const DbSet *db,
-                       std::vector<double> *d2byDB) {
+                       std::vector<double> *d2byDB, const void *const *trainPack) {
   // pos2Dev (optional, unsharded branch): the positions already live on the device; pos2Host is then not read
+  // trainPack (optional, unsharded branch): trainPack[i] != nullptr = the trains of problem i were packed there, with their
+  // positions (a stored image representation): d2[i] and the positions of that problem are not read, nothing is uploaded for it
   // db (optional, unsharded branch): MatchFlannFGINNPlusDB -- behind the matcher's launches, on the same stream, the queries that
   // give a record are selected and swept against the database (kernels_dbnn.hip); their dDB words travel down with the rows
   CtxBusy busy(c);
@@ -1094,7 +1096,8 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
     out[i].clear();
     if (d2byDB) d2byDB[i].clear();
     if (n1[i] <= 0 || n2[i] <= 0) continue;
-    posOfs[nl] = posB; posB += align_up((size_t)n2[i] * 16, 256);
+    posOfs[nl] = posB;
+    if (!(trainPack && trainPack[i])) posB += align_up((size_t)n2[i] * 16, 256);
     rowOfs[nl] = rowB; rowB += align_up((size_t)n1[i] * sizeof(MatchRow), 256);
     workOfs[nl] = workB; workB += align_up(match_workspace_bytes(n1[i], n2[i]), 256);
     live[nl++] = i;
@@ -1115,24 +1118,26 @@ int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int
   const double *ppos[MATCH_MAXB];
   MatchRow *prow[MATCH_MAXB];
   void *pwork[MATCH_MAXB];
+  const void *ppack[MATCH_MAXB];
   int pn1[MATCH_MAXB], pn2[MATCH_MAXB];
   double work = 0;
   for (int k = 0; k < nl; k++) {
     const int i = live[k];
     pd1[k] = d1[i]; pd2[k] = d2[i]; pn1[k] = n1[i]; pn2[k] = n2[i];
-    ppos[k] = pos2Dev ? pos2Dev[i] : (const double *)((char *)c->pos2.p + posOfs[k]);
+    ppack[k] = trainPack ? trainPack[i] : nullptr;
+    ppos[k] = ppack[k] ? nullptr : pos2Dev ? pos2Dev[i] : (const double *)((char *)c->pos2.p + posOfs[k]);
     prow[k] = (MatchRow *)((char *)c->matchRows.p + rowOfs[k]);
     pwork[k] = (char *)c->matchWork.p + workOfs[k];
-    if (!pos2Dev) memcpy(hpos + posOfs[k], pos2Host[i], (size_t)n2[i] * 16);
+    if (!pos2Dev && !ppack[k]) memcpy(hpos + posOfs[k], pos2Host[i], (size_t)n2[i] * 16);
     work += 2.0 * n1[i] * (double)n2[i] * 128;
   }
-  if (!pos2Dev) MX_HIP(ctx_copy(c, c->pos2.p, hpos, posB, hipMemcpyHostToDevice));
+  if (!pos2Dev && posB) MX_HIP(ctx_copy(c, c->pos2.p, hpos, posB, hipMemcpyHostToDevice));
   {
     // K_MATCH = every launch of the problem(s); K_MATCH_SWEEP1 = the one launch that carries the 2 N M 128 contraction
     hipEvent_t evS1[2];
     const bool tS1 = prof_reserve(c, K_MATCH_SWEEP1, work, evS1);
     ProfScope ps(c, K_MATCH, work);
-    launch_match_batch(s, nl, pd1, pn1, pd2, pn2, ppos, sqminratio, contrDistSq, nn, prow, pwork, tS1 ? evS1 : nullptr);
+    launch_match_batch(s, nl, pd1, pn1, pd2, pn2, ppos, sqminratio, contrDistSq, nn, prow, pwork, tS1 ? evS1 : nullptr, trainPack ? ppack : nullptr);
   }
   if (db) {
     int *psel[MATCH_MAXB], *pddb[MATCH_MAXB];
@@ -1164,7 +1169,7 @@ int match_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int
 // The matcher computes on u8: the reference's SIFT-family descriptors hold the integers 0..255
 // ((int)(512 v + 0.5) clamped, siftdesc.cpp:218-274).  Anything else (fractions, values out of range, NaN) would be
 // matched with different distances than FLANN's float L2, so it is refused instead of being truncated silently.
-static bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u) {
+bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u) {
   bool ok = true;
   for (size_t i = 0; i < n; i++) {
     const float v = f[i];

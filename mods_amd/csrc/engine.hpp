@@ -277,7 +277,11 @@ constexpr int MATCH_NN_MAX = 256;   // largest `nn` of the FGINN walk (matching.
 constexpr int MATCH_MAXB = 4;   // independent matching problems per launch set (blockIdx.z)
 void launch_match_batch(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                         const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
-                        void *const *workspace, hipEvent_t *evSweep1 = nullptr);   // evSweep1: two events recorded around sweep 1
+                        void *const *workspace, hipEvent_t *evSweep1 = nullptr,    // evSweep1: two events recorded around sweep 1
+                        const void *const *trainPack = nullptr);                   // trainPack[i]: problem i's trains were packed there
+// a train set packed once (the train side of a workspace, sized by n2 alone) and used as the train side of many problems
+size_t match_train_pack_bytes(int n2);
+void launch_match_pack_trains(hipStream_t s, const uint8_t *d2, int n2, const double *pos2, void *pack);
 void last_match_geometry(int *qs, int *fat, int *S, int *tilesPerSplit, int *ntilesUB);   // of problem 0 of the process's last launch
 // A descriptor database resident in HBM (kernels_dbnn.hip): the rows packed once into the matcher's operand form.  Read-only
 // after creation, so every context of its device may use it at the same time.

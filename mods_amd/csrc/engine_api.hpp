@@ -70,6 +70,14 @@ int detect_describe_views(modsx_ctx *c, const modsx_image *gray, const modsx_vie
                           const modsx_pair_params &pp, int view_begin, int view_step, std::vector<modsx_region> &regs,
                           float *devF, uint8_t *devU8, size_t devCapRegions, float *hostDesc, int *viewCounts,
                           const DescSet *ds = nullptr, uint8_t *const *devU8x = nullptr);
+// One image's side of a (detector, descriptor) class -- RegionVectorMap[det][desc] of one ImageRepresentation: the accumulated
+// regions, the device buffer of their [n][128] u8 descriptors and its capacity in regions.  The fused callers keep these in a
+// context's scratch for one call (engine_views.hip LadderClass), a stored representation owns them (engine_reps.hip).
+struct ClassSide { std::vector<modsx_region> *regs; size_t *cap; DevBuf *buf; };
+int class_side_reserve(modsx_ctx *c, const ClassSide &k, size_t keepRows);   // room for *k.cap regions, the first keepRows kept
+// SynthDetectDescribeKeypoints + AddRegions of one step for one image: ks[j] = the side of the step's j-th descriptor class
+int accumulate_views(modsx_ctx *c, const ClassSide *ks, const DescSet &ds, const modsx_image *img, const modsx_view *views, int nv,
+                     const modsx_pair_params &pp, modsx_comm *cm = nullptr, bool split = false);
 void ctx_worker_stop(modsx_ctx *c);   // joins the context's host thread, if it has one (ctx_destroy)
 void rebase_ids(std::vector<modsx_region> &regs, const int *viewCounts, int nv, size_t base);
 struct VerifyTask;
@@ -141,7 +149,8 @@ int match_sharded(modsx_ctx *c, modsx_comm *cm, const uint8_t *d1, int n1, const
 int match_device_batch(modsx_ctx *c, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                        const double *const *pos2Host, double ratioT, double contradDist, int nn,
                        std::vector<modsx_tentative> *out, const MatchShard *shard, const double *const *pos2Dev = nullptr,
-                       const DbSet *db = nullptr, std::vector<double> *d2byDB = nullptr);   // db: MatchFlannFGINNPlusDB; d2byDB[i] aligned with out[i]
+                       const DbSet *db = nullptr, std::vector<double> *d2byDB = nullptr,    // db: MatchFlannFGINNPlusDB; d2byDB[i] aligned with out[i]
+                       const void *const *trainPack = nullptr);                             // trainPack[i]: problem i's trains are pre-packed there
 int match_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2Host,
                  double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db = nullptr,
                  std::vector<double> *d2byDB = nullptr);
@@ -194,6 +203,23 @@ struct VerifyTask {
 };
 // deferred == nullptr: verification runs inline, pair by pair.  Otherwise the G matching problems share the matcher's
 // launches and one VerifyTask per pair is appended to *deferred instead of being verified.
+// ---- stored image representations (engine_reps.hip) ----
+// One (detector, descriptor) class of a stored representation: RegionVectorMap[det][desc].  `pack` is the train side of a
+// matcher workspace for exactly regs.size() descriptors and the regions' reproj_kp positions (kernels_match.hip).
+struct RepSlot {
+  std::vector<modsx_region> regs;
+  size_t cap = (size_t)1 << 16;     // regions `desc` has room for (grows x4)
+  DevBuf desc, pack;
+};
+// the tentatives of every class's last match against one partner (CorrespondencesMapMap[desc][det])
+struct RepTents { std::vector<modsx_tentative> t[2][4]; };
+bool rep_class_ok(int detector, int desc_type, int *det);
+int rep_add_views(modsx_ctx *c, modsx_rep *rep, const modsx_image *img, const modsx_ladder_step &st, const modsx_pair_params &pp);
+int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, const modsx_rep_class_sel *sel, int nsel,
+                     const modsx_pair_params &pp, RepTents *const *tents);
+void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, unsigned present, const RepTents &tents, modsx_pair_result *res,
+                      int dev, VerifyTask &task);
+bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u);   // false: a value that is not one of the integers 0..255
 int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_image *const *imgs2, int G,
                      const modsx_pair_params &pp, modsx_pair_result *res, std::vector<VerifyTask> *deferred = nullptr);
 int match_pair(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2, const modsx_pair_params &pp,
@@ -232,3 +258,5 @@ int loransac_h(const double *pts, const double *laf1, const double *laf2, int T,
                double confidence, int max_samples, int lo, double HLAFCoef, int doSymmCheck, unsigned seed, double *H,
                double *Hraw, unsigned char *inl, unsigned char *keep, int *data_out, int error_type = 0);
 }  // namespace mx
+
+struct modsx_rep { int dev; mx::RepSlot slot[2][4]; };   // slot[det][type]: det 0 = HessianAffine, 1 = MSER; type = MODSX_DESC_*

@@ -514,9 +514,6 @@ struct LadderClass {
   std::vector<modsx_tentative> tents;
 };
 
-// Append the regions + u8 descriptors of one step's views to the accumulated lists of one image side
-// (SynthDetectDescribeKeypoints + AddRegions, imagerepresentation.cpp:603-2047).  The accumulator is re-allocated
-// (device-to-device copy) when the step does not fit.
 // A peer / half context is driven by ONE host thread for as long as it lives: a thread spawned per call starts with a cold
 // allocator arena and fresh thread_local scratch every time (page faults worth milliseconds on some calls of a lone pair).
 struct CtxWorker {
@@ -568,42 +565,47 @@ void ctx_worker_stop(modsx_ctx *c) {
   c->worker = nullptr;
 }
 
+// The descriptor accumulator of one class side holds *k.cap regions, the first keepRows of them kept (device-to-device copy)
+int class_side_reserve(modsx_ctx *c, const ClassSide &k, size_t keepRows) {
+  DevBuf &buf = *k.buf;
+  if (buf.cap >= *k.cap * 128) return MODSX_OK;
+  DevBuf bigger;
+  if (!bigger.ensure(*k.cap * 128)) return MODSX_ERR_NOMEM;
+  if (keepRows) {
+    MX_HIP(hipMemcpyAsync(bigger.p, buf.p, keepRows * 128, hipMemcpyDeviceToDevice, c->stream));
+    MX_HIP(ctx_sync(c));
+  }
+  buf.release();
+  buf = bigger;
+  return MODSX_OK;
+}
+// Append the regions + u8 descriptors of one step's views to the accumulated lists of one image side
+// (SynthDetectDescribeKeypoints + AddRegions, imagerepresentation.cpp:603-2047).  The accumulator is re-allocated
+// (device-to-device copy) when the step does not fit.
 // split = true (a lone pair on an otherwise idle GPU): the views [m, nv) of the step run on a helper context -- its own
 // stream, scratch and host thread -- beside the views [0, m) on c; m balances the view areas.  A view's regions and
 // descriptors do not depend on which launch set it is part of, so the step is the concatenation of the two parts (the
 // second part's descriptors are moved behind the first's once its size is known).
-static int accumulate_views(modsx_ctx *c, LadderClass *const *ks, const DescSet &ds, int side, const modsx_image *img,
-                            const modsx_view *views, int nv, const modsx_pair_params &pp, modsx_comm *cm, bool split = false) {
-  // ks[j] = the class of the step's j-th descriptor: all of them receive the step's regions (one oriented list for the
-  // whole step), each its own descriptors.  Their lists may differ in length (earlier steps may have carried other
+int accumulate_views(modsx_ctx *c, const ClassSide *ks, const DescSet &ds, const modsx_image *img,
+                     const modsx_view *views, int nv, const modsx_pair_params &pp, modsx_comm *cm, bool split) {
+  // ks[j] = this image's side of the class of the step's j-th descriptor: all of them receive the step's regions (one oriented
+  // list for the whole step), each its own descriptors.  Their lists may differ in length (earlier steps may have carried other
   // descriptors), so every class has its own base.
   const int nd = ds.n;
   size_t base[MODSX_MAX_DESC];
-  for (int j = 0; j < nd; j++) base[j] = ks[j]->regs[side].size();
+  for (int j = 0; j < nd; j++) base[j] = ks[j].regs->size();
   std::vector<modsx_region> step;
   std::vector<int> counts(std::max(1, nv), 0);
   auto grow_bufs = [&]() -> int {     // the accumulated descriptors of the classes: cap regions, earlier steps' kept
-    for (int j = 0; j < nd; j++) {
-      DevBuf &buf = *ks[j]->buf[side];
-      const size_t cap = ks[j]->cap[side];
-      if (buf.cap >= cap * 128) continue;
-      DevBuf bigger;
-      if (!bigger.ensure(cap * 128)) return MODSX_ERR_NOMEM;
-      if (base[j]) {
-        MX_HIP(hipMemcpyAsync(bigger.p, buf.p, base[j] * 128, hipMemcpyDeviceToDevice, c->stream));
-        MX_HIP(ctx_sync(c));
-      }
-      buf.release();
-      buf = bigger;
-    }
+    for (int j = 0; j < nd; j++) { const int rg = class_side_reserve(c, ks[j], base[j]); if (rg) return rg; }
     return MODSX_OK;
   };
-  auto room = [&]() { size_t r = (size_t)-1; for (int j = 0; j < nd; j++) r = std::min(r, ks[j]->cap[side] - base[j]); return r; };
-  auto dst = [&](int j, size_t row) { return (uint8_t *)ks[j]->buf[side]->p + (base[j] + row) * 128; };
+  auto room = [&]() { size_t r = (size_t)-1; for (int j = 0; j < nd; j++) r = std::min(r, *ks[j].cap - base[j]); return r; };
+  auto dst = [&](int j, size_t row) { return (uint8_t *)ks[j].buf->p + (base[j] + row) * 128; };
   // the step's regions behind every class's list, ids re-based onto that list (AddRegionsToList)
   auto append = [&]() {
     for (int j = 0; j < nd; j++) {
-      std::vector<modsx_region> &acc = ks[j]->regs[side];
+      std::vector<modsx_region> &acc = *ks[j].regs;
       const size_t at = acc.size();
       acc.insert(acc.end(), step.begin(), step.end());
       size_t start = 0;
@@ -706,7 +708,7 @@ static int accumulate_views(modsx_ctx *c, LadderClass *const *ks, const DescSet 
   }
   if (cm) {   // view-sharded: this rank runs its views, the exchange appends the whole step in reference order (ids re-based)
     DevBuf *accs[MODSX_MAX_DESC];
-    for (int j = 0; j < nd; j++) accs[j] = ks[j]->buf[side];
+    for (int j = 0; j < nd; j++) accs[j] = ks[j].buf;
     int rc = detect_describe_views_sharded(c, cm, img, views, nv, pp, ds, step, accs, base, counts.data());
     if (rc) return rc;
     append();
@@ -716,8 +718,8 @@ static int accumulate_views(modsx_ctx *c, LadderClass *const *ks, const DescSet 
     { const int rg = grow_bufs(); if (rg) return rg; }
     uint8_t *xs[3] = {nd > 1 ? dst(1, 0) : nullptr, nd > 2 ? dst(2, 0) : nullptr, nd > 3 ? dst(3, 0) : nullptr};
     int rc = detect_describe_views(c, img, views, nv, pp, 0, 1, step, nullptr, dst(0, 0), room(), nullptr, counts.data(), &ds, xs);
-    if (rc == MODSX_ERR_CAPACITY && ks[0]->cap[side] < ((size_t)1 << 24)) {   // only "buffer too small" grows them
-      for (int j = 0; j < nd; j++) ks[j]->cap[side] *= 4;
+    if (rc == MODSX_ERR_CAPACITY && *ks[0].cap < ((size_t)1 << 24)) {   // only "buffer too small" grows them
+      for (int j = 0; j < nd; j++) *ks[j].cap *= 4;
       continue;
     }
     if (rc) return rc;
@@ -764,7 +766,11 @@ int match_ladder(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2,
     DescSet ds;
     { const int rd = resolve_descs(pp, &steps[step], ds); if (rd) { release_result_arrays(res); return rd; } }
     LadderClass *ks[MODSX_MAX_DESC];
-    for (int j = 0; j < ds.n; j++) ks[j] = &cls[det][ds.type[j]];
+    ClassSide sides[2][MODSX_MAX_DESC];
+    for (int j = 0; j < ds.n; j++) {
+      ks[j] = &cls[det][ds.type[j]];
+      for (int sd = 0; sd < 2; sd++) sides[sd][j] = {&ks[j]->regs[sd], &ks[j]->cap[sd], ks[j]->buf[sd]};
+    }
     modsx_pair_params ps = pp;
     ps.detector = det ? MODSX_DET_MSER : MODSX_DET_HESSIAN;
     {
@@ -782,10 +788,10 @@ int match_ladder(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2,
         modsx_ctx *pc = c->peer;
         prof_reset(pc, c->prof.enabled);
         ctx_worker_post(pc, [&]() {
-          rc1 = accumulate_views(pc, ks, ds, 1, imgs[1], steps[step].views, steps[step].nviews, ps, nullptr, true);
+          rc1 = accumulate_views(pc, sides[1], ds, imgs[1], steps[step].views, steps[step].nviews, ps, nullptr, true);
           if (rc1) err1 = last_error();
         });
-        rc0 = accumulate_views(c, ks, ds, 0, imgs[0], steps[step].views, steps[step].nviews, ps, nullptr, true);
+        rc0 = accumulate_views(c, sides[0], ds, imgs[0], steps[step].views, steps[step].nviews, ps, nullptr, true);
         ctx_worker_wait(pc);
         if (c->prof.enabled) {   // the peer's kernels belong to this call
           prof_collect(pc);
@@ -793,8 +799,8 @@ int match_ladder(modsx_ctx *c, const modsx_image *img1, const modsx_image *img2,
         }
         if (!rc0 && rc1) set_error(err1);
       } else {
-        rc0 = accumulate_views(c, ks, ds, 0, imgs[0], steps[step].views, steps[step].nviews, ps, cm);
-        if (!rc0) rc1 = accumulate_views(c, ks, ds, 1, imgs[1], steps[step].views, steps[step].nviews, ps, cm);
+        rc0 = accumulate_views(c, sides[0], ds, imgs[0], steps[step].views, steps[step].nviews, ps, cm);
+        if (!rc0) rc1 = accumulate_views(c, sides[1], ds, imgs[1], steps[step].views, steps[step].nviews, ps, cm);
       }
       if (rc0 || rc1) { release_result_arrays(res); return rc0 ? rc0 : rc1; }
     }

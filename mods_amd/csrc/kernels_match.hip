@@ -141,9 +141,13 @@ MX_D int sum8(int v) {
 //   tiles[slot >> 5] row slot & 31 = b - 128 in 16-byte slots, slot s stored at s ^ ((row >> 1) & 7); the odd class starts
 //   at tile offT.  hrow[slot] = (|b'|^2 + 2 sum b') >> 1, norm2[slot] = |b'|^2, perm[slot] = train, pos2p[slot] = position.
 //   The last workgroup knows the totals: it writes the tile geometry and the padding rows (zero row, NONE_H, -1).
+// The train half reads nothing of the queries and its output depends on the trains alone: k_match_pack runs it per call for a
+// plain problem (blockIdx.y == 1), k_match_pack_trains (TRAINS_ONLY: every workgroup is a train workgroup) once for a train set
+// that is kept (a stored image representation).
+template <bool TRAINS_ONLY>
 __device__ __forceinline__ void pack_body(const PackArgs &A) {
   const int tid = threadIdx.x;
-  if (blockIdx.y == 0) {
+  if (!TRAINS_ONLY && blockIdx.y == 0) {
     const int i = blockIdx.x * 32 + (tid >> 3);
     int s = 0;
     if (i < A.n1) {
@@ -855,15 +859,40 @@ __device__ __forceinline__ void pdf_body(const PdfArgs &A) {
 }
 
 // ---- workspace layout: ONE description used by the size query and by the launcher -------------------------------------------
+// The TRAIN side (norm2 .. geo) is sized by n2 alone and filled by the train half of the pack from the trains alone; the CALL side
+// (norm1, partial, und, pdf, counter) belongs to one (query set, train set) problem.  A workspace holds norm1, the train side, then
+// the rest of the call side; a kept train set (match_train_pack_bytes, launch_match_pack_trains) holds the train side only.
+struct MatchTrainLayout {
+  int ntilesUB, offT;
+  size_t norm2, hrow, perm, pos2p, tiles, status, geo, bytes;    // offsets from the train side's base
+};
+static MatchTrainLayout match_train_layout(int n2) {
+  MatchTrainLayout T;
+  T.ntilesUB = ntiles_ub(n2); T.offT = region_tiles(n2);
+  const size_t slots = (size_t)2 * T.offT * 32;       // two class regions
+  size_t w = 0;
+  auto take = [&](size_t bytes) { const size_t o = w; w += (bytes + 255) & ~(size_t)255; return o; };
+  T.norm2 = take(slots * 4);
+  T.hrow = take(slots * 4);
+  T.perm = take(slots * 4);
+  T.pos2p = take(slots * 16);
+  T.tiles = take(slots * 128);
+  T.status = take((size_t)((n2 + PB - 1) / PB) * 8);
+  T.geo = take(sizeof(TileGeo));
+  T.bytes = w;
+  return T;
+}
 struct MatchLayout {
-  int S, tilesPerSplit, ntilesUB, offT;
-  size_t norm1, norm2, hrow, perm, pos2p, tiles, status, geo, partial, und, pdf, counter, bytes;
+  int S, tilesPerSplit;
+  MatchTrainLayout T;
+  size_t norm1, train, partial, und, pdf, counter, bytes;         // train: base of the train side inside a workspace
 };
 static MatchLayout match_layout(int n1, int n2, int qs, bool fat) {
   MatchLayout L;
   const int QPB = s1_qpb(qs, fat);
   const int nQB = (n1 + QPB - 1) / QPB;
-  const int ntiles = ntiles_ub(n2);
+  L.T = match_train_layout(n2);
+  const int ntiles = L.T.ntilesUB;
   // one round of workgroups (one per CU); a second, partly filled round costs as much as the first.  Many query blocks
   // (N > 196 k) simply take several rounds.
 #ifdef MATCH_TRACE
@@ -878,18 +907,11 @@ static MatchLayout match_layout(int n1, int n2, int qs, bool fat) {
   tps = (tps + TPS - 1) & ~(TPS - 1);
   S = (ntiles + tps - 1) / tps;
   if (S < 1) S = 1;
-  L.S = S; L.tilesPerSplit = tps; L.ntilesUB = ntiles; L.offT = region_tiles(n2);
-  const size_t slots = (size_t)2 * L.offT * 32;       // two class regions
+  L.S = S; L.tilesPerSplit = tps;
   size_t w = 0;
   auto take = [&](size_t bytes) { const size_t o = w; w += (bytes + 255) & ~(size_t)255; return o; };
   L.norm1 = take((size_t)n1 * 4);
-  L.norm2 = take(slots * 4);
-  L.hrow = take(slots * 4);
-  L.perm = take(slots * 4);
-  L.pos2p = take(slots * 16);
-  L.tiles = take(slots * 128);
-  L.status = take((size_t)((n2 + PB - 1) / PB) * 8);
-  L.geo = take(sizeof(TileGeo));
+  L.train = take(L.T.bytes);
   L.partial = take((size_t)n1 * S * 2 * KTOP * 8);
   L.und = take((size_t)n1 * 32);
   L.pdf = take((size_t)PDF_NW * ntiles * 32 * 4);      // k_match_pdf's scratch rows (the ratio >= 1 mode)
@@ -903,6 +925,7 @@ size_t match_workspace_bytes(int n1, int n2) {     // whatever shape the launche
   for (int qs = 2; qs <= 4; qs += 2) for (int fat = 0; fat < 2; fat++) b = std::max(b, match_layout(n1, n2, qs, fat != 0).bytes);
   return b;
 }
+size_t match_train_pack_bytes(int n2) { return match_train_layout(n2).bytes; }
 
 // ---- batched entry points: blockIdx.z selects one of up to MATCH_MAXB independent problems (the pairs of a launch set).
 struct MatchProblem {
@@ -917,18 +940,35 @@ struct MatchProblem {
   UndRec *und;
   MatchRow *rows;
   MatchGeom g;
+  int packed;             // the train-side arrays point at a kept pack (launch_match_pack_trains filled them): nothing to pack here
 };
 struct MatchBatch { MatchProblem p[MATCH_MAXB]; unsigned epoch; };
+static void point_train_side(MatchProblem &P, char *base, const MatchTrainLayout &T) {
+  P.norm2 = (int *)(base + T.norm2); P.hrow = (int *)(base + T.hrow); P.perm = (int *)(base + T.perm);
+  P.pos2p = (double2 *)(base + T.pos2p); P.tiles = (unsigned char *)(base + T.tiles); P.status = (u64 *)(base + T.status);
+  P.geo = (TileGeo *)(base + T.geo);
+  P.g.ntilesUB = T.ntilesUB; P.g.offT = T.offT;
+}
+// the epoch stamps the status words of the pack's scan (nothing has to be cleared between launches)
+static unsigned next_pack_epoch() {
+  static std::atomic<unsigned> epochCtr{0};
+  unsigned ep = ++epochCtr;
+  if (ep == 0) ep = ++epochCtr;
+  return ep;
+}
 
 __global__ __launch_bounds__(256) void k_match_pack(MatchBatch b) {
   const MatchProblem &P = b.p[blockIdx.z];
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *P.counter = 0;   // the undecided count (decide adds to it): no fill launch of its own
+  if (blockIdx.y == 1 && P.packed) return;
   PackArgs A;
   A.d1 = P.d1; A.d2 = P.d2; A.pos2 = P.pos2; A.n1 = P.g.n1; A.n2 = P.g.n2; A.offT = P.g.offT; A.epoch = b.epoch;
   A.norm1 = P.norm1; A.norm2 = P.norm2; A.hrow = P.hrow; A.perm = P.perm; A.pos2p = P.pos2p; A.tiles = P.tiles;
   A.status = P.status; A.geo = P.geo;
-  pack_body(A);
+  pack_body<false>(A);
 }
+// the train half alone, for a train set that is kept: A holds the trains, their positions and the train-side arrays
+__global__ __launch_bounds__(256) void k_match_pack_trains(PackArgs A) { pack_body<true>(A); }
 #ifdef MATCH_TRACE
 // debugging aid (tools/trace_match.py): when and where every workgroup of the last k_match_sweep1 launch ran
 __device__ unsigned long long g_mtrace[16384][4];
@@ -993,40 +1033,52 @@ void last_match_geometry(int *qs, int *fat, int *S, int *tilesPerSplit, int *nti
 // Problems with n1 == 0 or n2 == 0 must be left out by the caller.  workspace[i] holds match_workspace_bytes(n1[i], n2[i]).
 static void launch_match_batch_once(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                                     const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
-                                    void *const *workspace, hipEvent_t *evSweep1);
+                                    void *const *workspace, hipEvent_t *evSweep1, const void *const *trainPack);
+// trainPack (optional): trainPack[i] != nullptr = the train side of problem i was packed by launch_match_pack_trains(.., n2[i], ..)
+// and lives there; d2[i] and pos2[i] are then not read.  A batch may mix such problems with plain ones.
 void launch_match_batch(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                         const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
-                        void *const *workspace, hipEvent_t *evSweep1) {
+                        void *const *workspace, hipEvent_t *evSweep1, const void *const *trainPack) {
   // (the four launches of a batch start from the inputs every time: issuing them twice -- MX_DUP, an experiment aid -- changes nothing)
-  MX_DUP(K_MATCH) launch_match_batch_once(s, nb, d1, n1, d2, n2, pos2, sqminratio, contrDistSq, nn, rows, workspace, evSweep1);
+  MX_DUP(K_MATCH) launch_match_batch_once(s, nb, d1, n1, d2, n2, pos2, sqminratio, contrDistSq, nn, rows, workspace, evSweep1, trainPack);
+}
+// Packs a train set that is kept: `pack` (match_train_pack_bytes(n2) bytes) receives what the train half of k_match_pack writes
+// for these trains and positions -- the same code, the same bytes.
+void launch_match_pack_trains(hipStream_t s, const uint8_t *d2, int n2, const double *pos2, void *pack) {
+  if (n2 <= 0) return;
+  MatchProblem P;
+  memset(&P, 0, sizeof P);
+  P.d2 = d2; P.pos2 = pos2; P.g.n2 = n2;
+  point_train_side(P, (char *)pack, match_train_layout(n2));
+  PackArgs A;
+  memset(&A, 0, sizeof A);
+  A.d2 = d2; A.pos2 = pos2; A.n2 = n2; A.offT = P.g.offT; A.epoch = next_pack_epoch();
+  A.norm2 = P.norm2; A.hrow = P.hrow; A.perm = P.perm; A.pos2p = P.pos2p; A.tiles = P.tiles; A.status = P.status; A.geo = P.geo;
+  hipLaunchKernelGGL(k_match_pack_trains, dim3((n2 + PB - 1) / PB), dim3(256), 0, s, A);
 }
 static void launch_match_batch_once(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, const uint8_t *const *d2, const int *n2,
                                     const double *const *pos2, double sqminratio, double contrDistSq, int nn, MatchRow *const *rows,
-                                    void *const *workspace, hipEvent_t *evSweep1) {
+                                    void *const *workspace, hipEvent_t *evSweep1, const void *const *trainPack) {
   if (nb <= 0) return;
   MatchBatch b;
   memset(&b, 0, sizeof b);
-  // the epoch stamps the status words of k_match_pack's scan (nothing has to be cleared between launches)
-  static std::atomic<unsigned> epochCtr{0};
-  unsigned ep = ++epochCtr;
-  if (ep == 0) ep = ++epochCtr;
-  b.epoch = ep;
+  b.epoch = next_pack_epoch();
   int maxN1 = 0, maxS = 0, maxWg = 0;
   const int qs = match_qsets(nb, n1[0], n2[0]);
   const bool fat = match_fat(n1[0]) && !gpu_shared();     // whole-CU workgroups only when no other context's launches want the CUs
   for (int i = 0; i < nb; i++) {
     MatchProblem &P = b.p[i];
     const MatchLayout L = match_layout(n1[i], n2[i], qs, fat);
-    P.g.n1 = n1[i]; P.g.n2 = n2[i]; P.g.S = L.S; P.g.tilesPerSplit = L.tilesPerSplit; P.g.qs = qs; P.g.ntilesUB = L.ntilesUB;
-    P.g.offT = L.offT;
+    P.g.n1 = n1[i]; P.g.n2 = n2[i]; P.g.S = L.S; P.g.tilesPerSplit = L.tilesPerSplit; P.g.qs = qs;
     char *w = (char *)workspace[i];
-    P.norm1 = (int *)(w + L.norm1); P.norm2 = (int *)(w + L.norm2); P.hrow = (int *)(w + L.hrow); P.perm = (int *)(w + L.perm);
-    P.pos2p = (double2 *)(w + L.pos2p); P.status = (u64 *)(w + L.status); P.geo = (TileGeo *)(w + L.geo);
-    P.tiles = (unsigned char *)(w + L.tiles);
+    P.packed = trainPack && trainPack[i] ? 1 : 0;
+    point_train_side(P, P.packed ? (char *)const_cast<void *>(trainPack[i]) : w + L.train, L.T);
+    P.norm1 = (int *)(w + L.norm1);
     P.partial = (int2 *)(w + L.partial);
     P.counter = (int *)(w + L.counter); P.und = (UndRec *)(w + L.und); P.pdf = (int *)(w + L.pdf);
     P.d1 = d1[i]; P.d2 = d2[i]; P.pos2 = pos2[i]; P.rows = rows[i];
-    maxN1 = std::max(maxN1, n1[i]); maxS = std::max(maxS, L.S); maxWg = std::max(maxWg, (n2[i] + PB - 1) / PB);
+    maxN1 = std::max(maxN1, n1[i]); maxS = std::max(maxS, L.S);
+    if (!P.packed) maxWg = std::max(maxWg, (n2[i] + PB - 1) / PB);
   }
   g_lastQs = qs; g_lastFat = fat ? 1 : 0; g_lastS = b.p[0].g.S; g_lastTilesPerSplit = b.p[0].g.tilesPerSplit; g_lastNtilesUB = b.p[0].g.ntilesUB;
   hipLaunchKernelGGL(k_match_pack, dim3(std::max((maxN1 + 31) / 32, maxWg), 2, nb), dim3(256), 0, s, b);
@@ -1050,7 +1102,7 @@ static void launch_match_batch_once(hipStream_t s, int nb, const uint8_t *const 
 void launch_match(hipStream_t s, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2,
                   double sqminratio, double contrDistSq, int nn, MatchRow *rows, void *workspace) {
   if (n1 <= 0 || n2 <= 0) return;
-  launch_match_batch(s, 1, &d1, &n1, &d2, &n2, &pos2, sqminratio, contrDistSq, nn, &rows, &workspace, nullptr);
+  launch_match_batch(s, 1, &d1, &n1, &d2, &n2, &pos2, sqminratio, contrDistSq, nn, &rows, &workspace, nullptr, nullptr);
 }
 
 }  // namespace mx
