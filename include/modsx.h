@@ -371,6 +371,18 @@ int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads);
  * workgroups (0 / 1), splits of the train tiles, tiles per split, upper bound of the tile count (measurement hook).  The five
  * values are written one by one: they belong together only while a single thread launches matcher work */
 int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, int *ntiles_ub);
+/* what the description stage planned on this context since modsx_create, cumulative (measurement hook); the contexts that work on
+ * its behalf (the peer of a lone multi-view pair, the chains of contexts that take parts of a view list) count with it.  Fills
+ * out[0 .. min(n, 14) - 1] and returns 14.  In order: description calls; chunks (launch sets, cut where the window arena of
+ * MODSX_ARENA_MB is full); the largest number of chunks in one call; chunks that began in the middle of an image's region list;
+ * chunks that began at an image other than the call's first; regions; regions of the direct branch (no smoothed window); windows
+ * whose sampling kernel also ran the column filter; row tiles and column tiles of the LDS filters; tiles of the global-memory
+ * sampling kernel, of the global-memory row filter and of the global-memory column filter; windows whose LDS row tile was clamped
+ * to 32 rows.  A call is counted when its planning begins and a chunk when its walk begins: a call refused for a window that is
+ * too large counts as one call and one chunk with no regions and leaves the largest-chunks value alone, and a call without any
+ * region counts as a call with no chunk.  Read it while no call runs on the context; tests work with the difference of two
+ * readings */
+int modsx_describe_counters(modsx_ctx *ctx, long *out, int n);
 /* orientation jobs launched by the pair and view pipelines of this process, and regions they left out of the orientation launch
  * because modsx_debug_reproject_certain_drop flags them, since the last reset (measurement hook; MODSX_ORI_PREFILTER=0 in the
  * environment launches them all).  modsx_detect_orientation itself never leaves a region out */

@@ -97,7 +97,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_loransac_h", "modsx_ransac_h_errtype", "modsx_loransac_h_errtype", "modsx_ransac_f", "modsx_loransac_f", "modsx_match_pair", "modsx_match_pairs", "modsx_match_pairs_views", "modsx_pair_result_release",
            "modsx_set_vs_pars", "modsx_synth_view", "modsx_detect_describe_views", "modsx_match_fginn_device",
            "modsx_match_pair_views", "modsx_match_ladder", "modsx_save_regions", "modsx_load_regions", "modsx_default_mser_params", "modsx_detect_msers", "modsx_detect_msers_u8", "modsx_last_timings", "modsx_profile",
-           "modsx_kernel_stats", "modsx_last_batch_verify", "modsx_last_match_geometry", "modsx_comm_unique_id", "modsx_comm_create", "modsx_comm_destroy", "modsx_comm_info",
+           "modsx_kernel_stats", "modsx_last_batch_verify", "modsx_last_match_geometry", "modsx_describe_counters", "modsx_comm_unique_id", "modsx_comm_create", "modsx_comm_destroy", "modsx_comm_info",
            "modsx_view_block_order", "modsx_detect_describe_views_sharded", "modsx_match_fginn_sharded",
            "modsx_match_pair_views_sharded", "modsx_match_pairs_views_sharded", "modsx_match_ladder_sharded", "modsx_comm_loopback_id", "modsx_comm_set_lanes",
            "modsx_comm_attach", "modsx_comm_lane_done", "modsx_comm_reset_lanes", "modsx_comm_set_timeout", "modsx_comm_stats",
@@ -115,6 +115,9 @@ EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HD
 
 SHARD_ROW_REGION, SHARD_ROW_KP = 0, 1     # include/modsx.h: what of a region travels in a row (all 200 B / the 56 B verification slice)
 EXCHANGE_ALL_GATHER, EXCHANGE_OWNER = 0, 1   # include/modsx.h: modsx_comm_set_exchange
+# include/modsx.h: modsx_describe_counters, in its order
+DESCRIBE_COUNTERS = ("calls", "chunks", "max_chunks", "chunks_mid_image", "chunks_later_image", "jobs", "direct_jobs", "fused_windows",
+                     "lds_row_tiles", "lds_col_tiles", "sample_tiles", "global_row_tiles", "global_col_tiles", "clamped_windows")
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -172,6 +175,7 @@ def lib():
         L.modsx_db_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_set_fginn_db.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_describe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_rep_create.restype = C.c_void_p
         L.modsx_rep_create.argtypes = [C.c_void_p]
@@ -610,6 +614,13 @@ class Context(object):
                                             patch_size, fast, photo_norm, desc_type, C.c_double(max_bin), _p(desc)),
                "describe_regions")
         return desc
+
+    def describe_counters(self):
+        """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative)."""
+        v = (C.c_long * len(DESCRIBE_COUNTERS))()
+        n = _check(lib().modsx_describe_counters(self._c(), v, len(DESCRIBE_COUNTERS)), "describe_counters")
+        assert n == len(DESCRIBE_COUNTERS), n
+        return dict(zip(DESCRIBE_COUNTERS, (int(x) for x in v)))
 
     def match_fginn(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
         d1 = np.ascontiguousarray(d1, np.float32)

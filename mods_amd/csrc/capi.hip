@@ -369,6 +369,20 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
   return MODSX_OK;
 }
 
+int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_describe_counters: bad argument"); return MODSX_ERR_ARG; }
+  // the contexts that describe on this one's behalf count with it: the peer (the second image of a lone multi-view pair) and the
+  // chains of half contexts of both (the further parts of a view list, engine_views.hip)
+  long sum[mx::DC_N] = {0};
+  for (const modsx_ctx *head : {(const modsx_ctx *)ctx, (const modsx_ctx *)ctx->peer})
+    for (const modsx_ctx *c = head; c; c = c->half)
+      for (int q = 0; q < mx::DC_N; q++)
+        if (q == mx::DC_MAX_CHUNKS) sum[q] = std::max(sum[q], c->descCnt[q]); else sum[q] += c->descCnt[q];
+  for (int q = 0; q < n && q < mx::DC_N; q++) out[q] = sum[q];
+  return mx::DC_N;
+}
+
 int modsx_describe_regions(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                            int patchSize, int fast_extraction, int photoNorm, int desc_type, double maxBinValue,
                            float *desc) {

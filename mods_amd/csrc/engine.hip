@@ -728,13 +728,14 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
   int curImg = 0, chunkNo = 0;
   size_t curReg = 0;
   while (curImg < n && regs[curImg].empty()) curImg++;
+  c->descCnt[DC_CALLS]++;
   while (curImg < n) {
     {
       std::vector<DescJob> jobs;
       std::vector<int> pfxSample(1, 0), pfxRow(1, 0), pfxCol(1, 0), pfxRowL(1, 0), pfxColL(1, 0);
       std::vector<float> taps, coordTab;
       std::vector<int> needTab;
-      struct PInfo { int tapOfs, ksize, needOfs, NC, coordOfs, touch, rows0, ro1; };
+      struct PInfo { int tapOfs, ksize, needOfs, NC, coordOfs, touch, rows0, ro1, clamped; };
       std::map<int, PInfo> pinfo;  // per window size P
       size_t arenaA = 0, arenaB = 0, arenaC = 0;
       bool full = false;
@@ -796,7 +797,8 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
           for (int a = 0; a + 1 < pi.NC; a += 2) pairs = pairs && need[a + 1] == need[a] + 1;
           pi.rows0 = pairs ? std::min(cap, BLUR_LDS / (P + 2 * R)) : 0;
           if (pi.rows0 < 2) pi.rows0 = 0;
-          if (pi.rows0 > 32 && pi.rows0 < 48 && pi.rows0 < P) pi.rows0 = 32;   // the fused sampling kernel parks 8 columns x <= 32 rows or 4 x <= 64 (MODSX_SR_HALF)
+          pi.clamped = pi.rows0 > 32 && pi.rows0 < 48 && pi.rows0 < P;
+          if (pi.clamped) pi.rows0 = 32;   // the fused sampling kernel parks 8 columns x <= 32 rows or 4 x <= 64 (MODSX_SR_HALF)
           pi.ro1 = 0;
           const int LS = pi.NC <= 64 ? 64 : 96;   // LDS row stride of the column filter
           for (int ro = std::min(capC, pi.NC); ro >= 2 && !pi.ro1 && pi.NC <= 96; ro--) {
@@ -815,6 +817,9 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
       for (int q = 0; q < n; q++) { beg[q] = end[q] = 0; }
       int i = curImg;
       size_t r = curReg, count = 0;
+      c->descCnt[DC_CHUNKS]++;
+      c->descCnt[DC_CHUNKS_MID_IMAGE] += curReg > 0;
+      c->descCnt[DC_CHUNKS_LATER_IMAGE] += curImg > 0;
       for (; i < n && !full; i++, r = 0) {
         beg[i] = r;
         for (; r < regs[i].size(); r++) {
@@ -919,7 +924,16 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
         pfxColL.push_back(pfxColL.back() + (j.P > 0 && j.ro1 > 0 ? (j.NC + j.ro1 - 1) / j.ro1 : 0));
         pfxRow.push_back(pfxRow.back() + (j.P > 0 && !j.rows0 ? (j.P * j.NC + 1023) / 1024 : 0));
         pfxCol.push_back(pfxCol.back() + (j.P > 0 && j.ro1 == 0 ? (j.NC * j.NC + 1023) / 1024 : 0));
+        c->descCnt[DC_DIRECT_JOBS] += j.P == 0;
+        c->descCnt[DC_FUSED_WINDOWS] += j.P > 0 && j.ro1 == -1;
+        c->descCnt[DC_CLAMPED_WINDOWS] += j.P > 0 && pinfo.find(j.P)->second.clamped;
       }
+      c->descCnt[DC_JOBS] += (long)nj;
+      c->descCnt[DC_LDS_ROW_TILES] += pfxRowL.back();
+      c->descCnt[DC_LDS_COL_TILES] += pfxColL.back();
+      c->descCnt[DC_SAMPLE_TILES] += pfxSample.back();
+      c->descCnt[DC_GLOBAL_ROW_TILES] += pfxRow.back();
+      c->descCnt[DC_GLOBAL_COL_TILES] += pfxCol.back();
       // the job table, the five tile prefixes and the three small tables travel as ONE pinned blob and one copy: nine
       // separate uploads cost nine ~6 us copy kernels per chunk on the stream
       const size_t oJobs = 0, oPfx = align_up(nj * sizeof(DescJob), 16), pfxB = align_up((nj + 1) * 4, 16);
@@ -981,6 +995,7 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
       chunkNo++;
     }
   }
+  c->descCnt[DC_MAX_CHUNKS] = std::max<long>(c->descCnt[DC_MAX_CHUNKS], chunkNo);
   hm.mark("desc launches");
   MX_HIP(ctx_sync(c));   // callers read the descriptor buffers and reuse the staging blobs
   hm.mark("desc wait");

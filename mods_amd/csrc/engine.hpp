@@ -329,6 +329,13 @@ struct Profiler {
 };
 }  // namespace mx
 
+namespace mx {
+// measurement hook (modsx_describe_counters): cumulative plan of describe_batch per context, in the order of include/modsx.h
+enum DescCounter { DC_CALLS = 0, DC_CHUNKS, DC_MAX_CHUNKS, DC_CHUNKS_MID_IMAGE, DC_CHUNKS_LATER_IMAGE, DC_JOBS, DC_DIRECT_JOBS,
+                   DC_FUSED_WINDOWS, DC_LDS_ROW_TILES, DC_LDS_COL_TILES, DC_SAMPLE_TILES, DC_GLOBAL_ROW_TILES, DC_GLOBAL_COL_TILES,
+                   DC_CLAMPED_WINDOWS, DC_N };
+}  // namespace mx
+
 struct modsx_db { mx::DbSet set; };
 
 struct modsx_image {
@@ -374,6 +381,7 @@ struct modsx_ctx {
   mx::Profiler prof;
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
   const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
+  long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side
