@@ -392,6 +392,14 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
  * certain (host only).  Returns n */
 int modsx_debug_reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk,
                                        unsigned char *drop);
+/* The description stage's plan of one call, without a device and without a context (host only; measurement hook): the region
+ * lists of `nimages` images (regs: one flat array, counts[i] regions of image i; modsx_describe_regions is nimages = 1) planned
+ * for mr_size and fast_extraction with a window arena of arena_floats floats (MODSX_ARENA_MB << 18).  counters[0 .. min(n, 14) - 1]
+ * get what modsx_describe_counters of a fresh context shows after that one call; cuts[0 .. min(*n_cuts, cap_cuts) - 1] the flat
+ * index of the first region of every chunk after the first, *n_cuts their number.  Returns MODSX_OK, or the call's refusal
+ * (MODSX_ERR_ARG and its modsx_last_error text) with the counters as the refused call leaves them */
+int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,
+                              unsigned long long arena_floats, long *counters, int n, long *cuts, int cap_cuts, int *n_cuts);
 /* per-stage time of the last modsx_match_pair in ms: detect, orient, describe, match, verify, total */
 int modsx_last_timings(modsx_ctx *ctx, double *ms6);
 

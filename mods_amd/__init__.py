@@ -105,7 +105,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_device_unpack", "modsx_verify_device_stats", "modsx_verify_device_timing", "modsx_comm_set_exchange",
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
-           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop",
+           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -177,6 +177,8 @@ def lib():
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.modsx_describe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_describe_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_rep_create.restype = C.c_void_p
         L.modsx_rep_create.argtypes = [C.c_void_p]
         L.modsx_rep_free.restype = None
@@ -895,6 +897,27 @@ def reproject_certain_drop(regs, H, w, h, boxk=2 * 3.0 * 3.0 ** 0.5):
     _check(lib().modsx_debug_reproject_certain_drop(_p(regs), len(regs), _p(H), int(w), int(h), C.c_double(boxk), _p(drop)),
            "reproject_certain_drop")
     return drop[:len(regs)].astype(bool)
+
+
+DEFAULT_ARENA_FLOATS = 192 << 18    # the window arena of a describe chunk without MODSX_ARENA_MB: 192 MiB
+
+
+def describe_plan(regs, mr_size, fast=0, arena_floats=DEFAULT_ARENA_FLOATS, max_cuts=4096):
+    """modsx_debug_describe_plan: what the description stage plans for one call, on the host alone (no GPU, no context).
+    regs: the region list of one image, or a list of them (one per image).  -> dict(rc, error, counters, cuts): rc 0 or the
+    refusal's code with its text in `error`; counters as Context.describe_counters() of a fresh context shows them after that
+    call; cuts: the flat index of the first region of every chunk after the first."""
+    lists = [regs] if isinstance(regs, np.ndarray) else list(regs)
+    counts = np.array([len(r) for r in lists], np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(r).view(REGION) for r in lists]) if lists else np.zeros(0, REGION), REGION)
+    cnt = (C.c_long * len(DESCRIBE_COUNTERS))()
+    cuts = (C.c_long * max(1, max_cuts))()
+    ncuts = C.c_int(0)
+    rc = lib().modsx_debug_describe_plan(_p(flat), _p(counts), len(lists), C.c_double(mr_size), int(fast), int(arena_floats), cnt,
+                                         len(DESCRIBE_COUNTERS), cuts, max_cuts, C.byref(ncuts))
+    assert ncuts.value <= max_cuts, "describe_plan: %d cuts, room for %d" % (ncuts.value, max_cuts)
+    return dict(rc=rc, error=_err() if rc else "", counters=dict(zip(DESCRIBE_COUNTERS, (int(x) for x in cnt))),
+                cuts=[int(cuts[i]) for i in range(ncuts.value)])
 
 
 def view_block_order(counts):

@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <deque>
 #include "engine_api.hpp"
+#include "describe_plan.hpp"
 
 using namespace mx;
 
@@ -381,6 +382,41 @@ int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
         if (q == mx::DC_MAX_CHUNKS) sum[q] = std::max(sum[q], c->descCnt[q]); else sum[q] += c->descCnt[q];
   for (int q = 0; q < n && q < mx::DC_N; q++) out[q] = sum[q];
   return mx::DC_N;
+}
+
+int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,
+                              unsigned long long arena_floats, long *counters, int n, long *cuts, int cap_cuts, int *n_cuts) {
+  if (nimages < 0 || (nimages > 0 && !counts) || n < 0 || (n > 0 && !counters) || cap_cuts < 0 || (cap_cuts > 0 && !cuts) || !n_cuts) {
+    mx::set_error("modsx_debug_describe_plan: bad argument"); return MODSX_ERR_ARG;
+  }
+  if (nimages > mx::MAXB) { mx::set_error("describe batch too large"); return MODSX_ERR_ARG; }
+  std::vector<modsx_region> v[mx::MAXB];
+  long first[mx::MAXB + 1] = {0};    // flat index of every image's first region
+  for (int i = 0; i < nimages; i++) {
+    if (counts[i] < 0 || (counts[i] > 0 && !regs)) { mx::set_error("modsx_debug_describe_plan: bad argument"); return MODSX_ERR_ARG; }
+    v[i].assign(regs + first[i], regs + first[i] + counts[i]);
+    first[i + 1] = first[i] + counts[i];
+  }
+  // describe_batch's loop (engine.hip) without its device half
+  mx::HostMark hm;
+  mx::DescBatch batch;
+  batch.regs = v; batch.n = nimages; batch.mrSize = mr_size; batch.fast = fast_extraction;
+  mx::DescCursor cur = mx::describe_windows(batch);
+  long cnt[mx::DC_N] = {0};
+  int chunkNo = 0, rc = MODSX_OK;
+  *n_cuts = 0;
+  cnt[mx::DC_CALLS]++;
+  for (; cur.img < nimages; chunkNo++) {
+    mx::DescChunkPlan cp;
+    if (chunkNo) { if (*n_cuts < cap_cuts) cuts[*n_cuts] = first[cur.img] + (long)cur.reg; (*n_cuts)++; }
+    rc = mx::describe_plan_chunk(batch, cur, (size_t)arena_floats, cp, hm);
+    for (int q = 0; q < mx::DC_N; q++) cnt[q] += cp.cnt[q];
+    if (rc) break;
+    cur = cp.next;
+  }
+  if (!rc) cnt[mx::DC_MAX_CHUNKS] = chunkNo;
+  for (int q = 0; q < n && q < mx::DC_N; q++) counters[q] = cnt[q];
+  return rc;
 }
 
 int modsx_describe_regions(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,

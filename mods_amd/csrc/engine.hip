@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include "engine_api.hpp"
+#include "describe_plan.hpp"
 
 #ifdef MODSX_DUP_BUILD
 namespace mx {
@@ -671,6 +672,63 @@ void reproject_certain_drop(const modsx_region *regs, int n, const double *H, in
   }
 }
 
+// One planned chunk of describe_batch on the device: its blob staged through pinned slot `slot` (two in turn: the copy of chunk k
+// may still be in flight while chunk k + 1 is being prepared), then the launch set.
+static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot, HostMark &hm, int photoNorm, const DescSet &ds,
+                                 double maxBin, const DescOut &outs) {
+  hipStream_t s = c->stream;
+  const size_t nj = cp.jobs.size();
+  const int nS = cp.pfxSample.back(), nR = cp.pfxRow.back(), nC = cp.pfxCol.back(), nRL = cp.pfxRowL.back(), nCL = cp.pfxColL.back();
+  const DescBlobLayout L(cp);
+  PinBuf &hblob = slot ? c->hDescB : c->hDesc;
+  if (c->descEvPending[slot]) { MX_HIP(c->descByEvent[slot] ? hipEventSynchronize(c->descEv[slot]) : ctx_wait_mark(c, c->descMark[slot])); c->descEvPending[slot] = false; }
+  if (!c->descJobs.ensure(L.blobB) || !hblob.ensure(L.blobB) ||
+      !c->scratchA.ensure(std::max<size_t>(1, cp.arenaA) * 4) || !c->scratchB.ensure(std::max<size_t>(1, cp.arenaB) * 4) ||
+      !c->scratchC.ensure(std::max<size_t>(1, cp.arenaC) * 4) || !c->rowStarts.ensure(std::max<size_t>(1, cp.rowStarts) * 8) ||
+      !c->tileJob.ensure(((size_t)nS + nR + nC + 3) * 4))
+    return MODSX_ERR_NOMEM;
+  int *tjS = (int *)c->tileJob.p, *tjR = tjS + nS, *tjC = tjR + nR;
+  if (!c->blurTiles.ensure(((size_t)nRL + nCL + 1) * sizeof(BlurTile))) return MODSX_ERR_NOMEM;
+  BlurTile *btR = (BlurTile *)c->blurTiles.p, *btC = btR + nRL;
+  char *hb = (char *)hblob.p, *db = (char *)c->descJobs.p;
+  describe_fill_blob(cp, L, hb);
+  hm.mark("desc tables + blob");
+  MX_HIP(ctx_copy(c, db, hb, L.blobB, hipMemcpyHostToDevice));
+  c->descByEvent[slot] = c->waitRuntime || !c->hFlag;
+  if (c->descByEvent[slot]) MX_HIP(hipEventRecord(c->descEv[slot], s)); else c->descMark[slot] = ctx_mark(c);
+  c->descEvPending[slot] = true;
+  int *dPfxS = (int *)(db + L.pfx(0)), *dPfxR = (int *)(db + L.pfx(1)), *dPfxC = (int *)(db + L.pfx(2));
+  int *dPfxRL = (int *)(db + L.pfx(3)), *dPfxCL = (int *)(db + L.pfx(4));
+  float *dTaps = (float *)(db + L.oTaps), *dCoord = (float *)(db + L.oCoord);
+  int *dNeed = (int *)(db + L.oNeed);
+  const DescJob *dj = (const DescJob *)(db + L.oJobs);
+  // tile -> job tables of the global-memory fallbacks: most chunks have no such tiles at all
+  if (nS) launch_expand_tiles(s, dPfxS, (int)nj, tjS);
+  if (nR) launch_expand_tiles(s, dPfxR, (int)nj, tjR);
+  if (nC) launch_expand_tiles(s, dPfxC, (int)nj, tjC);
+  // algorithmic work of the describe STAGE per SURVEY section 8(d): the (P+2)^2 f32 window of every region read once
+  // (booked here) + 128 B written per region (booked on k_describe); the arenas between the four kernels are an
+  // artefact of the split and are not algorithmic bytes
+  if (nRL + nCL)
+    launch_expand_blur_tiles(s, dj, dPfxRL, dPfxCL, (int)nj, dNeed, btR, btC, (float2 *)c->rowStarts.p);
+  { ProfScope ps(c, K_PATCH_SAMPLE, (double)cp.windowFloats * 4);
+    launch_sample_rows(s, dj, btR, nRL, (ImgRef *)c->imgRefs.p, dTaps, dNeed, (float *)c->scratchB.p,
+                       (const float2 *)c->rowStarts.p, (float *)c->scratchC.p);
+    launch_patch_sample(s, dj, dPfxS, tjS, nS, (ImgRef *)c->imgRefs.p, (float *)c->scratchA.p); }
+  { ProfScope ps(c, K_BLUR_ROWS, 0.0);
+    launch_patch_blur(s, dj, dPfxR, tjR, nR, dTaps, dNeed, (float *)c->scratchA.p,
+                      (float *)c->scratchB.p, 0); }
+  { ProfScope ps(c, K_BLUR_COLS, 0.0);
+    launch_blur_cols(s, btC, nCL, dTaps, dNeed, (float *)c->scratchB.p, (float *)c->scratchC.p);
+    launch_patch_blur(s, dj, dPfxC, tjC, nC, dTaps, dNeed, (float *)c->scratchB.p,
+                      (float *)c->scratchC.p, 1); }
+  ProfScope psd(c, K_DESCRIBE, (double)nj * 128 * ds.n);
+  launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
+                  c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
+                  c->dSiftBins, c->dSiftW, photoNorm, ds.packed(), ds.n, maxBin, outs);
+  return MODSX_OK;
+}
+
 // DescribeRegions<SIFTDescriptor>, synth-detection.hpp:169-255, for a batch.  Descriptors stay in HBM
 // (c->descF[i], c->descU8[i]); descHost[i] (optional) receives the f32 copy.
 int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *regs,
@@ -706,294 +764,22 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
     }
   }
   // the regions of all images of the batch go through one launch set per chunk (a chunk ends when the window arena is
-  // full); region order inside an image is kept, outIdx addresses the image's own descriptor buffer
-  // The window size of every region, once for the whole batch (one pool task per image): P = patchImageSize + 2 of the
-  // smoothed branch, 0 for the direct branch (imageToPatchScale <= 0.4, or fast extraction)
+  // full); region order inside an image is kept, outIdx addresses the image's own descriptor buffer.  What a chunk holds is
+  // planned on the host (describe_plan.cpp), one chunk at a time: chunk k + 1 is planned and staged while chunk k runs
   HostMark hm;
-  std::vector<int> winP[MAXB];
-  host_parallel_light(n, [&](int i) {
-    winP[i].resize(regs[i].size());
-    for (size_t r = 0; r < regs[i].size(); r++) {
-      int P = 0;
-      if (!fast) {
-        const modsx_keypoint &k = regs[i][r].det_kp;
-        float mrScale = (float)ceil(k.s * mrSize);
-        int patchImageSize = 2 * int(mrScale) + 1;
-        float i2p = float(patchImageSize) / float(patchSize);
-        if (i2p > 0.4) P = patchImageSize + 2;
-      }
-      winP[i][r] = P;
-    }
-  });
-  int curImg = 0, chunkNo = 0;
-  size_t curReg = 0;
-  while (curImg < n && regs[curImg].empty()) curImg++;
+  DescBatch batch;
+  batch.regs = regs; batch.n = n; batch.mrSize = mrSize; batch.fast = fast;
+  DescCursor cur = describe_windows(batch);
+  int chunkNo = 0;
   c->descCnt[DC_CALLS]++;
-  while (curImg < n) {
-    {
-      std::vector<DescJob> jobs;
-      std::vector<int> pfxSample(1, 0), pfxRow(1, 0), pfxCol(1, 0), pfxRowL(1, 0), pfxColL(1, 0);
-      std::vector<float> taps, coordTab;
-      std::vector<int> needTab;
-      struct PInfo { int tapOfs, ksize, needOfs, NC, coordOfs, touch, rows0, ro1, clamped; };
-      std::map<int, PInfo> pinfo;  // per window size P
-      size_t arenaA = 0, arenaB = 0, arenaC = 0;
-      bool full = false;
-      // the tables of a window size (taps, needed columns, sample coordinates, tile shapes), built when the size first appears
-      auto make_pinfo = [&](int P, PInfo &pi) -> int {
-        const float i2p = float(P - 2) / float(patchSize);
-        float sigma = 1.5f * i2p;
-        pi.ksize = blur_ksize(sigma);
-        if (pi.ksize > 512) { set_error("descriptor window too large (blur kernel > 512 taps)"); return MODSX_ERR_ARG; }
-        std::vector<float> kk = gaussian_kernel(pi.ksize, sigma);
-        pi.tapOfs = (int)taps.size();
-        taps.insert(taps.end(), kk.begin(), kk.end());
-        // coordinates of interpolate(smoothed, P/2, P/2, i2p, 0, 0, i2p, patch41): f32 running sums
-        // (helpers.cpp:563-585); rows and columns run the same recurrence (a12 = a21 = 0, ofsx = ofsy)
-        const float o = (float)(P >> 1);
-        pi.touch = check_borders_host(P, P, o, o, i2p, 0.f, 0.f, i2p, 41, 41) ? 1 : 0;
-        float W[41];
-        {
-          float rx = o - (float)20 * 0.f;
-          float WX = rx - (float)20 * i2p;
-          for (int q = 0; q < 41; q++) { W[q] = WX; WX += i2p; }
-        }
-        int x0[41], valid[41];
-        std::vector<int> need;
-        for (int q = 0; q < 41; q++) {
-          if (!pi.touch) {
-            int x = (int)W[q];
-            x = x < 0 ? 0 : (x > P - 2 ? P - 2 : x);
-            x0[q] = x; valid[q] = 1;
-          } else {
-            int x = (int)floorf(W[q]);
-            valid[q] = (W[q] >= 0 && x < P - 1) ? 1 : 0;
-            x0[q] = valid[q] ? x : 0;
-          }
-          if (valid[q]) { need.push_back(x0[q]); need.push_back(x0[q] + 1); }
-        }
-        std::sort(need.begin(), need.end());
-        need.erase(std::unique(need.begin(), need.end()), need.end());
-        if (need.empty()) need.push_back(0);
-        pi.NC = (int)need.size();
-        pi.needOfs = (int)needTab.size();
-        needTab.insert(needTab.end(), need.begin(), need.end());
-        for (int q = 0; q < 41; q++) {
-          int i0 = 0, i1 = 0;
-          if (valid[q]) {
-            i0 = (int)(std::lower_bound(need.begin(), need.end(), x0[q]) - need.begin());
-            i1 = (int)(std::lower_bound(need.begin(), need.end(), x0[q] + 1) - need.begin());
-          }
-          needTab.push_back(i0); needTab.push_back(i1); needTab.push_back(x0[q]); needTab.push_back(valid[q]);
-        }
-        pi.coordOfs = (int)coordTab.size();
-        coordTab.insert(coordTab.end(), W, W + 41);
-        {  // tile shapes of the LDS blur kernels: <= BLUR_OUT outputs and <= BLUR_LDS floats per workgroup
-          const int BLUR_LDS = MODSX_SR_WIN, BLUR_LDS_C = MODSX_BLUR_LDS_C, R = pi.ksize >> 1, NP2 = 2 * ((pi.NC + 1) / 2);
-          const int cap = 2048 / NP2, capC = 4096 / NP2;
-          // the row filter pairs needed columns (2m, 2m+1); they are neighbours in the window by construction
-          // (x0, x0 + 1 of one sample, or a contiguous range) -- if ever not, the job takes the global-memory kernel
-          bool pairs = true;
-          for (int a = 0; a + 1 < pi.NC; a += 2) pairs = pairs && need[a + 1] == need[a] + 1;
-          pi.rows0 = pairs ? std::min(cap, BLUR_LDS / (P + 2 * R)) : 0;
-          if (pi.rows0 < 2) pi.rows0 = 0;
-          pi.clamped = pi.rows0 > 32 && pi.rows0 < 48 && pi.rows0 < P;
-          if (pi.clamped) pi.rows0 = 32;   // the fused sampling kernel parks 8 columns x <= 32 rows or 4 x <= 64 (MODSX_SR_HALF)
-          pi.ro1 = 0;
-          const int LS = pi.NC <= 64 ? 64 : 96;   // LDS row stride of the column filter
-          for (int ro = std::min(capC, pi.NC); ro >= 2 && !pi.ro1 && pi.NC <= 96; ro--) {
-            int span = 0;
-            for (int a = 0; a < pi.NC; a += ro) span = std::max(span, need[std::min(a + ro, pi.NC) - 1] - need[a] + 2 * R + 1);
-            if (span * LS <= BLUR_LDS_C) pi.ro1 = ro;
-          }
-          // a window that is one row tile, with <= 64 needed columns and <= 80 block rows (kernels_describe.hip: FC_LS,
-          // FC_ROWS): the fused sampling kernel runs the column filter too
-          if (pi.rows0 >= P && pi.NC <= 64 && P + 2 * R <= MODSX_FC_ROWS) pi.ro1 = -1;
-        }
-        return MODSX_OK;
-      };
-      // which regions this chunk takes (a light sequential walk over the window sizes), then the job records in parallel
-      size_t beg[MAXB], end[MAXB], at[MAXB + 1];
-      for (int q = 0; q < n; q++) { beg[q] = end[q] = 0; }
-      int i = curImg;
-      size_t r = curReg, count = 0;
-      c->descCnt[DC_CHUNKS]++;
-      c->descCnt[DC_CHUNKS_MID_IMAGE] += curReg > 0;
-      c->descCnt[DC_CHUNKS_LATER_IMAGE] += curImg > 0;
-      for (; i < n && !full; i++, r = 0) {
-        beg[i] = r;
-        for (; r < regs[i].size(); r++) {
-          const int P = winP[i][r];
-          if (P > 0) {
-            if (pinfo.find(P) == pinfo.end()) {
-              PInfo pi;
-              const int prc = make_pinfo(P, pi);
-              if (prc) return prc;
-              pinfo.insert({P, pi});
-            }
-            const size_t needA = (size_t)P * P;
-            if (arenaA + needA > ARENA_FLOATS && count) { full = true; break; }
-            arenaA += needA;
-          }
-          count++;
-        }
-        end[i] = r;
-        if (full) break;
-      }
-      at[0] = 0;
-      for (int q = 0; q < n; q++) at[q + 1] = at[q] + (end[q] - beg[q]);
-      jobs.resize(count);
-      host_parallel_light(n, [&](int q) {
-        for (size_t rr = beg[q]; rr < end[q]; rr++) {
-          const modsx_keypoint &k = regs[q][rr].det_kp;
-          DescJob j;
-          memset(&j, 0, sizeof j);
-          j.img = q;
-          j.outIdx = (int)rr;
-          j.x = (float)k.x; j.y = (float)k.y;
-          if (!fast) {
-            float mrScale = (float)ceil(k.s * mrSize);
-            int patchImageSize = 2 * int(mrScale) + 1;
-            float i2p = float(patchImageSize) / float(patchSize);
-            j.i2p = i2p;
-            const int P = winP[q][rr];
-            if (P > 0) {
-              const PInfo &pi = pinfo.find(P)->second;
-              j.P = P;
-              j.a11 = (float)k.a11; j.a12 = (float)k.a12; j.a21 = (float)k.a21; j.a22 = (float)k.a22;
-              j.tapOfs = pi.tapOfs; j.ksize = pi.ksize; j.NC = pi.NC; j.needOfs = pi.needOfs; j.coordOfs = pi.coordOfs;
-              j.touch = pi.touch; j.rows0 = pi.rows0; j.ro1 = pi.ro1;
-            } else {
-              j.P = 0;
-              j.a11 = (float)k.a11 * i2p; j.a12 = (float)k.a12 * i2p; j.a21 = (float)k.a21 * i2p; j.a22 = (float)k.a22 * i2p;
-            }
-          } else {
-            double mrScale = (double)mrSize * k.s;
-            int patchImageSize = 2 * int(mrScale) + 1;
-            double i2pd = double(patchImageSize) / (double)patchSize;
-            float curr_sc = i2pd;
-            j.P = 0; j.i2p = curr_sc;
-            j.a11 = (float)k.a11 * curr_sc; j.a12 = (float)k.a12 * curr_sc; j.a21 = (float)k.a21 * curr_sc; j.a22 = (float)k.a22 * curr_sc;
-          }
-          jobs[at[q] + (rr - beg[q])] = j;
-        }
-      });
-      // (i, r) = first region that did not fit, or i == n
-      if (full) { curImg = i; curReg = r; } else { curImg = n; curReg = 0; }
-      hm.mark("desc jobs");
-      const size_t nj = jobs.size();
-      // Launch order of the chunk: by image, then by 64-pixel row band, then by x.  The sampling kernel hands every XCD one
-      // contiguous eighth of this order (kernels_describe.hip: xcd_chunk), i.e. one part of the images; outIdx keeps every
-      // descriptor at its region's place, so the reference's list order is untouched.
-      // (a stable LSD radix sort of one key per job: jobs are generated in (image, outIdx) order, which breaks the ties)
-      {
-        // the key in the high half of a word, the job's position in the low half; sorted by the key's bits alone, the low halves
-        // are the order.  MAXB = 32 leaves room: the key needs 31 bits (image 5 | band 10 | x 16) of its 32
-        static_assert(MAXB <= 64, "describe job sort key: the image index has 6 bits at the most");
-        std::vector<uint64_t> key(nj), key2;
-        for (size_t q = 0; q < nj; q++) {
-          const DescJob &a = jobs[q];
-          // the order only places neighbouring windows on neighbouring workgroups (no result depends on it): whole pixels
-          // are enough, and a 32-bit key is three passes instead of six
-          const int xi = (int)a.x, yb = (int)a.y >> 6;
-          const uint32_t x16 = (uint32_t)(xi < 0 ? 0 : (xi > 65535 ? 65535 : xi));
-          const uint32_t band = (uint32_t)(yb < 0 ? 0 : (yb > 1023 ? 1023 : yb));
-          key[q] = ((((uint64_t)(uint32_t)a.img << 26) | ((uint64_t)band << 16) | x16) << 32) | (uint32_t)q;
-        }
-        host_radix_sort_u64(key, key2, 32, 63);
-        std::vector<DescJob> sorted(nj);
-        for (size_t q = 0; q < nj; q++) sorted[q] = jobs[(uint32_t)key[q]];
-        jobs.swap(sorted);
-      }
-      hm.mark("desc job sort");
-      const size_t windowFloats = arenaA;   // all P x P windows of the chunk: its size limit and its algorithmic bytes
-      arenaA = 0;                           // arena A itself only holds the windows that do not take the fused kernel
-      size_t rowStarts = 0;                 // the fused ones get their P row starts (float2) instead
-      for (DescJob &j : jobs) {
-        if (j.P > 0) {
-          j.rowOfs = arenaB; j.gridOfs = arenaC;
-          if (!j.rows0) { j.scratchOfs = arenaA; arenaA += (size_t)j.P * j.P; }
-          else { j.scratchOfs = rowStarts; rowStarts += (size_t)j.P; }
-          arenaB += (size_t)j.P * j.NC; arenaC += (size_t)j.NC * j.NC;
-        }
-        // windows whose row tile fits LDS are sampled by the fused sample + row-filter kernel (arena A is not touched); the
-        // others go through k_patch_sample (64 x SAMPLE_COLS tiles) and the global-memory row filter
-        pfxSample.push_back(pfxSample.back() + (j.P > 0 && !j.rows0 ? ((j.P + 63) / 64) * ((j.P + 127) / 128) : 0));
-        // the blur passes: LDS kernels where a tile fits, k_patch_blur (BLUR_TILE outputs per workgroup) otherwise
-        pfxRowL.push_back(pfxRowL.back() + (j.P > 0 && j.rows0 ? (j.P + j.rows0 - 1) / j.rows0 : 0));
-        pfxColL.push_back(pfxColL.back() + (j.P > 0 && j.ro1 > 0 ? (j.NC + j.ro1 - 1) / j.ro1 : 0));
-        pfxRow.push_back(pfxRow.back() + (j.P > 0 && !j.rows0 ? (j.P * j.NC + 1023) / 1024 : 0));
-        pfxCol.push_back(pfxCol.back() + (j.P > 0 && j.ro1 == 0 ? (j.NC * j.NC + 1023) / 1024 : 0));
-        c->descCnt[DC_DIRECT_JOBS] += j.P == 0;
-        c->descCnt[DC_FUSED_WINDOWS] += j.P > 0 && j.ro1 == -1;
-        c->descCnt[DC_CLAMPED_WINDOWS] += j.P > 0 && pinfo.find(j.P)->second.clamped;
-      }
-      c->descCnt[DC_JOBS] += (long)nj;
-      c->descCnt[DC_LDS_ROW_TILES] += pfxRowL.back();
-      c->descCnt[DC_LDS_COL_TILES] += pfxColL.back();
-      c->descCnt[DC_SAMPLE_TILES] += pfxSample.back();
-      c->descCnt[DC_GLOBAL_ROW_TILES] += pfxRow.back();
-      c->descCnt[DC_GLOBAL_COL_TILES] += pfxCol.back();
-      // the job table, the five tile prefixes and the three small tables travel as ONE pinned blob and one copy: nine
-      // separate uploads cost nine ~6 us copy kernels per chunk on the stream
-      const size_t oJobs = 0, oPfx = align_up(nj * sizeof(DescJob), 16), pfxB = align_up((nj + 1) * 4, 16);
-      const size_t oTaps = oPfx + 5 * pfxB, oNeed = oTaps + align_up(taps.size() * 4, 16), oCoord = oNeed + align_up(needTab.size() * 4, 16);
-      const size_t blobB = oCoord + align_up(coordTab.size() * 4, 16) + 16;
-      // two staging blobs in turn: the copy of chunk k may still be in flight while chunk k + 1 is being prepared
-      const int slot = chunkNo & 1;
-      PinBuf &hblob = slot ? c->hDescB : c->hDesc;
-      if (c->descEvPending[slot]) { MX_HIP(c->descByEvent[slot] ? hipEventSynchronize(c->descEv[slot]) : ctx_wait_mark(c, c->descMark[slot])); c->descEvPending[slot] = false; }
-      if (!c->descJobs.ensure(blobB) || !hblob.ensure(blobB) ||
-          !c->scratchA.ensure(std::max<size_t>(1, arenaA) * 4) || !c->scratchB.ensure(std::max<size_t>(1, arenaB) * 4) ||
-          !c->scratchC.ensure(std::max<size_t>(1, arenaC) * 4) || !c->rowStarts.ensure(std::max<size_t>(1, rowStarts) * 8) ||
-          !c->tileJob.ensure(((size_t)pfxSample.back() + pfxRow.back() + pfxCol.back() + 3) * 4))
-        return MODSX_ERR_NOMEM;
-      int *tjS = (int *)c->tileJob.p, *tjR = tjS + pfxSample.back(), *tjC = tjR + pfxRow.back();
-      if (!c->blurTiles.ensure(((size_t)pfxRowL.back() + pfxColL.back() + 1) * sizeof(BlurTile))) return MODSX_ERR_NOMEM;
-      BlurTile *btR = (BlurTile *)c->blurTiles.p, *btC = btR + pfxRowL.back();
-      char *hb = (char *)hblob.p, *db = (char *)c->descJobs.p;
-      memcpy(hb + oJobs, jobs.data(), nj * sizeof(DescJob));
-      const std::vector<int> *pf[5] = {&pfxSample, &pfxRow, &pfxCol, &pfxRowL, &pfxColL};
-      for (int q = 0; q < 5; q++) memcpy(hb + oPfx + q * pfxB, pf[q]->data(), (nj + 1) * 4);
-      if (!taps.empty()) memcpy(hb + oTaps, taps.data(), taps.size() * 4);
-      if (!needTab.empty()) memcpy(hb + oNeed, needTab.data(), needTab.size() * 4);
-      if (!coordTab.empty()) memcpy(hb + oCoord, coordTab.data(), coordTab.size() * 4);
-      hm.mark("desc tables + blob");
-      MX_HIP(ctx_copy(c, db, hb, blobB, hipMemcpyHostToDevice));
-      c->descByEvent[slot] = c->waitRuntime || !c->hFlag;
-      if (c->descByEvent[slot]) MX_HIP(hipEventRecord(c->descEv[slot], s)); else c->descMark[slot] = ctx_mark(c);
-      c->descEvPending[slot] = true;
-      int *dPfxS = (int *)(db + oPfx), *dPfxR = (int *)(db + oPfx + pfxB), *dPfxC = (int *)(db + oPfx + 2 * pfxB);
-      int *dPfxRL = (int *)(db + oPfx + 3 * pfxB), *dPfxCL = (int *)(db + oPfx + 4 * pfxB);
-      float *dTaps = (float *)(db + oTaps), *dCoord = (float *)(db + oCoord);
-      int *dNeed = (int *)(db + oNeed);
-      const DescJob *dj = (const DescJob *)c->descJobs.p;
-      // tile -> job tables of the global-memory fallbacks: most chunks have no such tiles at all
-      if (pfxSample.back()) launch_expand_tiles(s, dPfxS, (int)nj, tjS);
-      if (pfxRow.back()) launch_expand_tiles(s, dPfxR, (int)nj, tjR);
-      if (pfxCol.back()) launch_expand_tiles(s, dPfxC, (int)nj, tjC);
-      // algorithmic work of the describe STAGE per SURVEY section 8(d): the (P+2)^2 f32 window of every region read once
-      // (booked here) + 128 B written per region (booked on k_describe); the arenas between the four kernels are an
-      // artefact of the split and are not algorithmic bytes
-      if (pfxRowL.back() + pfxColL.back())
-        launch_expand_blur_tiles(s, dj, dPfxRL, dPfxCL, (int)nj, dNeed, btR, btC, (float2 *)c->rowStarts.p);
-      { ProfScope ps(c, K_PATCH_SAMPLE, (double)windowFloats * 4);
-        launch_sample_rows(s, dj, btR, pfxRowL.back(), (ImgRef *)c->imgRefs.p, dTaps, dNeed, (float *)c->scratchB.p,
-                           (const float2 *)c->rowStarts.p, (float *)c->scratchC.p);
-        launch_patch_sample(s, dj, dPfxS, tjS, pfxSample.back(), (ImgRef *)c->imgRefs.p, (float *)c->scratchA.p); }
-      { ProfScope ps(c, K_BLUR_ROWS, 0.0);
-        launch_patch_blur(s, dj, dPfxR, tjR, pfxRow.back(), dTaps, dNeed, (float *)c->scratchA.p,
-                          (float *)c->scratchB.p, 0); }
-      { ProfScope ps(c, K_BLUR_COLS, 0.0);
-        launch_blur_cols(s, btC, pfxColL.back(), dTaps, dNeed, (float *)c->scratchB.p, (float *)c->scratchC.p);
-        launch_patch_blur(s, dj, dPfxC, tjC, pfxCol.back(), dTaps, dNeed, (float *)c->scratchB.p,
-                          (float *)c->scratchC.p, 1); }
-      ProfScope psd(c, K_DESCRIBE, (double)nj * 128 * ds->n);
-      launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
-                      c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
-                      c->dSiftBins, c->dSiftW, photoNorm, ds->packed(), ds->n, maxBin, outs);
-      chunkNo++;
-    }
+  for (; cur.img < n; chunkNo++) {
+    DescChunkPlan cp;
+    const int prc = describe_plan_chunk(batch, cur, ARENA_FLOATS, cp, hm);
+    for (int q = 0; q < DC_N; q++) c->descCnt[q] += cp.cnt[q];
+    if (prc) return prc;
+    rc = launch_describe_chunk(c, cp, chunkNo & 1, hm, photoNorm, *ds, maxBin, outs);
+    if (rc) return rc;
+    cur = cp.next;
   }
   c->descCnt[DC_MAX_CHUNKS] = std::max<long>(c->descCnt[DC_MAX_CHUNKS], chunkNo);
   hm.mark("desc launches");

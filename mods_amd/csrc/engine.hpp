@@ -256,7 +256,7 @@ void launch_views_fused(hipStream_t s, const ViewJob *jobs, int n, int tiles, co
 size_t match_workspace_bytes(int n1, int n2);
 void launch_match(hipStream_t s, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2,
                   double sqminratio, double contrDistSq, int nn, MatchRow *rows, void *workspace);
-// Shapes of the fused sampling + row-filter kernel (kernels_describe.hip k_sample_rows_lds; engine.hip sizes the tiles with the
+// Shapes of the fused sampling + row-filter kernel (kernels_describe.hip k_sample_rows_lds; describe_plan.cpp sizes the tiles with the
 // same numbers): LDS floats of the sampled row tile, block rows of a fully fused small window, whether a wave parks 4 / 8
 // columns of coordinates at a time (1) or 8 / 16 (0), and the workgroups per CU the kernel is built for
 // The kernel's time follows its residency far more than its tile shapes: with 4 workgroups per CU (20 KB tile + 20 KB of
@@ -269,7 +269,7 @@ void launch_match(hipStream_t s, const uint8_t *d1, int n1, const uint8_t *d2, i
 #define MODSX_SR_HALF 1
 #define MODSX_SR_WGS 8
 #endif
-// LDS floats of a column-filter workgroup (kernels_describe.hip k_blur_cols_lds; engine.hip sizes the tiles with the same number)
+// LDS floats of a column-filter workgroup (kernels_describe.hip k_blur_cols_lds; describe_plan.cpp sizes the tiles with the same number)
 #ifndef MODSX_BLUR_LDS_C
 #define MODSX_BLUR_LDS_C 9984
 #endif
@@ -330,7 +330,8 @@ struct Profiler {
 }  // namespace mx
 
 namespace mx {
-// measurement hook (modsx_describe_counters): cumulative plan of describe_batch per context, in the order of include/modsx.h
+// measurement hook (modsx_describe_counters): cumulative plan of describe_batch per context (describe_plan.cpp books the chunks), in
+// the order of include/modsx.h
 enum DescCounter { DC_CALLS = 0, DC_CHUNKS, DC_MAX_CHUNKS, DC_CHUNKS_MID_IMAGE, DC_CHUNKS_LATER_IMAGE, DC_JOBS, DC_DIRECT_JOBS,
                    DC_FUSED_WINDOWS, DC_LDS_ROW_TILES, DC_LDS_COL_TILES, DC_SAMPLE_TILES, DC_GLOBAL_ROW_TILES, DC_GLOBAL_COL_TILES,
                    DC_CLAMPED_WINDOWS, DC_N };

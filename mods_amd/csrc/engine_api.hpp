@@ -1,5 +1,5 @@
-// engine_api.hpp -- functions shared between engine.hip, engine_detect.hip, engine_views.hip, engine_shard.hip, ransac.cpp,
-// filters.cpp and capi.hip.
+// engine_api.hpp -- functions shared between engine.hip, engine_detect.hip, engine_views.hip, engine_shard.hip, describe_plan.cpp,
+// ransac.cpp, filters.cpp and capi.hip.
 #pragma once
 #include <stdio.h>
 #include <chrono>

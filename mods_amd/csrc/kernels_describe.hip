@@ -681,7 +681,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     // Addresses: 32-bit BYTE offsets from the region's (wave-uniform) grid base -- one 24-bit multiply per grid row and an
     // add + shift per load, the loads in the scalar base + vector offset form (the size_t row products this replaces were
     // quarter-rate 32-bit multiplies and 64-bit adds: two thirds of the issue slots of the sampling).  An entry that is not valid
-    // has idx0 = idx1 = 0 in the host's table (engine.hip), so every address is inside the grid whatever `valid` says and the
+    // has idx0 = idx1 = 0 in the host's table (describe_plan.cpp), so every address is inside the grid whatever `valid` says and the
     // select happens once, on the value.  (r, c) of p = tid + 128 k advance by (3, 5): 128 = 3 * 41 + 5 -- no division per sample.
     typedef const char __attribute__((address_space(1))) *gbyte_p;
     const gbyte_p Gb = (gbyte_p)as_global(G);

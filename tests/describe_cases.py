@@ -1,16 +1,19 @@
-"""The inputs of the describe-path tests (tests/test_describe_cases_cpu.py, tests/test_gpu_describe_paths.py,
-tests/test_gpu_describe_chunks.py, tests/describe_chunk_child.py), built once per process and left alone.
+"""The inputs of the describe-path tests (tests/test_describe_cases_cpu.py, tests/test_describe_plan_cpu.py,
+tests/test_gpu_describe_paths.py, tests/test_gpu_describe_chunks.py, tests/describe_chunk_child.py), built once per process and
+left alone.
 
 Image: 240x320 f32 with full mantissas (a smooth term plus uniform noise that is not floored, clipped to [0, 255]).  The floored
 synthetic images make many of the describe stage's sums exact; this one does not.
 
 Window sizes: a region with scale s described at mr_size = 1.0 gets the window P = 2 * ceil(s) + 3, so s = (P - 3) / 2 picks P
 exactly.  SIZES holds every odd P of 19..135 and, above that, the smallest P of every distinct (rows per LDS row tile, columns per
-LDS column tile, last row tile ragged or not) that describe_batch (mods_amd/csrc/engine.hip) plans today, plus both sides of every
-path boundary: 33|35 (fused column filter | separate), 43|45 (whole-window row tile | clamp to 32 rows), 65|67 (column-filter
-stride 64, one tile | stride 96, several tiles), 471|473 (LDS column filter | global-memory one), 983|985 (fused sampling kernel |
-k_patch_sample + global row filter), 1023|1025 (the 128-column tile edge of k_patch_sample), 2329 (the last size accepted; 2331 is
-refused).  Which path a size takes is READ from the library (Context.describe_counters()) by the GPU test, never restated here.
+LDS column tile, last row tile ragged or not) that the planner of the description stage (mods_amd/csrc/describe_plan.cpp) plans
+today, plus both sides of every path boundary: 33|35 (fused column filter | separate), 43|45 (whole-window row tile | clamp to 32
+rows), 65|67 (column-filter stride 64, one tile | stride 96, several tiles), 471|473 (LDS column filter | global-memory one),
+983|985 (fused sampling kernel | k_patch_sample + global row filter), 1023|1025 (the 128-column tile edge of k_patch_sample), 2329
+(the last size accepted; 2331 is refused).  Which path a size takes is READ from the library, never restated here: on the CPU from
+the planner alone (mods_amd.describe_plan, tests/test_describe_plan_cpu.py), on the GPU from what the device call booked
+(Context.describe_counters()), and the GPU tests assert that the two agree.  class_of() names the path of a per-window signature.
 
 Regions per P (three, in this order): interior -- the whole P x P window samples inside the image, the no-border path; top-left and
 bottom-right -- most of the window lies outside, the border path.
@@ -38,6 +41,45 @@ GROUPS = (("p19_65", tuple(p for p in SIZES if p <= 65)), ("p67_135", tuple(p fo
           ("p2083", (2083,)), ("p2329", (2329,)))
 assert tuple(p for _, g in GROUPS for p in g) == SIZES
 ARENA_FLOOR_FLOATS = 16 << 18      # MODSX_ARENA_MB = 16, the smallest arena describe_batch accepts
+
+# the path classes of the planner, in the order of P in which they occur, and what the sweep over SIZES must show
+CLASSES = ("fused", "whole_window_row_tile", "clamp_32_rows", "row_tiles_le_32", "several_col_tiles", "lds_rows_global_cols", "all_global")
+CLASS_SIZE = dict(zip(CLASSES, (25, 39, 47, 63, 77, 493, 985)))        # the size of each class that gets the extra calls
+ROW_TILE_VALUES = 47        # distinct LDS row tiles per window over SIZES (1 .. 492), as the counters gave them on an MI355X and as
+                            # the planner alone gives them on a CPU (tests/test_describe_plan_cpu.py)
+COL_TILE_VALUES = 15        # distinct LDS column tiles per window over SIZES (1 .. 41): every value the planner can give
+PER_WINDOW = ("fused_windows", "clamped_windows", "lds_row_tiles", "lds_col_tiles", "sample_tiles", "global_row_tiles", "global_col_tiles")
+# the counters that add up over calls (max_chunks is a running maximum): a device call's difference of two readings equals the
+# planner's counters of the same call in these
+SUMMED = ("calls", "chunks", "chunks_mid_image", "chunks_later_image", "jobs", "direct_jobs") + PER_WINDOW
+
+
+def class_of(sig):
+    """the path class of a per-window signature {counter of PER_WINDOW: value for one window}"""
+    fused, clamped, rt, ct, st, gr, gc = (sig[k] for k in PER_WINDOW)
+    if fused:
+        assert (rt, ct, st, gr, gc) == (1, 0, 0, 0, 0), sig
+        return "fused"
+    if st:
+        assert rt == 0 and ct == 0 and gr > 0 and gc > 0, sig
+        return "all_global"
+    assert rt > 0 and gr == 0, sig
+    if gc:
+        assert ct == 0, sig
+        return "lds_rows_global_cols"
+    assert ct > 0, sig
+    if ct > 1:
+        return "several_col_tiles"
+    if rt == 1:
+        return "whole_window_row_tile"
+    return "clamp_32_rows" if clamped else "row_tiles_le_32"
+
+
+def arena_floats():
+    """the window arena of this process, as describe_batch reads it: MODSX_ARENA_MB (at least 16) or 192 MiB, in floats"""
+    import os
+    mb = os.environ.get("MODSX_ARENA_MB")
+    return max(192 if mb is None else int(mb or 0), 16) << 18
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,6 +193,21 @@ VIEWS_DESC_MR = 24.0
 CRAFTED_RUNS = ((315, 60), (2083, 1), (0, 20), (315, 60))      # (P, regions) of the crafted single image, in list order
 
 
+_VIEWS = []
+
+
+def views_case(oracle, small_a):
+    """(regions, descriptors) of the views case from the oracle: image 0 of the small pair under VIEW_TILTS with desc_mrSize =
+    VIEWS_DESC_MR; computed once per process (small_a is the session's small pair, always the same image)"""
+    if not _VIEWS:
+        regs, desc = oracle.detect_describe_views(small_a, oracle.set_vs_pars([1.0], list(VIEW_TILTS), 360.0, 0.5, 1, []),
+                                                  desc=(VIEWS_DESC_MR, 41, 0, 1, 1, 0.2), threads=8)
+        for a in (regs, desc):
+            a.setflags(write=False)
+        _VIEWS.append((regs, desc))
+    return _VIEWS[0]
+
+
 @functools.lru_cache(maxsize=None)
 def crafted_regions():
     """60 regions of P = 315, one of P = 2083 (larger than the 16 MiB arena: it must travel alone), 20 direct-branch regions,
@@ -171,8 +228,9 @@ def crafted_regions():
 
 
 def greedy_cuts(windows, arena=ARENA_FLOOR_FLOATS):
-    """first region of every chunk after the first: describe_batch closes a chunk before the region whose P * P floats would
-    overflow the arena, unless the chunk is still empty (restated from the issue of the planner, for the CPU proof only)"""
+    """first region of every chunk after the first: the planner closes a chunk before the region whose P * P floats would
+    overflow the arena, unless the chunk is still empty (an independent restatement of the rule: the planner itself,
+    mods_amd.describe_plan, is checked against it in tests/test_describe_plan_cpu.py)"""
     cuts, used, count = [], 0, 0
     for i, P in enumerate(windows):
         need = P * P

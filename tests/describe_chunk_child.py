@@ -3,8 +3,9 @@
 
 MODSX_ARENA_MB is read once per process, so the run with the 16 MiB window arena gets a process of its own.  It opens one context
 and makes the calls of run_all() below -- the ones the parent makes in its own process at the default arena -- and writes what they
-returned together with what every call added to Context.describe_counters().  Nothing is compared here.  Progress goes to stderr,
-so that the tail of a child that did not come back says where it was."""
+returned together with what every call added to Context.describe_counters() and, for the views and the crafted case, with what
+the planner alone (mods_amd.describe_plan, no device) gives for the same regions at this process's arena.  Nothing is compared
+here.  Progress goes to stderr, so that the tail of a child that did not come back says where it was."""
 import os
 import sys
 
@@ -31,9 +32,15 @@ def _delta(modsx, ctx, before):
     return np.array([d[k] for k in modsx.DESCRIBE_COUNTERS], np.int64)
 
 
+def _plan(modsx, lists, mr_size):
+    p = modsx.describe_plan(lists, mr_size, arena_floats=DC.arena_floats())
+    assert p["rc"] == 0, p
+    return np.array([p["counters"][k] for k in modsx.DESCRIBE_COUNTERS], np.int64)
+
+
 def run_all(modsx, ctx, small_a, small_b, log=lambda s: None):
     """-> dict of arrays: the three chunk cases, each with what it added to the describe counters (max_chunks: the reading
-    after the case)"""
+    after the case); views_plan / crafted_plan: the planner's counters of the same regions (the views as 11 images)"""
     out = {}
     log("views")
     im = ctx.upload(np.ascontiguousarray(small_a, np.float32))
@@ -42,12 +49,15 @@ def run_all(modsx, ctx, small_a, small_b, log=lambda s: None):
                                                    want_counts=True)
     out["views_counters"] = _delta(modsx, ctx, c0)
     out["views_regs"], out["views_desc"], out["views_per_view"] = regs, desc, counts
+    # the 11 views go through one describe_batch call, view by view in list order: its images are the views' region lists
+    out["views_plan"] = _plan(modsx, np.split(regs, np.cumsum(counts)[:-1]), DC.VIEWS_DESC_MR)
     im.free()
     log("crafted")
     im = ctx.upload(DC.image())
     c0 = ctx.describe_counters()
     out["crafted_desc"] = ctx.describe_regions(im, DC.crafted_regions().view(modsx.REGION), mr_size=DC.MR_SIZE)
     out["crafted_counters"] = _delta(modsx, ctx, c0)
+    out["crafted_plan"] = _plan(modsx, DC.crafted_regions(), DC.MR_SIZE)
     im.free()
     log("pair")
     ia, ib = ctx.upload(small_a), ctx.upload(small_b)

@@ -74,8 +74,7 @@ def test_reference_descriptors_are_distinct_and_fill_both_halves(refs):
 def test_chunk_cases_cut_where_the_gpu_test_needs_them(oracle, small_pair):
     a = small_pair[0]
     assert a.shape == (DC.ROWS, DC.COLS)
-    regs, _ = oracle.detect_describe_views(a, oracle.set_vs_pars([1.0], list(DC.VIEW_TILTS), 360.0, 0.5, 1, []),
-                                           desc=(DC.VIEWS_DESC_MR, 41, 0, 1, 1, 0.2), threads=8)
+    regs, _ = DC.views_case(oracle, a)
     windows = [DC.window_of(s, DC.VIEWS_DESC_MR) for s in regs["det_kp"]["s"]]
     cuts = DC.greedy_cuts(windows)
     # the regions of a view: the identity carries img_id 0, view v > 0 carries v

@@ -5,7 +5,8 @@ of the oracle.
 The window arena is 192 MiB by default and every other describe call of the suite fits it many times over: one chunk.
 MODSX_ARENA_MB is read once per process, so ONE child (tests/describe_chunk_child.py) runs the cases at MODSX_ARENA_MB=16, the
 floor (4 194 304 floats); the parent runs the same run_all in process at the default arena.  Cases (tests/describe_cases.py; the
-cuts they give are proven on the CPU in tests/test_describe_cases_cpu.py):
+cuts the planner itself -- mods_amd/csrc/describe_plan.cpp through mods_amd.describe_plan -- gives for them are proven on the CPU
+in tests/test_describe_plan_cpu.py, and here the counters of the views and the crafted device calls must equal that plan's):
   views    image 0 of the small pair under TiltSet 1, 2, 4, 6, 8 (11 views) with desc_mrSize = 24: against
            oracle.detect_describe_views, regions field by field, descriptors byte by byte
   crafted  60 regions of P = 315, one of P = 2083 (larger than the arena: the `&& count` guard lets it open a chunk of its own
@@ -51,11 +52,9 @@ def _cnt(modsx, arr):
 @pytest.fixture(scope="module")
 def ref(oracle, small_pair):
     """the oracle on the views case and on the crafted image, computed once"""
-    regs, desc = oracle.detect_describe_views(small_pair[0], oracle.set_vs_pars([1.0], list(DC.VIEW_TILTS), 360.0, 0.5, 1, []),
-                                              desc=(DC.VIEWS_DESC_MR, 41, 0, 1, 1, 0.2), threads=8)
+    regs, desc = DC.views_case(oracle, small_pair[0])
     crafted = oracle.describe_regions(DC.image(), DC.crafted_regions(), mr_size=DC.MR_SIZE)
-    for a in (regs, desc, crafted):
-        a.setflags(write=False)
+    crafted.setflags(write=False)
     return dict(views_regs=regs, views_desc=desc, crafted=crafted)
 
 
@@ -89,6 +88,14 @@ def chunked(small_pair, tmp_path_factory):
     return dict(np.load(outp))
 
 
+def _booked_equals_plan(modsx, got, case):
+    """what the device call booked is what the planner alone gives for its regions at the same arena (max_chunks is a running
+    maximum of the context: at least the plan's)"""
+    c, p = _cnt(modsx, got[case + "_counters"]), _cnt(modsx, got[case + "_plan"])
+    assert {k: c[k] for k in DC.SUMMED} == {k: p[k] for k in DC.SUMMED}, (case, c, p)
+    assert c["max_chunks"] >= p["max_chunks"] == p["chunks"], (case, c, p)
+
+
 def _views_equal_oracle(got, ref, modsx):
     assert len(ref["views_regs"]) > 400
     assert same_records(got["views_regs"].view(modsx.REGION), ref["views_regs"].view(modsx.REGION))
@@ -105,6 +112,8 @@ def test_one_chunk_views_and_crafted_equal_oracle(one_chunk, ref, modsx):
         print("default arena, %s: %r" % (case, c))
         assert c["calls"] >= 1 and c["chunks"] == c["calls"], "%s: every call must be exactly one chunk at the default arena: %r" % (case, c)
         assert c["chunks_mid_image"] == 0 and c["chunks_later_image"] == 0, (case, c)
+    for case in ("views", "crafted"):
+        _booked_equals_plan(modsx, one_chunk, case)
     assert _cnt(modsx, one_chunk["crafted_counters"])["jobs"] == len(DC.crafted_regions())
     assert _cnt(modsx, one_chunk["views_counters"])["jobs"] == len(ref["views_regs"])
 
@@ -116,6 +125,7 @@ def test_chunked_views_equal_oracle(chunked, ref, modsx):
     _views_equal_oracle(chunked, ref, modsx)
     assert c["jobs"] == len(ref["views_regs"])
     assert c["chunks"] > c["calls"] and c["chunks_mid_image"] >= 1 and c["chunks_later_image"] >= 1, c
+    _booked_equals_plan(modsx, chunked, "views")
 
 
 def test_chunked_crafted_image_equals_oracle(chunked, ref, modsx):
@@ -127,6 +137,7 @@ def test_chunked_crafted_image_equals_oracle(chunked, ref, modsx):
     # one call of one image: every chunk after the first begins in the middle of the list, none at a later image
     assert (c["calls"], c["chunks"], c["chunks_mid_image"], c["chunks_later_image"]) == (1, len(DC.greedy_cuts(windows)) + 1, len(DC.greedy_cuts(windows)), 0), c
     assert c["jobs"] == len(windows) and c["direct_jobs"] == windows.count(0)
+    _booked_equals_plan(modsx, chunked, "crafted")
     assert c["sample_tiles"] == ((2083 + 63) // 64) * ((2083 + 127) // 128), "the P = 2083 window goes through k_patch_sample: %r" % (c,)
 
 

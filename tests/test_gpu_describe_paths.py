@@ -1,10 +1,14 @@
-"""GPU: the description stage against the oracle at every window-size path of describe_batch (mods_amd/csrc/engine.hip) and its
-five kernels (k_sample_rows_lds fused / row filter only, k_blur_cols_lds, k_patch_sample, k_patch_blur, k_describe).
+"""GPU: the description stage against the oracle at every window-size path of its planner (mods_amd/csrc/describe_plan.cpp, driven by
+describe_batch in engine.hip) and its five kernels (k_sample_rows_lds fused / row filter only, k_blur_cols_lds, k_patch_sample,
+k_patch_blur, k_describe).
 
 For every window size P of tests/describe_cases.py: ONE Context.describe_regions call for its three regions (interior: no-border
 sampling; top-left and bottom-right: the border path) against oracle.describe_regions on the same records, np.array_equal.  Which
 path the call took is read from the library: the difference of two Context.describe_counters() readings gives the size's signature
 (fused or not, row tile clamped to 32 or not, LDS row tiles and LDS column tiles per window, global-memory tiles of each kind).
+Every such difference must equal what the planner alone gives for the same regions and options (mods_amd.describe_plan): the
+path classes themselves are proven without a device in tests/test_describe_plan_cpu.py, and this equality ties that plan to what
+the device call ran.
 
 From the signatures (test_every_path_class_and_both_sides_of_every_change):
   - all seven path classes occur, in this order of P, each a contiguous run: fused; whole-window row tile + one LDS column tile;
@@ -29,11 +33,8 @@ from tests import describe_cases as DC
 
 pytestmark = pytest.mark.gpu
 
-CLASSES = ("fused", "whole_window_row_tile", "clamp_32_rows", "row_tiles_le_32", "several_col_tiles", "lds_rows_global_cols", "all_global")
-CLASS_SIZE = dict(zip(CLASSES, (25, 39, 47, 63, 77, 493, 985)))        # the size of each class that gets the extra calls
-ROW_TILE_VALUES = 47        # distinct LDS row tiles per window over SIZES (1 .. 492), as the counters gave them on an MI355X
-COL_TILE_VALUES = 15        # distinct LDS column tiles per window over SIZES (1 .. 41): every value the planner can give
-PER_WINDOW = ("fused_windows", "clamped_windows", "lds_row_tiles", "lds_col_tiles", "sample_tiles", "global_row_tiles", "global_col_tiles")
+CLASSES, CLASS_SIZE, PER_WINDOW, ROW_TILE_VALUES, COL_TILE_VALUES = DC.CLASSES, DC.CLASS_SIZE, DC.PER_WINDOW, DC.ROW_TILE_VALUES, DC.COL_TILE_VALUES
+_class_of = DC.class_of
 
 
 def _delta(ctx, before):
@@ -41,24 +42,11 @@ def _delta(ctx, before):
     return {k: now[k] - before[k] for k in now}
 
 
-def _class_of(sig):
-    fused, clamped, rt, ct, st, gr, gc = (sig[k] for k in PER_WINDOW)
-    if fused:
-        assert (rt, ct, st, gr, gc) == (1, 0, 0, 0, 0), sig
-        return "fused"
-    if st:
-        assert rt == 0 and ct == 0 and gr > 0 and gc > 0, sig
-        return "all_global"
-    assert rt > 0 and gr == 0, sig
-    if gc:
-        assert ct == 0, sig
-        return "lds_rows_global_cols"
-    assert ct > 0, sig
-    if ct > 1:
-        return "several_col_tiles"
-    if rt == 1:
-        return "whole_window_row_tile"
-    return "clamp_32_rows" if clamped else "row_tiles_le_32"
+def _same_as_plan(modsx, d, regs, fast=0):
+    """what the device call booked (the difference d of two counter readings) is what the planner alone gives for its regions"""
+    plan = modsx.describe_plan(regs, DC.MR_SIZE, fast=fast, arena_floats=DC.arena_floats())
+    assert plan["rc"] == 0, plan
+    assert {k: d[k] for k in DC.SUMMED} == {k: plan["counters"][k] for k in DC.SUMMED}, (d, plan)
 
 
 @pytest.fixture(scope="module")
@@ -77,6 +65,7 @@ def sweep(ctx, image, modsx):
         got = ctx.describe_regions(image, DC.regions_of(P).view(modsx.REGION), mr_size=DC.MR_SIZE)
         d = _delta(ctx, c0)
         assert (d["calls"], d["chunks"], d["jobs"], d["direct_jobs"]) == (1, 1, 3, 0), (P, d)
+        _same_as_plan(modsx, d, DC.regions_of(P))
         assert all(d[k] % 3 == 0 for k in PER_WINDOW), "P = %d: three windows of one size, three times the tiles: %r" % (P, d)
         out[P] = (got, {k: d[k] // 3 for k in PER_WINDOW})
     return out
@@ -149,6 +138,7 @@ def test_options_and_region_counts_at_one_size_per_class(ctx, image, modsx, orac
         d = _delta(ctx, c0)
         direct = len(regs) if kw.get("fast") else int(sum(DC.window_of(s) == 0 for s in regs["det_kp"]["s"]))
         assert (d["calls"], d["chunks"], d["jobs"], d["direct_jobs"]) == (1, 1, len(regs), direct), (what, d)
+        _same_as_plan(modsx, d, regs, fast=kw.get("fast", 0))
         assert ref.any(1).all(), what
         if not np.array_equal(got, ref):
             bad.append("P = %d (%s), %s: rows %r differ" % (P, cls, what, np.nonzero((got != ref).any(1))[0].tolist()))
