@@ -106,6 +106,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
            "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
+           "modsx_debug_baumberg_geometry", "modsx_debug_baumberg", "modsx_debug_check_borders",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -179,6 +180,10 @@ def lib():
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_describe_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_debug_baumberg_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_debug_baumberg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_check_borders.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_rep_create.restype = C.c_void_p
         L.modsx_rep_create.argtypes = [C.c_void_p]
         L.modsx_rep_free.restype = None
@@ -600,6 +605,21 @@ class Context(object):
                    "detect_affine_keypoints")
         return _take(out, n, KEYPOINT)
 
+    def debug_baumberg(self, planes, plane_of, xyspd, params, variant=0, chunk=0):
+        """modsx_debug_baumberg: one Baumberg launch for a job list (planes: Images of this context; plane_of[k], xyspd[k] = x, y,
+        s, pixelDistance of job k).  -> dict(u [n, 4] f32, ok, iters, geometry): geometry as baumberg_geometry() gives it."""
+        plane_of = np.ascontiguousarray(plane_of, np.int32)
+        xyspd = np.ascontiguousarray(xyspd, np.float32).reshape(-1, 4)
+        n = len(plane_of)
+        assert len(xyspd) == n
+        ptrs = (C.c_void_p * max(1, len(planes)))(*[im.h for im in planes])
+        u = np.zeros((max(n, 1), 4), np.float32)
+        ok, iters = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        geo = np.zeros(4, np.int32)
+        _check(lib().modsx_debug_baumberg(self._c(), ptrs, len(planes), _p(plane_of), _p(xyspd), n, C.byref(params), int(variant),
+                                          int(chunk), _p(u), _p(ok), _p(iters), _p(geo)), "debug_baumberg")
+        return dict(u=u[:n], ok=ok[:n], iters=iters[:n], geometry=dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo))))
+
     def detect_orientation(self, img, regs, mr_size=1.0, patch_size=41, half=0, max_ang=1, th=0.8, upright=0):
         regs = np.ascontiguousarray(regs, REGION)
         out = C.c_void_p()
@@ -879,6 +899,26 @@ def last_match_geometry():
     v = [C.c_int() for _ in range(5)]
     lib().modsx_last_match_geometry(*[C.byref(x) for x in v])
     return dict(zip(("qs", "fat", "S", "tiles_per_split", "ntiles_ub"), (x.value for x in v)))
+
+
+BAUMBERG_GEOMETRY = ("kernel", "chunk", "nchunks", "grid")   # include/modsx.h: modsx_debug_baumberg_geometry, in its order
+
+
+def baumberg_geometry(n, W=19, variant=0, chunk=0):
+    """dict(kernel, chunk, nchunks, grid): what a Baumberg launch of n keypoints at window W runs (host only, no GPU).  kernel 0 =
+    the two-slot stream kernel, 1 = k_baumberg<19>, 2 = k_baumberg<0>; raises where there is no such launch."""
+    geo = np.zeros(4, np.int32)
+    _check(lib().modsx_debug_baumberg_geometry(int(n), int(W), int(variant), int(chunk), _p(geo)), "baumberg_geometry")
+    return dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo)))
+
+
+def check_borders(tuples):
+    """interpolateCheckBorders as the kernels evaluate it (kmath.hpp check_borders, host build; no GPU) for an [n, 9] array of
+    (cols, rows, ofsx, ofsy, a11, a12, a21, a22, W) -> bool [n]."""
+    t = np.ascontiguousarray(tuples, np.float32).reshape(-1, 9)
+    out = np.zeros(max(1, len(t)), np.uint8)
+    _check(lib().modsx_debug_check_borders(_p(t), len(t), _p(out)), "check_borders")
+    return out[:len(t)].astype(bool)
 
 
 def orientation_counts(reset=False):

@@ -370,6 +370,34 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
   return MODSX_OK;
 }
 
+int modsx_debug_baumberg_geometry(int n, int W, int variant, int chunk, int *geometry) {
+  NEED(geometry);
+  const mx::BaumGeo g = mx::baumberg_geometry(n, W, variant, chunk);
+  geometry[0] = g.kernel; geometry[1] = g.chunk; geometry[2] = g.nchunks; geometry[3] = g.grid;
+  if (g.kernel < 0) { mx::set_error("modsx_debug_baumberg_geometry: no kernel for this window size / variant / chunk"); return MODSX_ERR_ARG; }
+  return MODSX_OK;
+}
+
+int modsx_debug_baumberg(modsx_ctx *ctx, const modsx_image *const *planes, int nplanes, const int *plane_of, const float *xyspd,
+                         int n, const modsx_hessaff_params *par, int variant, int chunk, float *u, int *ok, int *iters,
+                         int *geometry) {
+  NEED(ctx); NEED(par); NEED(geometry);
+  if (n < 0 || nplanes < 0 || (nplanes > 0 && !planes) || (n > 0 && (!plane_of || !xyspd || !u || !ok || !iters))) {
+    mx::set_error("modsx_debug_baumberg: bad argument"); return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  return debug_baumberg(ctx, planes, nplanes, plane_of, xyspd, n, *par, variant, chunk, u, ok, iters, geometry);
+}
+
+int modsx_debug_check_borders(const float *tuples, int n, unsigned char *touch) {
+  if (n < 0 || (n > 0 && (!tuples || !touch))) { mx::set_error("modsx_debug_check_borders: bad argument"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) {
+    const float *t = tuples + 9 * (size_t)i;
+    touch[i] = mx::check_borders((int)t[0], (int)t[1], t[2], t[3], t[4], t[5], t[6], t[7], (int)t[8], (int)t[8]) ? 1 : 0;
+  }
+  return n;
+}
+
 int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
   NEED(ctx);
   if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_describe_counters: bad argument"); return MODSX_ERR_ARG; }

@@ -217,8 +217,11 @@ int launch_cand_order(hipStream_t s, const Candidate *cand, const unsigned *coun
 constexpr int NMS_QUEUES = 64;      // sub-queues of the NMS extremum queue; counter k lives at counter[32 * (k + 1)]
 constexpr int NMS_TILE_ROWS = 16;   // rows of a 64-column NMS tile (kernels_pyramid.hip: NMS_ROWS)
 void launch_gray(hipStream_t s, const void *src, float *dst, size_t n, int channels, int dtype);
+// kernel 0 = k_baumberg_stream, 1 = k_baumberg<19>, 2 = k_baumberg<0> (-1: refused); keypoints per wavefront, wavefronts with work, workgroups
+struct BaumGeo { int kernel, chunk, nchunks, grid; };
+BaumGeo baumberg_geometry(int n, int W, int variant, int chunk);   // kernels_affine.hip (host only)
 void launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
-                     float convTh, float affInitialSigma);
+                     float convTh, float affInitialSigma, int variant = 0, int chunk = 0);
 constexpr int ATAN_CASES = 2048 + 64;   // 8 x 256 (sign / octant bits, table index) values of atan2LUTff's angle + the special case (entry 2048), padded
 constexpr int ORI_NV = 1344;   // entries of the orientation kernel's voting-pixel list (1245 under the mask, padded to 64 lanes x 21)
 void launch_orientation(hipStream_t s, const OriJob *jobs, float *out, int n, const ImgRef *imgs,

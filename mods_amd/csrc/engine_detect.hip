@@ -534,6 +534,54 @@ static int ensure_smm_mask(modsx_ctx *c, int W) {
   return MODSX_OK;
 }
 
+// Test entry (modsx_debug_baumberg): a Baumberg launch on a caller's job list, through the production launcher.  Job k reads
+// planes[planeOf[k]] at xyspd[4k ..] = x, y, s, pixelDistance.  The result buffer is filled with 0xFF bytes first, so a keypoint
+// that no wavefront wrote shows iters == -1.  geo: what baumberg_geometry gives for the launch.
+int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, const int *planeOf, const float *xyspd, int n,
+                   const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo) {
+  const BaumGeo g = baumberg_geometry(n, p.smmWindowSize, variant, chunk);
+  if (g.kernel < 0) { set_error("modsx_debug_baumberg: no kernel for this window size / variant / chunk"); return MODSX_ERR_ARG; }
+  geo[0] = g.kernel; geo[1] = g.chunk; geo[2] = g.nchunks; geo[3] = g.grid;
+  for (int i = 0; i < nplanes; i++)
+    if (!planes[i] || !planes[i]->d || planes[i]->rows < 4 || planes[i]->cols < 4) { set_error("modsx_debug_baumberg: planes must be at least 4 x 4"); return MODSX_ERR_ARG; }
+  for (int k = 0; k < n; k++) {
+    const float *q = xyspd + 4 * (size_t)k;
+    if ((unsigned)planeOf[k] >= (unsigned)nplanes || !std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) ||
+        !(q[3] > 0.f) || !std::isfinite(q[3])) {
+      set_error("modsx_debug_baumberg: job outside the contract (plane index, finite x / y / s, pixelDistance > 0)");
+      return MODSX_ERR_ARG;
+    }
+  }
+  if (!n) return MODSX_OK;
+  int rc = ensure_smm_mask(c, p.smmWindowSize);
+  if (rc) return rc;
+  const size_t total = (size_t)n;
+  if (!c->hAff.ensure(total * sizeof(AffJob) + total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
+  if (!c->affJobs.ensure(total * sizeof(AffJob)) || !c->affOut.ensure(total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
+  AffJob *hj = (AffJob *)c->hAff.p;
+  AffOut *ho = (AffOut *)((char *)c->hAff.p + total * sizeof(AffJob));
+  for (int k = 0; k < n; k++) {
+    const modsx_image *im = planes[planeOf[k]];
+    const float *q = xyspd + 4 * (size_t)k;
+    AffJob &j = hj[k];
+    j.blur = im->d; j.rows = im->rows; j.cols = im->cols;
+    j.x = q[0]; j.y = q[1]; j.s = q[2]; j.pixelDistance = q[3];
+  }
+  hipStream_t s = c->stream;
+  MX_HIP(hipMemcpyAsync(c->affJobs.p, hj, total * sizeof(AffJob), hipMemcpyHostToDevice, s));
+  MX_HIP(hipMemsetAsync(c->affOut.p, 0xFF, total * sizeof(AffOut), s));
+  launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, n, c->dSmmMask, p.smmWindowSize, p.maxIterations,
+                  p.convergenceThreshold, p.affInitialSigma, variant, chunk);
+  MX_HIP(hipGetLastError());
+  MX_HIP(hipMemcpyAsync(ho, c->affOut.p, total * sizeof(AffOut), hipMemcpyDeviceToHost, s));
+  MX_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < n; k++) {
+    u[4 * k] = ho[k].u11; u[4 * k + 1] = ho[k].u12; u[4 * k + 2] = ho[k].u21; u[4 * k + 3] = ho[k].u22;
+    ok[k] = ho[k].ok; iters[k] = ho[k].iters;
+  }
+  return MODSX_OK;
+}
+
 // AffineDetector::prepareKeysForExport, scale-space-detector.hpp:118-198
 static void prepare_keys_for_export(std::vector<modsx_keypoint> &keys, const modsx_hessaff_params &p) {
   if (keys.empty() || p.mode == MODSX_FIXED_TH) return;

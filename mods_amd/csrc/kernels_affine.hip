@@ -491,20 +491,42 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
 #define MODSX_BAUMBERG_CHUNK 8
 #endif
 
-void launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
-                     float convTh, float affInitialSigma) {
-  if (n <= 0) return;
+// Which kernel a Baumberg launch runs and in what shape: the one place that decides it (the launcher and the tests read it).
+// variant 0 = the production choice: the stream kernel at the default window (W == 19, K > 1 slots), k_baumberg<19> at W == 19 in
+// a K = 1 build, k_baumberg<0> at every other window; 1 = k_baumberg<19> (W == 19 only); 2 = k_baumberg<0> (any odd W in 3..19).
+// chunk 0 = the production chunk rule of the stream kernel, otherwise the keypoints per wavefront (>= 1; 1 leaves the second slot
+// empty); the one-keypoint kernels take a keypoint per workgroup whatever `chunk` says.  kernel = -1: no such launch.
+BaumGeo baumberg_geometry(int n, int W, int variant, int chunk) {
   constexpr int K = MODSX_BAUMBERG_K;
-  if (W == 19 && K > 1) {
+  BaumGeo g = {-1, 0, 0, 0};
+  if (n < 0 || chunk < 0 || W < 3 || W > AW_MAX || !(W & 1)) return g;
+  if (variant == 0) g.kernel = W == AW_MAX ? (K > 1 ? 0 : 1) : 2;
+  else if (variant == 1 && W == AW_MAX) g.kernel = 1;
+  else if (variant == 2) g.kernel = 2;
+  else return g;
+  if (g.kernel != 0) { g.chunk = 1; g.nchunks = n; g.grid = n; return g; }
+  if (!chunk) {
     // chunk per wavefront: long enough to keep the slots full across keypoints of different iteration counts, short enough
     // for >= 4 rounds of wavefronts over the chip (256 CUs x 16 resident) so that the tail of the launch stays short
-    int chunk = n / 16384;
+    chunk = n / 16384;
     chunk = chunk < K ? K : (chunk > MODSX_BAUMBERG_CHUNK ? MODSX_BAUMBERG_CHUNK : chunk);
-    const int nchunks = (n + chunk - 1) / chunk;
-    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL(k_baumberg_stream<K>, dim3(8 * ((nchunks + 7) / 8)), dim3(64), 0, s, jobs, out, n, mask, chunk, nchunks, maxIter,
+  }
+  g.chunk = chunk;
+  g.nchunks = (int)(((long long)n + chunk - 1) / chunk);
+  g.grid = 8 * ((g.nchunks + 7) / 8);
+  return g;
+}
+
+void launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                     float convTh, float affInitialSigma, int variant, int chunk) {
+  if (n <= 0) return;
+  constexpr int K = MODSX_BAUMBERG_K;
+  const BaumGeo g = baumberg_geometry(n, W, variant, chunk);
+  if (g.kernel == 0) {
+    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL(k_baumberg_stream<K>, dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks, maxIter,
                        convTh, affInitialSigma);
-  } else if (W == 19) hipLaunchKernelGGL(k_baumberg<19>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
-  else hipLaunchKernelGGL(k_baumberg<0>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
+  } else if (g.kernel == 1) hipLaunchKernelGGL(k_baumberg<19>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
+  else if (g.kernel == 2) hipLaunchKernelGGL(k_baumberg<0>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
 }
 
 }  // namespace mx

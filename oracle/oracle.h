@@ -116,6 +116,17 @@ int orc_detect_hessaff(const float *img, int rows, int cols, const orc_hessaff_p
                        double tilt, double zoom, orc_keypoint *out, int cap);
 int orc_find_affine_shape(const float *blur, int rows, int cols, const orc_hessaff_params *p,
                           float x, float y, float s, float pixelDistance, float *u /*4*/);
+/* findAffineShape over a job list: job k reads planes[plane_of[k]] (rows[] x cols[]) at xyspd[4k .. 4k+3] = x, y, s,
+ * pixelDistance.  Per job: u[4] = the state when the loop was left, whichever exit (identity for maxIterations <= 0); ok;
+ * iters = the loop counter at the break, maxIterations when the loop runs out; reason 0 converged, 1 NaN, 2 negative
+ * discriminant, 3 anisotropy, 4 iteration limit; touch 1 = every iteration took interpolate()'s border branch, 2 = none did,
+ * 3 = both occurred (0: no iteration ran).  Returns n, -1 for a plane index out of range. */
+int orc_find_affine_shape_batch(const float *const *planes, const int *rows, const int *cols, int nplanes, const int *plane_of,
+                                const float *xyspd, int n, const orc_hessaff_params *p, float *u /*n*4*/, int *ok, int *iters,
+                                int *reason, int *touch);
+/* interpolateCheckBorders, detectors/helpers.cpp:524-549 */
+int orc_interpolate_check_borders(int orig_w, int orig_h, float ofsx, float ofsy, float a11, float a12, float a21, float a22,
+                                  int res_w, int res_h);
 int orc_detect_affine_regions(const orc_keypoint *kps, int n, int img_id, int det_type, orc_region *out);
 int orc_detect_orientation(const float *img, int rows, int cols, const orc_region *in, int n,
                            double mrSize, int patchSize, int doHalfSIFT, int maxAngNum, double th,

@@ -81,19 +81,24 @@ static void gradient(const Img &img, Img &gx, Img &gy) {
     }
 }
 
-/* AffineShape::findAffineShape (AFF_BMBRG_SMM branch), affinedetectors/affine.cpp:26-169.
- * Returns 1 and u[4] when the Baumberg iteration converges. */
-int find_affine_shape(const Img &blur, const orc_hessaff_params &p, const Img &mask, float x, float y,
-                      float s, float pixelDistance, float *u) {
+/* AffineShape::findAffineShape (AFF_BMBRG_SMM branch), affinedetectors/affine.cpp:26-169, with a report of how the loop was
+ * left.  u[4] is the state at that moment, whichever exit; *iters the loop counter at the break (maxIterations when the loop
+ * runs out); *reason 0 converged, 1 NaN, 2 negative discriminant, 3 anisotropy, 4 iteration limit; *touch bit 0 = an iteration
+ * took interpolate()'s border branch, bit 1 = an iteration did not (0 when no iteration ran).  Returns 1 when converged. */
+static int find_affine_shape_report(const Img &blur, const orc_hessaff_params &p, const Img &mask, float x, float y, float s,
+                                    float pixelDistance, float *u, int *iters, int *reason, int *touch) {
   float era = 0.0f, erb = 0.0f;
   float u11 = 1.0f, u12 = 0.0f, u21 = 0.0f, u22 = 1.0f, l1 = 1.0f, l2 = 1.0f;
   float lx = x / pixelDistance, ly = y / pixelDistance;
   float ratio = s / (p.affInitialSigma * pixelDistance);
+  *iters = 0; *reason = 0; *touch = 0;
   if (!p.doBaumberg) { u[0] = u11; u[1] = u12; u[2] = u21; u[3] = u22; return 1; }
   const int W = p.smmWindowSize, maskPixels = W * W;
   Img img(W, W), fx(W, W), fy(W, W);
-  for (int l = 0; l < p.maxIterations; l++) {
+  int ok = 0, l, why = 4;
+  for (l = 0; l < p.maxIterations; l++) {
     float a = 0, b = 0, c = 0;
+    *touch |= interpolate_check_borders(blur.cols, blur.rows, lx, ly, u11 * ratio, u12 * ratio, u21 * ratio, u22 * ratio, W, W) ? 1 : 2;
     interpolate(blur, lx, ly, u11 * ratio, u12 * ratio, u21 * ratio, u22 * ratio, img);
     gradient(img, fx, fy);
     for (int i = 0; i < maskPixels; ++i) {
@@ -105,7 +110,7 @@ int find_affine_shape(const Img &blur, const orc_hessaff_params &p, const Img &m
     }
     a /= maskPixels; b /= maskPixels; c /= maskPixels;
     inv_sqrt(a, b, c, l1, l2);
-    if ((a != a) || (b != b) || (c != c)) break;
+    if ((a != a) || (b != b) || (c != c)) { why = 1; break; }
     erb = era;
     era = 1.0 - l2 / l1;
     float u11t = u11, u12t = u12;
@@ -113,14 +118,23 @@ int find_affine_shape(const Img &blur, const orc_hessaff_params &p, const Img &m
     u12 = a * u12t + b * u22;
     u21 = b * u11t + c * u21;
     u22 = b * u12t + c * u22;
-    if (!eigenvalues(u11, u12, u21, u22, l1, l2)) break;
-    if ((l1 / l2 > 6) || (l2 / l1 > 6)) break;
-    if (era < p.convergenceThreshold && erb < p.convergenceThreshold) {
-      u[0] = u11; u[1] = u12; u[2] = u21; u[3] = u22;
-      return 1;
-    }
+    if (!eigenvalues(u11, u12, u21, u22, l1, l2)) { why = 2; break; }
+    if ((l1 / l2 > 6) || (l2 / l1 > 6)) { why = 3; break; }
+    if (era < p.convergenceThreshold && erb < p.convergenceThreshold) { why = 0; ok = 1; break; }
   }
-  return 0;
+  u[0] = u11; u[1] = u12; u[2] = u21; u[3] = u22;
+  *iters = l; *reason = why;
+  return ok;
+}
+
+/* Returns 1 and u[4] when the Baumberg iteration converges (u is left alone otherwise). */
+int find_affine_shape(const Img &blur, const orc_hessaff_params &p, const Img &mask, float x, float y,
+                      float s, float pixelDistance, float *u) {
+  float v[4];
+  int iters, reason, touch;
+  if (!find_affine_shape_report(blur, p, mask, x, y, s, pixelDistance, v, &iters, &reason, &touch)) return 0;
+  u[0] = v[0]; u[1] = v[1]; u[2] = v[2]; u[3] = v[3];
+  return 1;
 }
 
 struct Detector {
@@ -424,6 +438,27 @@ int orc_find_affine_shape(const float *blur, int rows, int cols, const orc_hessa
   Img mask(p->smmWindowSize, p->smmWindowSize);
   gauss_mask(mask);
   return find_affine_shape(Img(rows, cols, blur), *p, mask, x, y, s, pixelDistance, u);
+}
+
+int orc_find_affine_shape_batch(const float *const *planes, const int *rows, const int *cols, int nplanes, const int *plane_of,
+                                const float *xyspd, int n, const orc_hessaff_params *p, float *u, int *ok, int *iters,
+                                int *reason, int *touch) {
+  Img mask(p->smmWindowSize, p->smmWindowSize);
+  gauss_mask(mask);
+  std::vector<Img> im;
+  for (int i = 0; i < nplanes; i++) im.emplace_back(rows[i], cols[i], planes[i]);
+  for (int k = 0; k < n; k++) {
+    if (plane_of[k] < 0 || plane_of[k] >= nplanes) return -1;
+    const float *q = xyspd + 4 * (size_t)k;
+    ok[k] = find_affine_shape_report(im[plane_of[k]], *p, mask, q[0], q[1], q[2], q[3], u + 4 * (size_t)k, iters + k, reason + k,
+                                     touch + k);
+  }
+  return n;
+}
+
+int orc_interpolate_check_borders(int orig_w, int orig_h, float ofsx, float ofsy, float a11, float a12, float a21, float a22,
+                                  int res_w, int res_h) {
+  return interpolate_check_borders(orig_w, orig_h, ofsx, ofsy, a11, a12, a21, a22, res_w, res_h) ? 1 : 0;
 }
 
 /* DetectAffineRegions<>, synth-detection.hpp:93-126 */

@@ -176,6 +176,33 @@ def find_affine_shape(blur, params, x, y, s, pixel_distance):
     return ok, u
 
 
+def find_affine_shape_batch(planes, plane_of, xyspd, params):
+    """findAffineShape over a job list (planes: list of 2-D arrays; plane_of[k], xyspd[k] = x, y, s, pixelDistance of job k).
+    -> dict(u [n, 4] f32, ok, iters, reason, touch): see orc_find_affine_shape_batch in oracle.h."""
+    planes = [_f32(a) for a in planes]
+    plane_of = np.ascontiguousarray(plane_of, np.int32)
+    xyspd = np.ascontiguousarray(xyspd, np.float32).reshape(-1, 4)
+    n = len(plane_of)
+    assert len(xyspd) == n
+    ptrs = (C.c_void_p * max(1, len(planes)))(*[a.ctypes.data for a in planes])
+    rows = np.array([a.shape[0] for a in planes], np.int32)
+    cols = np.array([a.shape[1] for a in planes], np.int32)
+    u = np.zeros((n, 4), np.float32)
+    ok, iters, reason, touch = (np.zeros(n, np.int32) for _ in range(4))
+    rc = lib().orc_find_affine_shape_batch(ptrs, _p(rows), _p(cols), len(planes), _p(plane_of), _p(xyspd), n, C.byref(params),
+                                           _p(u), _p(ok), _p(iters), _p(reason), _p(touch))
+    assert rc == n, rc
+    return dict(u=u, ok=ok, iters=iters, reason=reason, touch=touch)
+
+
+def interpolate_check_borders(t):
+    """interpolateCheckBorders for an [n, 9] array of (cols, rows, ofsx, ofsy, a11, a12, a21, a22, W) tuples -> bool [n]."""
+    t = np.asarray(t)
+    f = lib().orc_interpolate_check_borders
+    f.argtypes = [C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_int, C.c_int]
+    return np.array([f(int(r[0]), int(r[1]), r[2], r[3], r[4], r[5], r[6], r[7], int(r[8]), int(r[8])) for r in t.tolist()], bool)
+
+
 def detect_affine_regions(kps, img_id=0, det_type=0):
     kps = np.ascontiguousarray(kps, KEYPOINT)
     out = np.zeros(len(kps), REGION)
