@@ -402,21 +402,32 @@ int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int n
                               unsigned long long arena_floats, long *counters, int n, long *cuts, int cap_cuts, int *n_cuts);
 /* Test entries of the Baumberg stage (AffineShape::findAffineShape, affinedetectors/affine.cpp:26-169).
  * modsx_debug_baumberg_geometry (host only): what a launch of n keypoints at window W runs, geometry[4] = kernel (0 = the
- * two-slot stream kernel, 1 = the one-keypoint kernel with the window size compiled in, 2 = the one-keypoint kernel for any
- * window), keypoints per wavefront, wavefronts with work, workgroups.  variant 0 = what modsx_detect_affine_keypoints launches,
- * 1 = kernel 1 (W = 19 only), 2 = kernel 2 (odd W in 3..19); chunk 0 = the production rule, otherwise the keypoints per
- * wavefront of the stream kernel (>= 1).  MODSX_ERR_ARG (kernel -1) where there is no such launch.
+ * two-slot stream kernel on static chunks, 1 = the one-keypoint kernel with the window size compiled in, 2 = the one-keypoint
+ * kernel for any window), keypoints per wavefront, wavefronts with work, workgroups.  variant 0 = the stream kernel on static
+ * chunks where there is one (W = 19), else kernel 1 / 2; 1 = kernel 1 (W = 19 only), 2 = kernel 2 (odd W in 3..19); chunk 0 =
+ * the production rule, otherwise the keypoints per wavefront of the stream kernel (>= 1).  variant 3 (W = 19 only) = the stream
+ * kernel fed from a launch-wide queue, geometry[4] = kernel 3, wavefronts per range of the job list, ranges (8), workgroups
+ * (8 x wavefronts per range); chunk > 0 = that many wavefronts per range (<= 2^20).  Its production rule, chunk 0, is one
+ * resident set of wavefronts of the launching context's device (never more than ceil(n / 2), rounded up to a multiple of 8):
+ * the host-only entry does not know a device and refuses it, modsx_debug_baumberg_geometry_ctx answers for a context (which
+ * asks the runtime once).  MODSX_ERR_ARG (kernel -1) where there is no such launch.
+ * modsx_debug_baumberg_variant (host only): the variant modsx_detect_affine_keypoints launches at window W: 3 at W = 19, else
+ * 0.  MODSX_BAUMBERG_QUEUE in the environment (read once per process) overrides it for A/B runs: 0 = always variant 0, another
+ * number = variant 3 at W = 19.
  * modsx_debug_baumberg: runs that launch on the context's stream for a job list -- job k reads planes[plane_of[k]] (f32 images;
  * a 1-channel f32 upload is stored unchanged) at xyspd[4k ..] = x, y, s, pixelDistance -- and returns per job the shape u[4]
  * when the loop was left, ok and iters (the loop counter at the exit, maxIterations when the loop ran out; -1: no wavefront
- * wrote the job).  n = 0 returns MODSX_OK without a launch.  Non-finite x, y, s, pixelDistance <= 0 and planes below 4 x 4 are
- * refused with MODSX_ERR_ARG.
+ * wrote the job).  *handed_out (may be NULL): the keypoints the eight counters of variant 3 handed out, each counter clipped to
+ * the length of its range (n after a complete launch; 0 for the other variants).  n = 0 returns MODSX_OK without a launch.
+ * Non-finite x, y, s, pixelDistance <= 0 and planes below 4 x 4 are refused with MODSX_ERR_ARG.
  * modsx_debug_check_borders (host only): interpolateCheckBorders (detectors/helpers.cpp:524-549) as the kernels evaluate it, for n
  * tuples of 9 floats (cols, rows, ofsx, ofsy, a11, a12, a21, a22, W); touch[i] = 0 / 1.  Returns n. */
 int modsx_debug_baumberg_geometry(int n, int W, int variant, int chunk, int *geometry);
+int modsx_debug_baumberg_geometry_ctx(modsx_ctx *ctx, int n, int W, int variant, int chunk, int *geometry);
+int modsx_debug_baumberg_variant(int W);
 int modsx_debug_baumberg(modsx_ctx *ctx, const modsx_image *const *planes, int nplanes, const int *plane_of, const float *xyspd,
                          int n, const modsx_hessaff_params *par, int variant, int chunk, float *u, int *ok, int *iters,
-                         int *geometry);
+                         int *geometry, int *handed_out);
 int modsx_debug_check_borders(const float *tuples, int n, unsigned char *touch);
 /* per-stage time of the last modsx_match_pair in ms: detect, orient, describe, match, verify, total */
 int modsx_last_timings(modsx_ctx *ctx, double *ms6);

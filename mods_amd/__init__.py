@@ -106,7 +106,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
            "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
-           "modsx_debug_baumberg_geometry", "modsx_debug_baumberg", "modsx_debug_check_borders",
+           "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
+           "modsx_debug_baumberg", "modsx_debug_check_borders",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -182,7 +183,9 @@ def lib():
                                                 C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_debug_baumberg_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_baumberg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_baumberg_variant.argtypes = [C.c_int]
+        L.modsx_debug_baumberg_geometry_ctx.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_check_borders.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_rep_create.restype = C.c_void_p
         L.modsx_rep_create.argtypes = [C.c_void_p]
@@ -607,7 +610,8 @@ class Context(object):
 
     def debug_baumberg(self, planes, plane_of, xyspd, params, variant=0, chunk=0):
         """modsx_debug_baumberg: one Baumberg launch for a job list (planes: Images of this context; plane_of[k], xyspd[k] = x, y,
-        s, pixelDistance of job k).  -> dict(u [n, 4] f32, ok, iters, geometry): geometry as baumberg_geometry() gives it."""
+        s, pixelDistance of job k).  -> dict(u [n, 4] f32, ok, iters, geometry, handed_out): geometry as baumberg_geometry() gives
+        it, handed_out the keypoints the queue's counters handed out (variant 3; 0 otherwise)."""
         plane_of = np.ascontiguousarray(plane_of, np.int32)
         xyspd = np.ascontiguousarray(xyspd, np.float32).reshape(-1, 4)
         n = len(plane_of)
@@ -616,9 +620,18 @@ class Context(object):
         u = np.zeros((max(n, 1), 4), np.float32)
         ok, iters = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         geo = np.zeros(4, np.int32)
+        handed = C.c_int(0)
         _check(lib().modsx_debug_baumberg(self._c(), ptrs, len(planes), _p(plane_of), _p(xyspd), n, C.byref(params), int(variant),
-                                          int(chunk), _p(u), _p(ok), _p(iters), _p(geo)), "debug_baumberg")
-        return dict(u=u[:n], ok=ok[:n], iters=iters[:n], geometry=dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo))))
+                                          int(chunk), _p(u), _p(ok), _p(iters), _p(geo), C.byref(handed)), "debug_baumberg")
+        return dict(u=u[:n], ok=ok[:n], iters=iters[:n], geometry=dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo))),
+                    handed_out=handed.value)
+
+    def baumberg_geometry(self, n, W=19, variant=0, chunk=0):
+        """baumberg_geometry() as this context launches: the production rule of the queue form (variant 3, chunk 0) is one resident
+        set of wavefronts of the context's device, which the module-level function cannot know."""
+        geo = np.zeros(4, np.int32)
+        _check(lib().modsx_debug_baumberg_geometry_ctx(self._c(), int(n), int(W), int(variant), int(chunk), _p(geo)), "baumberg_geometry")
+        return dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo)))
 
     def detect_orientation(self, img, regs, mr_size=1.0, patch_size=41, half=0, max_ang=1, th=0.8, upright=0):
         regs = np.ascontiguousarray(regs, REGION)
@@ -906,10 +919,18 @@ BAUMBERG_GEOMETRY = ("kernel", "chunk", "nchunks", "grid")   # include/modsx.h: 
 
 def baumberg_geometry(n, W=19, variant=0, chunk=0):
     """dict(kernel, chunk, nchunks, grid): what a Baumberg launch of n keypoints at window W runs (host only, no GPU).  kernel 0 =
-    the two-slot stream kernel, 1 = k_baumberg<19>, 2 = k_baumberg<0>; raises where there is no such launch."""
+    the two-slot stream kernel on static chunks, 1 = k_baumberg<19>, 2 = k_baumberg<0>, 3 = the stream kernel fed from the launch-wide
+    queue (variant 3: chunk = wavefronts per range, nchunks = 8 ranges; its production rule, chunk 0, depends on the device:
+    Context.baumberg_geometry); raises where there is no such launch."""
     geo = np.zeros(4, np.int32)
     _check(lib().modsx_debug_baumberg_geometry(int(n), int(W), int(variant), int(chunk), _p(geo)), "baumberg_geometry")
     return dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo)))
+
+
+def baumberg_production_variant(W=19):
+    """the variant detect_affine_keypoints launches at window W (3 = the queue form, 0 = static chunks; MODSX_BAUMBERG_QUEUE=0 / 1 in
+    the environment, read once per process, forces one or the other)"""
+    return int(lib().modsx_debug_baumberg_variant(int(W)))
 
 
 def check_borders(tuples):

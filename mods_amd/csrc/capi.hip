@@ -378,15 +378,23 @@ int modsx_debug_baumberg_geometry(int n, int W, int variant, int chunk, int *geo
   return MODSX_OK;
 }
 
+int modsx_debug_baumberg_geometry_ctx(modsx_ctx *ctx, int n, int W, int variant, int chunk, int *geometry) {
+  NEED(ctx); NEED(geometry);
+  hipSetDevice(ctx->dev);
+  return debug_baumberg_geometry(ctx, n, W, variant, chunk, geometry);
+}
+
+int modsx_debug_baumberg_variant(int W) { return mx::baumberg_production_variant(W); }
+
 int modsx_debug_baumberg(modsx_ctx *ctx, const modsx_image *const *planes, int nplanes, const int *plane_of, const float *xyspd,
                          int n, const modsx_hessaff_params *par, int variant, int chunk, float *u, int *ok, int *iters,
-                         int *geometry) {
+                         int *geometry, int *handed_out) {
   NEED(ctx); NEED(par); NEED(geometry);
   if (n < 0 || nplanes < 0 || (nplanes > 0 && !planes) || (n > 0 && (!plane_of || !xyspd || !u || !ok || !iters))) {
     mx::set_error("modsx_debug_baumberg: bad argument"); return MODSX_ERR_ARG;
   }
   hipSetDevice(ctx->dev);
-  return debug_baumberg(ctx, planes, nplanes, plane_of, xyspd, n, *par, variant, chunk, u, ok, iters, geometry);
+  return debug_baumberg(ctx, planes, nplanes, plane_of, xyspd, n, *par, variant, chunk, u, ok, iters, geometry, handed_out);
 }
 
 int modsx_debug_check_borders(const float *tuples, int n, unsigned char *touch) {

@@ -217,11 +217,19 @@ int launch_cand_order(hipStream_t s, const Candidate *cand, const unsigned *coun
 constexpr int NMS_QUEUES = 64;      // sub-queues of the NMS extremum queue; counter k lives at counter[32 * (k + 1)]
 constexpr int NMS_TILE_ROWS = 16;   // rows of a 64-column NMS tile (kernels_pyramid.hip: NMS_ROWS)
 void launch_gray(hipStream_t s, const void *src, float *dst, size_t n, int channels, int dtype);
-// kernel 0 = k_baumberg_stream, 1 = k_baumberg<19>, 2 = k_baumberg<0> (-1: refused); keypoints per wavefront, wavefronts with work, workgroups
+// kernel 0 = k_baumberg_stream on static chunks, 1 = k_baumberg<19>, 2 = k_baumberg<0>, 3 = k_baumberg_stream fed from the launch-wide
+// queue (-1: refused); kernels 0..2: keypoints per wavefront, wavefronts with work, workgroups; kernel 3: wavefronts per range, ranges,
+// workgroups
 struct BaumGeo { int kernel, chunk, nchunks, grid; };
-BaumGeo baumberg_geometry(int n, int W, int variant, int chunk);   // kernels_affine.hip (host only)
-void launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
-                     float convTh, float affInitialSigma, int variant = 0, int chunk = 0);
+BaumGeo baumberg_geometry(int n, int W, int variant, int chunk, int resident = 0);   // kernels_affine.hip (host only)
+int baumberg_resident_waves();                                     // wavefronts of the queue form the current device holds at once
+int baumberg_production_variant(int W);                            // the variant detect_keypoints_batch launches at window W
+// the queue form's counters: one per range of the job list, 128 bytes apart.  They live behind the NMS counters in the context's
+// counter block, which scan_extrema zeroes once per launch set and nothing touches between that fill and the Baumberg launch
+constexpr int BAUM_RANGES = 8, BAUM_COUNTER_STRIDE = 32, BAUM_QUEUE_BYTES = BAUM_RANGES * BAUM_COUNTER_STRIDE * 4;
+MX_HD int baum_range_start(int n, int r) { return (int)(((long long)n * r) / BAUM_RANGES); }   // range r = keypoints start(r) .. start(r + 1)
+bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                     float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean);
 constexpr int ATAN_CASES = 2048 + 64;   // 8 x 256 (sign / octant bits, table index) values of atan2LUTff's angle + the special case (entry 2048), padded
 constexpr int ORI_NV = 1344;   // entries of the orientation kernel's voting-pixel list (1245 under the mask, padded to 64 lanes x 21)
 void launch_orientation(hipStream_t s, const OriJob *jobs, float *out, int n, const ImgRef *imgs,
@@ -368,6 +376,7 @@ struct modsx_ctx {
   mx::PinBuf hCand, hAff, hOri, hDesc, hMisc, hNms, hMatch, hViewTaps, hViewJobs, hMser, hRefs;
   // constant tables on device
   float *dSmmMask = nullptr;   // 19x19 computeGaussMask
+  int baumResident = 0;        // baumberg_resident_waves() of this context's device, asked at the first Baumberg launch (-1: no answer)
   int smmW = 0;
   std::vector<uint64_t> candKeys, candKeys2, candClaim;   // detection-order sort + octaveMap claim scratch (host)
   std::vector<uint32_t> candOrder, candOrder2;

@@ -22,8 +22,9 @@ int detect_scalespace_batch(modsx_ctx *c, const modsx_image *const *imgs, int n,
                             std::vector<modsx_sskp> *out);
 int detect_keypoints_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &par,
                            const double *tilts, const double *zooms, std::vector<modsx_keypoint> *out);
+int debug_baumberg_geometry(modsx_ctx *c, int n, int W, int variant, int chunk, int *geo);
 int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, const int *planeOf, const float *xyspd, int n,
-                   const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo);
+                   const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo, int *handedOut);
 void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out);
 // reproj (optional, one entry per image): what the caller's reproject_regions will be called with.  A region that
 // reproject_certain_drop flags for it is treated like one at the view's border: no orientation job and no output entry,

@@ -256,6 +256,14 @@ static NmsBatch nms_thresholds(const modsx_hessaff_params &p) {
   return nb;
 }
 
+// the context's counter block: the NMS words and sub-queue counters, then the Baumberg queue's counters
+constexpr size_t COUNTER_BYTES = (NMS_QUEUES + 1) * 128 + BAUM_QUEUE_BYTES;
+static unsigned *baum_queue(modsx_ctx *c) { return (unsigned *)c->counter.p + (NMS_QUEUES + 1) * 32; }
+static int baum_resident(modsx_ctx *c) {   // asked once per context; 0: the runtime gave no answer
+  if (!c->baumResident) { const int w = baumberg_resident_waves(); c->baumResident = w > 0 ? w : -1; }
+  return c->baumResident > 0 ? c->baumResident : 0;
+}
+
 // All (image, octave, level) scans of the batch in one launch (NMS_MAXJ jobs at most per launch): the accepted candidates
 // end up in c->cand, their count in word 0 of c->counter.  With the shipped numberOfScales = 3 the tiles number OCTAVES and a
 // tile scans the three levels of its octave in one pass over the five response planes (k_nms_localize_oct); otherwise a tile
@@ -263,9 +271,10 @@ static NmsBatch nms_thresholds(const modsx_hessaff_params &p) {
 static int scan_extrema(modsx_ctx *c, int n, const modsx_hessaff_params &p) {
   hipStream_t s = c->stream;
   if (!c->cand.ensure((size_t)CAND_CAP * sizeof(Candidate)) || !c->nmsQueue.ensure((size_t)CAND_CAP * 16)) return MODSX_ERR_NOMEM;
-  if (!c->counter.ensure((NMS_QUEUES + 1) * 128)) return MODSX_ERR_NOMEM;
-  // [0] accepted candidates, [1] extremum-queue overflow flag, from word 32 on the sub-queue counters: one fill for the lot
-  MX_HIP(hipMemsetAsync(c->counter.p, 0, 128 + NMS_QUEUES * 128, s));
+  if (!c->counter.ensure(COUNTER_BYTES)) return MODSX_ERR_NOMEM;
+  // [0] accepted candidates, [1] extremum-queue overflow flag, from word 32 on the sub-queue counters, behind them the counters of
+  // the Baumberg queue (baum_queue: nothing before that launch writes them): one fill for the lot
+  MX_HIP(hipMemsetAsync(c->counter.p, 0, COUNTER_BYTES, s));
   bool queuesClean = true;   // the sub-queue counters are zero (no scan has run since the fill)
   const NmsBatch nb = nms_thresholds(p);
   int maxOct = 0;
@@ -534,12 +543,22 @@ static int ensure_smm_mask(modsx_ctx *c, int W) {
   return MODSX_OK;
 }
 
+// baumberg_geometry as this context launches: the production rule of the queue form counts the resident wavefronts of its device
+int debug_baumberg_geometry(modsx_ctx *c, int n, int W, int variant, int chunk, int *geo) {
+  const BaumGeo g = baumberg_geometry(n, W, variant, chunk, baum_resident(c));
+  geo[0] = g.kernel; geo[1] = g.chunk; geo[2] = g.nchunks; geo[3] = g.grid;
+  if (g.kernel < 0) { set_error("modsx_debug_baumberg_geometry_ctx: no kernel for this window size / variant / chunk"); return MODSX_ERR_ARG; }
+  return MODSX_OK;
+}
+
 // Test entry (modsx_debug_baumberg): a Baumberg launch on a caller's job list, through the production launcher.  Job k reads
 // planes[planeOf[k]] at xyspd[4k ..] = x, y, s, pixelDistance.  The result buffer is filled with 0xFF bytes first, so a keypoint
-// that no wavefront wrote shows iters == -1.  geo: what baumberg_geometry gives for the launch.
+// that no wavefront wrote shows iters == -1.  geo: what baumberg_geometry gives for the launch.  handedOut (may be null): the
+// keypoints the counters of the queue form handed out, each counter clipped to the length of its range (0 for the other kernels).
 int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, const int *planeOf, const float *xyspd, int n,
-                   const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo) {
-  const BaumGeo g = baumberg_geometry(n, p.smmWindowSize, variant, chunk);
+                   const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo, int *handedOut) {
+  const BaumGeo g = baumberg_geometry(n, p.smmWindowSize, variant, chunk, baum_resident(c));
+  if (handedOut) *handedOut = 0;
   if (g.kernel < 0) { set_error("modsx_debug_baumberg: no kernel for this window size / variant / chunk"); return MODSX_ERR_ARG; }
   geo[0] = g.kernel; geo[1] = g.chunk; geo[2] = g.nchunks; geo[3] = g.grid;
   for (int i = 0; i < nplanes; i++)
@@ -558,6 +577,7 @@ int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, 
   const size_t total = (size_t)n;
   if (!c->hAff.ensure(total * sizeof(AffJob) + total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
   if (!c->affJobs.ensure(total * sizeof(AffJob)) || !c->affOut.ensure(total * sizeof(AffOut))) return MODSX_ERR_NOMEM;
+  if (!c->counter.ensure(COUNTER_BYTES) || !c->hMisc.ensure(BAUM_QUEUE_BYTES)) return MODSX_ERR_NOMEM;
   AffJob *hj = (AffJob *)c->hAff.p;
   AffOut *ho = (AffOut *)((char *)c->hAff.p + total * sizeof(AffJob));
   for (int k = 0; k < n; k++) {
@@ -570,11 +590,23 @@ int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, 
   hipStream_t s = c->stream;
   MX_HIP(hipMemcpyAsync(c->affJobs.p, hj, total * sizeof(AffJob), hipMemcpyHostToDevice, s));
   MX_HIP(hipMemsetAsync(c->affOut.p, 0xFF, total * sizeof(AffOut), s));
-  launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, n, c->dSmmMask, p.smmWindowSize, p.maxIterations,
-                  p.convergenceThreshold, p.affInitialSigma, variant, chunk);
+  // (no scan has filled the counter block for this launch: the launcher zeroes the queue's counters)
+  if (!launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, n, c->dSmmMask, p.smmWindowSize, p.maxIterations,
+                       p.convergenceThreshold, p.affInitialSigma, variant, chunk, baum_resident(c), baum_queue(c), false)) {
+    MX_HIP(hipGetLastError());
+    set_error("modsx_debug_baumberg: nothing was launched"); return MODSX_ERR_INTERNAL;
+  }
   MX_HIP(hipGetLastError());
   MX_HIP(hipMemcpyAsync(ho, c->affOut.p, total * sizeof(AffOut), hipMemcpyDeviceToHost, s));
+  if (g.kernel == 3) MX_HIP(hipMemcpyAsync(c->hMisc.p, baum_queue(c), BAUM_QUEUE_BYTES, hipMemcpyDeviceToHost, s));
   MX_HIP(hipStreamSynchronize(s));
+  if (g.kernel == 3 && handedOut) {
+    const unsigned *w = (const unsigned *)c->hMisc.p;
+    for (int r = 0; r < BAUM_RANGES; r++) {
+      const unsigned len = (unsigned)(baum_range_start(n, r + 1) - baum_range_start(n, r));
+      *handedOut += (int)std::min(w[BAUM_COUNTER_STRIDE * r], len);
+    }
+  }
   for (int k = 0; k < n; k++) {
     u[4 * k] = ho[k].u11; u[4 * k + 1] = ho[k].u12; u[4 * k + 2] = ho[k].u21; u[4 * k + 3] = ho[k].u22;
     ok[k] = ho[k].ok; iters[k] = ho[k].iters;
@@ -656,8 +688,17 @@ int detect_keypoints_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, 
   if (p.doBaumberg) {
     MX_HIP(ctx_copy(c, c->affJobs.p, hj, total * sizeof(AffJob), hipMemcpyHostToDevice));
     ProfScope ps(c, K_BAUMBERG, (double)total * 361 * 4 * 2);
-    launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, (int)total, c->dSmmMask, p.smmWindowSize,
-                    p.maxIterations, p.convergenceThreshold, p.affInitialSigma);
+    // (the queue's counters are zero since scan_extrema's fill of the counter block)
+    const int variant = baumberg_production_variant(p.smmWindowSize);
+    if (variant == 3 && !baum_resident(c)) {
+      set_error("Baumberg: the occupancy query that sizes the queue form's grid failed (MODSX_BAUMBERG_QUEUE=0 runs the static chunks)");
+      return MODSX_ERR_DEVICE;
+    }
+    if (!launch_baumberg(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, (int)total, c->dSmmMask, p.smmWindowSize, p.maxIterations,
+                         p.convergenceThreshold, p.affInitialSigma, variant, 0, baum_resident(c), baum_queue(c), true)) {
+      MX_HIP(hipGetLastError());
+      set_error("Baumberg: no kernel for this window size"); return MODSX_ERR_INTERNAL;
+    }
     MX_HIP(ctx_copy(c, ho, c->affOut.p, total * sizeof(AffOut), hipMemcpyDeviceToHost));
     MX_HIP(ctx_sync(c));
   } else {

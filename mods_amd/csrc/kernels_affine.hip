@@ -7,7 +7,12 @@
 // The 19x19 window lives in LDS.  The 64 lanes produce the warped samples and the
 // gradient products in parallel; the three second-moment sums are accumulated by three
 // lanes in raster order because the reference's f32 running sums are order dependent.
+// Kernels: k_baumberg<WT> (one keypoint per wavefront, any odd window up to 19) and k_baumberg_stream<K, QUEUE> (the default window:
+// K keypoint slots per wavefront, fed from the wavefront's own chunk of the job list, or -- QUEUE, what production launches -- from
+// a launch-wide queue by a persistent grid, so that a slot idles only when the whole list is handed out).  baumberg_geometry picks
+// kernel and shape, baumberg_production_variant says which variant detection launches.
 #include "engine.hpp"
+#include <algorithm>
 
 namespace mx {
 
@@ -222,9 +227,23 @@ __device__ unsigned long long g_btrace[16];
 #ifndef MODSX_BAUMBERG_K
 #define MODSX_BAUMBERG_K 2
 #endif
-template <int K>
+#ifndef MODSX_BAUMBERG_STEAL
+#define MODSX_BAUMBERG_STEAL 1
+#endif
+// QUEUE = true: the slots are fed from a launch-wide queue instead of the wavefront's own chunk.  The job list is cut into
+// BAUM_RANGES contiguous ranges (range r = keypoints n r / 8 .. n (r + 1) / 8: one per XCD, the L2 locality of xcd_chunk), each
+// with a counter of its own on its own 128-byte line (engine.hpp), zero at launch.  A wavefront starts on range blockIdx.x & 7
+// and, once that is exhausted, takes from the following ranges in turn (the tilt-8 views at the end of a list hold far more
+// 16-iteration keypoints than the first, so the ranges are not equally heavy); it never asks a range again that it has seen
+// empty, so a counter ends at most at its range's length + wavefronts x K.  The grid is one resident set of wavefronts
+// (baumberg_geometry), and a round with an idle slot happens only when all eight ranges are exhausted.
+// NO WAVEFRONT EVER WAITS FOR ANOTHER: there is no spin loop and no flag, nothing depends on another wavefront being resident or
+// having run, and every loop ends because a counter passed the end of its range or because maxIter was reached.  That makes the
+// launch safe when the other streams of the pipeline hold part of the chip: a wavefront dispatched late finds what is left.
+template <int K, bool QUEUE>
 __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffOut *out, int n, const float *mask, int chunk,
-                                                        int nchunks, int maxIter, float convTh, float affInitialSigma) {
+                                                        int nchunks, int maxIter, float convTh, float affInitialSigma,
+                                                        unsigned *queue) {
   constexpr int W = AW_MAX, WW = W * W, half = W >> 1, CH = AW_MAX * AW_MAX + 3;
   constexpr int PERM = (WW + 63) / 64;
   __shared__ __attribute__((aligned(16))) float buf[K][3][CH];
@@ -253,10 +272,27 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
   // the job list is image-major in detection order (octave, level, row, column): XCD x takes the x-th contiguous eighth of
   // the chunks, so that the blur planes a keypoint's windows read stay in ONE L2 (round 2: 1.03 GB fetched per launch, every
   // window a miss)
-  int next = min(xcd_chunk(blockIdx.x, nchunks) * chunk, n);           // wave-uniform: next keypoint of the chunk
-  const int end = min(next + chunk, n);
+  int next = QUEUE ? 0 : min(xcd_chunk(blockIdx.x, nchunks) * chunk, n);   // wave-uniform: next keypoint of the chunk
+  const int end = QUEUE ? 0 : min(next + chunk, n);
+  int rg = blockIdx.x & (BAUM_RANGES - 1);                             // queue form: the range this wavefront takes from now
+  // ... and the ranges it has found exhausted, one bit each (MODSX_BAUMBERG_STEAL=0 builds, for A/B runs: every other range counts
+  // as exhausted from the start, so a wavefront stops at its own)
+  unsigned emptyRanges = MODSX_BAUMBERG_STEAL ? 0u : ((1u << BAUM_RANGES) - 1u) & ~(1u << rg);
   bool live = false;
   if (maxIter <= 0) {   // no iteration at all: identity shape, not converged (the loop of the reference does not run)
+    if constexpr (QUEUE) {   // 64 keypoints per draw, the own range first
+      for (int t = 0; t < BAUM_RANGES; t++, rg = (rg + 1) & (BAUM_RANGES - 1)) {
+        const int lo = baum_range_start(n, rg), len = baum_range_start(n, rg + 1) - lo;
+        for (;;) {
+          unsigned got = 0;
+          if (lane == 0) got = atomicAdd(queue + BAUM_COUNTER_STRIDE * rg, 64u);
+          got = __builtin_amdgcn_readfirstlane(got);
+          if (got >= (unsigned)len) break;
+          if (got + lane < (unsigned)len) { AffOut o; o.u11 = 1; o.u12 = 0; o.u21 = 0; o.u22 = 1; o.ok = 0; o.iters = 0; out[lo + (int)got + lane] = o; }
+        }
+      }
+      return;
+    }
     for (int i = next + lane; i < end; i += 64) { AffOut o; o.u11 = 1; o.u12 = 0; o.u21 = 0; o.u22 = 1; o.ok = 0; o.iters = 0; out[i] = o; }
     return;
   }
@@ -264,23 +300,53 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
   unsigned long long bt_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, btl_ = __builtin_readcyclecounter();
 #endif
   for (;;) {
-    // refill: every idle slot takes the next keypoint of the chunk, in slot order
+    // refill: every idle slot takes the next keypoint of the chunk (of the queue), in slot order
     {
       const bool want = slotLane && !live;
       const unsigned long long wm = __ballot(want && !(lane & 1));           // one bit per idle slot (its even lane)
       const int rank = __popcll(wm & ((1ull << (lane & ~1)) - 1ull));
-      const int cand = next + rank;
-      if (want && cand < end) {
-        kidx = cand;
-        const AffJob sj = jobs[cand];
-        ratio = sj.s / (affInitialSigma * sj.pixelDistance);
-        slx = sj.x / sj.pixelDistance; sly = sj.y / sj.pixelDistance;
-        scols = sj.cols; srows = sj.rows;
-        u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f; l1 = 1.0f; l2 = 1.0f; era = 0.0f; erb = 0.0f;
-        ok = 0; it = 0;
-        live = true;
+      if constexpr (QUEUE) {
+        // one draw for all idle slots: lane 0 adds their number to the range's counter, the slots take base + rank while that
+        // is inside the range.  A draw that comes back short marks the range exhausted for this wavefront, which then goes
+        // on to the next range it has not seen empty; with all eight marked it draws no more.
+        int need = __popcll(wm), done = 0;
+        while (need > 0 && emptyRanges != (1u << BAUM_RANGES) - 1u) {
+          const int lo = baum_range_start(n, rg), len = baum_range_start(n, rg + 1) - lo;
+          unsigned got = 0;
+          if (lane == 0) got = atomicAdd(queue + BAUM_COUNTER_STRIDE * rg, (unsigned)need);
+          got = __builtin_amdgcn_readfirstlane(got);
+          const int avail = got >= (unsigned)len ? 0 : min(need, len - (int)got);
+          if (want && rank >= done && rank < done + avail) {
+            const int cand = lo + (int)got + (rank - done);
+            kidx = cand;
+            const AffJob sj = jobs[cand];
+            ratio = sj.s / (affInitialSigma * sj.pixelDistance);
+            slx = sj.x / sj.pixelDistance; sly = sj.y / sj.pixelDistance;
+            scols = sj.cols; srows = sj.rows;
+            u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f; l1 = 1.0f; l2 = 1.0f; era = 0.0f; erb = 0.0f;
+            ok = 0; it = 0;
+            live = true;
+          }
+          done += avail; need -= avail;
+          if (need > 0) {
+            emptyRanges |= 1u << rg;
+            for (int t = 1; t < BAUM_RANGES && ((emptyRanges >> rg) & 1u); t++) rg = (rg + 1) & (BAUM_RANGES - 1);
+          }
+        }
+      } else {
+        const int cand = next + rank;
+        if (want && cand < end) {
+          kidx = cand;
+          const AffJob sj = jobs[cand];
+          ratio = sj.s / (affInitialSigma * sj.pixelDistance);
+          slx = sj.x / sj.pixelDistance; sly = sj.y / sj.pixelDistance;
+          scols = sj.cols; srows = sj.rows;
+          u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f; l1 = 1.0f; l2 = 1.0f; era = 0.0f; erb = 0.0f;
+          ok = 0; it = 0;
+          live = true;
+        }
+        next = min(next + __popcll(wm), end);
       }
-      next = min(next + __popcll(wm), end);
     }
     const unsigned long long liveMask = __ballot(live);
     if (!liveMask) break;
@@ -491,15 +557,50 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
 #define MODSX_BAUMBERG_CHUNK 8
 #endif
 
+// The queue form's production grid: one resident set of wavefronts of the current device (CUs x workgroups of the kernel a CU holds
+// at once, as the runtime reports them; a context asks once, engine_detect.hip).  0: no device to ask.
+int baumberg_resident_waves() {
+  int dev = 0, cus = 0, perCu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_baumberg_stream<MODSX_BAUMBERG_K, true>, 64, 0) != hipSuccess ||
+      cus <= 0 || perCu <= 0) { (void)hipGetLastError(); return 0; }
+  return cus * perCu;
+}
+
+// Which variant production launches (detect_keypoints_batch): the queue form where there is one.  MODSX_BAUMBERG_QUEUE in the
+// environment (read once per process) overrides the default for A/B runs: 0 = always variant 0, any other number = the queue form.
+#ifndef MODSX_BAUMBERG_QUEUE_DEFAULT
+#define MODSX_BAUMBERG_QUEUE_DEFAULT 1
+#endif
+int baumberg_production_variant(int W) {
+  static const char *const env = getenv("MODSX_BAUMBERG_QUEUE");
+  static const bool queue = env ? atoi(env) != 0 : MODSX_BAUMBERG_QUEUE_DEFAULT != 0;
+  return (queue && W == AW_MAX && MODSX_BAUMBERG_K > 1) ? 3 : 0;
+}
+
 // Which kernel a Baumberg launch runs and in what shape: the one place that decides it (the launcher and the tests read it).
-// variant 0 = the production choice: the stream kernel at the default window (W == 19, K > 1 slots), k_baumberg<19> at W == 19 in
+// variant 0 = the stream kernel on static chunks at the default window (W == 19, K > 1 slots), k_baumberg<19> at W == 19 in
 // a K = 1 build, k_baumberg<0> at every other window; 1 = k_baumberg<19> (W == 19 only); 2 = k_baumberg<0> (any odd W in 3..19).
 // chunk 0 = the production chunk rule of the stream kernel, otherwise the keypoints per wavefront (>= 1; 1 leaves the second slot
-// empty); the one-keypoint kernels take a keypoint per workgroup whatever `chunk` says.  kernel = -1: no such launch.
-BaumGeo baumberg_geometry(int n, int W, int variant, int chunk) {
+// empty); the one-keypoint kernels take a keypoint per workgroup whatever `chunk` says.
+// variant 3 = the stream kernel fed from the queue (kernel 3; W == 19 and K > 1 only): nchunks = the 8 ranges, chunk = wavefronts per
+// range, grid = 8 x chunk.  chunk 0 = the production rule: `resident` wavefronts (baumberg_resident_waves of the launching context's
+// device; without that number the rule has no answer), never more than ceil(n / K), rounded up to a multiple of 8; otherwise
+// that many wavefronts per range.  kernel = -1: no such launch.
+BaumGeo baumberg_geometry(int n, int W, int variant, int chunk, int resident) {
   constexpr int K = MODSX_BAUMBERG_K;
   BaumGeo g = {-1, 0, 0, 0};
   if (n < 0 || chunk < 0 || W < 3 || W > AW_MAX || !(W & 1)) return g;
+  if (variant == 3) {
+    if (W != AW_MAX || K <= 1 || chunk > (1 << 20)) return g;
+    if (!chunk) {
+      if (resident <= 0) return g;
+      const long long waves = std::min<long long>(resident, ((long long)n + K - 1) / K);
+      chunk = (int)((waves + BAUM_RANGES - 1) / BAUM_RANGES);
+    }
+    g.kernel = 3; g.chunk = chunk; g.nchunks = BAUM_RANGES; g.grid = BAUM_RANGES * chunk;
+    return g;
+  }
   if (variant == 0) g.kernel = W == AW_MAX ? (K > 1 ? 0 : 1) : 2;
   else if (variant == 1 && W == AW_MAX) g.kernel = 1;
   else if (variant == 2) g.kernel = 2;
@@ -517,16 +618,28 @@ BaumGeo baumberg_geometry(int n, int W, int variant, int chunk) {
   return g;
 }
 
-void launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
-                     float convTh, float affInitialSigma, int variant, int chunk) {
-  if (n <= 0) return;
+// queue: the BAUM_RANGES counters of the queue form (BAUM_QUEUE_BYTES, device memory); queueClean: they are zero and nothing on
+// the stream writes them before this launch, otherwise the launcher fills them first.  false: there is no such launch (or the
+// queue form was asked for without its counters) and nothing was launched
+bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                     float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean) {
+  if (n <= 0) return true;
   constexpr int K = MODSX_BAUMBERG_K;
-  const BaumGeo g = baumberg_geometry(n, W, variant, chunk);
+  const BaumGeo g = baumberg_geometry(n, W, variant, chunk, resident);
   if (g.kernel == 0) {
-    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL(k_baumberg_stream<K>, dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks, maxIter,
-                       convTh, affInitialSigma);
+    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL((k_baumberg_stream<K, false>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks,
+                       maxIter, convTh, affInitialSigma, (unsigned *)nullptr);
+  } else if (g.kernel == 3 && queue) {
+    MX_DUP(K_BAUMBERG) {
+      if (!queueClean && hipMemsetAsync(queue, 0, BAUM_QUEUE_BYTES, s) != hipSuccess) return false;   // (the caller reads the runtime's error)
+      queueClean = false;
+      hipLaunchKernelGGL((k_baumberg_stream<K, true>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks, maxIter,
+                         convTh, affInitialSigma, queue);
+    }
   } else if (g.kernel == 1) hipLaunchKernelGGL(k_baumberg<19>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
   else if (g.kernel == 2) hipLaunchKernelGGL(k_baumberg<0>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
+  else return false;
+  return true;
 }
 
 }  // namespace mx
