@@ -429,6 +429,19 @@ int modsx_debug_baumberg(modsx_ctx *ctx, const modsx_image *const *planes, int n
                          int n, const modsx_hessaff_params *par, int variant, int chunk, float *u, int *ok, int *iters,
                          int *geometry, int *handed_out);
 int modsx_debug_check_borders(const float *tuples, int n, unsigned char *touch);
+/* Which lane does which element in the LDS describe kernels (csrc/describe_lanes.hpp; both entries are host only).
+ * modsx_debug_describe_lanes: for a window of P x P, counts[16] = blur taps, needed columns NC, rows per row tile (0: the window
+ * takes the global-memory kernels), needed rows per column tile (0: global-memory kernel, -1: the sampling kernel filters the
+ * columns too), then for each of sampling taps, row filter, column filter inside the sampling kernel, separate column filter
+ * three lane-slot counts over the whole window: slots that hold a sample / an output pair, slots this build issues, slots the
+ * rule before it issued (fixed 4-slot chunks of 4 x 64 or 8 x 32 coordinates; whole rounds of 1024 pairs), restated for comparison.
+ * modsx_debug_describe_lane_map: the tap slots of one parked chunk of a row pass of `rows` (1 .. 64) rows.  rule[5] = columns of
+ * a full chunk, row stride of the coordinate park (words, odd), words of the park per array, and for a chunk of nc columns
+ * (1 .. the full chunk; nc = 0 asks for the first three only) the multiplier M of e / nc == e * M >> 16 and the 64-lane slots
+ * issued.  map[3 e ..] = row, column, park word of sample e -- lane e % 64 of slot e / 64 -- for e < min(rows * nc, cap), computed
+ * as the kernel computes them.  Returns rows * nc. */
+int modsx_debug_describe_lanes(int P, long *counts);
+int modsx_debug_describe_lane_map(int rows, int nc, int *rule, int *map, int cap);
 /* per-stage time of the last modsx_match_pair in ms: detect, orient, describe, match, verify, total */
 int modsx_last_timings(modsx_ctx *ctx, double *ms6);
 

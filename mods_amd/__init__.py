@@ -107,7 +107,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
            "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
            "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
-           "modsx_debug_baumberg", "modsx_debug_check_borders",
+           "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -187,6 +187,8 @@ def lib():
         L.modsx_debug_baumberg_variant.argtypes = [C.c_int]
         L.modsx_debug_baumberg_geometry_ctx.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_check_borders.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_debug_describe_lanes.argtypes = [C.c_int, C.c_void_p]
+        L.modsx_debug_describe_lane_map.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_rep_create.restype = C.c_void_p
         L.modsx_rep_create.argtypes = [C.c_void_p]
         L.modsx_rep_free.restype = None
@@ -940,6 +942,35 @@ def check_borders(tuples):
     out = np.zeros(max(1, len(t)), np.uint8)
     _check(lib().modsx_debug_check_borders(_p(t), len(t), _p(out)), "check_borders")
     return out[:len(t)].astype(bool)
+
+
+DESCRIBE_LANE_PHASES = ("sample", "rows", "cols_fused", "cols")   # include/modsx.h: modsx_debug_describe_lanes, in its order
+
+
+def describe_lanes(P):
+    """Lane slots of the LDS describe kernels for one P x P window (host only, no GPU): dict(ksize, NC, rows0, ro1) plus, per
+    phase of DESCRIBE_LANE_PHASES, (useful, issued, issued_parent): slots that hold a sample or an output pair, slots this
+    build issues, slots the rule before it issued."""
+    k = np.zeros(16, np.int64)
+    _check(lib().modsx_debug_describe_lanes(int(P), _p(k)), "describe_lanes")
+    out = dict(zip(("ksize", "NC", "rows0", "ro1"), (int(x) for x in k[:4])))
+    for q, name in enumerate(DESCRIBE_LANE_PHASES):
+        out[name] = tuple(int(x) for x in k[4 + 3 * q:7 + 3 * q])
+    return out
+
+
+def describe_lane_map(rows, nc=0):
+    """The tap slots of one parked chunk of the sampling kernel (host only): dict(cols, stride, park_words, magic, slots) for a
+    row pass of `rows` rows and, for a chunk of nc columns, map = int32 [rows * nc, 3] of (row, column, park word) per sample e
+    (lane e % 64 of slot e / 64)."""
+    rule = np.zeros(5, np.int32)
+    m = np.zeros((max(1, int(rows) * int(nc)), 3), np.int32)
+    n = lib().modsx_debug_describe_lane_map(int(rows), int(nc), _p(rule), _p(m), len(m))
+    if n < 0:
+        _check(n, "describe_lane_map")
+    out = dict(zip(("cols", "stride", "park_words", "magic", "slots"), (int(x) for x in rule)))
+    out["map"] = m[:n]
+    return out
 
 
 def orientation_counts(reset=False):

@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/modsx.h.
 #include <math.h>
 #include <malloc.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -9,6 +10,7 @@
 #include <deque>
 #include "engine_api.hpp"
 #include "describe_plan.hpp"
+#include "describe_lanes.hpp"
 
 using namespace mx;
 
@@ -385,6 +387,45 @@ int modsx_debug_baumberg_geometry_ctx(modsx_ctx *ctx, int n, int W, int variant,
 }
 
 int modsx_debug_baumberg_variant(int W) { return mx::baumberg_production_variant(W); }
+
+int modsx_debug_describe_lanes(int P, long *counts) {
+  NEED(counts);
+  if (P < 3) { mx::set_error("modsx_debug_describe_lanes: no such window"); return MODSX_ERR_ARG; }
+  mx::DescSizePlan sp;
+  const int rc = mx::describe_size_plan(P, sp);
+  if (rc) return rc;
+  mx::LaneCount k[4] = {};   // sampling taps, row filter, column filter of the fused small-window path, separate column filter
+  const int NP = (sp.NC + 1) / 2;
+  for (int r0 = 0; sp.rows0 > 0 && r0 < P; r0 += sp.rows0) {
+    const int nr = std::min(sp.rows0, P - r0);
+    mx::lanes_count_sampling(P, nr, mx::BF_T / 64, k[0]);
+    mx::lanes_count_filter(nr * NP, k[1]);
+  }
+  if (sp.ro1 < 0) mx::lanes_count_filter(sp.NC * NP, k[2]);
+  for (int ro0 = 0; sp.ro1 > 0 && ro0 < sp.NC; ro0 += sp.ro1) mx::lanes_count_filter(std::min(sp.ro1, sp.NC - ro0) * NP, k[3]);
+  counts[0] = sp.ksize; counts[1] = sp.NC; counts[2] = sp.rows0; counts[3] = sp.ro1;
+  for (int q = 0; q < 4; q++) { counts[4 + 3 * q] = k[q].useful; counts[5 + 3 * q] = k[q].issued; counts[6 + 3 * q] = k[q].issuedParent; }
+  return MODSX_OK;
+}
+
+int modsx_debug_describe_lane_map(int rows, int nc, int *rule, int *map, int cap) {
+  NEED(rule);
+  if (rows < 1 || rows > 64) { mx::set_error("modsx_debug_describe_lane_map: a row pass has 1 .. 64 rows"); return MODSX_ERR_ARG; }
+  constexpr mx::SrLaneTable T = mx::sr_lane_table();
+  const int ncFull = mx::sr_table_cols(T.w[rows]), CP = mx::sr_stride(ncFull);
+  rule[0] = ncFull; rule[1] = CP; rule[2] = mx::SR_PARK; rule[3] = 0; rule[4] = 0;
+  if (nc == 0) return 0;
+  if (nc < 0 || nc > ncFull || cap < 0 || (cap > 0 && !map)) { mx::set_error("modsx_debug_describe_lane_map: bad argument"); return MODSX_ERR_ARG; }
+  const unsigned magic = mx::sr_table_magic(T.w[nc]);
+  const int tot = rows * nc;
+  rule[3] = (int)magic; rule[4] = mx::sr_slots(rows, nc);
+  for (int e = 0; e < tot && e < cap; e++) {
+    unsigned r, c;
+    mx::sr_sample_rc((unsigned)e, nc, magic, r, c);
+    map[3 * e] = (int)r; map[3 * e + 1] = (int)c; map[3 * e + 2] = (int)(r * (unsigned)CP + c);
+  }
+  return tot;
+}
 
 int modsx_debug_baumberg(modsx_ctx *ctx, const modsx_image *const *planes, int nplanes, const int *plane_of, const float *xyspd,
                          int n, const modsx_hessaff_params *par, int variant, int chunk, float *u, int *ok, int *iters,

@@ -268,8 +268,8 @@ size_t match_workspace_bytes(int n1, int n2);
 void launch_match(hipStream_t s, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2,
                   double sqminratio, double contrDistSq, int nn, MatchRow *rows, void *workspace);
 // Shapes of the fused sampling + row-filter kernel (kernels_describe.hip k_sample_rows_lds; describe_plan.cpp sizes the tiles with the
-// same numbers): LDS floats of the sampled row tile, block rows of a fully fused small window, whether a wave parks 4 / 8
-// columns of coordinates at a time (1) or 8 / 16 (0), and the workgroups per CU the kernel is built for
+// same numbers): LDS floats of the sampled row tile, block rows of a fully fused small window, whether a wave's coordinate
+// park is 2 x 64 x 5 words (1) or 2 x 64 x 9 (0; describe_lanes.hpp fills 320 of them), and the workgroups per CU the kernel is built for
 // The kernel's time follows its residency far more than its tile shapes: with 4 workgroups per CU (20 KB tile + 20 KB of
 // coordinates / fused block) it took 1.9 ms per 31-view pair on one stream, padded to 3 per CU 3.4 ms, and at 6 / 7 / 8 per CU
 // 1.33 / 1.18 / 1.13 ms (175 -> 179 / 179.5 / 180.5 pairs/s), although fewer windows are then small enough for the fused

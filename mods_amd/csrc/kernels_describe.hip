@@ -12,6 +12,7 @@
 // k_describe, which resamples it to 41x41 in LDS.  Windows whose row tile does not fit LDS take k_patch_sample (arena A)
 // and the global-memory filter k_patch_blur.
 #include "engine.hpp"
+#include "describe_lanes.hpp"
 
 namespace mx {
 
@@ -298,25 +299,28 @@ __global__ __launch_bounds__(256) void k_patch_blur(const DescJob *jobs, const i
 constexpr int BLUR_T = 256, BLUR_W = BLUR_T / 64;   // threads / waves per workgroup of the LDS blur kernels
 constexpr int BLUR_LDS = MODSX_SR_WIN;   // row tile of the fused sampling + row-filter kernel: 20 KB
 constexpr int BLUR_LDS_C = MODSX_BLUR_LDS_C;                               // column filter: fatter tiles re-read fewer halo rows
+MX_D int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
 // the row filter proper, on a tile parked in LDS as nr rows of R + P + R floats (replicated border written out)
 // (dst = the tile's place in arena B, row stride NC; or, for the fully fused small windows, an LDS block of row stride ostride)
-__device__ __forceinline__ void blur_rows_from_lds(const BlurTile &bt, const float *win, const int *sneed, const float *__restrict__ taps,
-                                                   float *__restrict__ out, int ostride) {
-  const int NC = bt.NC, n = bt.n, R = n >> 1, RW = bt.P + 2 * R, nr = bt.count;
+// one round of it: BLUR_T threads x NQ pairs from pair `done` on
+template <int NQ>
+__device__ __forceinline__ void blur_rows_round(const BlurTile &bt, const float *win, const int *sneed, const float *__restrict__ taps,
+                                                float *__restrict__ out, int ostride, int done, int total) {
+  const int NC = bt.NC, n = bt.n, R = n >> 1, RW = bt.P + 2 * R;
   // A thread forms 4 PAIRS of horizontally adjacent outputs (needed columns 2m, 2m+1 -- the host checks that such pairs are
   // neighbours in the window, which the x0 / x0+1 construction gives): both members of a pair take tap j from adjacent LDS
   // words, so a tap of a pair is one 2-word read, one packed multiply and one packed add.
   const float *kg = taps + bt.tapOfs;
-  const int NP = (NC + 1) >> 1, total = nr * NP;
-  constexpr int NQ = 4;
-  for (int base = threadIdx.x; base < total; base += BLUR_T * NQ) {
+  const int NP = (NC + 1) >> 1;
+  {
+    const int base = done + threadIdx.x;
     int p[NQ];     // win[p[q] + j], win[p[q] + j + 1] = window columns need[2m] + j - R, + 1 of the pair's row
     float v0[NQ], v1[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       int e = base + q * BLUR_T;
-      e = e < total ? e : total - 1;                                      // idle slots repeat the last pair, not stored
+      e = e < total ? e : total - 1;                     // idle lanes of the last live slot repeat the last pair, not stored
       // e / NP (exact for e < 4096, NP <= 96); every product here is 24 bit x 24 bit (e < 2^12, magic <= 2^20, rows and strides
       // < 2^12): v_mul_u32_u24 issues at the full rate, the 32-bit v_mul_lo_u32 the plain `*` compiles to at a quarter of it
       const int r = (int)(__umul24((unsigned)e, (unsigned)bt.magic) >> 20), m = e - (int)__umul24((unsigned)r, (unsigned)NP);
@@ -361,17 +365,35 @@ __device__ __forceinline__ void blur_rows_from_lds(const BlurTile &bt, const flo
     }
   }
 }
+// Whole rounds while BLUR_T x 4 pairs remain; of the last round a wavefront runs only the slots that have a pair
+// (describe_lanes.hpp: bf_live_slots, wave-uniform), in a body of that many slots -- the tap loops carry no per-lane branch.
+// A P = 29 window is 29 x 15 = 435 pairs: 7 wavefront slots instead of the 16 of a full round.
+static_assert(BF_T == BLUR_T, "describe_lanes.hpp describes the rounds of these kernels");
+__device__ __forceinline__ void blur_rows_from_lds(const BlurTile &bt, const float *win, const int *sneed, const float *__restrict__ taps,
+                                                   float *__restrict__ out, int ostride) {
+  const int total = bt.count * ((bt.NC + 1) >> 1);
+  int done = 0;
+  for (; done + BLUR_T * BF_NQ <= total; done += BLUR_T * BF_NQ) blur_rows_round<BF_NQ>(bt, win, sneed, taps, out, ostride, done, total);
+  if (done >= total) return;
+  // (three slots run as two and one: with a 3-slot body next to the others the sampling kernel no longer fits 64 VGPRs -- it
+  // spilled two -- and the 8 workgroups per CU are worth far more than one pass over the scalar tap loads)
+  const int k = bf_live_slots(total - done, wave_id());
+  if (k == 4) { blur_rows_round<4>(bt, win, sneed, taps, out, ostride, done, total); return; }
+  if (k & 2) blur_rows_round<2>(bt, win, sneed, taps, out, ostride, done, total);
+  if (k & 1) blur_rows_round<1>(bt, win, sneed, taps, out, ostride, done + (k & 2) * BLUR_T, total);
+}
 
 // the column filter proper on source rows parked in LDS from row `lo` on (row stride LS, replicated border rows written
 // out): needed rows ro0 .. ro0 + nro - 1, all NC columns; out = first output of the tile (row stride NC)
-template <int LS>
-__device__ __forceinline__ void blur_cols_from_lds(int NC, int n, int ro0, int nro, int lo, int magic, const float *win, const int *sneed,
-                                                   const float *__restrict__ kg, float *__restrict__ out) {
+// one round of it: BLUR_T threads x NQ pairs from pair `done` on
+template <int LS, int NQ>
+__device__ __forceinline__ void blur_cols_round(int NC, int n, int ro0, int lo, int magic, const float *win, const int *sneed,
+                                                const float *__restrict__ kg, float *__restrict__ out, int done, int total) {
   const int R = n >> 1;
   // pairs of horizontally adjacent outputs again: (ri, 2m) and (ri, 2m+1) read adjacent LDS words in every parked row
-  const int NP = (NC + 1) >> 1, total = nro * NP;
-  constexpr int NQ = 4;
-  for (int base = threadIdx.x; base < total; base += BLUR_T * NQ) {
+  const int NP = (NC + 1) >> 1;
+  {
+    const int base = done + threadIdx.x;
     int pc[NQ];
     float2 v[NQ];
 #pragma unroll
@@ -414,71 +436,105 @@ __device__ __forceinline__ void blur_cols_from_lds(int NC, int n, int ro0, int n
     }
   }
 }
+template <int LS>
+__device__ __forceinline__ void blur_cols_from_lds(int NC, int n, int ro0, int nro, int lo, int magic, const float *win, const int *sneed,
+                                                   const float *__restrict__ kg, float *__restrict__ out) {
+  const int total = nro * ((NC + 1) >> 1);
+  int done = 0;
+  for (; done + BLUR_T * BF_NQ <= total; done += BLUR_T * BF_NQ) blur_cols_round<LS, BF_NQ>(NC, n, ro0, lo, magic, win, sneed, kg, out, done, total);
+  if (done >= total) return;
+  switch (bf_live_slots(total - done, wave_id())) {   // as in blur_rows_from_lds
+    case 1: blur_cols_round<LS, 1>(NC, n, ro0, lo, magic, win, sneed, kg, out, done, total); break;
+    case 2: blur_cols_round<LS, 2>(NC, n, ro0, lo, magic, win, sneed, kg, out, done, total); break;
+    case 3: blur_cols_round<LS, 3>(NC, n, ro0, lo, magic, win, sneed, kg, out, done, total); break;
+    case 4: blur_cols_round<LS, 4>(NC, n, ro0, lo, magic, win, sneed, kg, out, done, total); break;
+    default: break;
+  }
+}
 
 // Stage 1 + the row pass of stage 2 in one launch: a workgroup SAMPLES its tile of window rows (interpolate(), the f32
 // running-sum coordinates of k_patch_sample) straight into the LDS tile of the row filter and filters it there, so the
 // P x P window never exists in HBM (arena A was written once and read once per region: 2 x 4 P^2 bytes, the largest
 // traffic item of the describe stage).  Lane j of a wave walks row j of the tile over the wave's QUARTER of the columns
-// (its coordinates start with col0 dependent adds, as for the column tiles of k_patch_sample) and parks SR_C columns at a
+// (its coordinates start with col0 dependent adds, as for the column tiles of k_patch_sample) and parks a chunk of columns at a
 // time; the taps are then taken with the lanes running along the rows.  Coordinates, taps, filter sums: term for term those
 // of k_patch_sample + the row filter.
-// A wave parks C columns of up to 64 rows at a time in its 64 x 9 words of coordinates: C = 8 for tiles of more than 32 rows,
-// C = 16 for tiles of up to 32 rows (the host keeps row tiles out of the 33..48 range), so that a lane has 8 samples --
-// 16 loads -- in flight either way.
-constexpr int SR_CW = MODSX_SR_HALF ? 4 : 8;      // columns parked per pass for tiles of more than 32 rows (twice that up to 32 rows)
-constexpr int SR_WORDS = 64 * (SR_CW + 1);
+// Per row pass (<= 64 rows) a wave parks as many columns as give it at most SR_SLOTS x 64 samples (describe_lanes.hpp:
+// 4 columns of 64 rows, 21 of 12, 63 of 4 and fewer), at an odd row stride, and takes the samples e = r * nc + c of the chunk
+// with lane l of slot u on e = 64 u + l: only the slots that hold a sample are issued, all of them together, so a lane has up
+// to 4 samples -- 16 loads -- in flight.  Tiles of a few rows (the large windows) and the last, short chunk of a wave's
+// columns used to issue four slots for a fraction of that many samples.
+constexpr int SR_CW = MODSX_SR_HALF ? 4 : 8;
+constexpr int SR_WORDS = 64 * (SR_CW + 1);           // coordinate words per wave and array
+static_assert(SR_PARK <= SR_WORDS, "a chunk of describe_lanes.hpp fits the wave's coordinate park");
 constexpr int FC_LS = 64, FC_ROWS = MODSX_FC_ROWS;   // fully fused small windows: NC <= FC_LS needed columns, P + 2 R <= FC_ROWS block rows
-MX_D int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+__device__ const SrLaneTable g_srLanes = sr_lane_table();   // [x] = ceil(2^16 / x) << 8 | columns per chunk of x rows
 
-template <bool TOUCH, int C>
-__device__ __forceinline__ void sample_chunk_lds(const ImgRef &im, const float *cx, const float *cy, float *dst, int RW, int tot, int nc,
-                                                 int lane) {
-  constexpr int CP = C + 1, PER = SR_CW;   // tot <= 64 * PER (64 rows x SR_CW columns, or 32 x 2 SR_CW)
-  float v[PER];
+// the taps of one parked chunk of nc columns (row stride CP words): K slots, the last of which may be part empty
+template <bool TOUCH, int K>
+__device__ __forceinline__ void sample_chunk_lds(const ImgRef &im, const float *cx, const float *cy, float *dst, int RW, int CP, int tot,
+                                                 int nc, unsigned magic, int lane) {
+  float v[K];
 #pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const int e = lane + 64 * u, r = e / C, c = e - r * C;
-    v[u] = (e < tot && c < nc) ? bilinear_tap(as_global(im.d), im.rows, im.cols, cx[r * CP + c], cy[r * CP + c], TOUCH) : 0.f;
+  for (int u = 0; u < K; u++) {
+    const unsigned e = (unsigned)lane + 64u * u;
+    unsigned r, c;
+    sr_sample_rc(e, nc, magic, r, c);
+    const unsigned ci = __umul24(r, (unsigned)CP) + c;
+    v[u] = (u + 1 < K || (int)e < tot) ? bilinear_tap(as_global(im.d), im.rows, im.cols, cx[ci], cy[ci], TOUCH) : 0.f;
   }
 #pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const int e = lane + 64 * u, r = e / C, c = e - r * C;
-    if (e < tot && c < nc) dst[__umul24((unsigned)r, (unsigned)RW) + (unsigned)c] = v[u];
+  for (int u = 0; u < K; u++) {
+    const unsigned e = (unsigned)lane + 64u * u;
+    unsigned r, c;
+    sr_sample_rc(e, nc, magic, r, c);
+    if (u + 1 < K || (int)e < tot) dst[__umul24(r, (unsigned)RW) + c] = v[u];
   }
 }
+template <bool TOUCH>
+__device__ __forceinline__ void sample_chunk_slots(const ImgRef &im, const float *cx, const float *cy, float *dst, int RW, int CP, int tot,
+                                                   int nc, unsigned magic, int lane) {
+  switch (sr_slots(1, tot)) {   // wave-uniform; 1 .. SR_SLOTS
+    case 1: sample_chunk_lds<TOUCH, 1>(im, cx, cy, dst, RW, CP, tot, nc, magic, lane); break;
+    case 2: sample_chunk_lds<TOUCH, 2>(im, cx, cy, dst, RW, CP, tot, nc, magic, lane); break;
+    case 3: sample_chunk_lds<TOUCH, 3>(im, cx, cy, dst, RW, CP, tot, nc, magic, lane); break;
+    default: sample_chunk_lds<TOUCH, 4>(im, cx, cy, dst, RW, CP, tot, nc, magic, lane); break;
+  }
+}
+static_assert(SR_SLOTS == 4, "sample_chunk_slots dispatches 1 .. 4 slots");
 
-template <int C>
 __device__ __forceinline__ void sample_rows_tile(const BlurTile &bt, const DescJob &jb, const ImgRef &im, const float2 *rowStart,
                                                  float *win, float *cx, float *cy, int lane, int wave) {
-  constexpr int CP = C + 1, RG = C == SR_CW ? 64 : 32;   // rows per pass of the wave
   const int P = bt.P, R = bt.n >> 1, RW = P + 2 * R, nr = bt.count, r0 = bt.first;
   const int half = P >> 1;
   const bool touch = check_borders(im.cols, im.rows, jb.x, jb.y, jb.a11, jb.a12, jb.a21, jb.a22, P, P);
   const int cper = (P + BLUR_W - 1) / BLUR_W, cb = wave * cper, ce = (cb + cper) < P ? (cb + cper) : P;
-  for (int rb = 0; rb < nr; rb += RG) {
-    const bool active = lane < RG && rb + lane < nr;
+  for (int rb = 0; rb < nr; rb += 64) {
+    const int rowsHere = (nr - rb) < 64 ? (nr - rb) : 64;
+    const bool active = lane < rowsHere;
     const float2 rs = rowStart[active ? r0 + rb + lane : r0];   // the running sums of the window's rows (k_expand_blur_tiles)
     float WX = rs.x - (float)half * jb.a11;
     float WY = rs.y - (float)half * jb.a21;
     for (int i = 0; i < cb; i++) { WX += jb.a11; WY += jb.a21; }
-    const int rowsHere = (nr - rb) < RG ? (nr - rb) : RG;
-    for (int c0 = cb; c0 < ce; c0 += C) {
-      const int nc = (ce - c0) < C ? (ce - c0) : C;
+    const int ncFull = sr_table_cols(g_srLanes.w[rowsHere]), CP = sr_stride(ncFull);
+    const unsigned wFull = g_srLanes.w[ncFull];
+    const int po = lane * CP;
+    for (int c0 = cb; c0 < ce; c0 += ncFull) {
+      const int nc = (ce - c0) < ncFull ? (ce - c0) : ncFull;
+      const unsigned magic = sr_table_magic(nc == ncFull ? wFull : g_srLanes.w[nc]);
       if (active) {
-#pragma unroll
-        for (int i = 0; i < C; i++) {
-          if (i < nc) {
-            cx[lane * CP + i] = WX;
-            cy[lane * CP + i] = WY;
-            WX += jb.a11;
-            WY += jb.a21;
-          }
+#pragma unroll 4
+        for (int i = 0; i < nc; i++) {
+          cx[po + i] = WX;
+          cy[po + i] = WY;
+          WX += jb.a11;
+          WY += jb.a21;
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       float *d = win + rb * RW + R + c0;
-      if (!touch) sample_chunk_lds<false, C>(im, cx, cy, d, RW, rowsHere * C, nc, lane);
-      else sample_chunk_lds<true, C>(im, cx, cy, d, RW, rowsHere * C, nc, lane);
+      if (!touch) sample_chunk_slots<false>(im, cx, cy, d, RW, CP, rowsHere * nc, nc, magic, lane);
+      else sample_chunk_slots<true>(im, cx, cy, d, RW, CP, rowsHere * nc, nc, magic, lane);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
   }
@@ -511,8 +567,7 @@ __global__ __launch_bounds__(BLUR_T, MODSX_SR_WGS) void k_sample_rows_lds(const 
   for (int i = threadIdx.x; i < NC; i += BLUR_T) sneed[i] = needTab[bt.needOfs + i];
   const ImgRef im = imgs[jb.img];
   const float2 *rowStart = rowStarts + jb.scratchOfs;
-  if (nr <= 32) sample_rows_tile<2 * SR_CW>(bt, jb, im, rowStart, win, cxw, cyw, lane, wave);
-  else sample_rows_tile<SR_CW>(bt, jb, im, rowStart, win, cxw, cyw, lane, wave);
+  sample_rows_tile(bt, jb, im, rowStart, win, cxw, cyw, lane, wave);
   __syncthreads();
   // replicated border: R copies of the first and of the last sample of every row
   // (2^s >= 2 R lanes per row, 64 >> s rows per wavefront and pass: no division by the run-time 2 R per element)
