@@ -508,6 +508,47 @@ int modsx_match_fginn_db_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1
  * attachment must therefore be alike on all ranks. */
 int modsx_set_fginn_db(modsx_ctx *ctx, const modsx_db *db);
 
+/* Matching of binary descriptors (ORB, BRISK, FREAK, the AKAZE bit strings) by a distance threshold: MatchFLANNDistance
+ * (matching/matching.cpp:607-666), which MatchImgReps calls for every class with DistanceThreshold > 0
+ * (correspondencebank.cpp:283-284, 342-343), with binary_matcher = linear and binary_dist = HAMMING.  The search is exact (the
+ * reference's default is an approximate hierarchical index).  The library does not produce such descriptors: the caller brings
+ * them, e.g. a 32-value ORB class read with modsx_load_regions.
+ *   descriptors  nbytes bytes per region, 1 <= nbytes <= MODSX_HAMMING_MAX_BYTES; the reference stores Row[j] = floor(desc.vec[j])
+ *                as uchar.  From the host: dtype 0 = u8, dtype 1 = f32 holding the integers 0..255; anything else (fractions,
+ *                values out of range, NaN, another dtype) is MODSX_ERR_ARG, the rule of every other descriptor entry.
+ *   search       for every query the two nearest trains by (Hamming distance, train index) in lexicographic order: equal
+ *                distances keep the lower train index, for the first neighbour and for the second.
+ *   record rule  max_distance = (int)(float)distanceThreshold; a query gives a record iff d(first) <= max_distance; records come
+ *                in query order: q, t0 = first, tj = t1 = second, d1 = d(first), d2 = d2by2ndcl = d(second),
+ *                ratio = (double)d1 / (double)d2.  0 / 0 gives NaN and is returned as such; d1 <= d2, so no infinity occurs.
+ *   edges        n1 == 0 or n2 == 0: 0 records.  n2 == 1: MODSX_ERR_ARG whatever n1 is -- the reference reads a second
+ *                neighbour that was never written.  distanceThreshold <= 0 or not finite: MODSX_ERR_ARG (the reference only
+ *                calls with > 0).  nbytes outside 1..64 or a side of more than 2 000 000 rows: MODSX_ERR_ARG.
+ * The reference function starts with corresp.TCList.clear(): the returned records replace, they are not appended. */
+#define MODSX_HAMMING_MAX_BYTES 64
+/* stage tap + matcher, descriptors from the host */
+int modsx_match_hamming(modsx_ctx *ctx, const void *desc1, int n1, const void *desc2, int n2, int nbytes, int dtype,
+                        double distanceThreshold, modsx_tentative **out);
+/* the same on dense [n][nbytes] u8 rows that already live in HBM (any alignment) */
+int modsx_match_hamming_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2, int nbytes,
+                               double distanceThreshold, modsx_tentative **out);
+/* host only, no context: the record rule of matching.cpp:647-661 on the search result
+ * nn2 = [n1][4] = {first, d(first), second, d(second)} -- the one copy of that rule, every entry above and below goes through it */
+int modsx_hamming_tentatives(const int *nn2, int n1, double distanceThreshold, modsx_tentative **out);
+/* debug: the raw search result of the device path, with the train axis forced into `splits` parts (0 = production geometry; more
+ * than one per tile is cut down to one per tile); geometry[4] (optional) = {tile length in trains, splits used, workgroups of
+ * k_hamming_2nn, W = ceil(nbytes / 4)}.  nn2: n1 x 4 ints, the caller's.  Needs n1 >= 1 and n2 >= 2. */
+int modsx_debug_match_hamming(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2, int nbytes,
+                              int splits, int *nn2, int *geometry);
+/* host only, no context: the geometry modsx_debug_match_hamming would report for these sizes (one function of n1, n2, W) */
+int modsx_debug_hamming_geometry(int n1, int n2, int nbytes, int splits, int *geometry);
+/* One binary-descriptor step of mods.cpp:229-415 on caller-supplied regions: MatchFLANNDistance + DuplicateFiltering (key =
+ * ratio, as for FGINN records) + LORANSACFiltering (H or F per par) -- what modsx_match_pair leaves, with the match stage
+ * replaced.  An empty side gives the zeroed result with H = -1; n2 == 1 is MODSX_ERR_ARG before any work. */
+int modsx_match_regions_hamming(modsx_ctx *ctx, const modsx_region *regs1, const void *desc1, int n1,
+                                const modsx_region *regs2, const void *desc2, int n2, int nbytes, int dtype,
+                                double distanceThreshold, const modsx_pair_params *par, modsx_pair_result *res);
+
 /* One step of mods.cpp:229-415 with a ladder of synthesised views per image (same views for both images,
  * as in iters_mods_cviu.ini). */
 int modsx_match_pair_views(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,

@@ -109,7 +109,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
            "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
-           "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many"]
+           "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many",
+           "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
+           "modsx_match_regions_hamming", "modsx_debug_hamming_geometry"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -202,6 +204,14 @@ def lib():
                                        C.c_void_p]
         L.modsx_match_one_to_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_match_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_match_hamming_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_hamming_tentatives.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_debug_match_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p]
+        L.modsx_debug_hamming_last_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_match_regions_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -750,6 +760,49 @@ class Context(object):
                                                   C.byref(out)), "match_fginn_device")
         return _take(out, n, TENT)
 
+    def match_hamming(self, d1, d2, distance_threshold):
+        """MatchFLANNDistance (exact Hamming search): [n][nbytes] rows, uint8 or anything convertible to float32 holding 0..255."""
+        d1, d2, nbytes, dtype = _hamming_rows(d1, d2)
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_hamming(self._c(), _p(d1), len(d1), _p(d2), len(d2), nbytes, dtype,
+                                             C.c_double(distance_threshold), C.byref(out)), "match_hamming")
+        return _take(out, n, TENT)
+
+    def match_hamming_device(self, p1, n1, p2, n2, nbytes, distance_threshold):
+        """The same on dense [n][nbytes] u8 rows in HBM (device pointers, any alignment)."""
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_hamming_device(self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), int(nbytes),
+                                                    C.c_double(distance_threshold), C.byref(out)), "match_hamming_device")
+        return _take(out, n, TENT)
+
+    def debug_match_hamming(self, p1, n1, p2, n2, nbytes, splits=0):
+        """(nn2 [n1][4] = first, d(first), second, d(second); dict(tile, splits, workgroups, W)) of the device search with the train
+        axis forced into `splits` parts (0 = production geometry)."""
+        nn2 = np.zeros((max(int(n1), 1), 4), np.int32)
+        geo = np.zeros(4, np.int32)
+        _check(lib().modsx_debug_match_hamming(self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), int(nbytes), int(splits),
+                                               _p(nn2), _p(geo)), "debug_match_hamming")
+        return nn2[:int(n1)], dict(zip(HAMMING_GEOMETRY, (int(x) for x in geo)))
+
+    def hamming_last_ms(self):
+        """(packing ms, search ms) of this context's last Hamming search, HIP events; filled while profile() is on."""
+        ms = np.zeros(2, np.float64)
+        _check(lib().modsx_debug_hamming_last_ms(self._c(), _p(ms)), "hamming_last_ms")
+        return float(ms[0]), float(ms[1])
+
+    def match_regions_hamming(self, regs1, d1, regs2, d2, distance_threshold, params):
+        """One binary-descriptor step on caller-supplied regions: MatchFLANNDistance + DuplicateFiltering + LO-RANSAC."""
+        regs1 = np.ascontiguousarray(regs1, REGION)
+        regs2 = np.ascontiguousarray(regs2, REGION)
+        d1, d2, nbytes, dtype = _hamming_rows(d1, d2)
+        if len(regs1) != len(d1) or len(regs2) != len(d2):
+            raise ValueError("match_regions_hamming: one descriptor row per region is expected")
+        res = PairResult()
+        _check(lib().modsx_match_regions_hamming(self._c(), _p(regs1), _p(d1), len(d1), _p(regs2), _p(d2), len(d2), nbytes, dtype,
+                                                 C.c_double(distance_threshold), C.byref(params), C.byref(res)),
+               "match_regions_hamming")
+        return _unpack_pair_result(res)
+
     def rep_match_fginn(self, rep1, rep2, detector=0, desc_type=1, ratio=0.8, contrad_dist=30.0, nn=50):
         """MatchFlannFGINN of one class of two stored representations: rep1 the queries, rep2 (pre-packed) the trains."""
         out = C.c_void_p()
@@ -914,6 +967,36 @@ def last_match_geometry():
     v = [C.c_int() for _ in range(5)]
     lib().modsx_last_match_geometry(*[C.byref(x) for x in v])
     return dict(zip(("qs", "fat", "S", "tiles_per_split", "ntiles_ub"), (x.value for x in v)))
+
+
+HAMMING_GEOMETRY = ("tile", "splits", "workgroups", "W")   # include/modsx.h: modsx_debug_match_hamming, in its order
+
+
+def _hamming_rows(d1, d2):
+    """the two sides as contiguous [n][nbytes] arrays of one dtype: uint8 if both are, float32 otherwise"""
+    d1, d2 = np.asarray(d1), np.asarray(d2)
+    dt = np.uint8 if d1.dtype == np.uint8 and d2.dtype == np.uint8 else np.float32
+    d1, d2 = np.ascontiguousarray(d1, dt), np.ascontiguousarray(d2, dt)
+    if d1.ndim != 2 or d2.ndim != 2 or d1.shape[1] != d2.shape[1]:
+        raise ValueError("hamming: two [n][nbytes] arrays of one width are expected")
+    return d1, d2, d1.shape[1], 0 if dt == np.uint8 else 1
+
+
+def hamming_geometry(n1, n2, nbytes, splits=0):
+    """dict(tile, splits, workgroups, W): what the Hamming search launches for these sizes (host only, no GPU); splits = 0 is the
+    production geometry, more splits than tiles are cut down to one per tile."""
+    geo = np.zeros(4, np.int32)
+    _check(lib().modsx_debug_hamming_geometry(int(n1), int(n2), int(nbytes), int(splits), _p(geo)), "hamming_geometry")
+    return dict(zip(HAMMING_GEOMETRY, (int(x) for x in geo)))
+
+
+def hamming_tentatives(nn2, distance_threshold):
+    """The record rule of MatchFLANNDistance (matching.cpp:647-661) on a search result nn2 = [n1][4] = first, d(first), second,
+    d(second) (host only, no GPU)."""
+    nn2 = np.ascontiguousarray(nn2, np.int32).reshape(-1, 4)
+    out = C.c_void_p()
+    n = _check(lib().modsx_hamming_tentatives(_p(nn2), len(nn2), C.c_double(distance_threshold), C.byref(out)), "hamming_tentatives")
+    return _take(out, n, TENT)
 
 
 BAUMBERG_GEOMETRY = ("kernel", "chunk", "nchunks", "grid")   # include/modsx.h: modsx_debug_baumberg_geometry, in its order

@@ -1166,6 +1166,71 @@ int modsx_set_fginn_db(modsx_ctx *ctx, const modsx_db *db) {
   return MODSX_OK;
 }
 
+// ---- MatchFLANNDistance: exact Hamming matching of binary descriptors (engine_hamming.hip) ---------------------------------------
+int modsx_match_hamming(modsx_ctx *ctx, const void *desc1, int n1, const void *desc2, int n2, int nbytes, int dtype,
+                        double distanceThreshold, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  if ((n1 > 0 && !desc1) || (n2 > 0 && !desc2)) { mx::set_error("modsx_match_hamming: null descriptors"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  int rc = match_hamming_host(ctx, desc1, n1, desc2, n2, nbytes, dtype, distanceThreshold, t);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_match_hamming_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2, int nbytes,
+                               double distanceThreshold, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  if ((n1 > 0 && !dev_desc1_u8) || (n2 > 0 && !dev_desc2_u8)) { mx::set_error("modsx_match_hamming_device: null descriptors"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  int rc = match_hamming_device(ctx, (const uint8_t *)dev_desc1_u8, n1, (const uint8_t *)dev_desc2_u8, n2, nbytes, distanceThreshold, t);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_hamming_tentatives(const int *nn2, int n1, double distanceThreshold, modsx_tentative **out) {
+  NEED(out);
+  std::vector<modsx_tentative> t;
+  int rc = hamming_tentatives(nn2, n1, distanceThreshold, t);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_debug_match_hamming(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2, int nbytes,
+                              int splits, int *nn2, int *geometry) {
+  NEED(ctx); NEED(dev_desc1_u8); NEED(dev_desc2_u8); NEED(nn2);
+  int rc = hamming_check_args("modsx_debug_match_hamming", n1, n2, nbytes);
+  if (rc) return rc;
+  if (n1 < 1 || n2 < 2 || splits < 0) { mx::set_error("modsx_debug_match_hamming: needs n1 >= 1, n2 >= 2, splits >= 0"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  return hamming_search_device(ctx, (const uint8_t *)dev_desc1_u8, n1, (const uint8_t *)dev_desc2_u8, n2, nbytes, splits, nn2, geometry);
+}
+int modsx_debug_hamming_geometry(int n1, int n2, int nbytes, int splits, int *geometry) {
+  NEED(geometry);
+  int rc = hamming_check_args("modsx_debug_hamming_geometry", n1, n2, nbytes);
+  if (rc) return rc;
+  if (n1 < 1 || n2 < 2 || splits < 0) { mx::set_error("modsx_debug_hamming_geometry: needs n1 >= 1, n2 >= 2, splits >= 0"); return MODSX_ERR_ARG; }
+  const HammingGeo g = hamming_geometry(n1, n2, (nbytes + 3) / 4, splits);
+  geometry[0] = g.tile; geometry[1] = g.S; geometry[2] = g.gx * g.S; geometry[3] = g.W;
+  return MODSX_OK;
+}
+// under modsx_profile(ctx, 1): HIP-event times in ms of the last Hamming search of this context -- ms2[0] the two k_hamming_pack
+// launches, ms2[1] k_hamming_2nn + k_hamming_merge (tools/bench_hamming.py)
+extern "C" __attribute__((visibility("default"))) int modsx_debug_hamming_last_ms(modsx_ctx *ctx, double *ms2) {
+  NEED(ctx); NEED(ms2);
+  ms2[0] = ctx->hammingMs[0]; ms2[1] = ctx->hammingMs[1];
+  return MODSX_OK;
+}
+int modsx_match_regions_hamming(modsx_ctx *ctx, const modsx_region *regs1, const void *desc1, int n1, const modsx_region *regs2,
+                                const void *desc2, int n2, int nbytes, int dtype, double distanceThreshold, const modsx_pair_params *par,
+                                modsx_pair_result *res) {
+  NEED(ctx); NEED(par); NEED(res);
+  if ((n1 > 0 && (!regs1 || !desc1)) || (n2 > 0 && (!regs2 || !desc2))) { mx::set_error("modsx_match_regions_hamming: null regions or descriptors"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  return match_regions_hamming(ctx, regs1, desc1, n1, regs2, desc2, n2, nbytes, dtype, distanceThreshold, *par, res);
+}
+
 int modsx_match_ladder(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,
                        const modsx_ladder_step *steps, int nsteps, int min_matches, const modsx_pair_params *par,
                        modsx_pair_result *res, int *steps_done) {

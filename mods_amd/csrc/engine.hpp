@@ -315,6 +315,13 @@ void launch_db_select(hipStream_t s, int nb, const MatchRow *const *rows, const 
                       int *const *dmin);
 void launch_dbnn_min(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, int *const *sel, int *cnt, int *const *dmin,
                      const DbSet &db);
+// The Hamming 2-NN search of MatchFLANNDistance (kernels_hamming.hip).  W = ceil(nbytes / 4) dwords per row, WK the kernel width
+// it rounds up to; tile = trains per LDS tile; the train axis is cut into S splits of tilesPerSplit tiles; gx x S workgroups.
+struct HammingGeo { int W, WK, tile, ntiles, tilesPerSplit, S, gx; };
+HammingGeo hamming_geometry(int n1, int n2, int W, int splits);   // splits = 0: production; > 0: forced (at most one per tile)
+size_t hamming_workspace_bytes(const HammingGeo &g, int n1);
+void launch_hamming(hipStream_t s, const HammingGeo &g, const uint8_t *d1, int n1, const uint8_t *d2, int n2, int nbytes, void *work,
+                    int *nn2, hipEvent_t *ev = nullptr);             // ev: three events, around the packing and the search launches
 
 }  // namespace mx
 
@@ -395,6 +402,7 @@ struct modsx_ctx {
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
   const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
   long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
+  double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

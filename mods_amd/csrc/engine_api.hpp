@@ -160,6 +160,16 @@ int match_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int
 int match_host_desc(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
                     double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const DbSet *db = nullptr,
                     std::vector<double> *d2byDB = nullptr);
+// ---- MatchFLANNDistance, exact Hamming search (engine_hamming.hip) ----
+int hamming_tentatives(const int *nn2, int n1, double distanceThreshold, std::vector<modsx_tentative> &out);   // the record rule (host)
+int hamming_check_args(const char *fn, int n1, int n2, int nbytes);
+int hamming_search_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, int nbytes, int splits, int *nn2, int *geo4);
+int match_hamming_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, int nbytes, double distanceThreshold,
+                         std::vector<modsx_tentative> &out);
+int match_hamming_host(modsx_ctx *c, const void *desc1, int n1, const void *desc2, int n2, int nbytes, int dtype, double distanceThreshold,
+                       std::vector<modsx_tentative> &out);
+int match_regions_hamming(modsx_ctx *c, const modsx_region *regs1, const void *desc1, int n1, const modsx_region *regs2, const void *desc2,
+                          int n2, int nbytes, int dtype, double distanceThreshold, const modsx_pair_params &pp, modsx_pair_result *res);
 DbSet *db_create(modsx_ctx *c, const void *rows, long n, int dtype);
 void db_free(DbSet *db);
 int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *dmin);
