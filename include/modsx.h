@@ -106,6 +106,13 @@ typedef struct modsx_sskp {
   float x, y, s, pixelDistance;
 } modsx_sskp;
 
+/* a localised 3x3x3 extremum as the scan kernels append it, before the detection order and the octaveMap claim
+ * (modsx_debug_scan_levels) */
+typedef struct modsx_candidate {
+  int img, octave, level, type, r0, c0, r, c;
+  float b0, b1, b2, val;
+} modsx_candidate;
+
 /* the fields MatchFlannFGINN fills in a TentativeCorrespExt (matching/matching.hpp:39-52):
  * first = list1[q], second = list2[t0], secondbad = list2[tj], secondbadby2ndcl = list2[t1] */
 typedef struct modsx_tentative {
@@ -383,6 +390,38 @@ int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, i
  * region counts as a call with no chunk.  Read it while no call runs on the context; tests work with the difference of two
  * readings */
 int modsx_describe_counters(modsx_ctx *ctx, long *out, int n);
+/* Test entries and measurement hooks of the scale-space front end (ScaleSpaceDetector, affinedetectors/pyramid.cpp).
+ * modsx_blur_geometry (host only): the tile rule of the pyramid's blur launch over n planes of rows[i] x cols[i] (1 <= n <= 32):
+ * geometry[0] = rows of a 64-column tile, 32 when the launch has at least 2560 such tiles and 16 otherwise; geometry[1] = the
+ * tiles (workgroups) of the launch.  The launcher calls the same function.
+ * modsx_detect_counters: what the front end launched on this context since modsx_create (host-side counts; the contexts that
+ * work on its behalf count with it in the cumulative entries).  Fills out[0 .. min(n, 19) - 1] and returns 19.  In order: blur
+ * launches with 16-row and with 32-row tiles; blur launches by instantiated half width R = 1 .. 8 (8 entries; ksize = 2 R + 1);
+ * launches of the stand-alone Hessian kernel; of the resize (+ Hessian) kernel; extrema scan launches that number their tiles
+ * per octave (numberOfScales = 3) and per level (every other count, or MODSX_NMS_PER_LEVEL in the environment); scan launches
+ * made because the table of 1024 (image, octave, level) jobs was full, i.e. before a scan's last launch; then, of the context's
+ * LAST scan: its jobs and its tiles over all its launches; the accepted candidates of the last candidate set that was
+ * downloaded; and (cumulative again) downloads that had to copy the records a second time because the set held more than the
+ * speculative copy (the previous set's count + 1/4 + 1024).  Read it while no call runs on the context; tests work with the
+ * difference of two readings.
+ * modsx_debug_pyramids: builds the pyramids of a batch of n <= 32 images (sizes may differ) as modsx_detect_scalespace does.
+ * geometry[49 i] = octaves of image i, geometry[49 i + 1 + 2 o], [.. + 2 + 2 o] = rows, cols of its octave o; *need_floats =
+ * the floats of all planes.  planes = NULL: geometry and size only, nothing is launched.  Otherwise planes (cap_floats floats)
+ * receives image after image, octave after octave, the numberOfScales + 2 blur planes and then as many response planes.
+ * modsx_debug_scan_levels: the production extrema scan, detection order and octaveMap claim on the L = numberOfScales + 2
+ * response and blur planes (each L * rows * cols f32) of ONE octave supplied by the caller (octave 0, pixelDistance 1, sides
+ * below 16384).  *cands / *n_cands: the accepted records as the device appended them, in no particular order; the return value
+ * and *out: the keypoints after the order and the claim.  Both arrays are released with modsx_free.
+ * modsx_debug_detect_scalespace_batch: modsx_detect_scalespace for n <= 32 images in ONE launch set; out[i] / counts[i] per image.
+ * All of them refuse border < 1 (MODSX_ERR_ARG), as every detection entry does: the scan would read before the planes. */
+int modsx_blur_geometry(const int *rows, const int *cols, int n, int *geometry);
+int modsx_detect_counters(modsx_ctx *ctx, long *out, int n);
+int modsx_debug_pyramids(modsx_ctx *ctx, const modsx_image *const *imgs, int n, const modsx_hessaff_params *par, int *geometry,
+                         float *planes, unsigned long long cap_floats, unsigned long long *need_floats);
+int modsx_debug_scan_levels(modsx_ctx *ctx, const float *resps, const float *blurs, int L, int rows, int cols,
+                            const modsx_hessaff_params *par, modsx_candidate **cands, int *n_cands, modsx_sskp **out);
+int modsx_debug_detect_scalespace_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n, const modsx_hessaff_params *par,
+                                        modsx_sskp **out, int *counts);
 /* orientation jobs launched by the pair and view pipelines of this process, and regions they left out of the orientation launch
  * because modsx_debug_reproject_certain_drop flags them, since the last reset (measurement hook; MODSX_ORI_PREFILTER=0 in the
  * environment launches them all).  modsx_detect_orientation itself never leaves a region out */

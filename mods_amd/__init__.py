@@ -24,6 +24,8 @@ SSKP = np.dtype([("octave", "i4"), ("level", "i4"), ("r0", "i4"), ("c0", "i4"), 
                  ("x", "f4"), ("y", "f4"), ("s", "f4"), ("pixelDistance", "f4")], align=True)
 TENT = np.dtype([("q", "i4"), ("t0", "i4"), ("tj", "i4"), ("t1", "i4"), ("d1", "f8"), ("d2", "f8"),
                  ("d2by2ndcl", "f8"), ("ratio", "f8")], align=True)
+CANDIDATE = np.dtype([("img", "i4"), ("octave", "i4"), ("level", "i4"), ("type", "i4"), ("r0", "i4"), ("c0", "i4"), ("r", "i4"),
+                      ("c", "i4"), ("b0", "f4"), ("b1", "f4"), ("b2", "f4"), ("val", "f4")], align=True)
 
 
 class HessAffParams(C.Structure):
@@ -111,7 +113,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many",
            "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
-           "modsx_match_regions_hamming", "modsx_debug_hamming_geometry"]
+           "modsx_match_regions_hamming", "modsx_debug_hamming_geometry",
+           "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
+           "modsx_debug_detect_scalespace_batch"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -122,6 +126,10 @@ EXCHANGE_ALL_GATHER, EXCHANGE_OWNER = 0, 1   # include/modsx.h: modsx_comm_set_e
 # include/modsx.h: modsx_describe_counters, in its order
 DESCRIBE_COUNTERS = ("calls", "chunks", "max_chunks", "chunks_mid_image", "chunks_later_image", "jobs", "direct_jobs", "fused_windows",
                      "lds_row_tiles", "lds_col_tiles", "sample_tiles", "global_row_tiles", "global_col_tiles", "clamped_windows")
+# include/modsx.h: modsx_detect_counters, in its order
+DETECT_COUNTERS = ("blur_th16", "blur_th32") + tuple("blur_r%d" % r for r in range(1, 9)) + (
+    "hessian", "resize", "scan_per_octave", "scan_per_level", "nms_flushes", "last_jobs", "last_tiles", "last_accepted",
+    "second_copies")
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -181,6 +189,13 @@ def lib():
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.modsx_describe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_blur_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_detect_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_pyramids.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong,
+                                           C.c_void_p]
+        L.modsx_debug_scan_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_detect_scalespace_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_debug_describe_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_debug_baumberg_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -669,6 +684,58 @@ class Context(object):
         assert n == len(DESCRIBE_COUNTERS), n
         return dict(zip(DESCRIBE_COUNTERS, (int(x) for x in v)))
 
+    def detect_counters(self):
+        """dict of DETECT_COUNTERS: what the pyramid and the extrema scan launched on this context since it was created (the
+        last_* entries describe its last scan / candidate set)."""
+        v = (C.c_long * len(DETECT_COUNTERS))()
+        n = _check(lib().modsx_detect_counters(self._c(), v, len(DETECT_COUNTERS)), "detect_counters")
+        assert n == len(DETECT_COUNTERS), n
+        return dict(zip(DETECT_COUNTERS, (int(x) for x in v)))
+
+    def debug_pyramids(self, images, params):
+        """modsx_debug_pyramids: the pyramids of a batch of Images (sizes may differ) -> per image a list of (blurs, resps) per
+        octave, each [numberOfScales + 2, rows, cols] f32."""
+        n, L = len(images), params.numberOfScales + 2
+        ptrs = (C.c_void_p * max(1, n))(*[im.h for im in images])
+        geo = np.zeros((max(1, n), 49), np.int32)
+        need = C.c_ulonglong(0)
+        _check(lib().modsx_debug_pyramids(self._c(), ptrs, n, C.byref(params), _p(geo), None, 0, C.byref(need)), "debug_pyramids")
+        planes = np.empty(max(1, need.value), np.float32)
+        _check(lib().modsx_debug_pyramids(self._c(), ptrs, n, C.byref(params), _p(geo), _p(planes), need.value, C.byref(need)),
+               "debug_pyramids")
+        out, at = [], 0
+        for i in range(n):
+            octs = []
+            for o in range(int(geo[i, 0])):
+                r, c = int(geo[i, 1 + 2 * o]), int(geo[i, 2 + 2 * o])
+                m = L * r * c
+                octs.append((planes[at:at + m].reshape(L, r, c), planes[at + m:at + 2 * m].reshape(L, r, c)))
+                at += 2 * m
+            out.append(octs)
+        assert at == need.value
+        return out
+
+    def debug_scan_levels(self, resps, blurs, params):
+        """modsx_debug_scan_levels: the production extrema scan on the numberOfScales + 2 response / blur planes ([L, rows, cols])
+        of one octave -> (raw accepted CANDIDATE records in device order, SSKP keypoints after detection order and claim)."""
+        resps, blurs = np.ascontiguousarray(resps, np.float32), np.ascontiguousarray(blurs, np.float32)
+        assert resps.ndim == 3 and resps.shape == blurs.shape
+        L, rows, cols = resps.shape
+        cands, out, nc = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        n = _check(lib().modsx_debug_scan_levels(self._c(), _p(resps), _p(blurs), L, rows, cols, C.byref(params), C.byref(cands),
+                                                 C.byref(nc), C.byref(out)), "debug_scan_levels")
+        return _take(cands, nc.value, CANDIDATE), _take(out, n, SSKP)
+
+    def debug_detect_scalespace_batch(self, images, params):
+        """modsx_debug_detect_scalespace_batch: detect_scalespace of up to 32 Images in one launch set -> list of SSKP arrays."""
+        n = len(images)
+        ptrs = (C.c_void_p * max(1, n))(*[im.h for im in images])
+        outs = (C.c_void_p * max(1, n))()
+        counts = np.zeros(max(1, n), np.int32)
+        _check(lib().modsx_debug_detect_scalespace_batch(self._c(), ptrs, n, C.byref(params), outs, _p(counts)),
+               "debug_detect_scalespace_batch")
+        return [_take(C.c_void_p(outs[i]), int(counts[i]), SSKP) for i in range(n)]
+
     def match_fginn(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
         d1 = np.ascontiguousarray(d1, np.float32)
         d2 = np.ascontiguousarray(d2, np.float32)
@@ -997,6 +1064,16 @@ def hamming_tentatives(nn2, distance_threshold):
     out = C.c_void_p()
     n = _check(lib().modsx_hamming_tentatives(_p(nn2), len(nn2), C.c_double(distance_threshold), C.byref(out)), "hamming_tentatives")
     return _take(out, n, TENT)
+
+
+def blur_geometry(shapes):
+    """modsx_blur_geometry (host only): (tile rows, tiles) of the pyramid's blur launch over planes of the given (rows, cols):
+    32-row tiles from 2560 tiles on, 16-row tiles below."""
+    sh = np.ascontiguousarray(shapes, np.int32).reshape(-1, 2)
+    rows, cols = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    geo = np.zeros(2, np.int32)
+    _check(lib().modsx_blur_geometry(_p(rows), _p(cols), len(sh), _p(geo)), "blur_geometry")
+    return int(geo[0]), int(geo[1])
 
 
 BAUMBERG_GEOMETRY = ("kernel", "chunk", "nchunks", "grid")   # include/modsx.h: modsx_debug_baumberg_geometry, in its order

@@ -248,7 +248,7 @@ int modsx_gaussian_blur(modsx_ctx *ctx, const modsx_image *img, float sigma, flo
   for (int i = 0; i < n; i++) b.k[i] = k[i];
   b.j[0].src = img->d; b.j[0].blur = (float *)ctx->scratchA.p; b.j[0].resp = nullptr; b.j[0].rows = img->rows;
   b.j[0].cols = img->cols; b.j[0].norm = 1.f;
-  launch_blur_hess(ctx->stream, b, 1, img->rows, img->cols);
+  mx::book_blur(ctx, launch_blur_hess(ctx->stream, b, 1, img->rows, img->cols));
   MX_HIP(hipMemcpyAsync(out, ctx->scratchA.p, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
   MX_HIP(hipStreamSynchronize(ctx->stream));
   MX_HIP(hipGetLastError());
@@ -290,7 +290,7 @@ int modsx_response(modsx_ctx *ctx, const modsx_image *img, int detector_type, fl
     BlurBatch bt;
     memset(&bt, 0, sizeof bt);
     bt.j[0].src = img->d; bt.j[0].resp = res; bt.j[0].rows = rows; bt.j[0].cols = cols; bt.j[0].norm = norm;
-    launch_hessian(s, bt, 1, rows, cols);
+    ctx->detCnt[mx::DT_HESSIAN] += launch_hessian(s, bt, 1, rows, cols);
   } else if (detector_type == MODSX_DET_DOG) {
     rc = blur_any(ctx, img->d, a, tmp, dT, hT, rows, cols, sigma);
     if (rc) return rc;
@@ -322,7 +322,7 @@ int modsx_resize_half(modsx_ctx *ctx, const modsx_image *img, float *out, int *o
   memset(&rb, 0, sizeof rb);
   rb.j[0].src = img->d; rb.j[0].dst = (float *)ctx->scratchA.p;
   rb.j[0].srows = img->rows; rb.j[0].scols = img->cols; rb.j[0].drows = dr; rb.j[0].dcols = dc;
-  launch_resize_half(ctx->stream, rb, 1, dr, dc);
+  ctx->detCnt[mx::DT_RESIZE] += launch_resize_half(ctx->stream, rb, 1, dr, dc);
   MX_HIP(hipMemcpyAsync(out, ctx->scratchA.p, (size_t)dr * dc * 4, hipMemcpyDeviceToHost, ctx->stream));
   MX_HIP(hipStreamSynchronize(ctx->stream));
   MX_HIP(hipGetLastError());
@@ -459,6 +459,68 @@ int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
         if (q == mx::DC_MAX_CHUNKS) sum[q] = std::max(sum[q], c->descCnt[q]); else sum[q] += c->descCnt[q];
   for (int q = 0; q < n && q < mx::DC_N; q++) out[q] = sum[q];
   return mx::DC_N;
+}
+
+int modsx_blur_geometry(const int *rows, const int *cols, int n, int *geometry) {
+  NEED(rows); NEED(cols); NEED(geometry);
+  if (n < 1 || n > mx::MAXB) { mx::set_error("modsx_blur_geometry: 1 .. 32 planes"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++)
+    if (rows[i] < 1 || cols[i] < 1 || !image_size_ok(rows[i], cols[i])) { mx::set_error("modsx_blur_geometry: plane size"); return MODSX_ERR_ARG; }
+  const mx::BlurGeo g = mx::blur_geometry(rows, cols, n);
+  geometry[0] = g.th; geometry[1] = g.tiles;
+  return MODSX_OK;
+}
+
+int modsx_detect_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_detect_counters: bad argument"); return MODSX_ERR_ARG; }
+  long sum[mx::DT_N] = {0};
+  for (const modsx_ctx *head : {(const modsx_ctx *)ctx, (const modsx_ctx *)ctx->peer})
+    for (const modsx_ctx *c = head; c; c = c->half)
+      for (int q = 0; q < mx::DT_N; q++)
+        if (q != mx::DT_LAST_JOBS && q != mx::DT_LAST_TILES && q != mx::DT_LAST_ACCEPTED) sum[q] += c->detCnt[q];
+  for (int q : {(int)mx::DT_LAST_JOBS, (int)mx::DT_LAST_TILES, (int)mx::DT_LAST_ACCEPTED}) sum[q] = ctx->detCnt[q];
+  for (int q = 0; q < n && q < mx::DT_N; q++) out[q] = sum[q];
+  return mx::DT_N;
+}
+
+int modsx_debug_pyramids(modsx_ctx *ctx, const modsx_image *const *imgs, int n, const modsx_hessaff_params *par, int *geometry,
+                         float *planes, unsigned long long cap_floats, unsigned long long *need_floats) {
+  NEED(ctx); NEED(imgs); NEED(par); NEED(geometry); NEED(need_floats);
+  if (n < 1 || n > mx::MAXB) { mx::set_error("batch size"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  return debug_pyramids(ctx, imgs, n, *par, geometry, planes, cap_floats, need_floats);
+}
+
+int modsx_debug_scan_levels(modsx_ctx *ctx, const float *resps, const float *blurs, int L, int rows, int cols,
+                            const modsx_hessaff_params *par, modsx_candidate **cands, int *n_cands, modsx_sskp **out) {
+  NEED(ctx); NEED(resps); NEED(blurs); NEED(par); NEED(cands); NEED(n_cands); NEED(out);
+  static_assert(sizeof(modsx_candidate) == sizeof(mx::Candidate), "modsx_candidate is the device record");
+  hipSetDevice(ctx->dev);
+  std::vector<mx::Candidate> cd;
+  std::vector<modsx_sskp> kp;
+  int rc = debug_scan_levels(ctx, resps, blurs, L, rows, cols, *par, cd, kp);
+  if (rc) return rc;
+  modsx_candidate *m = (modsx_candidate *)malloc(std::max<size_t>(1, cd.size()) * sizeof(modsx_candidate));
+  if (!m) return MODSX_ERR_NOMEM;
+  if (!cd.empty()) memcpy(m, cd.data(), cd.size() * sizeof(modsx_candidate));
+  *cands = m; *n_cands = (int)cd.size();
+  *out = to_malloc(kp);
+  return (int)kp.size();
+}
+
+int modsx_debug_detect_scalespace_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n, const modsx_hessaff_params *par,
+                                        modsx_sskp **out, int *counts) {
+  NEED(ctx); NEED(imgs); NEED(par); NEED(out); NEED(counts);
+  if (n < 1 || n > mx::MAXB) { mx::set_error("batch size"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_sskp> k[mx::MAXB];
+  int rc = detect_scalespace_batch(ctx, imgs, n, *par, k);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) { out[i] = to_malloc(k[i]); counts[i] = (int)k[i].size(); }
+  return n;
 }
 
 int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,

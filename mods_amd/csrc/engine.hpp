@@ -204,9 +204,15 @@ bool invert3(const double *S, double *t);
 void rectify(double &a11, double &a12, double &a21, double &a22);
 
 // kernel launchers
-void launch_blur_hess(hipStream_t s, const BlurBatch &b, int nj, int maxRows, int maxCols);
-void launch_hessian(hipStream_t s, const BlurBatch &b, int nj, int maxRows, int maxCols);
-void launch_resize_half(hipStream_t s, const ResizeBatch &b, int nj, int maxRows, int maxCols);
+// the tile height of a k_blur_hess launch over n planes and its tile count (host only): 32-row tiles when they fill two rounds of
+// workgroups, 16-row tiles below that (kernels_pyramid.hip)
+struct BlurGeo { int th, tiles; };
+BlurGeo blur_geometry(const int *rows, const int *cols, int n);
+// what launch_blur_hess launched: th = 0 when the batch held no pixel, R = the instantiated half width (1..8)
+struct BlurLaunch { int th, tiles, R; };
+BlurLaunch launch_blur_hess(hipStream_t s, const BlurBatch &b, int nj, int maxRows, int maxCols);
+bool launch_hessian(hipStream_t s, const BlurBatch &b, int nj, int maxRows, int maxCols);        // false: nothing to launch
+bool launch_resize_half(hipStream_t s, const ResizeBatch &b, int nj, int maxRows, int maxCols);
 void launch_nms(hipStream_t s, const NmsBatch &b, const NmsJob *jobs, const int *tilePrefix, const int *tileJob, int nj,
                 int nTiles, int4 *queue, unsigned *qcount, unsigned qcap, Candidate *out, unsigned *counter, unsigned cap,
                 const int *octFirst = nullptr, int levelsPerOctave = 0);
@@ -353,6 +359,10 @@ namespace mx {
 enum DescCounter { DC_CALLS = 0, DC_CHUNKS, DC_MAX_CHUNKS, DC_CHUNKS_MID_IMAGE, DC_CHUNKS_LATER_IMAGE, DC_JOBS, DC_DIRECT_JOBS,
                    DC_FUSED_WINDOWS, DC_LDS_ROW_TILES, DC_LDS_COL_TILES, DC_SAMPLE_TILES, DC_GLOBAL_ROW_TILES, DC_GLOBAL_COL_TILES,
                    DC_CLAMPED_WINDOWS, DC_N };
+// measurement hook (modsx_detect_counters): what the scale-space front end launched on a context since modsx_create, in the order
+// of include/modsx.h.  Host-side increments next to the launches; DT_LAST_* describe the context's last scan / candidate set.
+enum DetectCounter { DT_BLUR_TH16 = 0, DT_BLUR_TH32, DT_BLUR_R1, DT_BLUR_R8 = DT_BLUR_R1 + 7, DT_HESSIAN, DT_RESIZE, DT_SCAN_OCTAVE,
+                     DT_SCAN_LEVEL, DT_NMS_FLUSHES, DT_LAST_JOBS, DT_LAST_TILES, DT_LAST_ACCEPTED, DT_SECOND_COPIES, DT_N };
 }  // namespace mx
 
 struct modsx_db { mx::DbSet set; };
@@ -402,6 +412,7 @@ struct modsx_ctx {
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
   const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
   long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
+  long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
@@ -410,3 +421,11 @@ struct modsx_ctx {
   mx::DevBuf halfDesc[4];      // ... and writes its descriptors (one buffer per descriptor class of the step) here until the first part's count is known
   void *worker = nullptr;      // CtxWorker: the host thread that drives this context when it is a peer / half (engine_views.hip)
 };
+
+namespace mx {
+inline void book_blur(modsx_ctx *c, const BlurLaunch &g) {
+  if (!g.th) return;
+  c->detCnt[g.th == 32 ? DT_BLUR_TH32 : DT_BLUR_TH16]++;
+  c->detCnt[DT_BLUR_R1 + g.R - 1]++;
+}
+}  // namespace mx

@@ -22,6 +22,10 @@ int detect_scalespace_batch(modsx_ctx *c, const modsx_image *const *imgs, int n,
                             std::vector<modsx_sskp> *out);
 int detect_keypoints_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &par,
                            const double *tilts, const double *zooms, std::vector<modsx_keypoint> *out);
+int debug_pyramids(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &p, int *geo, float *planes,
+                   unsigned long long capFloats, unsigned long long *needFloats);
+int debug_scan_levels(modsx_ctx *c, const float *resps, const float *blurs, int L, int rows, int cols, const modsx_hessaff_params &p,
+                      std::vector<Candidate> &cands, std::vector<modsx_sskp> &out);
 int debug_baumberg_geometry(modsx_ctx *c, int n, int W, int variant, int chunk, int *geo);
 int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, const int *planeOf, const float *xyspd, int n,
                    const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo, int *handedOut);

@@ -117,8 +117,8 @@ static int launch_first_level(modsx_ctx *c, const modsx_image *const *imgs, cons
       j.src = oc.blur[0];
     }
   }
-  if (preBlur) { ProfScope ps(c, K_BLUR_HESS, lv.px * 12); launch_blur_hess(s, bb, lv.n, lv.mr, lv.mc); }
-  else if (hess) { ProfScope ps(c, K_HESSIAN, lv.px * 8); launch_hessian(s, bb, lv.n, lv.mr, lv.mc); }
+  if (preBlur) { ProfScope ps(c, K_BLUR_HESS, lv.px * 12); book_blur(c, launch_blur_hess(s, bb, lv.n, lv.mr, lv.mc)); }
+  else if (hess) { ProfScope ps(c, K_HESSIAN, lv.px * 8); c->detCnt[DT_HESSIAN] += launch_hessian(s, bb, lv.n, lv.mr, lv.mc); }
   return MODSX_OK;
 }
 
@@ -136,7 +136,7 @@ static void launch_resize_level(modsx_ctx *c, const LiveOctave &lv, int o, const
     spx += (double)pv.rows * pv.cols;
   }
   ProfScope ps(c, K_RESIZE, (spx + lv.px) * 4 + lv.px * 4);
-  launch_resize_half(c->stream, rb, lv.n, lv.mr, lv.mc);
+  c->detCnt[DT_RESIZE] += launch_resize_half(c->stream, rb, lv.n, lv.mr, lv.mc);
 }
 
 // DoG / Harris (ScaleSpaceDetector::dogResponse :176-181, HarrisResponse :283-305; norm = sigma^2 of the level, :475,490):
@@ -202,6 +202,9 @@ int build_pyramids(modsx_ctx *c, const modsx_image *const *imgs, int n, const mo
                    bool singleOctaveFromFirstLevel) {
   if (n <= 0 || n > MAXB) { set_error("batch size"); return MODSX_ERR_ARG; }
   if (p.numberOfScales < 1 || p.numberOfScales > 6) { set_error("numberOfScales"); return MODSX_ERR_ARG; }
+  // the scan reads rows r - 1 .. r + 1 of [border, rows - border): border 0 starts at row -1, a negative one before the plane
+  // (localizeKeypoint itself reads out of bounds there, so there is no reference result either)
+  if (p.border < 1) { set_error("border must be at least 1"); return MODSX_ERR_ARG; }
   if (p.detectorType != MODSX_DET_HESSIAN && p.detectorType != MODSX_DET_DOG && p.detectorType != MODSX_DET_HARRIS) {
     set_error("detectorType must be Hessian (0), DoG (1) or Harris (2)");
     return MODSX_ERR_ARG;
@@ -228,7 +231,7 @@ int build_pyramids(modsx_ctx *c, const modsx_image *const *imgs, int n, const mo
         j.norm = sp.curSigma[l] * sp.curSigma[l];
       }
       ProfScope ps(c, K_BLUR_HESS, lv.px * 12);
-      launch_blur_hess(c->stream, b2, lv.n, lv.mr, lv.mc);
+      book_blur(c, launch_blur_hess(c->stream, b2, lv.n, lv.mr, lv.mc));
     }
     if (!hess) rc = launch_other_responses(c, lv, o, p, sp);
     if (rc) return rc;
@@ -283,6 +286,7 @@ static int scan_extrema(modsx_ctx *c, int n, const modsx_hessaff_params &p) {
   std::vector<NmsJob> hjobs;
   std::vector<int> hpfx(1, 0), hfirst;
   double px = 0;
+  c->detCnt[DT_LAST_JOBS] = c->detCnt[DT_LAST_TILES] = 0;
   auto flush = [&](bool last) -> int {
     const int nj = (int)hjobs.size();
     if (!nj) return MODSX_OK;
@@ -297,6 +301,9 @@ static int scan_extrema(modsx_ctx *c, int n, const modsx_hessaff_params &p) {
     if (!c->tileJob.ensure((size_t)hpfx.back() * 4 + 4)) return MODSX_ERR_NOMEM;
     const int *dPfx = (const int *)((char *)c->nmsJobs.p + jobBytes);
     launch_expand_tiles(s, dPfx, np, (int *)c->tileJob.p);
+    c->detCnt[perOctave ? DT_SCAN_OCTAVE : DT_SCAN_LEVEL]++;
+    c->detCnt[DT_LAST_JOBS] += nj; c->detCnt[DT_LAST_TILES] += hpfx.back();
+    if (!last) c->detCnt[DT_NMS_FLUSHES]++;     // the job table was full: a launch before the scan's last
     {
       ProfScope ps(c, K_NMS, px * 12);
       if (!queuesClean) MX_HIP(hipMemsetAsync((unsigned *)c->counter.p + 32, 0, NMS_QUEUES * 128, s));
@@ -346,8 +353,10 @@ static int download_counted(modsx_ctx *c, const void *devRecords, int recWord, s
   const unsigned *w = (const unsigned *)c->hMisc.p;
   if (w[0] > CAND_CAP || w[1]) { set_error("candidate buffer overflow"); return MODSX_ERR_NOMEM; }
   c->lastCandCount = w[0];
+  c->detCnt[DT_LAST_ACCEPTED] = w[0];
   *nrec = w[recWord];
   if (w[0] > cap || *nrec <= spec) return MODSX_OK;
+  c->detCnt[DT_SECOND_COPIES]++;
   if (!c->hCand.ensure((size_t)*nrec * sizeof(Candidate))) return MODSX_ERR_NOMEM;   // (re-allocation loses the first part: copy all)
   MX_HIP(ctx_copy(c, c->hCand.p, devRecords, (size_t)*nrec * sizeof(Candidate), hipMemcpyDeviceToHost));
   MX_HIP(ctx_sync(c));
@@ -529,6 +538,71 @@ int detect_scalespace_batch(modsx_ctx *c, const modsx_image *const *imgs, int n,
   if (rc) return rc;
   static const bool deviceOrder = getenv("MODSX_DEVICE_ORDER") != nullptr && atoi(getenv("MODSX_DEVICE_ORDER")) != 0;
   return deviceOrder ? order_on_device(c, n, p, out) : order_on_host(c, n, p, out);
+}
+
+// Test entry (modsx_debug_pyramids): build_pyramids on a batch, every plane handed back.  geo[49 i ..] = image i's octave count,
+// then rows, cols of its octaves; planes (may be null: geometry only, nothing is launched) receives image after image, octave
+// after octave, the L blur planes and then the L response planes of the octave -- the layout of Pyramid::store.
+int debug_pyramids(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_hessaff_params &p, int *geo, float *planes,
+                   unsigned long long capFloats, unsigned long long *needFloats) {
+  if (n <= 0 || n > MAXB) { set_error("batch size"); return MODSX_ERR_ARG; }
+  if (p.numberOfScales < 1 || p.numberOfScales > 6) { set_error("numberOfScales"); return MODSX_ERR_ARG; }
+  if (p.border < 1) { set_error("border must be at least 1"); return MODSX_ERR_ARG; }
+  const int L = p.numberOfScales + 2;
+  int rc = MODSX_OK, maxOct = 0;
+  if (planes) rc = build_pyramids(c, imgs, n, p, false);
+  else rc = plan_octaves(c, imgs, n, L, 2 * p.border + 2, false, &maxOct);
+  if (rc) return rc;
+  unsigned long long total = 0;
+  for (int i = 0; i < n; i++) {
+    const Pyramid &py = c->pyr[i];
+    int *g = geo + 49 * i;
+    g[0] = py.nOct;
+    unsigned long long mine = 0;
+    for (int o = 0; o < py.nOct; o++) { g[1 + 2 * o] = py.oct[o].rows; g[2 + 2 * o] = py.oct[o].cols; mine += (unsigned long long)2 * L * py.oct[o].rows * py.oct[o].cols; }
+    if (planes && mine) {
+      if (total + mine > capFloats) { set_error("modsx_debug_pyramids: the plane buffer is too small"); return MODSX_ERR_ARG; }
+      MX_HIP(hipMemcpyAsync(planes + total, py.store.p, mine * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    total += mine;
+  }
+  *needFloats = total;
+  if (planes) MX_HIP(hipStreamSynchronize(c->stream));
+  return MODSX_OK;
+}
+
+// Test entry (modsx_debug_scan_levels): the production scan_extrema + order_on_host on the L = numberOfScales + 2 response and
+// blur planes of ONE octave that the caller supplies (they become octave 0 of the context's first pyramid).  cands: the accepted
+// records as the device appended them (any order); out: the keypoints after the detection order and the octaveMap claim.
+int debug_scan_levels(modsx_ctx *c, const float *resps, const float *blurs, int L, int rows, int cols, const modsx_hessaff_params &p,
+                      std::vector<Candidate> &cands, std::vector<modsx_sskp> &out) {
+  if (p.numberOfScales < 1 || p.numberOfScales > 6 || L != p.numberOfScales + 2) { set_error("modsx_debug_scan_levels: numberOfScales + 2 planes are expected"); return MODSX_ERR_ARG; }
+  if (p.border < 1) { set_error("border must be at least 1"); return MODSX_ERR_ARG; }
+  if (p.detectorType != MODSX_DET_HESSIAN && p.detectorType != MODSX_DET_DOG && p.detectorType != MODSX_DET_HARRIS) {
+    set_error("detectorType must be Hessian (0), DoG (1) or Harris (2)");
+    return MODSX_ERR_ARG;
+  }
+  if (rows < 1 || cols < 1 || rows >= (1 << 14) || cols >= (1 << 14)) { set_error("modsx_debug_scan_levels: plane size"); return MODSX_ERR_ARG; }
+  Pyramid &py = c->pyr[0];
+  const size_t npx = (size_t)rows * cols;
+  if (!py.store.ensure((size_t)2 * L * npx * sizeof(float) + 64)) return MODSX_ERR_NOMEM;
+  py.nOct = 1;
+  Octave &oc = py.oct[0];
+  oc.rows = rows; oc.cols = cols; oc.pixelDistance = 1.0f;
+  float *ptr = (float *)py.store.p;
+  for (int l = 0; l < L; l++) { oc.blur[l] = ptr; ptr += npx; }
+  for (int l = 0; l < L; l++) { oc.resp[l] = ptr; ptr += npx; }
+  MX_HIP(hipMemcpyAsync(oc.blur[0], blurs, (size_t)L * npx * 4, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipMemcpyAsync(oc.resp[0], resps, (size_t)L * npx * 4, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));    // the caller's planes are its own again
+  int rc = scan_extrema(c, 1, p);
+  std::vector<modsx_sskp> kp[1];
+  if (!rc) rc = order_on_host(c, 1, p, kp);
+  if (rc) return rc;
+  const Candidate *cd = (const Candidate *)c->hCand.p;
+  cands.assign(cd, cd + c->lastCandCount);
+  out.swap(kp[0]);
+  return MODSX_OK;
 }
 
 static int ensure_smm_mask(modsx_ctx *c, int W) {

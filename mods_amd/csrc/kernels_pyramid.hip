@@ -567,27 +567,43 @@ static void launch_blur_hess_th(hipStream_t s, const BlurBatch &b, int tiles) {
     default: hipLaunchKernelGGL((k_blur_hess<8, TH>), grid, dim3(256), 0, s, b); break;
   }
 }
-void launch_blur_hess(hipStream_t s, const BlurBatch &bin, int nj, int, int) {
-  BlurBatch b = bin;
-  int tiles = fill_tiles(b, nj, TW, 32);
-  if (tiles <= 0) return;
+BlurGeo blur_geometry(const int *rows, const int *cols, int n) {
+  auto tiles = [&](int th) {
+    int t = 0;
+    for (int i = 0; i < n; i++) t += ((cols[i] + TW - 1) / TW) * ((rows[i] + th - 1) / th);
+    return t;
+  };
   // under two rounds of workgroups (5-6 per CU x 256 CUs) the 16-row tile is faster
-  if (tiles >= 2560) { launch_blur_hess_th<32>(s, b, tiles); return; }
-  tiles = fill_tiles(b, nj, TW, 16);
-  launch_blur_hess_th<16>(s, b, tiles);
+  const int t32 = tiles(32);
+  if (t32 >= 2560) return {32, t32};
+  return {16, tiles(16)};
 }
-void launch_hessian(hipStream_t s, const BlurBatch &bin, int nj, int, int) {
+BlurLaunch launch_blur_hess(hipStream_t s, const BlurBatch &bin, int nj, int, int) {
+  BlurBatch b = bin;
+  int rows[MAXB], cols[MAXB];
+  for (int i = 0; i < nj; i++) { rows[i] = b.j[i].rows; cols[i] = b.j[i].cols; }
+  const BlurGeo g = blur_geometry(rows, cols, nj);
+  if (g.tiles <= 0) return {0, 0, 0};
+  const int tiles = fill_tiles(b, nj, TW, g.th);   // (the same count: it is the launch's grid)
+  if (g.th == 32) launch_blur_hess_th<32>(s, b, tiles);
+  else launch_blur_hess_th<16>(s, b, tiles);
+  const int R = b.n >> 1;
+  return {g.th, tiles, R >= 1 && R <= 7 ? R : 8};   // launch_blur_hess_th's switch
+}
+bool launch_hessian(hipStream_t s, const BlurBatch &bin, int nj, int, int) {
   BlurBatch b = bin;
   const int tiles = fill_tiles(b, nj, 64, 4);
   if (tiles > 0) hipLaunchKernelGGL(k_hessian, dim3(tiles), dim3(256), 0, s, b);
+  return tiles > 0;
 }
-void launch_resize_half(hipStream_t s, const ResizeBatch &bin, int nj, int, int) {
+bool launch_resize_half(hipStream_t s, const ResizeBatch &bin, int nj, int, int) {
   ResizeBatch b = bin;
   b.nj = nj;
   int t = 0;
   for (int i = 0; i < nj; i++) { b.tile0[i] = t; t += ((b.j[i].dcols + 63) / 64) * ((b.j[i].drows + 3) / 4); }
   b.tile0[nj] = t;
   if (t > 0) MX_DUP(K_RESIZE) hipLaunchKernelGGL(k_resize_half, dim3(t), dim3(256), 0, s, b);
+  return t > 0;
 }
 
 // The extrema found by the scan are few and scattered (about one per wavefront), and each needs a chain of ~10 dependent

@@ -114,6 +114,21 @@ int orc_detect_scalespace(const float *img, int rows, int cols, const orc_hessaf
                           orc_sskp *out, int cap);
 int orc_detect_hessaff(const float *img, int rows, int cols, const orc_hessaff_params *p,
                        double tilt, double zoom, orc_keypoint *out, int cap);
+/* findLevelKeypoints + localizeKeypoint of ONE octave on response and blur planes the caller supplies: resps and blurs hold
+ * L = numberOfScales + 2 planes of rows x cols each, levels 1 .. L - 2 are scanned in order (octave 0, pixelDistance 1).
+ * claim = 0 skips the octaveMap test, so every localised extremum is kept.  The report gets one record per 3x3x3 extremum in
+ * scan order (n_report: how many there are; the first cap_report are written): where it was found (level, r0, c0), where the
+ * walk stood when it returned (r, c), the Newton steps it had solved (1..5; 0 for the edge exits) and the return it took;
+ * b0, b1, b2, val as they were at that moment, type for accepted ones (-1 otherwise).  Returns the number of keypoints (the
+ * first cap are written to out), -1 for L != numberOfScales + 2 or border < 1 (localizeKeypoint reads out of bounds there). */
+enum { ORC_SCAN_ACCEPTED = 0, ORC_SCAN_EDGE_HIGH, ORC_SCAN_EDGE_NEGATIVE, ORC_SCAN_NAN, ORC_SCAN_BORDER_RIGHT,
+       ORC_SCAN_BORDER_BOTTOM, ORC_SCAN_BORDER_LEFT, ORC_SCAN_BORDER_TOP, ORC_SCAN_OFFSET, ORC_SCAN_VALUE, ORC_SCAN_CLAIMED };
+typedef struct orc_scan_extremum {
+  int level, r0, c0, r, c, iters, exit, type;
+  float b0, b1, b2, val;
+} orc_scan_extremum;
+int orc_scan_levels(const float *resps, const float *blurs, int L, int rows, int cols, const orc_hessaff_params *p, int claim,
+                    orc_scan_extremum *report, int cap_report, int *n_report, orc_sskp *out, int cap);
 int orc_find_affine_shape(const float *blur, int rows, int cols, const orc_hessaff_params *p,
                           float x, float y, float s, float pixelDistance, float *u /*4*/);
 /* findAffineShape over a job list: job k reads planes[plane_of[k]] (rows[] x cols[]) at xyspd[4k .. 4k+3] = x, y, s,

@@ -150,6 +150,8 @@ struct Detector {
   std::vector<orc_sskp> sskps;
   std::vector<orc_keypoint> keys;
   bool runAffine = true;
+  bool claim = true;                              /* false: the octaveMap test of localize() is skipped (orc_scan_levels) */
+  std::vector<orc_scan_extremum> *report = nullptr; /* localize() appends one record per call */
 
   explicit Detector(const orc_hessaff_params &p) : par(p) {
     edgeScoreThreshold = (p.edgeEigenValueRatio + 1.0f) * (p.edgeEigenValueRatio + 1.0f) / p.edgeEigenValueRatio;
@@ -175,13 +177,22 @@ struct Detector {
     return true;
   }
 
-  /* localizeKeypoint, affinedetectors/pyramid.cpp:308-430 */
+  /* localizeKeypoint, affinedetectors/pyramid.cpp:308-430.  With `report` set every call leaves one record: where the walk
+     started and stood at its exit, the Newton steps it solved and the return it took (ORC_SCAN_* of oracle.h). */
   void localize(int r, int c, float curScale, float pixelDistance) {
     const int cols = cur.cols, rows = cur.rows;
     const int r0 = r, c0 = c;
     float b[3] = {0, 0, 0};
     float val = 0;
     int nr = r, nc = c;
+    int steps = 0;
+    auto leave = [&](int code, int type) {
+      if (!report) return;
+      orc_scan_extremum e;
+      e.level = levelIdx; e.r0 = r0; e.c0 = c0; e.r = r; e.c = c; e.iters = steps; e.exit = code; e.type = type;
+      e.b0 = b[0]; e.b1 = b[1]; e.b2 = b[2]; e.val = val;
+      report->push_back(e);
+    };
     for (int iter = 0; iter < 5; iter++) {
       r = nr; c = nc;
       const float *c0p = cur.row(r - 1), *c1p = cur.row(r), *c2p = cur.row(r + 1);
@@ -193,7 +204,8 @@ struct Detector {
       float dxy = 0.25f * (c2p[c + 1] - c2p[c - 1] - c0p[c + 1] + c0p[c - 1]);
       if (iter == 0) {
         float edgeScore = (dxx + dyy) * (dxx + dyy) / (dxx * dyy - dxy * dxy);
-        if (edgeScore >= edgeScoreThreshold || edgeScore < 0) return;
+        if (edgeScore >= edgeScoreThreshold) return leave(ORC_SCAN_EDGE_HIGH, -1);
+        if (edgeScore < 0) return leave(ORC_SCAN_EDGE_NEGATIVE, -1);
       }
       float dxs = 0.25f * (h1p[c + 1] - h1p[c - 1] - l1p[c + 1] + l1p[c - 1]);
       float dys = 0.25f * (h2p[c] - h0p[c] - l2p[c] + l0p[c]);
@@ -203,17 +215,18 @@ struct Detector {
       float ds = 0.5f * (h1p[c] - l1p[c]);
       b[0] = -dx; b[1] = -dy; b[2] = -ds;
       solve3(A, b);
-      if (std::isnan(b[0]) || std::isnan(b[1]) || std::isnan(b[2])) return;
+      steps = iter + 1;
+      if (std::isnan(b[0]) || std::isnan(b[1]) || std::isnan(b[2])) return leave(ORC_SCAN_NAN, -1);
       val = c1p[c] + 0.5f * (dx * b[0] + dy * b[1] + ds * b[2]);
-      if (b[0] > 0.6) { if (c < cols - 3) nc++; else return; }
-      if (b[1] > 0.6) { if (r < rows - 3) nr++; else return; }
-      if (b[0] < -0.6) { if (c > 3) nc--; else return; }
-      if (b[1] < -0.6) { if (r > 3) nr--; else return; }
+      if (b[0] > 0.6) { if (c < cols - 3) nc++; else return leave(ORC_SCAN_BORDER_RIGHT, -1); }
+      if (b[1] > 0.6) { if (r < rows - 3) nr++; else return leave(ORC_SCAN_BORDER_BOTTOM, -1); }
+      if (b[0] < -0.6) { if (c > 3) nc--; else return leave(ORC_SCAN_BORDER_LEFT, -1); }
+      if (b[1] < -0.6) { if (r > 3) nr--; else return leave(ORC_SCAN_BORDER_TOP, -1); }
       if (nr == r && nc == c) break;
     }
-    if (fabs(b[0]) > 1.5 || fabs(b[1]) > 1.5 || fabs(b[2]) > 1.5 || fabsf(val) < finalThreshold ||
-        octaveMap[(size_t)r * cols + c] > 0)
-      return;
+    if (fabs(b[0]) > 1.5 || fabs(b[1]) > 1.5 || fabs(b[2]) > 1.5) return leave(ORC_SCAN_OFFSET, -1);
+    if (fabsf(val) < finalThreshold) return leave(ORC_SCAN_VALUE, -1);
+    if (claim && octaveMap[(size_t)r * cols + c] > 0) return leave(ORC_SCAN_CLAIMED, -1);
     octaveMap[(size_t)r * cols + c] = 1;
     float scale = curScale * powf(2.0f, b[2] / par.numberOfScales);
     /* getPointType, pyramid.cpp:66-130; DET_HESSIAN reads the detection-level blur */
@@ -234,6 +247,7 @@ struct Detector {
     k.s = pixelDistance * scale;
     k.pixelDistance = pixelDistance;
     sskps.push_back(k);
+    leave(ORC_SCAN_ACCEPTED, type);
     if (runAffine) {
       /* onKeypointDetected(prevBlur, ...) -> findAffineShape -> keys.push_back,
          scale-space-detector.hpp:48-88 */
@@ -417,6 +431,37 @@ int orc_detect_scalespace(const float *img, int rows, int cols, const orc_hessaf
   d.detect(Img(rows, cols, img));
   int n = (int)d.sskps.size();
   for (int i = 0; i < n && i < cap; i++) out[i] = d.sskps[i];
+  return n;
+}
+
+int orc_scan_levels(const float *resps, const float *blurs, int L, int rows, int cols, const orc_hessaff_params *p, int claim,
+                    orc_scan_extremum *report, int cap_report, int *n_report, orc_sskp *out, int cap) {
+  if (L != p->numberOfScales + 2 || L < 3 || rows < 1 || cols < 1) return -1;
+  /* localize() reads rows r - 1 .. r + 1 of the scan window [border, dim - border) and walks inside [3, dim - 3] */
+  if (p->border < 1) return -1;
+  Detector d(*p);
+  d.runAffine = false;
+  d.claim = claim != 0;
+  std::vector<orc_scan_extremum> rep;
+  d.report = &rep;
+  const size_t npx = (size_t)rows * cols;
+  d.octaveMap.assign(npx, 0);
+  d.octaveIdx = 0;
+  const float sigmaStep = powf(2.0f, 1.0f / (float)p->numberOfScales);
+  float curSigma = p->initialSigma;
+  for (int l = 1; l <= p->numberOfScales; l++) {
+    curSigma *= sigmaStep;   /* the sigma detectOctaveKeypoints holds when it scans level l */
+    d.low = Img(rows, cols, resps + (size_t)(l - 1) * npx);
+    d.cur = Img(rows, cols, resps + (size_t)l * npx);
+    d.high = Img(rows, cols, resps + (size_t)(l + 1) * npx);
+    d.blur = Img(rows, cols, blurs + (size_t)l * npx);
+    d.levelIdx = l;
+    d.find_level(curSigma, 1.0f);
+  }
+  if (n_report) *n_report = (int)rep.size();
+  for (size_t i = 0; report && i < rep.size() && (int)i < cap_report; i++) report[i] = rep[i];
+  const int n = (int)d.sskps.size();
+  for (int i = 0; out && i < n && i < cap; i++) out[i] = d.sskps[i];
   return n;
 }
 

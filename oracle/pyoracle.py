@@ -151,6 +151,31 @@ def detect_scalespace(img, params, cap=400000):
     return out[:n].copy()
 
 
+SCAN_EXTREMUM = np.dtype([("level", "i4"), ("r0", "i4"), ("c0", "i4"), ("r", "i4"), ("c", "i4"), ("iters", "i4"), ("exit", "i4"),
+                          ("type", "i4"), ("b0", "f4"), ("b1", "f4"), ("b2", "f4"), ("val", "f4")], align=True)
+assert SCAN_EXTREMUM.itemsize == 48
+# oracle.h: ORC_SCAN_*, in its order
+SCAN_EXITS = ("accepted", "edge_high", "edge_negative", "nan", "border_right", "border_bottom", "border_left", "border_top",
+              "offset", "value", "claimed")
+
+
+def scan_levels(resps, blurs, params, claim=True):
+    """orc_scan_levels: findLevelKeypoints + localizeKeypoint on the L = numberOfScales + 2 response / blur planes of one octave.
+    -> (keypoints SSKP, report SCAN_EXTREMUM: one record per 3x3x3 extremum in scan order, `exit` an index into SCAN_EXITS)."""
+    resps, blurs = _f32(resps), _f32(blurs)
+    assert resps.ndim == 3 and resps.shape == blurs.shape
+    L, rows, cols = resps.shape
+    nrep = C.c_int(0)
+    n = lib().orc_scan_levels(_p(resps), _p(blurs), L, rows, cols, C.byref(params), int(bool(claim)), None, 0, C.byref(nrep), None, 0)
+    if n < 0:
+        raise ValueError("orc_scan_levels refuses these planes / parameters")
+    rep, out = np.zeros(max(nrep.value, 1), SCAN_EXTREMUM), np.zeros(max(n, 1), SSKP)
+    n2 = lib().orc_scan_levels(_p(resps), _p(blurs), L, rows, cols, C.byref(params), int(bool(claim)), _p(rep), len(rep),
+                               C.byref(nrep), _p(out), len(out))
+    assert n2 == n
+    return out[:n].copy(), rep[:nrep.value].copy()
+
+
 def response(img, detector_type, norm):
     """ScaleSpaceDetector::Response (pyramid.cpp:132-175): 0 Hessian, 1 DoG, 2 Harris."""
     img = _f32(img)
