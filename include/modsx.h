@@ -588,6 +588,65 @@ int modsx_match_regions_hamming(modsx_ctx *ctx, const modsx_region *regs1, const
                                 const modsx_region *regs2, const void *desc2, int n2, int nbytes, int dtype,
                                 double distanceThreshold, const modsx_pair_params *par, modsx_pair_result *res);
 
+/* FGINN matching of float descriptors of any width: MatchFlannFGINN (matching/matching.cpp:357-461) with vector_matcher = linear
+ * as the reference runs it on every real-valued class -- desc.vec copied into a CV_32F matrix of desc_size columns, the linear
+ * index in f32 (SURF 64, LIOP 144, MROGH 192, DAISY 200, unquantised SIFT, learned 128-D / 256-D vectors, rows of a key file read
+ * with modsx_load_regions).  Every other descriptor entry keeps its rule (128 values holding the integers 0..255).
+ *   rows      [n][dim] f32, dim % 4 == 0 and 4 <= dim <= MODSX_FGINN32_MAX_DIM.  The % 4 rule is the loop of the linear index as
+ *             the test oracle states it; the tail loop of FLANN's L2 for other widths is not restated anywhere: refused.
+ *             Values must be finite with |x| <= 1e17, so that no distance overflows (256 * (2e17)^2 < FLT_MAX); anything else is
+ *             MODSX_ERR_ARG.  The host entries check on the host; the device entry checks in its pack kernel and reports
+ *             through a flag word that is read with the result.
+ *   limits    all refused with MODSX_ERR_ARG before any launch: more than 2 000 000 rows on a side; nn outside [2, 256] (as for
+ *             modsx_match_fginn); ratio NaN; ratio * ratio >= 1 -- the "all points" branch (:397-428) is NOT built for float rows.
+ *   distance  for each (query, train) one f32 chain over k = 0, 4, 8, ...: e_i = a[k+i] - b[k+i],
+ *             r = r + (((e0*e0 + e1*e1) + e2*e2) + e3*e3), every operation rounded to f32, no FMA, subnormals kept.
+ *   order     neighbours by (distance, train index), lexicographically: equal distances keep the lower train index.
+ *   walk      with the neighbours j = 0, 1, ... of a query in that order, for j = 1 .. nn - 1:
+ *               1. ratio_j = (double)(d_0 / d_j), an f32 IEEE division; 0 / 0 is NaN and passes nothing
+ *               2. ratio_j <= ratio^2: one record {q, t0 = idx_0, tj = idx_j, t1 = idx_1, d1 = d_0, d2 = d_j, d2by2ndcl = d_1,
+ *                  ratio = sqrt(ratio_j)}, and the walk ends
+ *               3. otherwise, if the f64 squared distance between pos2[idx_0] and pos2[idx_j] exceeds contradDist^2, the walk
+ *                  ends without a record
+ *             It also ends without a record when the trains run out (n2 < nn).  Records come in query order.
+ *   result    a pure function of the inputs: not of tile length, split count, launch order or contexts in flight.
+ *   edges     n1 == 0 or n2 == 0: 0 records.
+ * pos2: [n2][2] f64 on the host (x, y of the train regions), also for the device entry. */
+#define MODSX_FGINN32_MAX_DIM 256
+/* rows from the host */
+int modsx_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                          double ratio, double contradDist, int nn, modsx_tentative **out);
+/* the same on dense [n][dim] f32 rows that already live in HBM (4-byte aligned, no more) */
+int modsx_match_fginn_f32_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim,
+                                 const double *pos2, double ratio, double contradDist, int nn, modsx_tentative **out);
+/* One step of mods.cpp:229-415 on caller-supplied regions: the matcher above with ratio = par->match_ratio, par->contradDist,
+ * par->nn and pos2 = reproj_kp.x, y of regs2 (as the reference takes it), then DuplicateFiltering (key = ratio) and
+ * LORANSACFiltering (H or F per par) -- the pair tail of modsx_match_regions_hamming with the match stage replaced.  An empty
+ * side gives the zeroed result with H = -1. */
+int modsx_match_regions_f32(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                            const float *desc2, int n2, int dim, const modsx_pair_params *par, modsx_pair_result *res);
+/* debug: modsx_match_fginn_f32 (rows from the host) with the train axis forced into `splits` parts (0 = production geometry; more
+ * than one per tile is cut down to one per tile) and the stage behind the first switched by stage_mask: 1 = the top-4 search
+ * and the host's walk over j = 1..3, 3 = + the resolve sweep (production); a query that needs a stage that is off gives no
+ * record.  Outputs, each optional, the caller's memory:
+ *   top4      [n1][4] keys (f32 bit pattern of the distance << 32) | train index, ascending, all ones where there is no train
+ *   stage     [n1] how the query was closed: 0 = within the four nearest, 1 = by the resolve sweep (the nearest train behind
+ *             the fourth that ends the walk), 2 = by the resolve sweep's count (that train passes the ratio test, but
+ *             3 + count + 1 > nn - 1: the nn run out first; no counting sweep is needed, see kernels_fginn32.hip)
+ *   geometry  [6] = {tile length in trains, splits used, workgroups of k_f32_topk, kernel width DK, tiles, tiles per split}
+ *   counters  [4] = {queries sent to resolve, of those closed by the count, records, validity flag word}
+ *   out       the records (modsx_free)
+ * Needs n1 >= 1 and n2 >= 1.  Returns the record count. */
+int modsx_debug_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                                double ratio, double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4,
+                                unsigned char *stage, int *geometry, int *counters, modsx_tentative **out);
+/* host only, no context: the geometry[6] modsx_debug_match_fginn_f32 would report for these sizes (one function of its arguments) */
+int modsx_debug_fginn32_geometry(int n1, int n2, int dim, int splits, int *geometry);
+/* host only, no context: dpass[i] = the smallest f32 d > 0 with (double)(d0[i] / d) <= ratio[i]^2 (f32 division), found by
+ * bisection over the f32 bit patterns -- what the resolve sweep compares distances with instead of dividing; +inf when no
+ * finite d passes.  d0 finite and >= 0. */
+int modsx_debug_fginn32_dpass(const float *d0, const double *ratio, int n, float *dpass);
+
 /* One step of mods.cpp:229-415 with a ladder of synthesised views per image (same views for both images,
  * as in iters_mods_cviu.ini). */
 int modsx_match_pair_views(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,

@@ -115,7 +115,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
            "modsx_match_regions_hamming", "modsx_debug_hamming_geometry",
            "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
-           "modsx_debug_detect_scalespace_batch"]
+           "modsx_debug_detect_scalespace_batch",
+           "modsx_match_fginn_f32", "modsx_match_fginn_f32_device", "modsx_match_regions_f32", "modsx_debug_match_fginn_f32",
+           "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -227,6 +229,17 @@ def lib():
         L.modsx_debug_hamming_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_match_regions_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                   C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        L.modsx_match_fginn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                            C.c_double, C.c_int, C.c_void_p]
+        L.modsx_match_fginn_f32_device.argtypes = L.modsx_match_fginn_f32.argtypes
+        L.modsx_match_regions_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p]
+        L.modsx_debug_match_fginn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                                  C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        L.modsx_debug_fginn32_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_debug_fginn32_dpass.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_debug_fginn32_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -870,6 +883,60 @@ class Context(object):
                "match_regions_hamming")
         return _unpack_pair_result(res)
 
+    def match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
+        """MatchFlannFGINN on float rows of any width: [n][dim] float32, dim % 4 == 0, dim <= 256; pos2 [n2][2]."""
+        d1, d2, dim = _f32_rows(d1, d2)
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_fginn_f32(self._c(), _p(d1), len(d1), _p(d2), len(d2), dim, _p(pos2), C.c_double(ratio),
+                                               C.c_double(contrad_dist), int(nn), C.byref(out)), "match_fginn_f32")
+        return _take(out, n, TENT)
+
+    def match_fginn_f32_device(self, p1, n1, p2, n2, dim, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
+        """The same on dense [n][dim] float32 rows in HBM (device pointers, 4-byte aligned)."""
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_fginn_f32_device(self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), int(dim), _p(pos2),
+                                                      C.c_double(ratio), C.c_double(contrad_dist), int(nn), C.byref(out)),
+                   "match_fginn_f32_device")
+        return _take(out, n, TENT)
+
+    def debug_match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50, splits=0, stage_mask=3):
+        """dict(tentatives, top4 [n1][4] uint64 keys, stage [n1] (0 host walk, 1 resolve sweep, 2 its count: the nn ran out), geometry,
+        resolve, by_count, records, flag) of the matcher with the train axis forced into `splits` parts (0 = production) and the
+        stages of `stage_mask` (1 = top-4 search + host walk, 3 = + resolve sweep)."""
+        d1, d2, dim = _f32_rows(d1, d2)
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        top4 = np.zeros((max(len(d1), 1), 4), np.uint64)
+        stage = np.zeros(max(len(d1), 1), np.uint8)
+        geo, cnt = np.zeros(6, np.int32), np.zeros(4, np.int32)
+        out = C.c_void_p()
+        n = _check(lib().modsx_debug_match_fginn_f32(self._c(), _p(d1), len(d1), _p(d2), len(d2), dim, _p(pos2), C.c_double(ratio),
+                                                     C.c_double(contrad_dist), int(nn), int(splits), int(stage_mask), _p(top4),
+                                                     _p(stage), _p(geo), _p(cnt), C.byref(out)), "debug_match_fginn_f32")
+        return dict(tentatives=_take(out, n, TENT), top4=top4[:len(d1)], stage=stage[:len(d1)],
+                    geometry=dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo))), resolve=int(cnt[0]), by_count=int(cnt[1]),
+                    records=int(cnt[2]), flag=int(cnt[3]))
+
+    def fginn32_last_ms(self):
+        """(packing ms, search ms) of this context's last f32 FGINN search, HIP events; filled while profile() is on."""
+        ms = np.zeros(2, np.float64)
+        _check(lib().modsx_debug_fginn32_last_ms(self._c(), _p(ms)), "fginn32_last_ms")
+        return float(ms[0]), float(ms[1])
+
+    def match_regions_f32(self, regs1, d1, regs2, d2, params):
+        """One float-descriptor step on caller-supplied regions: MatchFlannFGINN (params.match_ratio, contradDist, nn; positions
+        = reproj_kp of regs2) + DuplicateFiltering + LO-RANSAC."""
+        regs1 = np.ascontiguousarray(regs1, REGION)
+        regs2 = np.ascontiguousarray(regs2, REGION)
+        d1, d2, dim = _f32_rows(d1, d2)
+        if len(regs1) != len(d1) or len(regs2) != len(d2):
+            raise ValueError("match_regions_f32: one descriptor row per region is expected")
+        res = PairResult()
+        _check(lib().modsx_match_regions_f32(self._c(), _p(regs1), _p(d1), len(d1), _p(regs2), _p(d2), len(d2), dim,
+                                             C.byref(params), C.byref(res)), "match_regions_f32")
+        return _unpack_pair_result(res)
+
     def rep_match_fginn(self, rep1, rep2, detector=0, desc_type=1, ratio=0.8, contrad_dist=30.0, nn=50):
         """MatchFlannFGINN of one class of two stored representations: rep1 the queries, rep2 (pre-packed) the trains."""
         out = C.c_void_p()
@@ -1074,6 +1141,36 @@ def blur_geometry(shapes):
     geo = np.zeros(2, np.int32)
     _check(lib().modsx_blur_geometry(_p(rows), _p(cols), len(sh), _p(geo)), "blur_geometry")
     return int(geo[0]), int(geo[1])
+
+
+FGINN32_GEOMETRY = ("tile", "splits", "workgroups", "DK", "tiles", "tiles_per_split")   # include/modsx.h, in its order
+
+
+def _f32_rows(d1, d2):
+    """the two sides as contiguous [n][dim] float32 arrays of one width"""
+    d1, d2 = np.ascontiguousarray(d1, np.float32), np.ascontiguousarray(d2, np.float32)
+    if d1.ndim != 2 or d2.ndim != 2 or d1.shape[1] != d2.shape[1]:
+        raise ValueError("fginn_f32: two [n][dim] arrays of one width are expected")
+    return d1, d2, d1.shape[1]
+
+
+def fginn32_geometry(n1, n2, dim, splits=0):
+    """dict(tile, splits, workgroups, DK, tiles, tiles_per_split): what the f32 FGINN search launches for these sizes (host only, no
+    GPU); splits = 0 is the production geometry, more splits than tiles are cut down to one per tile."""
+    geo = np.zeros(6, np.int32)
+    _check(lib().modsx_debug_fginn32_geometry(int(n1), int(n2), int(dim), int(splits), _p(geo)), "fginn32_geometry")
+    return dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo)))
+
+
+def fginn32_dpass(d0, ratio):
+    """the smallest float32 d > 0 with float64(float32(d0) / d) <= ratio^2 per pair, by the library's bisection (host only)"""
+    d0 = np.ascontiguousarray(d0, np.float32).reshape(-1)
+    ratio = np.ascontiguousarray(ratio, np.float64).reshape(-1)
+    if len(d0) != len(ratio):
+        raise ValueError("fginn32_dpass: one ratio per d0 is expected")
+    out = np.zeros(len(d0), np.float32)
+    _check(lib().modsx_debug_fginn32_dpass(_p(d0), _p(ratio), len(d0), _p(out)), "fginn32_dpass")
+    return out
 
 
 BAUMBERG_GEOMETRY = ("kernel", "chunk", "nchunks", "grid")   # include/modsx.h: modsx_debug_baumberg_geometry, in its order

@@ -1293,6 +1293,80 @@ int modsx_match_regions_hamming(modsx_ctx *ctx, const modsx_region *regs1, const
   return match_regions_hamming(ctx, regs1, desc1, n1, regs2, desc2, n2, nbytes, dtype, distanceThreshold, *par, res);
 }
 
+// ---- MatchFlannFGINN on f32 rows of any width (engine_fginn32.hip) ----------------------------------------------------------------
+int modsx_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                          double ratio, double contradDist, int nn, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  if ((n1 > 0 && !desc1) || (n2 > 0 && (!desc2 || !pos2))) { mx::set_error("modsx_match_fginn_f32: null rows or positions"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  int rc = match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_match_fginn_f32_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim, const double *pos2,
+                                 double ratio, double contradDist, int nn, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  int rc = fginn32_check_args("modsx_match_fginn_f32_device", n1, n2, dim, ratio, nn);
+  if (rc) return rc;
+  if ((n1 > 0 && !dev_desc1) || (n2 > 0 && (!dev_desc2 || !pos2))) { mx::set_error("modsx_match_fginn_f32_device: null rows or positions"); return MODSX_ERR_ARG; }
+  if (((uintptr_t)dev_desc1 | (uintptr_t)dev_desc2) & 3) { mx::set_error("modsx_match_fginn_f32_device: rows must be 4-byte aligned"); return MODSX_ERR_ARG; }
+  std::vector<modsx_tentative> t;
+  if (n1 > 0 && n2 > 0) {
+    hipSetDevice(ctx->dev);
+    rc = match_fginn32_device(ctx, (const float *)dev_desc1, n1, (const float *)dev_desc2, n2, dim, pos2, ratio, contradDist, nn, t);
+    if (rc) return rc;
+  }
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_match_regions_f32(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                            const float *desc2, int n2, int dim, const modsx_pair_params *par, modsx_pair_result *res) {
+  NEED(ctx); NEED(par); NEED(res);
+  if ((n1 > 0 && (!regs1 || !desc1)) || (n2 > 0 && (!regs2 || !desc2))) { mx::set_error("modsx_match_regions_f32: null regions or rows"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  return match_regions_f32(ctx, regs1, desc1, n1, regs2, desc2, n2, dim, *par, res);
+}
+int modsx_debug_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                                double ratio, double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4,
+                                unsigned char *stage, int *geometry, int *counters, modsx_tentative **out) {
+  NEED(ctx); NEED(desc1); NEED(desc2); NEED(pos2);
+  if (n1 < 1 || n2 < 1 || splits < 0 || (stage_mask != 1 && stage_mask != 3)) {
+    mx::set_error("modsx_debug_match_fginn_f32: needs n1 >= 1, n2 >= 1, splits >= 0 and a stage mask of 1 or 3");
+    return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  const Fginn32Tap tap = {splits, stage_mask, top4, stage, geometry, counters};
+  std::vector<modsx_tentative> t;
+  int rc = match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t, &tap);
+  if (rc) return rc;
+  if (out) *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_debug_fginn32_geometry(int n1, int n2, int dim, int splits, int *geometry) {
+  NEED(geometry);
+  int rc = fginn32_check_args("modsx_debug_fginn32_geometry", n1, n2, dim, 0.5, 2);
+  if (rc) return rc;
+  if (n1 < 1 || n2 < 1 || splits < 0) { mx::set_error("modsx_debug_fginn32_geometry: needs n1 >= 1, n2 >= 1, splits >= 0"); return MODSX_ERR_ARG; }
+  return fginn32_geometry_report(n1, n2, dim, splits, geometry);
+}
+int modsx_debug_fginn32_dpass(const float *d0, const double *ratio, int n, float *dpass) {
+  if (n < 0 || (n > 0 && (!d0 || !ratio || !dpass))) { mx::set_error("modsx_debug_fginn32_dpass: bad argument"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) {
+    if (!(d0[i] >= 0.f) || isinf(d0[i]) || !(ratio[i] * ratio[i] >= 0)) { mx::set_error("modsx_debug_fginn32_dpass: d0 must be finite and >= 0, ratio not NaN"); return MODSX_ERR_ARG; }
+    dpass[i] = fginn32_dpass(d0[i], ratio[i] * ratio[i]);
+  }
+  return MODSX_OK;
+}
+// under modsx_profile(ctx, 1): HIP-event times in ms of the last f32 FGINN search of this context -- ms2[0] the two k_f32_pack
+// launches, ms2[1] k_f32_topk + k_f32_merge (tools/bench_fginn32.py)
+extern "C" __attribute__((visibility("default"))) int modsx_debug_fginn32_last_ms(modsx_ctx *ctx, double *ms2) {
+  NEED(ctx); NEED(ms2);
+  ms2[0] = ctx->fginn32Ms[0]; ms2[1] = ctx->fginn32Ms[1];
+  return MODSX_OK;
+}
+
 int modsx_match_ladder(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,
                        const modsx_ladder_step *steps, int nsteps, int min_matches, const modsx_pair_params *par,
                        modsx_pair_result *res, int *steps_done) {

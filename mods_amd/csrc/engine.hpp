@@ -328,6 +328,19 @@ HammingGeo hamming_geometry(int n1, int n2, int W, int splits);   // splits = 0:
 size_t hamming_workspace_bytes(const HammingGeo &g, int n1);
 void launch_hamming(hipStream_t s, const HammingGeo &g, const uint8_t *d1, int n1, const uint8_t *d2, int n2, int nbytes, void *work,
                     int *nn2, hipEvent_t *ev = nullptr);             // ev: three events, around the packing and the search launches
+// FGINN matching of f32 rows of any width (kernels_fginn32.hip).  DK = the kernel width dim rounds up to; tile = trains per LDS
+// tile; the train axis is cut into S splits of tilesPerSplit tiles; gx x S workgroups of k_f32_topk.
+struct Fginn32Geo { int dim, DK, tile, ntiles, tilesPerSplit, S, gx; };
+// an undecided query on its way to k_f32_resolve, and what comes back
+struct F32Open { unsigned long long klast; int q, t0; float dpass; int pad; };
+struct F32Closed { unsigned long long kterm; unsigned cnt, pad; };
+struct Fginn32Work { float *queries, *trains; unsigned long long *keys; F32Open *open; F32Closed *closed; };
+Fginn32Geo fginn32_geometry(int n1, int n2, int dim, int splits);   // splits = 0: production; > 0: forced (at most one per tile)
+size_t fginn32_workspace_bytes(const Fginn32Geo &g, int n1);
+Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work);
+void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, int n1, const float *d2, int n2, void *work,
+                         void *flagAndTop4, hipEvent_t *ev = nullptr);
+void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work);
 
 }  // namespace mx
 
@@ -414,6 +427,7 @@ struct modsx_ctx {
   long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
+  double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search: packing, k_f32_topk + k_f32_merge
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

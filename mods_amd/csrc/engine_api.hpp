@@ -174,6 +174,21 @@ int match_hamming_host(modsx_ctx *c, const void *desc1, int n1, const void *desc
                        std::vector<modsx_tentative> &out);
 int match_regions_hamming(modsx_ctx *c, const modsx_region *regs1, const void *desc1, int n1, const modsx_region *regs2, const void *desc2,
                           int n2, int nbytes, int dtype, double distanceThreshold, const modsx_pair_params &pp, modsx_pair_result *res);
+// ---- MatchFlannFGINN on f32 rows of any width (engine_fginn32.hip) ----
+// debug tap: splits forces the split count (0 = production); stageMask: 1 = top-4 + host walk (always run), 2 = k_f32_resolve
+// (a query that needs a stage that is masked off gives no record).  Outputs (each optional): top4 [n1][4] keys, stage [n1] = how
+// the query was closed (0 host walk, 1 resolve sweep, 2 resolve sweep and its count: the rank bound exceeded nn - 1), geometry [6],
+// counters [4] = {queries sent to resolve, of those closed by the count, records, validity flag}
+struct Fginn32Tap { int splits, stageMask; unsigned long long *top4; unsigned char *stage; int *geometry; int *counters; };
+float fginn32_dpass(float d0, double rsq);
+int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, int nn);
+int fginn32_geometry_report(int n1, int n2, int dim, int splits, int *geo6);
+int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
+                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
+int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2, double ratioT,
+                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
+int match_regions_f32(modsx_ctx *c, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2, const float *desc2,
+                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res);
 DbSet *db_create(modsx_ctx *c, const void *rows, long n, int dtype);
 void db_free(DbSet *db);
 int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *dmin);

@@ -1,0 +1,218 @@
+// engine_fginn32.hip -- MatchFlannFGINN (matching/matching.cpp:357-461, vector_matcher = linear, ratio^2 < 1) on f32 rows of any
+// width: the search on the device (kernels_fginn32.hip), the walk over the neighbours on the host.  The device hands down the four
+// nearest keys of every query (32 bytes); the host walks j = 1..3 exactly as the reference does (its f32 division, its f64 positions).
+// A walk that is still open behind the fourth neighbour is closed by one more sweep (k_f32_resolve: the nearest train behind the
+// fourth that ends the walk, and how many trains do not end it).  That count gives the rank of a passing terminal train exactly, so
+// there is no further sweep (kernels_fginn32.hip).  No list of nn neighbours exists anywhere.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+#include <string>
+#include <vector>
+#include "engine_api.hpp"
+
+namespace mx {
+
+static inline float key_dist(unsigned long long k) { const uint32_t b = (uint32_t)(k >> 32); float f; memcpy(&f, &b, 4); return f; }
+static inline int key_idx(unsigned long long k) { return (int)(uint32_t)k; }
+constexpr unsigned long long KEY_NONE = ~0ull;
+
+// (double)(d0 / d) <= ratio^2 with the f32 division of matching.cpp:392: the ratio test of the walk
+static inline bool ratio_passes(float d0, float d, double rsq, double *ratio) {
+  const double r = d0 / d;
+  if (ratio) *ratio = r;
+  return r <= rsq;
+}
+
+// The smallest f32 d > 0 with (double)(d0 / d) <= rsq, by bisection over the bit patterns: the quotient does not grow with the
+// divisor (rounding is monotone), d0 / inf = 0 passes (rsq >= 0), so the patterns that pass are an upper range of [1, 0x7f800000].
+// d0 = 0 gives the smallest subnormal: 0 / d = 0 passes for every d > 0, 0 / 0 is NaN and passes nothing.  d0 >= 0 and finite.
+float fginn32_dpass(float d0, double rsq) {
+  uint32_t lo = 1, hi = 0x7f800000u;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    float d;
+    memcpy(&d, &mid, 4);
+    if (ratio_passes(d0, d, rsq, nullptr)) hi = mid; else lo = mid + 1;
+  }
+  float d;
+  memcpy(&d, &lo, 4);
+  return d;
+}
+
+bool fginn32_rows_ok(const float *f, size_t n) {
+  bool ok = true;
+  for (size_t i = 0; i < n; i++) ok = ok && fabs((double)f[i]) <= 1e17;      // NaN fails the comparison
+  return ok;
+}
+
+// the argument rules every f32 FGINN entry shares, all before any launch
+int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, int nn) {
+  const std::string f(fn);
+  if (dim < 4 || dim > MODSX_FGINN32_MAX_DIM || dim % 4) {
+    set_error(f + ": dim must be a multiple of 4 in [4, MODSX_FGINN32_MAX_DIM] (the linear index's groups of four; the tail loop for other widths is not built)");
+    return MODSX_ERR_ARG;
+  }
+  if (n1 < 0 || n2 < 0) { set_error(f + ": negative row count"); return MODSX_ERR_ARG; }
+  if (n1 > 2000000 || n2 > 2000000) { set_error(f + ": more than 2 000 000 rows on one side"); return MODSX_ERR_ARG; }
+  if (nn < 2 || nn > MATCH_NN_MAX) { set_error(f + ": nn must be in [2, 256]"); return MODSX_ERR_ARG; }
+  if (isnan(ratioT)) { set_error(f + ": ratio is NaN"); return MODSX_ERR_ARG; }
+  if (ratioT * ratioT >= 1.0) {
+    set_error(f + ": ratio^2 >= 1 (the \"all points\" branch, matching.cpp:397-428) is not built for float rows");
+    return MODSX_ERR_ARG;
+  }
+  return MODSX_OK;
+}
+
+static void geo_out(const Fginn32Geo &g, int *geo) {
+  geo[0] = g.tile; geo[1] = g.S; geo[2] = g.gx * g.S; geo[3] = g.DK; geo[4] = g.ntiles; geo[5] = g.tilesPerSplit;
+}
+int fginn32_geometry_report(int n1, int n2, int dim, int splits, int *geo6) {
+  geo_out(fginn32_geometry(n1, n2, dim, splits), geo6);
+  return MODSX_OK;
+}
+
+static modsx_tentative make_record(int q, const unsigned long long *k, unsigned long long kj, double ratio) {
+  modsx_tentative t;
+  t.q = q; t.t0 = key_idx(k[0]); t.tj = key_idx(kj); t.t1 = key_idx(k[1]);
+  t.d1 = key_dist(k[0]); t.d2 = key_dist(kj); t.d2by2ndcl = key_dist(k[1]);
+  t.ratio = sqrt(ratio);
+  return t;
+}
+
+// d1 / d2: dense [n][dim] f32 rows in HBM, pos2: [n2][2] f64 on the host.  n1 >= 1, n2 >= 1, arguments checked by the caller.
+// tap (optional): forced split count, stage mask, and what the stages did.
+int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
+                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+  out.clear();
+  CtxBusy busy(c);
+  const int stageMask = tap ? tap->stageMask : 3;
+  const Fginn32Geo g = fginn32_geometry(n1, n2, dim, tap ? tap->splits : 0);
+  if (tap && tap->geometry) geo_out(g, tap->geometry);
+  const double rsq = ratioT * ratioT, cd2 = contradDist * contradDist;
+  const size_t rowB = 16 + (size_t)n1 * 32;
+  if (!c->matchWork.ensure(fginn32_workspace_bytes(g, n1)) || !c->matchRows.ensure(rowB) || !c->hMatch.ensure(rowB)) return MODSX_ERR_NOMEM;
+  hipEvent_t ev[3];
+  const bool timed = c->prof.enabled;     // modsx_profile: the launches are timed into the context (tools/bench_fginn32.py)
+  if (timed) for (int i = 0; i < 3; i++) MX_HIP(hipEventCreate(&ev[i]));
+  launch_fginn32_topk(c->stream, g, d1, n1, d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr);
+  hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, rowB, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = ctx_sync(c);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (timed) {
+    float a = 0, b = 0;
+    if (e == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) {
+      c->fginn32Ms[0] = a; c->fginn32Ms[1] = b;
+    }
+    for (int i = 0; i < 3; i++) hipEventDestroy(ev[i]);
+  }
+  MX_HIP(e);
+  const unsigned flag = *(const unsigned *)c->hMatch.p;
+  if (tap && tap->counters) { tap->counters[0] = tap->counters[1] = tap->counters[2] = 0; tap->counters[3] = (int)flag; }
+  if (flag) {
+    set_error(std::string("modsx_match_fginn_f32: rows must be finite with |x| <= 1e17 (") + (flag & 1 ? "queries" : "") +
+              (flag == 3 ? ", " : "") + (flag & 2 ? "trains" : "") + ")");
+    return MODSX_ERR_ARG;
+  }
+  // the keys are copied: the stages below reuse hMatch
+  std::vector<unsigned long long> top4((size_t)n1 * 4);
+  memcpy(top4.data(), (const char *)c->hMatch.p + 16, (size_t)n1 * 32);
+  if (tap && tap->top4) memcpy(tap->top4, top4.data(), (size_t)n1 * 32);
+
+  std::vector<modsx_tentative> rec(n1);
+  std::vector<unsigned char> has(n1, 0), stage(n1, 0);
+  std::vector<F32Open> open;
+  const int jTop = std::min(3, nn - 1);
+  for (int q = 0; q < n1; q++) {
+    const unsigned long long *k = &top4[(size_t)q * 4];
+    const float d0 = key_dist(k[0]);
+    bool ended = k[0] == KEY_NONE;
+    for (int j = 1; j <= jTop && !ended; j++) {
+      if (k[j] == KEY_NONE) { ended = true; break; }            // the trains ran out (the oracle's ir[j] < 0)
+      double ratio;
+      if (ratio_passes(d0, key_dist(k[j]), rsq, &ratio)) { rec[q] = make_record(q, k, k[j], ratio); has[q] = 1; ended = true; break; }
+      const int i0 = key_idx(k[0]), ij = key_idx(k[j]);
+      const double dx = pos2[2 * (size_t)i0] - pos2[2 * (size_t)ij], dy = pos2[2 * (size_t)i0 + 1] - pos2[2 * (size_t)ij + 1];
+      if (dx * dx + dy * dy > cd2) ended = true;
+    }
+    if (ended || nn - 1 <= 3) continue;
+    F32Open o;
+    o.klast = k[3]; o.q = q; o.t0 = key_idx(k[0]); o.dpass = fginn32_dpass(d0, rsq); o.pad = 0;
+    open.push_back(o);
+    stage[q] = 1;
+  }
+
+  // the open queries go through one more sweep: open[] and the initial closed[] up, closed[] down
+  int nResolve = (int)open.size(), nByCount = 0;
+  if (!open.empty() && (stageMask & 2)) {
+    const Fginn32Work w = fginn32_work(g, n1, c->matchWork.p);
+    const int nu = (int)open.size();
+    std::vector<F32Closed> closed(nu, F32Closed{KEY_NONE, 0u, 0u});
+    if (!c->pos2.ensure((size_t)n2 * 16)) return MODSX_ERR_NOMEM;
+    MX_HIP(hipMemcpyAsync(c->pos2.p, pos2, (size_t)n2 * 16, hipMemcpyHostToDevice, c->stream));
+    MX_HIP(hipMemcpyAsync(w.open, open.data(), (size_t)nu * sizeof(F32Open), hipMemcpyHostToDevice, c->stream));
+    MX_HIP(hipMemcpyAsync(w.closed, closed.data(), (size_t)nu * sizeof(F32Closed), hipMemcpyHostToDevice, c->stream));
+    launch_fginn32_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p);
+    MX_HIP(hipMemcpyAsync(closed.data(), w.closed, (size_t)nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
+    MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
+    MX_HIP(hipGetLastError());
+    for (int u = 0; u < nu; u++) {
+      const F32Open &o = open[u];
+      const unsigned long long kt = closed[u].kterm;
+      if (kt == KEY_NONE) continue;                             // nothing ends the walk before the trains or the nn run out
+      const unsigned long long *k = &top4[(size_t)o.q * 4];
+      double ratio;
+      if (!ratio_passes(key_dist(k[0]), key_dist(kt), rsq, &ratio)) continue;      // it ends the walk by contradiction, reached or not
+      // it passes, so d >= d_pass, and every non-terminal train (d < d_pass) comes before it: its rank is 3 + cnt + 1 exactly
+      if ((long)closed[u].cnt + 4 <= nn - 1) { rec[o.q] = make_record(o.q, k, kt, ratio); has[o.q] = 1; }
+      else { stage[o.q] = 2; nByCount++; }                      // the nn run out first
+    }
+  }
+  for (int q = 0; q < n1; q++) if (has[q]) out.push_back(rec[q]);
+  if (tap && tap->stage) memcpy(tap->stage, stage.data(), n1);
+  if (tap && tap->counters) { tap->counters[0] = nResolve; tap->counters[1] = nByCount; tap->counters[2] = (int)out.size(); }
+  return MODSX_OK;
+}
+
+// rows from the host: checked here, uploaded, matched
+int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2, double ratioT,
+                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+  out.clear();
+  int rc = fginn32_check_args("modsx_match_fginn_f32", n1, n2, dim, ratioT, nn);
+  if (rc) return rc;
+  if (n1 == 0 || n2 == 0) return MODSX_OK;
+  const size_t f1 = (size_t)n1 * dim, f2 = (size_t)n2 * dim;
+  if (!fginn32_rows_ok(desc1, f1) || !fginn32_rows_ok(desc2, f2)) {
+    set_error("modsx_match_fginn_f32: rows must be finite with |x| <= 1e17");
+    return MODSX_ERR_ARG;
+  }
+  CtxBusy busy(c);
+  if (!c->descF[0].ensure(f1 * 4) || !c->descF[1].ensure(f2 * 4)) return MODSX_ERR_NOMEM;
+  MX_HIP(hipMemcpyAsync(c->descF[0].p, desc1, f1 * 4, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipMemcpyAsync(c->descF[1].p, desc2, f2 * 4, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable
+  return match_fginn32_device(c, (const float *)c->descF[0].p, n1, (const float *)c->descF[1].p, n2, dim, pos2, ratioT, contradDist, nn, out, tap);
+}
+
+// MatchFlannFGINN + DuplicateFiltering + LORANSACFiltering on caller-supplied regions: what match_pair leaves with the match stage
+// replaced.  pos2 = reproj_kp of the second list, as the reference takes it.  An empty side gives the zeroed result with H = -1.
+int match_regions_f32(modsx_ctx *c, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2, const float *desc2,
+                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res) {
+  memset(res, 0, sizeof *res);
+  for (int i = 0; i < 9; i++) res->H[i] = -1;
+  int rc = fginn32_check_args("modsx_match_regions_f32", n1, n2, dim, pp.match_ratio, pp.nn);
+  if (rc) return rc;
+  std::vector<double> pos2((size_t)n2 * 2);
+  for (int i = 0; i < n2; i++) { pos2[2 * (size_t)i] = regs2[i].reproj_kp.x; pos2[2 * (size_t)i + 1] = regs2[i].reproj_kp.y; }
+  std::vector<modsx_tentative> tents;
+  rc = match_fginn32_host(c, desc1, n1, desc2, n2, dim, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr);
+  if (rc) return rc;
+  res->n_regions1 = n1; res->n_regions2 = n2;
+  if (n1 == 0 || n2 == 0) return MODSX_OK;
+  RegList l1, l2;
+  l1.add(regs1, (size_t)n1); l2.add(regs2, (size_t)n2);
+  verify_tentatives(l1, l2, tents, pp, res);
+  return MODSX_OK;
+}
+
+}  // namespace mx
