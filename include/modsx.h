@@ -887,6 +887,52 @@ int modsx_save_regions(const char *path, const modsx_region_class *classes, int 
 int modsx_load_regions(const char *path, const char *det_name, const char *desc_name, modsx_region **regs, float **desc,
                        int *dim, char *found_det, char *found_desc);
 
+/* ---- Normalised patches and the LIOP descriptor -----------------------------------------------------------------------------
+ * DescribeRegions<FuncType> (synth-detection.hpp:169-255, called for LIOP at imagerepresentation.cpp:1615-1623) cuts a window
+ * of mrSize * s around every region, blurs it, resamples it to patchSize x patchSize, runs photometricallyNormalize
+ * (detectors/helpers.cpp:666-715) and hands the patch to the functor.  For SIFTDescriptor that is modsx_describe_regions; the
+ * entries below expose the patch itself and the LIOP functor.  patchSize must be 41, as everywhere in this library; mrSize,
+ * fast_extraction and photoNorm mean what they mean for modsx_describe_regions.  LIOP has no parameters: LIOPDescriptor builds
+ * vl_liopdesc_new_basic(patchSize) (matching/liopdesc.hpp:55-63: 4 neighbours, 6 spatial bins, radius 6, intensity threshold
+ * -(5 / 255)); the neighbours / bins / radius / threshold keys of a [LIOPDescriptor] section never reach VLFeat.
+ * Every entry: n < 0, patchSize != 41 or a null pointer is MODSX_ERR_ARG (nothing is launched); n == 0 succeeds and writes
+ * nothing.  The _device forms take a DEVICE pointer for the output (and, for modsx_liop_patches_device, the input), 4-byte
+ * aligned, dense rows; they return after the work has finished.  The entries that compute return n. */
+#define MODSX_LIOP_DIM 144
+#define MODSX_LIOP_PIXELS 673
+/* the patches DescribeRegions<> hands to its functor (synth-detection.hpp:214-238): patches [n][41][41] f32 */
+int modsx_extract_patches(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                          int fast_extraction, int photoNorm, float *patches);
+int modsx_extract_patches_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                 int patchSize, int fast_extraction, int photoNorm, void *dev_patches);
+/* vl_liopdesc_process (vlfeat/vl/liop.c:440-555) on n patches [n][41][41] f32 -> desc [n][144] f32, bit for bit what the
+ * reference's code gives, the order of equal intensities in its patch_sort (vl/qsort-def.h:126-165) included: the spatial bins
+ * are cut by rank, so that order decides the bin of pixels that tie across a cut.  Patch values must be finite (the reference's
+ * comparator, an f32 difference tested <= 0, is inconsistent on NaN and infinities: such rows give unspecified descriptors, no
+ * fault); -0 ties with +0; subnormal values are compared, not flushed.  The two samples of liop.c:513-516 that touch column /
+ * row 41 (pixels (34, 20) and (20, 34), weights exactly 0) read nothing outside the patch: what lies outside its 1681 floats
+ * counts as 0.0. */
+int modsx_liop_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc);
+int modsx_liop_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, void *dev_desc);
+/* DescribeRegions<LIOPDescriptor>(regions, image, liop, mrSize, patchSize, fast_extraction, photoNorm)
+ * (imagerepresentation.cpp:1615-1623): desc [n][144] f32 = modsx_liop_patches of modsx_extract_patches.  The patches stay on
+ * the device, in a per-context buffer of at most 64 MiB that the call fills and consumes in sub-batches. */
+int modsx_describe_regions_liop(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                int patchSize, int fast_extraction, int photoNorm, float *desc);
+int modsx_describe_regions_liop_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                       int patchSize, int fast_extraction, int photoNorm, void *dev_desc);
+/* host only: the tables of vl_liopdesc_new_basic(patchSize) (liop.c:346-395) -- pixels[i] = x + 41 y of measurement pixel i
+ * (raster order), sx / sy [i][4] = neighSamplesX / Y, built with libm as the reference builds them.  Fills the first `cap`
+ * pixels (any of the three pointers may be NULL) and returns their number, 673. */
+int modsx_liop_tables(int patchSize, int *pixels, double *sx, double *sy, int cap);
+/* debug: modsx_liop_patches (patches from the host) that also reports, per patch, path[i] = 0 when no group of equal
+ * intensities lay across a bin cut (any order by key is the reference's; perm is the stable one) or 1 when one did (perm is the
+ * reference's patch_sort permutation, replayed), and perm [n][673] = measurement pixel of every rank */
+int modsx_debug_liop(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc, int *path, int *perm);
+/* LIOP work of this context since modsx_create, cumulative (measurement hook): calls that launched, patches described, patches
+ * that took the exact path, sub-batches (launches of the LIOP kernel).  Fills out[0 .. min(n, 4) - 1], returns 4. */
+int modsx_liop_counters(modsx_ctx *ctx, long *out, int n);
+
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:

@@ -117,7 +117,10 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
            "modsx_debug_detect_scalespace_batch",
            "modsx_match_fginn_f32", "modsx_match_fginn_f32_device", "modsx_match_regions_f32", "modsx_debug_match_fginn_f32",
-           "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass"]
+           "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass",
+           "modsx_extract_patches", "modsx_extract_patches_device", "modsx_liop_patches", "modsx_liop_patches_device",
+           "modsx_describe_regions_liop", "modsx_describe_regions_liop_device", "modsx_liop_tables", "modsx_debug_liop",
+           "modsx_liop_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -132,6 +135,9 @@ DESCRIBE_COUNTERS = ("calls", "chunks", "max_chunks", "chunks_mid_image", "chunk
 DETECT_COUNTERS = ("blur_th16", "blur_th32") + tuple("blur_r%d" % r for r in range(1, 9)) + (
     "hessian", "resize", "scan_per_octave", "scan_per_level", "nms_flushes", "last_jobs", "last_tiles", "last_accepted",
     "second_copies")
+# include/modsx.h: modsx_liop_counters, in its order
+LIOP_COUNTERS = ("calls", "regions", "exact_path", "sub_batches")
+LIOP_DIM, LIOP_PIXELS = 144, 673      # include/modsx.h: MODSX_LIOP_DIM, MODSX_LIOP_PIXELS
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -240,6 +246,15 @@ def lib():
         L.modsx_debug_fginn32_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_fginn32_dpass.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_debug_fginn32_last_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_extract_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_extract_patches_device.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_describe_regions_liop.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_describe_regions_liop_device.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_liop_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_liop_patches_device.argtypes = L.modsx_liop_patches.argtypes
+        L.modsx_liop_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_liop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_liop_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -248,6 +263,27 @@ def lib():
 
 def _err():
     return lib().modsx_last_error().decode()
+
+
+def _liop_patch_rows(patches):
+    patches = np.ascontiguousarray(patches, np.float32)
+    if patches.ndim == 2 and patches.shape == (41, 41):
+        patches = patches[None]
+    if patches.shape[1:] not in ((41, 41), (1681,)):
+        raise ValueError("LIOP patches are [n][41][41] float32")
+    return patches
+
+
+def liop_tables(patch_size=41):
+    """(pixels [673] int32, sx [673][4] float64, sy [673][4] float64): the measurement pixels (x + 41 y, raster order) and
+    neighbour sample coordinates of vl_liopdesc_new_basic(41), as the library builds them on the host (no device needed)."""
+    n = lib().modsx_liop_tables(int(patch_size), None, None, None, 0)
+    if n < 0:
+        raise RuntimeError("liop_tables failed: " + _err())
+    pixels, sx, sy = np.zeros(n, np.int32), np.zeros((n, 4), np.float64), np.zeros((n, 4), np.float64)
+    got = lib().modsx_liop_tables(int(patch_size), _p(pixels), _p(sx), _p(sy), n)
+    assert got == n, (got, n)
+    return pixels, sx, sy
 
 
 def _p(a):
@@ -689,6 +725,63 @@ class Context(object):
                                             patch_size, fast, photo_norm, desc_type, C.c_double(max_bin), _p(desc)),
                "describe_regions")
         return desc
+
+    # ---- normalised patches and LIOP (engine_liop.hip) ----
+    def extract_patches(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, out_ptr=None):
+        """The patches DescribeRegions<> hands to its functor: [n][41][41] float32.  out_ptr: a device pointer that receives them
+        instead (4-byte aligned, n * 1681 floats); the call then returns None."""
+        regs = np.ascontiguousarray(regs, REGION)
+        if out_ptr is not None:
+            _check(lib().modsx_extract_patches_device(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                      int(patch_size), int(fast), int(photo_norm), C.c_void_p(out_ptr)),
+                   "extract_patches_device")
+            return None
+        out = np.zeros((len(regs), 41, 41), np.float32)
+        _check(lib().modsx_extract_patches(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size), int(patch_size),
+                                           int(fast), int(photo_norm), _p(out)), "extract_patches")
+        return out
+
+    def liop_patches(self, patches, patch_size=41):
+        """vl_liopdesc_process on [n][41][41] float32 patches (finite values) -> [n][144] float32."""
+        patches = _liop_patch_rows(patches)
+        desc = np.zeros((len(patches), LIOP_DIM), np.float32)
+        _check(lib().modsx_liop_patches(self._c(), _p(patches), len(patches), int(patch_size), _p(desc)), "liop_patches")
+        return desc
+
+    def liop_patches_device(self, patches_ptr, n, desc_ptr, patch_size=41):
+        """The same on dense [n][1681] float32 rows in HBM -> [n][144] float32 rows in HBM (device pointers, 4-byte aligned)."""
+        _check(lib().modsx_liop_patches_device(self._c(), C.c_void_p(patches_ptr), int(n), int(patch_size), C.c_void_p(desc_ptr)),
+               "liop_patches_device")
+
+    def describe_regions_liop(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, out_ptr=None):
+        """DescribeRegions<LIOPDescriptor>: [n][144] float32 (out_ptr: into that device pointer instead, returns None)."""
+        regs = np.ascontiguousarray(regs, REGION)
+        if out_ptr is not None:
+            _check(lib().modsx_describe_regions_liop_device(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                            int(patch_size), int(fast), int(photo_norm), C.c_void_p(out_ptr)),
+                   "describe_regions_liop_device")
+            return None
+        desc = np.zeros((len(regs), LIOP_DIM), np.float32)
+        _check(lib().modsx_describe_regions_liop(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                 int(patch_size), int(fast), int(photo_norm), _p(desc)), "describe_regions_liop")
+        return desc
+
+    def debug_liop(self, patches, patch_size=41):
+        """dict(desc [n][144], path [n] (0: no tie group across a bin cut, 1: the reference's quicksort was replayed), perm [n][673]
+        = measurement pixel of every rank, the permutation the spatial bins were cut from)."""
+        patches = _liop_patch_rows(patches)
+        n = len(patches)
+        desc = np.zeros((n, LIOP_DIM), np.float32)
+        path, perm = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), LIOP_PIXELS), np.int32)
+        _check(lib().modsx_debug_liop(self._c(), _p(patches), n, int(patch_size), _p(desc), _p(path), _p(perm)), "debug_liop")
+        return dict(desc=desc, path=path[:n], perm=perm[:n])
+
+    def liop_counters(self):
+        """dict of LIOP_COUNTERS: LIOP work of this context since it was created (cumulative)."""
+        v = (C.c_long * len(LIOP_COUNTERS))()
+        n = _check(lib().modsx_liop_counters(self._c(), v, len(LIOP_COUNTERS)), "liop_counters")
+        assert n == len(LIOP_COUNTERS), n
+        return dict(zip(LIOP_COUNTERS, (int(x) for x in v)))
 
     def describe_counters(self):
         """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative)."""

@@ -1486,6 +1486,76 @@ int modsx_profile(modsx_ctx *ctx, int enable) {
   return MODSX_OK;
 }
 
+// ---- normalised patches and LIOP (engine_liop.hip) ----
+#define LIOP_ARGS(fn, bad)                                                                                       \
+  do {                                                                                                           \
+    if (n < 0 || (bad)) { mx::set_error(fn ": bad argument"); return MODSX_ERR_ARG; }                            \
+    if (patchSize != 41) { mx::set_error(fn ": patchSize must be 41"); return MODSX_ERR_ARG; }                   \
+  } while (0)
+int modsx_extract_patches(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                          int fast_extraction, int photoNorm, float *patches) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_extract_patches", !regs || !patches);
+  hipSetDevice(ctx->dev);
+  const int rc = extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, patches, false);
+  return rc ? rc : n;
+}
+int modsx_extract_patches_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                 int patchSize, int fast_extraction, int photoNorm, void *dev_patches) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_extract_patches_device", !regs || !dev_patches || ((uintptr_t)dev_patches & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_patches, true);
+  return rc ? rc : n;
+}
+int modsx_liop_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc) {
+  NEED(ctx);
+  LIOP_ARGS("modsx_liop_patches", !patches || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = liop_patches(ctx, patches, n, patchSize, desc, false, nullptr, nullptr);
+  return rc ? rc : n;
+}
+int modsx_liop_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, void *dev_desc) {
+  NEED(ctx);
+  LIOP_ARGS("modsx_liop_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = liop_patches(ctx, (const float *)dev_patches, n, patchSize, (float *)dev_desc, true, nullptr, nullptr);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_liop(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                int patchSize, int fast_extraction, int photoNorm, float *desc) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_liop", !regs || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_liop_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                       int patchSize, int fast_extraction, int photoNorm, void *dev_desc) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_liop_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_liop_tables(int patchSize, int *pixels, double *sx, double *sy, int cap) {
+  if (cap < 0) { mx::set_error("modsx_liop_tables: bad argument"); return MODSX_ERR_ARG; }
+  return liop_tables(patchSize, pixels, sx, sy, cap);
+}
+int modsx_debug_liop(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc, int *path, int *perm) {
+  NEED(ctx);
+  LIOP_ARGS("modsx_debug_liop", !patches || !desc || !path || !perm);
+  hipSetDevice(ctx->dev);
+  const int rc = liop_patches(ctx, patches, n, patchSize, desc, false, path, perm);
+  return rc ? rc : n;
+}
+int modsx_liop_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_liop_counters: bad argument"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n && q < 4; q++) out[q] = ctx->liopCounters[q];
+  return 4;
+}
+
 int modsx_kernel_stats(modsx_ctx *ctx, double *ms, double *work, long *launches, int n) {
   NEED(ctx); NEED(ms); NEED(work); NEED(launches);
   prof_collect(ctx);

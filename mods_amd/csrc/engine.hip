@@ -400,6 +400,7 @@ void ctx_destroy(modsx_ctx *c) {
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) for (int sd = 0; sd < 2; sd++) c->descCls[d][t][sd].release();
   for (int t = 0; t < 4; t++) c->halfDesc[t].release();
   c->candSort.release(); c->candOut.release();
+  c->liopTab.release(); c->liopPatches.release(); c->liopOut.release(); c->liopDbg.release(); c->liopCnt.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();
   hipFree(c->dSmmMask); hipFree(c->dOriMask); hipFree(c->dOriIdx); hipFree(c->dSiftMask); hipFree(c->dSiftMaskIdx); hipFree(c->dAtan); hipFree(c->dOriBinTab); hipFree(c->dSiftOTab); hipFree(c->dSiftBins);
@@ -675,7 +676,7 @@ void reproject_certain_drop(const modsx_region *regs, int n, const double *H, in
 // One planned chunk of describe_batch on the device: its blob staged through pinned slot `slot` (two in turn: the copy of chunk k
 // may still be in flight while chunk k + 1 is being prepared), then the launch set.
 static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot, HostMark &hm, int photoNorm, const DescSet &ds,
-                                 double maxBin, const DescOut &outs) {
+                                 double maxBin, const DescOut &outs, const DescTail *tail) {
   hipStream_t s = c->stream;
   const size_t nj = cp.jobs.size();
   const int nS = cp.pfxSample.back(), nR = cp.pfxRow.back(), nC = cp.pfxCol.back(), nRL = cp.pfxRowL.back(), nCL = cp.pfxColL.back();
@@ -722,6 +723,8 @@ static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot
     launch_blur_cols(s, btC, nCL, dTaps, dNeed, (float *)c->scratchB.p, (float *)c->scratchC.p);
     launch_patch_blur(s, dj, dPfxC, tjC, nC, dTaps, dNeed, (float *)c->scratchB.p,
                       (float *)c->scratchC.p, 1); }
+  // the patch-out callers (engine_liop.hip): the normalised patches of the chunk's jobs instead of their SIFT descriptors
+  if (tail) return tail->run(c, tail->self, dj, (int)nj, (const float *)c->scratchC.p, dNeed, dCoord, photoNorm);
   ProfScope psd(c, K_DESCRIBE, (double)nj * 128 * ds.n);
   launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
                   c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
@@ -731,10 +734,10 @@ static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot
 
 // DescribeRegions<SIFTDescriptor>, synth-detection.hpp:169-255, for a batch.  Descriptors stay in HBM
 // (c->descF[i], c->descU8[i]); descHost[i] (optional) receives the f32 copy.
-int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *regs,
-                   double mrSize, int patchSize, int fast, int photoNorm, int descType, double maxBin,
-                   float *const *descHost, float *const *devF, uint8_t *const *devU8, const DescSet *ds,
-                   uint8_t *const *const *devU8x) {
+static int describe_batch_impl(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *regs,
+                               double mrSize, int patchSize, int fast, int photoNorm, int descType, double maxBin,
+                               float *const *descHost, float *const *devF, uint8_t *const *devU8, const DescSet *ds,
+                               uint8_t *const *const *devU8x, const DescTail *tail) {
   if (patchSize != 41) { set_error("descriptor patchSize must be 41"); return MODSX_ERR_ARG; }
   DescSet one;
   if (!ds) { one.n = 1; one.type[0] = descType; ds = &one; }
@@ -750,7 +753,7 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
   const size_t ARENA_FLOATS = std::max<size_t>(arenaMB, 16) << 18;  // MiB -> floats
   DescOut outs;
   memset(&outs, 0, sizeof outs);
-  for (int i = 0; i < n; i++) {
+  for (int i = 0; i < n && !tail; i++) {
     const size_t nr = regs[i].size();
     float *outF = devF ? devF[i] : nullptr;
     uint8_t *outU8 = devU8 ? devU8[i] : nullptr;
@@ -777,7 +780,7 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
     const int prc = describe_plan_chunk(batch, cur, ARENA_FLOATS, cp, hm);
     for (int q = 0; q < DC_N; q++) c->descCnt[q] += cp.cnt[q];
     if (prc) return prc;
-    rc = launch_describe_chunk(c, cp, chunkNo & 1, hm, photoNorm, *ds, maxBin, outs);
+    rc = launch_describe_chunk(c, cp, chunkNo & 1, hm, photoNorm, *ds, maxBin, outs, tail);
     if (rc) return rc;
     cur = cp.next;
   }
@@ -786,7 +789,7 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
   MX_HIP(ctx_sync(c));   // callers read the descriptor buffers and reuse the staging blobs
   hm.mark("desc wait");
   c->descEvPending[0] = c->descEvPending[1] = false;
-  if (descHost) {
+  if (descHost && !tail) {
     bool any = false;
     for (int i = 0; i < n; i++)
       if (descHost[i] && !regs[i].empty()) {
@@ -797,6 +800,22 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
   }
   MX_HIP(hipGetLastError());
   return MODSX_OK;
+}
+
+int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const std::vector<modsx_region> *regs,
+                   double mrSize, int patchSize, int fast, int photoNorm, int descType, double maxBin,
+                   float *const *descHost, float *const *devF, uint8_t *const *devU8, const DescSet *ds,
+                   uint8_t *const *const *devU8x) {
+  return describe_batch_impl(c, imgs, n, regs, mrSize, patchSize, fast, photoNorm, descType, maxBin, descHost, devF, devU8, ds, devU8x,
+                             nullptr);
+}
+// one image's regions through the same windows, planner and launch sets, with `tail` in place of k_describe; returns after the
+// stream has drained
+int describe_batch_tail(modsx_ctx *c, const modsx_image *img, const std::vector<modsx_region> &regs, double mrSize, int patchSize,
+                        int fast, int photoNorm, const DescTail &tail) {
+  const modsx_image *imgs[1] = {img};
+  return describe_batch_impl(c, imgs, 1, &regs, mrSize, patchSize, fast, photoNorm, MODSX_DESC_ROOT_SIFT, 0.2, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, &tail);
 }
 
 // the host half of the matcher: per-query result rows -> TentativeCorrespExt records (matching.cpp:435-457)

@@ -341,6 +341,16 @@ Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work);
 void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, int n1, const float *d2, int n2, void *work,
                          void *flagAndTop4, hipEvent_t *ev = nullptr);
 void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work);
+// LIOP (kernels_liop.hip).  One neighbour sample of a measurement pixel: floor and fraction of neighSamplesX / Y (liop.c:376-395,
+// 503-507), built by the host with libm (engine_liop.hip: liop_tables)
+struct LiopSample { double wx, wy; int ix, iy; };
+static_assert(sizeof(LiopSample) == 24, "sample table entries are 24 bytes");
+void launch_liop(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const unsigned short *pixels,
+                 const LiopSample *samples, unsigned *exactCount, int *dbgPath, int *dbgPerm);
+// the patch-out form of k_describe (kernels_describe.hip): [slot][1681] f32, slot = outIdx (patchByOutIdx) or the job's index
+void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
+                           const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
+                           int patchByOutIdx);
 
 }  // namespace mx
 
@@ -428,6 +438,10 @@ struct modsx_ctx {
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
   double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search: packing, k_f32_topk + k_f32_merge
+  // LIOP (engine_liop.hip): the measurement pixels + sample table (built at the first LIOP call), the patches of one sub-batch
+  // (at most 64 MiB), descriptors / patches / debug rows on their way to the host, the exact-path counter word
+  mx::DevBuf liopTab, liopPatches, liopOut, liopDbg, liopCnt;
+  long liopCounters[4] = {0, 0, 0, 0};   // modsx_liop_counters: calls, regions, regions on the exact path, sub-batches
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

@@ -61,6 +61,24 @@ int describe_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const st
                    double mrSize, int patchSize, int fast, int photoNorm, int descType, double maxBin,
                    float *const *descHost, float *const *devF, uint8_t *const *devU8, const DescSet *ds = nullptr,
                    uint8_t *const *const *devU8x = nullptr);
+// What follows a chunk's sampling and blur launches in place of k_describe (engine_liop.hip): run() gets the chunk's jobs and
+// tables on the device and launches on c->stream.  describe_batch_tail is describe_batch for one image's regions with such a
+// tail: the same windows, the same chunk planner, the same launch sets in front of it.
+struct DescTail {
+  int (*run)(modsx_ctx *c, void *self, const DescJob *jobs, int n, const float *grid, const int *needTab, const float *coordTab,
+             int photoNorm);
+  void *self;
+};
+int describe_batch_tail(modsx_ctx *c, const modsx_image *img, const std::vector<modsx_region> &regs, double mrSize, int patchSize,
+                        int fast, int photoNorm, const DescTail &tail);
+// LIOP and the normalised patches (engine_liop.hip).  out / patches: host pointers, or device pointers (4-byte aligned) when
+// onDevice; dbgPath [n] / dbgPerm [n][673] (host, optional): modsx_debug_liop
+int liop_tables(int patchSize, int *pixels, double *sx, double *sy, int cap);
+int extract_patches(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
+                    int photoNorm, float *patches, bool onDevice);
+int liop_patches(modsx_ctx *c, const float *patches, int n, int patchSize, float *desc, bool onDevice, int *dbgPath, int *dbgPerm);
+int describe_regions_liop(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
+                          int photoNorm, float *desc, bool onDevice);
 int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt, double phi_base, double InitSigma,
                 int doBlur, modsx_view *par, int cap, modsx_view *prev, int *nprev, int cap_prev);
 // slot < 0: the view is a fresh allocation owned by the returned image (public API).  slot in [0, MAXB): the view lives in

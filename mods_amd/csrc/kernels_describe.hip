@@ -665,12 +665,19 @@ struct SiftConst {
 #endif
 constexpr int DR = MODSX_DESCRIBE_REGIONS;
 
+// Two instantiations of one body.  k_describe<false> is the SIFT kernel.  k_describe<true> is the patch-out form: the same front
+// end -- resampling, photometricallyNormalize -- which stores the normalised 41 x 41 patch (what DescribeRegions<> hands to its
+// functor, synth-detection.hpp:214-238) to patchOut[slot][1681] and returns; slot = the region's outIdx (patchByOutIdx) or its
+// index in `jobs`.  Everything behind that store is dead code of that instantiation, and the tables it reads may be null.
+// (The body is the kernel itself, not a function both kernels call: inlined from a function, k_describe<false> compiled to 71
+// VGPRs instead of 70.)
+template <bool PATCH_OUT>
 __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
                                                   const int *needTab, const float *coordTab,
                                                   const float *mask, const unsigned short *maskIdx,
                                                   const float *oTab, const int *binTab, const double *wTab,
                                                   SiftConst sc, int photoNorm, int descTypes, int nOut, double maxBin,
-                                                  DescOut outs) {
+                                                  DescOut outs, float *patchOut, int patchByOutIdx) {
   const int tidw = threadIdx.x;                                    // thread of the workgroup
   const int reg = __builtin_amdgcn_readfirstlane(tidw >> 7);       // region of the workgroup (a wavefront is inside one region)
   const int tid = tidw & 127;                                      // thread of the region
@@ -708,7 +715,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   if (tidw == 0) spad_[MODSX_DESCRIBE_PAD - 1] = 1;
 #endif
   const DescJob jb = jobs[k];
-  if (tidw < PS) {
+  if (!PATCH_OUT && tidw < PS) {
     const float w0 = (float)wTab[tidw], w1 = (float)wTab[PS + tidw];   // const float wr0 = w0[r] (siftdesc.cpp:79-81)
     const int q = tidw >> 3, b0 = min(max(q - 1, 0), 3), b1 = min(q, 3);   // a bin outside 0..3 comes with weight 0
     const float wm = w0 > 0 ? (w1 > 0 ? fminf(w0, w1) : w0) : (w1 > 0 ? w1 : 1.f);
@@ -854,6 +861,13 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
       }
     }
     __syncthreads();
+  }
+  if constexpr (PATCH_OUT) {
+    if (alive) {
+      float *dst = patchOut + (size_t)(patchByOutIdx ? jb.outIdx : kreal) * NPX;
+      for (int i = tid; i < NPX; i += 128) dst[i] = patch[i];
+    }
+    return;
   }
   // -- gradients, orientation, per-pixel weights (siftdesc.cpp:346-379, 73-131)
   float ov[PER_T], vv[PER_T];   // o and val = mask * |grad| of the thread's pixels p = tid + 128 k
@@ -1169,9 +1183,21 @@ void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *im
   if (n <= 0) return;
   SiftConst sc;
   sc.nmask = nmask;
-  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
+  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<false>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
                      wts, sc,
-                     photoNorm, descTypes, nOut, maxBin, outs);
+                     photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0);
+}
+void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
+                           const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
+                           int patchByOutIdx) {
+  if (n <= 0) return;
+  SiftConst sc;
+  sc.nmask = nmask;
+  DescOut none;
+  memset(&none, 0, sizeof none);
+  hipLaunchKernelGGL(k_describe<true>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab,
+                     (const float *)nullptr, maskIdx, (const float *)nullptr, (const int *)nullptr, (const double *)nullptr, sc, photoNorm, 0, 0, 0.0,
+                     none, patchOut, patchByOutIdx);
 }
 
 }  // namespace mx
