@@ -933,6 +933,45 @@ int modsx_debug_liop(modsx_ctx *ctx, const float *patches, int n, int patchSize,
  * that took the exact path, sub-batches (launches of the LIOP kernel).  Fills out[0 .. min(n, 4) - 1], returns 4. */
 int modsx_liop_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- DSP-SIFT: pooled raw SIFT histograms and the f32 SIFT norm --------------------------------------------------------------
+ * The "DSPSIFT" branch of the reference (domain-size pooling, imagerepresentation.cpp:1547-1598) describes every region at
+ * numScales + 1 measurement sizes with SIFTDescriptor{useRootSIFT = false, doNorm = false}, adds the raw 128-bin histograms in
+ * f32 in scale order, and applies SIFTnorm(std::vector<float>&) (matching/siftdesc.cpp:263-278) -- the f32 overload, not the f64
+ * norm behind modsx_describe_regions.  The result is a row of 128 integers 0..255 held in f32, which the int8 matcher
+ * (modsx_match_fginn), modsx_match_regions_f32, the key file and modsx_rep_append take as they are.  The entries below give the two halves and the whole.
+ * DSP-SIFT is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder, of modsx_rep or of the
+ * sharded path.  patchSize must be 41; mrSize, fast_extraction and photoNorm mean what they mean for modsx_describe_regions.
+ * Every entry: n < 0, patchSize != 41, a null pointer, a measurement size that is not finite and positive, or a region whose
+ * window modsx_describe_regions would refuse (a blur of more than 512 taps) is MODSX_ERR_ARG with a message, before anything is
+ * launched; n == 0 succeeds and writes nothing.  The _device forms take DEVICE pointers, 4-byte aligned, dense rows; they
+ * return after the work has finished.  The entries that compute return n. */
+/* the output of the doNorm = false functor (siftdesc.cpp:436-440): hist [n][128] f32 = (float) of samplePatch's f64 bins */
+int modsx_describe_regions_raw(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                               int fast_extraction, int photoNorm, float *hist);
+int modsx_describe_regions_raw_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                      int patchSize, int fast_extraction, int photoNorm, void *dev_hist);
+/* SIFTnorm(std::vector<float>&) with par.maxBinValue = maxBinValue on rows [n][128] f32 -> out [n][128] f32 holding 0..255, bit
+ * for bit: the length is a serial f32 sum of the 32 group sums ((v0^2 + v1^2) + v2^2) + v3^2, its square root f32, the factor
+ * (float)(1.0 / (double)len); values above maxBinValue (compared in f64) become (float)maxBinValue and the row is normalised
+ * again; b = (int)((double)(512.0f * v) + 0.5) clamped to 0..255.  For callers that pool histograms of their own.  out may be
+ * rows.  Rows must be finite: a row of zeros gives zeros (as the reference does on x86-64, where its NaN values convert to
+ * INT_MIN); NaN and infinities give unspecified values, no fault. */
+int modsx_sift_norm_rows(modsx_ctx *ctx, const float *rows, int n, double maxBinValue, float *out);
+int modsx_sift_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, double maxBinValue, void *dev_out);
+/* the whole branch: pass k = 0 .. numScales at mrSize_k = mrSize * (startCoef + k * (endCoef - startCoef) / numScales), evaluated
+ * in f64 as written, pooled in f32 in that order, then the norm: desc [n][128] f32 holding 0..255.  numScales outside 1..64 is
+ * MODSX_ERR_ARG (the reference divides by zero at 0), and so is any mrSize_k that is not finite and positive; all scales are
+ * checked before the first runs. */
+int modsx_describe_regions_dspsift(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                   int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef, double endCoef,
+                                   double maxBinValue, float *desc);
+int modsx_describe_regions_dspsift_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                          int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef,
+                                          double endCoef, double maxBinValue, void *dev_desc);
+/* DSP-SIFT work of this context since modsx_create, cumulative (measurement hook): modsx_describe_regions_dspsift calls that
+ * launched, regions described, scale passes launched.  Fills out[0 .. min(n, 3) - 1], returns 3. */
+int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n);
+
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:

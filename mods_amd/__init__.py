@@ -120,7 +120,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass",
            "modsx_extract_patches", "modsx_extract_patches_device", "modsx_liop_patches", "modsx_liop_patches_device",
            "modsx_describe_regions_liop", "modsx_describe_regions_liop_device", "modsx_liop_tables", "modsx_debug_liop",
-           "modsx_liop_counters"]
+           "modsx_liop_counters",
+           "modsx_describe_regions_raw", "modsx_describe_regions_raw_device", "modsx_sift_norm_rows", "modsx_sift_norm_rows_device",
+           "modsx_describe_regions_dspsift", "modsx_describe_regions_dspsift_device", "modsx_dsp_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -138,6 +140,8 @@ DETECT_COUNTERS = ("blur_th16", "blur_th32") + tuple("blur_r%d" % r for r in ran
 # include/modsx.h: modsx_liop_counters, in its order
 LIOP_COUNTERS = ("calls", "regions", "exact_path", "sub_batches")
 LIOP_DIM, LIOP_PIXELS = 144, 673      # include/modsx.h: MODSX_LIOP_DIM, MODSX_LIOP_PIXELS
+# include/modsx.h: modsx_dsp_counters, in its order
+DSP_COUNTERS = ("calls", "regions", "scale_passes")
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -255,6 +259,14 @@ def lib():
         L.modsx_liop_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_liop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_liop_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_describe_regions_raw.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_describe_regions_raw_device.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_sift_norm_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_sift_norm_rows_device.argtypes = L.modsx_sift_norm_rows.argtypes
+        L.modsx_describe_regions_dspsift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        L.modsx_describe_regions_dspsift_device.argtypes = L.modsx_describe_regions_dspsift.argtypes
+        L.modsx_dsp_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -782,6 +794,57 @@ class Context(object):
         n = _check(lib().modsx_liop_counters(self._c(), v, len(LIOP_COUNTERS)), "liop_counters")
         assert n == len(LIOP_COUNTERS), n
         return dict(zip(LIOP_COUNTERS, (int(x) for x in v)))
+
+    # ---- raw SIFT histograms, the f32 SIFT norm and DSP-SIFT (engine_dsp.hip) ----
+    def describe_regions_raw(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, out_ptr=None):
+        """DescribeRegions<SIFTDescriptor{doNorm = false}>: the raw histograms, [n][128] float32 (out_ptr: into that device
+        pointer instead, 4-byte aligned; returns None)."""
+        regs = np.ascontiguousarray(regs, REGION)
+        if out_ptr is not None:
+            _check(lib().modsx_describe_regions_raw_device(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                           int(patch_size), int(fast), int(photo_norm), C.c_void_p(out_ptr)),
+                   "describe_regions_raw_device")
+            return None
+        hist = np.zeros((len(regs), 128), np.float32)
+        _check(lib().modsx_describe_regions_raw(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                int(patch_size), int(fast), int(photo_norm), _p(hist)), "describe_regions_raw")
+        return hist
+
+    def sift_norm_rows(self, rows, max_bin=0.2):
+        """SIFTnorm(std::vector<float>&) on [n][128] float32 rows (finite values) -> [n][128] float32 holding 0..255."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != 128:
+            raise ValueError("SIFT rows are [n][128] float32")
+        out = np.zeros(rows.shape, np.float32)
+        _check(lib().modsx_sift_norm_rows(self._c(), _p(rows), len(rows), C.c_double(max_bin), _p(out)), "sift_norm_rows")
+        return out
+
+    def sift_norm_rows_device(self, rows_ptr, n, out_ptr, max_bin=0.2):
+        """The same on dense [n][128] float32 rows in HBM (device pointers, 4-byte aligned; out_ptr may be rows_ptr)."""
+        _check(lib().modsx_sift_norm_rows_device(self._c(), C.c_void_p(rows_ptr), int(n), C.c_double(max_bin), C.c_void_p(out_ptr)),
+               "sift_norm_rows_device")
+
+    def describe_regions_dspsift(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, num_scales=3, start_coef=0.5,
+                                 end_coef=1.5, max_bin=0.2, out_ptr=None):
+        """The reference's "DSPSIFT" branch: raw SIFT histograms at num_scales + 1 measurement sizes, pooled in f32, then the f32
+        SIFT norm: [n][128] float32 holding 0..255 (out_ptr: into that device pointer instead, returns None).  The defaults are
+        DomainSizePolingParams' (matching/siftdesc.h:21-31)."""
+        regs = np.ascontiguousarray(regs, REGION)
+        args = (self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size), int(patch_size), int(fast), int(photo_norm),
+                int(num_scales), C.c_double(start_coef), C.c_double(end_coef), C.c_double(max_bin))
+        if out_ptr is not None:
+            _check(lib().modsx_describe_regions_dspsift_device(*args, C.c_void_p(out_ptr)), "describe_regions_dspsift_device")
+            return None
+        desc = np.zeros((len(regs), 128), np.float32)
+        _check(lib().modsx_describe_regions_dspsift(*args, _p(desc)), "describe_regions_dspsift")
+        return desc
+
+    def dsp_counters(self):
+        """dict of DSP_COUNTERS: DSP-SIFT work of this context since it was created (cumulative)."""
+        v = (C.c_long * len(DSP_COUNTERS))()
+        n = _check(lib().modsx_dsp_counters(self._c(), v, len(DSP_COUNTERS)), "dsp_counters")
+        assert n == len(DSP_COUNTERS), n
+        return dict(zip(DSP_COUNTERS, (int(x) for x in v)))
 
     def describe_counters(self):
         """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative)."""

@@ -1556,6 +1556,67 @@ int modsx_liop_counters(modsx_ctx *ctx, long *out, int n) {
   return 4;
 }
 
+// ---- raw SIFT histograms, the f32 SIFT norm and DSP-SIFT (engine_dsp.hip) ----
+int modsx_describe_regions_raw(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                               int fast_extraction, int photoNorm, float *hist) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_raw", !regs || !hist);
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, hist, false);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_raw_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                      int patchSize, int fast_extraction, int photoNorm, void *dev_hist) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_raw_device", !regs || !dev_hist || ((uintptr_t)dev_hist & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_hist, true);
+  return rc ? rc : n;
+}
+int modsx_sift_norm_rows(modsx_ctx *ctx, const float *rows, int n, double maxBinValue, float *out) {
+  NEED(ctx);
+  if (n < 0 || !rows || !out) { mx::set_error("modsx_sift_norm_rows: bad argument"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  const int rc = sift_norm_rows(ctx, rows, n, maxBinValue, out, false);
+  return rc ? rc : n;
+}
+int modsx_sift_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, double maxBinValue, void *dev_out) {
+  NEED(ctx);
+  if (n < 0 || !dev_rows || !dev_out || (((uintptr_t)dev_rows | (uintptr_t)dev_out) & 3)) {
+    mx::set_error("modsx_sift_norm_rows_device: bad argument");
+    return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  const int rc = sift_norm_rows(ctx, (const float *)dev_rows, n, maxBinValue, (float *)dev_out, true);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_dspsift(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                   int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef, double endCoef,
+                                   double maxBinValue, float *desc) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_dspsift", !regs || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
+                                          endCoef, maxBinValue, desc, false);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_dspsift_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                          int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef,
+                                          double endCoef, double maxBinValue, void *dev_desc) {
+  NEED(ctx); NEED(img);
+  LIOP_ARGS("modsx_describe_regions_dspsift_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
+                                          endCoef, maxBinValue, (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_dsp_counters: bad argument"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->dspCounters[q];
+  return 3;
+}
+
 int modsx_kernel_stats(modsx_ctx *ctx, double *ms, double *work, long *launches, int n) {
   NEED(ctx); NEED(ms); NEED(work); NEED(launches);
   prof_collect(ctx);

@@ -351,6 +351,13 @@ void launch_liop(hipStream_t s, const float *patches, int n, float *out, const D
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
                            int patchByOutIdx);
+// the raw-histogram form of k_describe: raw[outIdx][128] f32 = (float)vec[i] of the doNorm = false functor, stored (accumulate = 0)
+// or added in f32 to what is there (accumulate = 1)
+void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
+                         const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab,
+                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate);
+// SIFTnorm(std::vector<float>&) over [n][128] f32 rows (kernels_dsp.hip); out may be rows; 4-byte alignment suffices
+void launch_sift_norm_f32(hipStream_t s, const float *rows, int n, double maxBin, float *out);
 
 }  // namespace mx
 
@@ -442,6 +449,9 @@ struct modsx_ctx {
   // (at most 64 MiB), descriptors / patches / debug rows on their way to the host, the exact-path counter word
   mx::DevBuf liopTab, liopPatches, liopOut, liopDbg, liopCnt;
   long liopCounters[4] = {0, 0, 0, 0};   // modsx_liop_counters: calls, regions, regions on the exact path, sub-batches
+  // DSP-SIFT (engine_dsp.hip): rows on their way from / to the host
+  mx::DevBuf dspRows;
+  long dspCounters[3] = {0, 0, 0};       // modsx_dsp_counters: calls, regions, scale passes launched
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

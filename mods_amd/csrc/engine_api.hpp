@@ -79,6 +79,14 @@ int extract_patches(modsx_ctx *c, const modsx_image *img, const modsx_region *re
 int liop_patches(modsx_ctx *c, const float *patches, int n, int patchSize, float *desc, bool onDevice, int *dbgPath, int *dbgPerm);
 int describe_regions_liop(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                           int photoNorm, float *desc, bool onDevice);
+// Raw SIFT histograms, the f32 SIFT norm and DSP-SIFT (engine_dsp.hip).  hist / rows / out / desc: [n][128] f32, host pointers, or
+// device pointers (4-byte aligned) when onDevice
+int describe_regions_raw(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
+                         int photoNorm, float *hist, bool onDevice);
+int sift_norm_rows(modsx_ctx *c, const float *rows, int n, double maxBinValue, float *out, bool onDevice);
+int describe_regions_dspsift(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                             int fast, int photoNorm, int numScales, double startCoef, double endCoef, double maxBinValue, float *desc,
+                             bool onDevice);
 int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt, double phi_base, double InitSigma,
                 int doBlur, modsx_view *par, int cap, modsx_view *prev, int *nprev, int cap_prev);
 // slot < 0: the view is a fresh allocation owned by the returned image (public API).  slot in [0, MAXB): the view lives in

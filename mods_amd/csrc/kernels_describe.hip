@@ -665,19 +665,23 @@ struct SiftConst {
 #endif
 constexpr int DR = MODSX_DESCRIBE_REGIONS;
 
-// Two instantiations of one body.  k_describe<false> is the SIFT kernel.  k_describe<true> is the patch-out form: the same front
-// end -- resampling, photometricallyNormalize -- which stores the normalised 41 x 41 patch (what DescribeRegions<> hands to its
-// functor, synth-detection.hpp:214-238) to patchOut[slot][1681] and returns; slot = the region's outIdx (patchByOutIdx) or its
+// Three instantiations of one body.  k_describe<DM_SIFT> is the SIFT kernel.  k_describe<DM_PATCH> is the patch-out form: the same
+// front end -- resampling, photometricallyNormalize -- which stores the normalised 41 x 41 patch (what DescribeRegions<> hands to
+// its functor, synth-detection.hpp:214-238) to fOut[slot][1681] and returns; slot = the region's outIdx (fFlag) or its
 // index in `jobs`.  Everything behind that store is dead code of that instantiation, and the tables it reads may be null.
-// (The body is the kernel itself, not a function both kernels call: inlined from a function, k_describe<false> compiled to 71
+// k_describe<DM_RAW> is the SIFT kernel up to the histogram: it stores desc[i] = (float)vec[i] of the doNorm = false functor
+// (siftdesc.cpp:436-440) to fOut[outIdx][128] -- the value itself, or (fFlag) added in f32 to the one already there, which is
+// DSP-SIFT's pooling over measurement sizes when the sizes are launched in order on one stream (engine_dsp.hip) -- and returns.
+// (The body is the kernel itself, not a function the kernels call: inlined from a function, k_describe<DM_SIFT> compiled to 71
 // VGPRs instead of 70.)
-template <bool PATCH_OUT>
+enum { DM_SIFT = 0, DM_PATCH = 1, DM_RAW = 2 };
+template <int MODE>
 __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
                                                   const int *needTab, const float *coordTab,
                                                   const float *mask, const unsigned short *maskIdx,
                                                   const float *oTab, const int *binTab, const double *wTab,
                                                   SiftConst sc, int photoNorm, int descTypes, int nOut, double maxBin,
-                                                  DescOut outs, float *patchOut, int patchByOutIdx) {
+                                                  DescOut outs, float *fOut, int fFlag) {
   const int tidw = threadIdx.x;                                    // thread of the workgroup
   const int reg = __builtin_amdgcn_readfirstlane(tidw >> 7);       // region of the workgroup (a wavefront is inside one region)
   const int tid = tidw & 127;                                      // thread of the region
@@ -715,7 +719,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   if (tidw == 0) spad_[MODSX_DESCRIBE_PAD - 1] = 1;
 #endif
   const DescJob jb = jobs[k];
-  if (!PATCH_OUT && tidw < PS) {
+  if (MODE != DM_PATCH && tidw < PS) {
     const float w0 = (float)wTab[tidw], w1 = (float)wTab[PS + tidw];   // const float wr0 = w0[r] (siftdesc.cpp:79-81)
     const int q = tidw >> 3, b0 = min(max(q - 1, 0), 3), b1 = min(q, 3);   // a bin outside 0..3 comes with weight 0
     const float wm = w0 > 0 ? (w1 > 0 ? fminf(w0, w1) : w0) : (w1 > 0 ? w1 : 1.f);
@@ -862,9 +866,9 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     }
     __syncthreads();
   }
-  if constexpr (PATCH_OUT) {
+  if constexpr (MODE == DM_PATCH) {
     if (alive) {
-      float *dst = patchOut + (size_t)(patchByOutIdx ? jb.outIdx : kreal) * NPX;
+      float *dst = fOut + (size_t)(fFlag ? jb.outIdx : kreal) * NPX;
       for (int i = tid; i < NPX; i += 128) dst[i] = patch[i];
     }
     return;
@@ -1074,6 +1078,15 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   // with several descriptor classes (iters_mods_cviu_wxbs.ini:35: RootSIFT, HalfRootSIFT) emits all of them from one
   // histogram: output t has type (descTypes >> 4 t) & 15 and goes to outs.u8 (t = 0) or outs.u8x[t - 1].
   const double rawBin = vec[tid];
+  if constexpr (MODE == DM_RAW) {
+    // a region is written once per launch set and the launch sets of a stream run in order: no other thread touches the word
+    if (alive) {
+      float *dst = fOut + (size_t)jb.outIdx * 128 + tid;
+      const float h = (float)rawBin;
+      *dst = fFlag ? *dst + h : h;
+    }
+    return;
+  }
 #pragma unroll 1
   for (int ot = 0; ot < nOut; ot++) {
   const int descType = (descTypes >> (4 * ot)) & 15;
@@ -1183,7 +1196,7 @@ void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *im
   if (n <= 0) return;
   SiftConst sc;
   sc.nmask = nmask;
-  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<false>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
+  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<DM_SIFT>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
                      wts, sc,
                      photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0);
 }
@@ -1195,9 +1208,20 @@ void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgR
   sc.nmask = nmask;
   DescOut none;
   memset(&none, 0, sizeof none);
-  hipLaunchKernelGGL(k_describe<true>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab,
+  hipLaunchKernelGGL(k_describe<DM_PATCH>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab,
                      (const float *)nullptr, maskIdx, (const float *)nullptr, (const int *)nullptr, (const double *)nullptr, sc, photoNorm, 0, 0, 0.0,
                      none, patchOut, patchByOutIdx);
+}
+void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
+                         const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab,
+                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate) {
+  if (n <= 0) return;
+  SiftConst sc;
+  sc.nmask = nmask;
+  DescOut none;
+  memset(&none, 0, sizeof none);
+  hipLaunchKernelGGL(k_describe<DM_RAW>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx,
+                     oTab, bins, wts, sc, photoNorm, 0, 0, 0.0, none, raw, accumulate);
 }
 
 }  // namespace mx
