@@ -972,6 +972,47 @@ int modsx_describe_regions_dspsift_device(modsx_ctx *ctx, const modsx_image *img
  * launched, regions described, scale passes launched.  Fills out[0 .. min(n, 3) - 1], returns 3. */
 int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- The SURF descriptor (OpenSURF U-SURF-64 on normalised patches) ----------------------------------------------------------
+ * The "SURF" branch of the reference (imagerepresentation.cpp:1829-1838) runs DescribeRegions<SURFDescriptor>: the same window
+ * -> blur -> 41 x 41 resample -> photometricallyNormalize front end as LIOP (modsx_extract_patches), then a functor
+ * (descriptors/surfdescriptor.hpp:13-37) that builds OpenSURF's integral image of the patch / 255 and describes ONE fixed,
+ * upright interest point at x = y = patchSize / 2.0f of scale (float)(patchSize / mrSize) with Surf::getDescriptor(true)
+ * (opensurf/surf.cpp:152-248): 4 x 4 sub-regions x (dx, dy, |dx|, |dy|), 64 f32.  mrSize is therefore used twice, for the
+ * measurement window and for the scale; the fields thres, octaves, intervals and init_sample of SURFParams never reach the
+ * functor.  Results are bit for bit the reference's: the order of its f32 adds (row sums, then column sums of the integral image;
+ * the 81 samples of a sub-region; the 16 length terms) and its f64 normalisation are kept; the gaussian weights come from the C
+ * library's expf on the host, as the reference's do.  At the default mrSize 5.1962 the scale is 7.89, most samples lie outside
+ * the patch and 28 of the 64 entries are identically zero.  A patch whose responses are all zero (a patch of zeros, or any patch
+ * when the rounded scale is 0, mrSize > 82) has length 0 and gives a row of 64 NaN, as the reference does; sign and payload of
+ * those NaN are unspecified.  Patch values must be finite.
+ * SURF is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder, of modsx_rep or of the sharded
+ * path; the rows go to modsx_match_regions_f32 at dim 64 (finite rows only).  The detector (FastHessian) and getOrientation are
+ * not part of this library.
+ * Every entry: n < 0, patchSize != 41, a null pointer, an mrSize that is not finite and positive, or an mrSize below
+ * patchSize / 1024 (scale above 1024: beyond it the reference's int sample coordinates and the int squares inside its gaussian
+ * approach overflow) is MODSX_ERR_ARG with a message, before anything is launched; n == 0 succeeds and writes nothing.  The
+ * _device forms take DEVICE pointers, 4-byte aligned, dense rows; they return after the work has finished.  The entries that
+ * compute return n. */
+#define MODSX_SURF_DIM 64
+/* the functor on n patches [n][41][41] f32 -> desc [n][64] f32 */
+int modsx_surf_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, double mrSize, float *desc);
+int modsx_surf_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, double mrSize, void *dev_desc);
+/* DescribeRegions<SURFDescriptor>(regions, image, surf, mrSize, patchSize, fast_extraction, photoNorm): desc [n][64] f32 =
+ * modsx_surf_patches of modsx_extract_patches.  The patches stay on the device, in the per-context buffer of at most 64 MiB
+ * that modsx_describe_regions_liop uses, filled and consumed in sub-batches. */
+int modsx_describe_regions_surf(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                int patchSize, int fast_extraction, int photoNorm, float *desc);
+int modsx_describe_regions_surf_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                       int patchSize, int fast_extraction, int photoNorm, void *dev_desc);
+/* host only: the constants of (patchSize, mrSize) the kernel reads -- sample_x24[k + 12] for k = -12 .. 11 and sample_y24[l + 12]
+ * for l = -12 .. 11 (the sample coordinates, which depend on k resp. l alone for an upright point), w1 [16][81] = gauss_s1 of
+ * sub-region q = 4 (i index) + (j index) and sample 9 (k - i) + (l - j), w2 [16] = gauss_s2, *haar_size = 2 * fRound(scale).
+ * Any pointer may be NULL.  Returns 0, or MODSX_ERR_ARG as above. */
+int modsx_surf_tables(int patchSize, double mrSize, int *sample_x24, int *sample_y24, float *w1, float *w2, int *haar_size);
+/* SURF work of this context since modsx_create, cumulative (measurement hook): calls that launched, patches described,
+ * sub-batches (launches of the SURF kernel).  Fills out[0 .. min(n, 3) - 1], returns 3. */
+int modsx_surf_counters(modsx_ctx *ctx, long *out, int n);
+
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:

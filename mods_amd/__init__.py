@@ -122,7 +122,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_describe_regions_liop", "modsx_describe_regions_liop_device", "modsx_liop_tables", "modsx_debug_liop",
            "modsx_liop_counters",
            "modsx_describe_regions_raw", "modsx_describe_regions_raw_device", "modsx_sift_norm_rows", "modsx_sift_norm_rows_device",
-           "modsx_describe_regions_dspsift", "modsx_describe_regions_dspsift_device", "modsx_dsp_counters"]
+           "modsx_describe_regions_dspsift", "modsx_describe_regions_dspsift_device", "modsx_dsp_counters",
+           "modsx_surf_patches", "modsx_surf_patches_device", "modsx_describe_regions_surf", "modsx_describe_regions_surf_device",
+           "modsx_surf_tables", "modsx_surf_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -142,6 +144,9 @@ LIOP_COUNTERS = ("calls", "regions", "exact_path", "sub_batches")
 LIOP_DIM, LIOP_PIXELS = 144, 673      # include/modsx.h: MODSX_LIOP_DIM, MODSX_LIOP_PIXELS
 # include/modsx.h: modsx_dsp_counters, in its order
 DSP_COUNTERS = ("calls", "regions", "scale_passes")
+# include/modsx.h: modsx_surf_counters, in its order
+SURF_COUNTERS = ("calls", "patches", "sub_batches")
+SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -267,6 +272,12 @@ def lib():
                                                      C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
         L.modsx_describe_regions_dspsift_device.argtypes = L.modsx_describe_regions_dspsift.argtypes
         L.modsx_dsp_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_surf_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_surf_patches_device.argtypes = L.modsx_surf_patches.argtypes
+        L.modsx_describe_regions_surf.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_describe_regions_surf_device.argtypes = L.modsx_extract_patches.argtypes
+        L.modsx_surf_tables.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_surf_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -300,6 +311,17 @@ def liop_tables(patch_size=41):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def surf_tables(mr_size=5.1962, patch_size=41):
+    """dict(sample_x [24] int32, sample_y [24] int32, w1 [16][81] float32, w2 [16] float32, haar_size int): the sample
+    coordinates (index k + 12, l + 12), the gaussian weights and the Haar size of the SURF functor at (patch_size, mr_size), as
+    the library builds them on the host (no device needed)."""
+    sx, sy = np.zeros(24, np.int32), np.zeros(24, np.int32)
+    w1, w2, hs = np.zeros((16, 81), np.float32), np.zeros(16, np.float32), np.zeros(1, np.int32)
+    if lib().modsx_surf_tables(int(patch_size), C.c_double(mr_size), _p(sx), _p(sy), _p(w1), _p(w2), _p(hs)) != 0:
+        raise RuntimeError("surf_tables failed: " + _err())
+    return dict(sample_x=sx, sample_y=sy, w1=w1, w2=w2, haar_size=int(hs[0]))
 
 
 def _check(rc, what):
@@ -787,6 +809,46 @@ class Context(object):
         path, perm = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), LIOP_PIXELS), np.int32)
         _check(lib().modsx_debug_liop(self._c(), _p(patches), n, int(patch_size), _p(desc), _p(path), _p(perm)), "debug_liop")
         return dict(desc=desc, path=path[:n], perm=perm[:n])
+
+    # ---- SURF (engine_surf.hip) ----
+    def surf_patches(self, patches, mr_size=5.1962, patch_size=41):
+        """The SURF functor (OpenSURF U-SURF-64 of the fixed point of scale patch_size / mr_size) on [n][41][41] float32 patches
+        (finite values) -> [n][64] float32; a row of NaN where every response is zero."""
+        patches = _liop_patch_rows(patches)
+        desc = np.zeros((len(patches), SURF_DIM), np.float32)
+        _check(lib().modsx_surf_patches(self._c(), _p(patches), len(patches), int(patch_size), C.c_double(mr_size), _p(desc)),
+               "surf_patches")
+        return desc
+
+    def surf_patches_device(self, patches_ptr, n, desc_ptr, mr_size=5.1962, patch_size=41):
+        """surf_patches from a device pointer to [n][1681] float32 into a device pointer to [n][64] float32 (4-byte aligned)."""
+        _check(lib().modsx_surf_patches_device(self._c(), C.c_void_p(patches_ptr), int(n), int(patch_size), C.c_double(mr_size),
+                                               C.c_void_p(desc_ptr)), "surf_patches_device")
+
+    def describe_regions_surf(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, out_ptr=None):
+        """DescribeRegions<SURFDescriptor>: [n][64] float32 (out_ptr: into that device pointer instead, returns None).  mr_size
+        sets the measurement window and the scale of the described point, as in the reference."""
+        regs = np.ascontiguousarray(regs, REGION)
+        if out_ptr is not None:
+            _check(lib().modsx_describe_regions_surf_device(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                            int(patch_size), int(fast), int(photo_norm), C.c_void_p(out_ptr)),
+                   "describe_regions_surf_device")
+            return None
+        desc = np.zeros((len(regs), SURF_DIM), np.float32)
+        _check(lib().modsx_describe_regions_surf(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size),
+                                                 int(patch_size), int(fast), int(photo_norm), _p(desc)), "describe_regions_surf")
+        return desc
+
+    def describe_regions_surf_device(self, img, regs, out_ptr, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1):
+        """describe_regions_surf into a device pointer to [n][64] float32 (4-byte aligned)."""
+        return self.describe_regions_surf(img, regs, mr_size, patch_size, fast, photo_norm, out_ptr=out_ptr)
+
+    def surf_counters(self):
+        """dict of SURF_COUNTERS: SURF work of this context since it was created (cumulative)."""
+        v = (C.c_long * len(SURF_COUNTERS))()
+        n = _check(lib().modsx_surf_counters(self._c(), v, len(SURF_COUNTERS)), "surf_counters")
+        assert n == len(SURF_COUNTERS), n
+        return dict(zip(SURF_COUNTERS, (int(x) for x in v)))
 
     def liop_counters(self):
         """dict of LIOP_COUNTERS: LIOP work of this context since it was created (cumulative)."""

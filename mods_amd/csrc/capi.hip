@@ -1617,6 +1617,52 @@ int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n) {
   return 3;
 }
 
+// ---- SURF (engine_surf.hip) ----
+#define SURF_ARGS(fn, bad)                                                \
+  do {                                                                    \
+    LIOP_ARGS(fn, bad);                                                   \
+    if (surf_check_args(fn, patchSize, mrSize)) return MODSX_ERR_ARG;        \
+  } while (0)
+int modsx_surf_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, double mrSize, float *desc) {
+  NEED(ctx);
+  SURF_ARGS("modsx_surf_patches", !patches || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = surf_patches(ctx, patches, n, mrSize, desc, false);
+  return rc ? rc : n;
+}
+int modsx_surf_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, double mrSize, void *dev_desc) {
+  NEED(ctx);
+  SURF_ARGS("modsx_surf_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = surf_patches(ctx, (const float *)dev_patches, n, mrSize, (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_surf(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                int patchSize, int fast_extraction, int photoNorm, float *desc) {
+  NEED(ctx); NEED(img);
+  SURF_ARGS("modsx_describe_regions_surf", !regs || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_surf_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                       int patchSize, int fast_extraction, int photoNorm, void *dev_desc) {
+  NEED(ctx); NEED(img);
+  SURF_ARGS("modsx_describe_regions_surf_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_surf_tables(int patchSize, double mrSize, int *sample_x24, int *sample_y24, float *w1, float *w2, int *haar_size) {
+  return surf_tables(patchSize, mrSize, sample_x24, sample_y24, w1, w2, haar_size);
+}
+int modsx_surf_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_surf_counters: bad argument"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->surfCounters[q];
+  return 3;
+}
+
 int modsx_kernel_stats(modsx_ctx *ctx, double *ms, double *work, long *launches, int n) {
   NEED(ctx); NEED(ms); NEED(work); NEED(launches);
   prof_collect(ctx);

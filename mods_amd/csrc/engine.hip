@@ -402,6 +402,8 @@ void ctx_destroy(modsx_ctx *c) {
   c->candSort.release(); c->candOut.release();
   c->liopTab.release(); c->liopPatches.release(); c->liopOut.release(); c->liopDbg.release(); c->liopCnt.release();
   c->dspRows.release();
+  for (DevBuf &b : c->surfTab) b.release();
+  c->surfOut.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();
   hipFree(c->dSmmMask); hipFree(c->dOriMask); hipFree(c->dOriIdx); hipFree(c->dSiftMask); hipFree(c->dSiftMaskIdx); hipFree(c->dAtan); hipFree(c->dOriBinTab); hipFree(c->dSiftOTab); hipFree(c->dSiftBins);

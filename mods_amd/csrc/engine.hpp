@@ -347,6 +347,11 @@ struct LiopSample { double wx, wy; int ix, iy; };
 static_assert(sizeof(LiopSample) == 24, "sample table entries are 24 bytes");
 void launch_liop(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const unsigned short *pixels,
                  const LiopSample *samples, unsigned *exactCount, int *dbgPath, int *dbgPerm);
+// SURF (kernels_surf.hip).  The constants of (patchSize = 41, mrSize), built by the host with libm (engine_surf.hip: surf_tables):
+// sample_x of k = -12 .. 11, sample_y of l = -12 .. 11, the Haar size, gauss_s2 per sub-region, gauss_s1 per sub-region and sample
+struct SurfTab { int sx[24], sy[24]; int haar, pad[3]; float w2[16]; float w1[16 * 81]; };
+static_assert(sizeof(SurfTab) == (24 + 24 + 4 + 16 + 16 * 81) * 4, "the SURF table is a dense block of words");
+void launch_surf(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const SurfTab *tab);
 // the patch-out form of k_describe (kernels_describe.hip): [slot][1681] f32, slot = outIdx (patchByOutIdx) or the job's index
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -452,6 +457,13 @@ struct modsx_ctx {
   // DSP-SIFT (engine_dsp.hip): rows on their way from / to the host
   mx::DevBuf dspRows;
   long dspCounters[3] = {0, 0, 0};       // modsx_dsp_counters: calls, regions, scale passes launched
+  // SURF (engine_surf.hip): the tables of the mrSize values seen last (a slot is refilled round robin), descriptors on their way
+  // to the host; patches pass through liopPatches
+  static constexpr int SURF_TABS = 4;
+  mx::DevBuf surfTab[SURF_TABS], surfOut;
+  double surfTabMr[SURF_TABS] = {0, 0, 0, 0};   // 0: the slot is empty (mrSize is positive)
+  int surfTabNext = 0;
+  long surfCounters[3] = {0, 0, 0};      // modsx_surf_counters: calls, patches, sub-batches
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

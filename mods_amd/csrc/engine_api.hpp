@@ -87,6 +87,14 @@ int sift_norm_rows(modsx_ctx *c, const float *rows, int n, double maxBinValue, f
 int describe_regions_dspsift(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
                              int fast, int photoNorm, int numScales, double startCoef, double endCoef, double maxBinValue, float *desc,
                              bool onDevice);
+// SURF (engine_surf.hip).  patches [n][41][41] f32 / desc [n][64] f32: host pointers, or device pointers (4-byte aligned) when
+// onDevice.  surf_check_args: the refusals that need no device (patchSize, mrSize), made by the entries of capi.hip before they
+// call in here; fn names the entry in the error text
+int surf_tables(int patchSize, double mrSize, int *sample_x24, int *sample_y24, float *w1, float *w2, int *haar_size);
+int surf_check_args(const char *fn, int patchSize, double mrSize);
+int surf_patches(modsx_ctx *c, const float *patches, int n, double mrSize, float *desc, bool onDevice);
+int describe_regions_surf(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
+                          int photoNorm, float *desc, bool onDevice);
 int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt, double phi_base, double InitSigma,
                 int doBlur, modsx_view *par, int cap, modsx_view *prev, int *nprev, int cap_prev);
 // slot < 0: the view is a fresh allocation owned by the returned image (public API).  slot in [0, MAXB): the view lives in
