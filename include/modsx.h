@@ -1013,6 +1013,56 @@ int modsx_surf_tables(int patchSize, double mrSize, int *sample_x24, int *sample
  * sub-batches (launches of the SURF kernel).  Fills out[0 .. min(n, 3) - 1], returns 3. */
 int modsx_surf_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- The DAISY descriptor (libdaisy on normalised patches) ----------------------------------------------------------------------
+ * The "DAISY" branch of the reference (imagerepresentation.cpp:1954-1963) runs DescribeRegions<DAISYDescriptor>: the same window
+ * -> blur -> 41 x 41 resample -> photometricallyNormalize front end as LIOP and SURF (modsx_extract_patches), then a functor
+ * (descriptors/daisydescriptor.hpp:33-92) that converts the patch to bytes (round half to even, saturated), hands it to libdaisy
+ * and reads the descriptor of ONE fixed point at x = y = patchSize / 2, orientation 0: histq = 8 gradient-direction layers of the
+ * blurred patch / 255, smoothed into radq cubes of growing sigma, sampled bilinearly at the centre and at radq rings of thq grid
+ * points up to radius rad, (radq * thq + 1) * 8 f32 (200 at the reference's defaults rad 15, radq 3, thq 8, histq 8), then
+ * normalised: nrm_type 0 = NRM_PARTIAL (each 8-bin histogram by its own l2 norm; a histogram of norm 0 stays 0), 1 = NRM_FULL
+ * (the whole row), 2 = NRM_SIFT (up to 5 rounds of: divide by the norm if it exceeds 1e-5, clip at 0.154f; until nothing clips).
+ * mrSize only sizes the measurement window; the DAISY point and its grid do not depend on it.  Results are bit for bit the
+ * reference's: every f32 multiply and add of its filters (rows, then columns, taps in order, borders replicated), of the bilinear
+ * mix and of the norms keeps its order; taps, layer directions, grid points and weights come from the C library's expf, cos and
+ * sin on the host, as the reference's do.  A grid point outside [0, 40) on either axis, or one whose integer part is 39 or more,
+ * gives 8 zeros: at rad = 20, radq = 3, thq = 8 those are histograms 17 and 19.  A patch without gradients gives a row of zeros.
+ * Rows of patches with non-finite values are unspecified.
+ * DAISY is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder, of modsx_rep or of the sharded
+ * path; the rows go to modsx_match_regions_f32 at their width.
+ * Accepted: patchSize == 41, histq == 8, 1 <= thq <= 8, 1 <= radq <= 3, 1 <= rad <= 20 (no grid point then leaves [0, 40]),
+ * nrm_type 0 .. 2.  Every entry: anything else, n < 0 or a null pointer is MODSX_ERR_ARG with a message, before anything is
+ * launched, and the context stays usable; n == 0 succeeds and writes nothing.  The _device forms take DEVICE pointers, 4-byte
+ * aligned, dense rows; they return after the work has finished.  The entries that compute return n. */
+#define MODSX_DAISY_MAX_DIM 200
+#define MODSX_DAISY_MAX_TAPS 51
+/* host only: (radq * thq + 1) * histq, or MODSX_ERR_ARG for values outside the accepted ranges */
+int modsx_daisy_dim(int radq, int thq, int histq);
+/* the functor on n patches [n][41][41] f32 -> desc [n][modsx_daisy_dim] f32 */
+int modsx_daisy_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, int rad, int radq, int thq, int histq, int nrm_type,
+                        float *desc);
+int modsx_daisy_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, int rad, int radq, int thq, int histq,
+                               int nrm_type, void *dev_desc);
+/* DescribeRegions<DAISYDescriptor>(regions, image, daisy, mrSize, patchSize, fast_extraction, photoNorm): desc [n][dim] f32 =
+ * modsx_daisy_patches of modsx_extract_patches.  The patches stay on the device, in the per-context buffer of at most 64 MiB
+ * that modsx_describe_regions_liop uses, filled and consumed in sub-batches (MODSX_DAISY_BATCH patches each, read once per
+ * process; default: what fits the buffer). */
+int modsx_describe_regions_daisy(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                                 int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq, int nrm_type, float *desc);
+int modsx_describe_regions_daisy_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                        int patchSize, int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq,
+                                        int nrm_type, void *dev_desc);
+/* host only: the constants of (rad, radq, thq, histq) the kernel reads -- k5 [5] the gaussian of sigma 0.5; kos8 / zin8 [8] the
+ * layer directions; fsz [1 + radq] and taps [1 + radq][MODSX_DAISY_MAX_TAPS] (zero beyond fsz) the filters, 0: the smoothing of
+ * the layers, 1 + r: the step to cube r; selected [radq] the cube of ring r; and per grid point g (0: the centre, 1 + r thq + t
+ * the others) state [npts] (0 skipped, 1 zeroed, 2 sampled), base [npts] (pixel A = 41 y + x) and w [npts][4] (w0 .. w3, applied
+ * to A, C = A + 1, B = A + 41, D = A + 42 in this order).  Any pointer may be NULL.  Returns 0, or MODSX_ERR_ARG as above. */
+int modsx_daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *kos8, float *zin8, int *fsz, float *taps, int *selected,
+                       int *state, int *base, float *w);
+/* DAISY work of this context since modsx_create, cumulative (measurement hook): calls that launched, patches described,
+ * sub-batches (launches of the DAISY kernel).  Fills out[0 .. min(n, 3) - 1], returns 3. */
+int modsx_daisy_counters(modsx_ctx *ctx, long *out, int n);
+
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:

@@ -124,7 +124,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_describe_regions_raw", "modsx_describe_regions_raw_device", "modsx_sift_norm_rows", "modsx_sift_norm_rows_device",
            "modsx_describe_regions_dspsift", "modsx_describe_regions_dspsift_device", "modsx_dsp_counters",
            "modsx_surf_patches", "modsx_surf_patches_device", "modsx_describe_regions_surf", "modsx_describe_regions_surf_device",
-           "modsx_surf_tables", "modsx_surf_counters"]
+           "modsx_surf_tables", "modsx_surf_counters",
+           "modsx_daisy_dim", "modsx_daisy_patches", "modsx_daisy_patches_device", "modsx_describe_regions_daisy",
+           "modsx_describe_regions_daisy_device", "modsx_daisy_tables", "modsx_daisy_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
 EXPORTS_DEGENSAC = ["exp_ransacHcustom", "exp_ransacFcustom", "HDs", "HDsi", "HDsidx", "HDsSym", "HDsiSym", "HDsSymidx",
                     "HDsSymMax", "HDsiSymMax", "HDsSymidxMax", "FDs", "FDsSym", "exFDs", "exFDsSym",
@@ -147,6 +149,11 @@ DSP_COUNTERS = ("calls", "regions", "scale_passes")
 # include/modsx.h: modsx_surf_counters, in its order
 SURF_COUNTERS = ("calls", "patches", "sub_batches")
 SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
+# include/modsx.h: modsx_daisy_counters, in its order
+DAISY_COUNTERS = ("calls", "patches", "sub_batches")
+DAISY_MAX_DIM, DAISY_MAX_TAPS = 200, 51      # include/modsx.h: MODSX_DAISY_MAX_DIM, MODSX_DAISY_MAX_TAPS
+DAISY_NRM_PARTIAL, DAISY_NRM_FULL, DAISY_NRM_SIFT = 0, 1, 2
+DAISY_SKIPPED, DAISY_ZEROED, DAISY_SAMPLED = 0, 1, 2     # modsx_daisy_tables: the state of a grid point
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -278,6 +285,13 @@ def lib():
         L.modsx_describe_regions_surf_device.argtypes = L.modsx_extract_patches.argtypes
         L.modsx_surf_tables.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_surf_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_daisy_dim.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.modsx_daisy_patches.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+        L.modsx_daisy_patches_device.argtypes = L.modsx_daisy_patches.argtypes
+        L.modsx_describe_regions_daisy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double] + [C.c_int] * 8 + [C.c_void_p]
+        L.modsx_describe_regions_daisy_device.argtypes = L.modsx_describe_regions_daisy.argtypes
+        L.modsx_daisy_tables.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9
+        L.modsx_daisy_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -322,6 +336,29 @@ def surf_tables(mr_size=5.1962, patch_size=41):
     if lib().modsx_surf_tables(int(patch_size), C.c_double(mr_size), _p(sx), _p(sy), _p(w1), _p(w2), _p(hs)) != 0:
         raise RuntimeError("surf_tables failed: " + _err())
     return dict(sample_x=sx, sample_y=sy, w1=w1, w2=w2, haar_size=int(hs[0]))
+
+
+def daisy_dim(radq=3, thq=8, histq=8):
+    """(radq * thq + 1) * histq, the width of a DAISY row; raises for values the library refuses (no device needed)."""
+    d = lib().modsx_daisy_dim(int(radq), int(thq), int(histq))
+    if d < 0:
+        raise RuntimeError("daisy_dim failed: " + _err())
+    return d
+
+
+def daisy_tables(rad=15, radq=3, thq=8, histq=8):
+    """dict(k5 [5], kos [8], zin [8] float32, fsz [1 + radq] int32, taps [1 + radq][51] float32 (zero beyond fsz), selected [radq],
+    state / base [npts] int32, w [npts][4] float32): the filters, layer directions and grid points of the DAISY functor at (rad,
+    radq, thq, histq) on a 41 x 41 patch, as the library builds them on the host (no device needed); include/modsx.h:
+    modsx_daisy_tables."""
+    npts = daisy_dim(radq, thq, histq) // int(histq)
+    k5, kos, zin = np.zeros(5, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32)
+    fsz, taps = np.zeros(1 + radq, np.int32), np.zeros((1 + radq, DAISY_MAX_TAPS), np.float32)
+    sel, state, base, w = np.zeros(radq, np.int32), np.zeros(npts, np.int32), np.zeros(npts, np.int32), np.zeros((npts, 4), np.float32)
+    if lib().modsx_daisy_tables(int(rad), int(radq), int(thq), int(histq), _p(k5), _p(kos), _p(zin), _p(fsz), _p(taps), _p(sel), _p(state),
+                                _p(base), _p(w)) != 0:
+        raise RuntimeError("daisy_tables failed: " + _err())
+    return dict(k5=k5, kos=kos, zin=zin, fsz=fsz, taps=taps, selected=sel, state=state, base=base, w=w)
 
 
 def _check(rc, what):
@@ -849,6 +886,49 @@ class Context(object):
         n = _check(lib().modsx_surf_counters(self._c(), v, len(SURF_COUNTERS)), "surf_counters")
         assert n == len(SURF_COUNTERS), n
         return dict(zip(SURF_COUNTERS, (int(x) for x in v)))
+
+    # ---- DAISY (engine_daisy.hip) ----
+    def daisy_patches(self, patches, rad=15, radq=3, thq=8, histq=8, nrm_type=0, patch_size=41):
+        """The DAISY functor (libdaisy's descriptor of the patch centre at orientation 0) on [n][41][41] float32 patches ->
+        [n][(radq * thq + 1) * 8] float32.  nrm_type: 0 partial, 1 full, 2 sift."""
+        patches = _liop_patch_rows(patches)
+        desc = np.zeros((len(patches), (int(radq) * int(thq) + 1) * int(histq)), np.float32)
+        _check(lib().modsx_daisy_patches(self._c(), _p(patches), len(patches), int(patch_size), int(rad), int(radq), int(thq), int(histq),
+                                         int(nrm_type), _p(desc)), "daisy_patches")
+        return desc
+
+    def daisy_patches_device(self, patches_ptr, n, desc_ptr, rad=15, radq=3, thq=8, histq=8, nrm_type=0, patch_size=41):
+        """daisy_patches from a device pointer to [n][1681] float32 into a device pointer to [n][dim] float32 (4-byte aligned)."""
+        _check(lib().modsx_daisy_patches_device(self._c(), C.c_void_p(patches_ptr), int(n), int(patch_size), int(rad), int(radq), int(thq),
+                                                int(histq), int(nrm_type), C.c_void_p(desc_ptr)), "daisy_patches_device")
+
+    def describe_regions_daisy(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, rad=15, radq=3, thq=8, histq=8,
+                               nrm_type=0, out_ptr=None):
+        """DescribeRegions<DAISYDescriptor>: [n][(radq * thq + 1) * 8] float32 (out_ptr: into that device pointer instead, returns
+        None).  mr_size only sets the measurement window."""
+        regs = np.ascontiguousarray(regs, REGION)
+        args = (int(patch_size), int(fast), int(photo_norm), int(rad), int(radq), int(thq), int(histq), int(nrm_type))
+        if out_ptr is not None:
+            _check(lib().modsx_describe_regions_daisy_device(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size), *args,
+                                                             C.c_void_p(out_ptr)), "describe_regions_daisy_device")
+            return None
+        desc = np.zeros((len(regs), (int(radq) * int(thq) + 1) * int(histq)), np.float32)
+        _check(lib().modsx_describe_regions_daisy(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.c_double(mr_size), *args, _p(desc)),
+               "describe_regions_daisy")
+        return desc
+
+    def describe_regions_daisy_device(self, img, regs, out_ptr, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, rad=15, radq=3,
+                                      thq=8, histq=8, nrm_type=0):
+        """describe_regions_daisy into a device pointer to [n][dim] float32 (4-byte aligned)."""
+        return self.describe_regions_daisy(img, regs, mr_size, patch_size, fast, photo_norm, rad, radq, thq, histq, nrm_type,
+                                           out_ptr=out_ptr)
+
+    def daisy_counters(self):
+        """dict of DAISY_COUNTERS: DAISY work of this context since it was created (cumulative)."""
+        v = (C.c_long * len(DAISY_COUNTERS))()
+        n = _check(lib().modsx_daisy_counters(self._c(), v, len(DAISY_COUNTERS)), "daisy_counters")
+        assert n == len(DAISY_COUNTERS), n
+        return dict(zip(DAISY_COUNTERS, (int(x) for x in v)))
 
     def liop_counters(self):
         """dict of LIOP_COUNTERS: LIOP work of this context since it was created (cumulative)."""

@@ -1663,6 +1663,59 @@ int modsx_surf_counters(modsx_ctx *ctx, long *out, int n) {
   return 3;
 }
 
+// ---- DAISY (engine_daisy.hip) ----
+#define DAISY_ARGS(fn, bad)                                                                           \
+  do {                                                                                                \
+    LIOP_ARGS(fn, bad);                                                                               \
+    if (daisy_check_args(fn, patchSize, rad, radq, thq, histq, nrm_type)) return MODSX_ERR_ARG;      \
+  } while (0)
+int modsx_daisy_dim(int radq, int thq, int histq) { return daisy_dim(radq, thq, histq); }
+int modsx_daisy_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, int rad, int radq, int thq, int histq, int nrm_type,
+                        float *desc) {
+  NEED(ctx);
+  DAISY_ARGS("modsx_daisy_patches", !patches || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = daisy_patches(ctx, patches, n, rad, radq, thq, nrm_type, desc, false);
+  return rc ? rc : n;
+}
+int modsx_daisy_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, int rad, int radq, int thq, int histq,
+                               int nrm_type, void *dev_desc) {
+  NEED(ctx);
+  DAISY_ARGS("modsx_daisy_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = daisy_patches(ctx, (const float *)dev_patches, n, rad, radq, thq, nrm_type, (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_daisy(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
+                                 int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq, int nrm_type, float *desc) {
+  NEED(ctx); NEED(img);
+  DAISY_ARGS("modsx_describe_regions_daisy", !regs || !desc);
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type, desc,
+                                        false);
+  return rc ? rc : n;
+}
+int modsx_describe_regions_daisy_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                                        int patchSize, int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq,
+                                        int nrm_type, void *dev_desc) {
+  NEED(ctx); NEED(img);
+  DAISY_ARGS("modsx_describe_regions_daisy_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  hipSetDevice(ctx->dev);
+  const int rc = describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type,
+                                        (float *)dev_desc, true);
+  return rc ? rc : n;
+}
+int modsx_daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *kos8, float *zin8, int *fsz, float *taps, int *selected,
+                       int *state, int *base, float *w) {
+  return daisy_tables(rad, radq, thq, histq, k5, kos8, zin8, fsz, taps, selected, state, base, w);
+}
+int modsx_daisy_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_daisy_counters: bad argument"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->daisyCounters[q];
+  return 3;
+}
+
 int modsx_kernel_stats(modsx_ctx *ctx, double *ms, double *work, long *launches, int n) {
   NEED(ctx); NEED(ms); NEED(work); NEED(launches);
   prof_collect(ctx);

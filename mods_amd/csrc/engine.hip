@@ -404,6 +404,8 @@ void ctx_destroy(modsx_ctx *c) {
   c->dspRows.release();
   for (DevBuf &b : c->surfTab) b.release();
   c->surfOut.release();
+  for (DevBuf &b : c->daisyTab) b.release();
+  c->daisyOut.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();
   hipFree(c->dSmmMask); hipFree(c->dOriMask); hipFree(c->dOriIdx); hipFree(c->dSiftMask); hipFree(c->dSiftMaskIdx); hipFree(c->dAtan); hipFree(c->dOriBinTab); hipFree(c->dSiftOTab); hipFree(c->dSiftBins);

@@ -352,6 +352,21 @@ void launch_liop(hipStream_t s, const float *patches, int n, float *out, const D
 struct SurfTab { int sx[24], sy[24]; int haar, pad[3]; float w2[16]; float w1[16 * 81]; };
 static_assert(sizeof(SurfTab) == (24 + 24 + 4 + 16 + 16 * 81) * 4, "the SURF table is a dense block of words");
 void launch_surf(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const SurfTab *tab);
+// DAISY (kernels_daisy.hip).  The constants of (rad, radq, thq) at patchSize 41 and histq 8, built by the host with libm
+// (engine_daisy.hip: daisy_tables): the 5-tap kernel, (kos, zin) per layer, the 1 + radq filters (0: the smoothing of the layers,
+// 1 + r: cube r - 1 -> cube r), and per grid point its cube, its state, the index of pixel A and the bilinear weights w0 .. w3.
+// A row of taps is DAISY_TAP_PAD zeros, the fsz taps, then zeros: k_daisy reads windows of 14 entries in steps of 8
+constexpr int DAISY_MAX_PTS = MODSX_DAISY_MAX_DIM / 8, DAISY_MAX_TAPS = MODSX_DAISY_MAX_TAPS, DAISY_TAP_PAD = 6, DAISY_TAP_ROW = 72;
+static_assert((DAISY_MAX_TAPS + DAISY_TAP_PAD + 7) / 8 * 8 + DAISY_TAP_PAD <= DAISY_TAP_ROW, "the last window stays inside the row");
+struct DaisyTab {
+  int npts, nfilt, dim, pad;
+  float k5[8], kos[8], zin[8];
+  int fsz[4];
+  int cube[DAISY_MAX_PTS + 3], state[DAISY_MAX_PTS + 3], base[DAISY_MAX_PTS + 3];
+  float w[(DAISY_MAX_PTS + 3) * 4];
+  float taps[4 * DAISY_TAP_ROW];
+};
+void launch_daisy(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const DaisyTab *tab, int nrmType);
 // the patch-out form of k_describe (kernels_describe.hip): [slot][1681] f32, slot = outIdx (patchByOutIdx) or the job's index
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -464,6 +479,13 @@ struct modsx_ctx {
   double surfTabMr[SURF_TABS] = {0, 0, 0, 0};   // 0: the slot is empty (mrSize is positive)
   int surfTabNext = 0;
   long surfCounters[3] = {0, 0, 0};      // modsx_surf_counters: calls, patches, sub-batches
+  // DAISY (engine_daisy.hip): the tables of the (rad, radq, thq) triples seen last (a slot is refilled round robin), descriptors
+  // on their way to the host; patches pass through liopPatches
+  static constexpr int DAISY_TABS = 4;
+  mx::DevBuf daisyTab[DAISY_TABS], daisyOut;
+  int daisyTabKey[DAISY_TABS] = {0, 0, 0, 0};   // rad << 16 | radq << 8 | thq; 0: the slot is empty
+  int daisyTabNext = 0;
+  long daisyCounters[3] = {0, 0, 0};     // modsx_daisy_counters: calls, patches, sub-batches
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

@@ -95,6 +95,16 @@ int surf_check_args(const char *fn, int patchSize, double mrSize);
 int surf_patches(modsx_ctx *c, const float *patches, int n, double mrSize, float *desc, bool onDevice);
 int describe_regions_surf(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                           int photoNorm, float *desc, bool onDevice);
+// DAISY (engine_daisy.hip).  patches [n][41][41] f32 / desc [n][(radq * thq + 1) * 8] f32: host pointers, or device pointers
+// (4-byte aligned) when onDevice.  daisy_check_args: the refusals that need no device (patchSize, rad, radq, thq, histq, nrmType),
+// made by the entries of capi.hip before they call in here; fn names the entry in the error text
+int daisy_check_args(const char *fn, int patchSize, int rad, int radq, int thq, int histq, int nrmType);
+int daisy_dim(int radq, int thq, int histq);
+int daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *kos8, float *zin8, int *fsz, float *taps, int *selected,
+                 int *state, int *base, float *w);
+int daisy_patches(modsx_ctx *c, const float *patches, int n, int rad, int radq, int thq, int nrmType, float *desc, bool onDevice);
+int describe_regions_daisy(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
+                           int photoNorm, int rad, int radq, int thq, int nrmType, float *desc, bool onDevice);
 int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt, double phi_base, double InitSigma,
                 int doBlur, modsx_view *par, int cap, modsx_view *prev, int *nprev, int cap_prev);
 // slot < 0: the view is a fresh allocation owned by the returned image (public API).  slot in [0, MAXB): the view lives in
