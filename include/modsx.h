@@ -426,6 +426,22 @@ int modsx_debug_detect_scalespace_batch(modsx_ctx *ctx, const modsx_image *const
  * because modsx_debug_reproject_certain_drop flags them, since the last reset (measurement hook; MODSX_ORI_PREFILTER=0 in the
  * environment launches them all).  modsx_detect_orientation itself never leaves a region out */
 int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long long *skipped, int reset);
+/* launches of the orientation kernel by every context of this process since the last reset (measurement hook), by instance:
+ * *lds_table the launches that read the bin table from a copy in LDS (fewer than 8192 regions), *global_table those that read it
+ * in global memory.  modsx_detect_orientation and the pipelines count alike; a call with no region to orient launches nothing.
+ * Either pointer may be NULL.  Returns 0 */
+int modsx_debug_orientation_launches(unsigned long long *lds_table, unsigned long long *global_table, int reset);
+/* host only: the tables the orientation kernel reads, built by the function that fills a context's copies.
+ * bin_table [2049]: the histogram bin (int)(36 * (angle / pi + 1) / 2) of the atan2LUTff angle of case code * 256 + idx, code =
+ * (x > 0) << 2 | (y > 0) << 1 | (|x| > |y|), idx = (int)(255 * small / big) clamped to 0 .. 255; entry 2048 is the special case
+ * x == 0, y <= 0 (angle 0).
+ * index_raster / weight_raster [1344]: the pixels of the 41 x 41 patch that can vote (circular mask of sigma 41 / 3 above 0) in
+ * raster order, as row * 44 + column, and their mask values; entries from counts[0] on are padding (pixel 45, weight 0).
+ * index_lanes / weight_lanes [1344]: the same list as the kernel reads it, entry lane + 64 q = raster entry 21 lane + q.
+ * counts [4]: voting pixels (1245), list length (1344), row stride of the indices (44), the region count from which a launch
+ * reads the bin table in global memory (8192).  Any pointer may be NULL.  Returns 0 */
+int modsx_orientation_tables(unsigned char *bin_table, unsigned short *index_raster, float *weight_raster,
+                             unsigned short *index_lanes, float *weight_lanes, int *counts);
 /* drop[i] = 1 when modsx_reproject_regions (boxk = 2 * 3 * sqrt 3) / modsx_reproject_regions_touch_boundary (boxk = mrSize) with
  * the same H and size removes region i whatever rotation modsx_detect_orientation applies to its shape first, 0 when that is not
  * certain (host only).  Returns n */

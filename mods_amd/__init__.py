@@ -107,7 +107,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_device_unpack", "modsx_verify_device_stats", "modsx_verify_device_timing", "modsx_comm_set_exchange",
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
-           "modsx_debug_orientation_counts", "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
+           "modsx_debug_orientation_counts", "modsx_debug_orientation_launches", "modsx_orientation_tables",
+           "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
            "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
            "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
@@ -213,6 +214,8 @@ def lib():
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.modsx_describe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_orientation_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_orientation_tables.argtypes = [C.c_void_p] * 6
         L.modsx_blur_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_detect_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_pyramids.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong,
@@ -1534,6 +1537,31 @@ def orientation_counts(reset=False):
     a, b = C.c_ulonglong(), C.c_ulonglong()
     lib().modsx_debug_orientation_counts(C.byref(a), C.byref(b), int(reset))
     return a.value, b.value
+
+
+def orientation_launches(reset=False):
+    """(lds_table, global_table): launches of the orientation kernel by this process since the last reset, by the instance that
+    ran -- bin table copied to LDS (fewer than 8192 regions) or read in global memory."""
+    a, b = C.c_ulonglong(), C.c_ulonglong()
+    lib().modsx_debug_orientation_launches(C.byref(a), C.byref(b), int(reset))
+    return a.value, b.value
+
+
+def orientation_tables():
+    """The tables the orientation kernel reads, as the library builds them on the host (no device needed): dict(bin_table [2049]
+    uint8 -- entry code * 256 + idx, [2048] the special case --, index_raster / index_lanes [1344] uint16 (row * stride + column of
+    the voting pixels, raster order / the uploaded lane-major order), weight_raster / weight_lanes [1344] float32, n_real, length,
+    stride, global_table_from)."""
+    tab = np.zeros(2049, np.uint8)
+    ir, il = np.zeros(1344, np.uint16), np.zeros(1344, np.uint16)
+    wr, wl = np.zeros(1344, np.float32), np.zeros(1344, np.float32)
+    k = np.zeros(4, np.int32)
+    if lib().modsx_orientation_tables(None, None, None, None, None, _p(k)) != 0 or k[1] != 1344:
+        raise RuntimeError("orientation_tables failed: " + _err())
+    if lib().modsx_orientation_tables(_p(tab), _p(ir), _p(wr), _p(il), _p(wl), _p(k)) != 0:
+        raise RuntimeError("orientation_tables failed: " + _err())
+    return dict(bin_table=tab, index_raster=ir, weight_raster=wr, index_lanes=il, weight_lanes=wl, n_real=int(k[0]),
+                length=int(k[1]), stride=int(k[2]), global_table_from=int(k[3]))
 
 
 def reproject_certain_drop(regs, H, w, h, boxk=2 * 3.0 * 3.0 ** 0.5):

@@ -372,6 +372,25 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
   return MODSX_OK;
 }
 
+int modsx_debug_orientation_launches(unsigned long long *lds_table, unsigned long long *global_table, int reset) {
+  mx::orientation_launches(lds_table, global_table, reset != 0);
+  return MODSX_OK;
+}
+
+int modsx_orientation_tables(unsigned char *bin_table, unsigned short *index_raster, float *weight_raster,
+                             unsigned short *index_lanes, float *weight_lanes, int *counts) {
+  mx::OriTables t;
+  const int rc = mx::orientation_tables_host(t);
+  if (rc != MODSX_OK) return rc;
+  if (bin_table) memcpy(bin_table, t.binTab.data(), 2049);
+  if (index_raster) memcpy(index_raster, t.idxRaster.data(), mx::ORI_NV * sizeof(unsigned short));
+  if (weight_raster) memcpy(weight_raster, t.wRaster.data(), mx::ORI_NV * sizeof(float));
+  if (index_lanes) memcpy(index_lanes, t.idxLanes.data(), mx::ORI_NV * sizeof(unsigned short));
+  if (weight_lanes) memcpy(weight_lanes, t.wLanes.data(), mx::ORI_NV * sizeof(float));
+  if (counts) { counts[0] = t.nReal; counts[1] = mx::ORI_NV; counts[2] = mx::ORI_PSP; counts[3] = mx::ORI_LDS_TABLE_BELOW; }
+  return MODSX_OK;
+}
+
 int modsx_debug_baumberg_geometry(int n, int W, int variant, int chunk, int *geometry) {
   NEED(geometry);
   const mx::BaumGeo g = mx::baumberg_geometry(n, W, variant, chunk);

@@ -251,39 +251,59 @@ void prof_reset(modsx_ctx *c, bool enable) {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
+// The tables of k_orientation, on the host: the voting list and the bin table (one copy: upload_tables sends them to the device,
+// modsx_orientation_tables shows them)
+int orientation_tables_host(OriTables &t) {
+  const int PS = 41, PSP = ORI_PSP;
+  std::vector<float> m(PS * PS);
+  circular_gauss_mask(m.data(), PS, PS / 3.0f);  // EstimateDominantAnglesFunctor ctor, synth-detection.cpp:757-762
+  // the pixels that can vote (mask > 0; all lie inside the 1-pixel frame the gradient needs), raster order, as indices
+  // into k_orientation's 44-column patch
+  std::vector<unsigned short> &idx = t.idxRaster;
+  std::vector<float> &w = t.wRaster;
+  idx.clear(); w.clear();
+  for (int r = 1; r < PS - 1; r++)
+    for (int q = 1; q < PS - 1; q++)
+      if (m[r * PS + q] > 0) { idx.push_back((unsigned short)(r * PSP + q)); w.push_back(m[r * PS + q]); }
+  for (int r = 0; r < PS; r++)
+    for (int q = 0; q < PS; q++)
+      if ((r == 0 || q == 0 || r == PS - 1 || q == PS - 1) && m[r * PS + q] > 0) {
+        set_error("orientation mask reaches the patch frame");
+        return MODSX_ERR_ARG;
+      }
+  if ((int)idx.size() > ORI_NV) { set_error("orientation voting list exceeds ORI_NV"); return MODSX_ERR_ARG; }
+  t.nReal = (int)idx.size();
+  while ((int)idx.size() < ORI_NV) { idx.push_back((unsigned short)(PSP + 1)); w.push_back(0.f); }
+  {   // k_orientation's lane l takes the CONTIGUOUS list elements [PER_L l, PER_L (l + 1)) and reads table entry lane + 64 q
+    constexpr int PER_L = ORI_NV / 64;
+    t.idxLanes.assign(ORI_NV, 0);
+    t.wLanes.assign(ORI_NV, 0.f);
+    for (int l = 0; l < 64; l++)
+      for (int q = 0; q < PER_L; q++) { t.idxLanes[l + 64 * q] = idx[PER_L * l + q]; t.wLanes[l + 64 * q] = w[PER_L * l + q]; }
+  }
+  // the histogram bin is a function of atan2LUTff's angle, which takes 8 x 256 values (kmath.hpp: atan2lut_case / _value) and
+  // 0 in the special case (entry 2048): tabulated with the kernel's own expression
+  t.binTab.assign(ATAN_CASES, 0);
+  const double *L = atan_lut_host();
+  const float PIf = float(M_PI);
+  for (int e = 0; e < ATAN_CASES; e++) {
+    const float ori = e < 2048 ? atan2lut_value(L, e >> 8, e & 255) : 0.f;
+    t.binTab[e] = (unsigned char)(int)(36 * (ori / PIf + 1.0f) / 2.0f);          // synth-detection.cpp:781-786 as in k_orientation
+  }
+  return MODSX_OK;
+}
+
 static int upload_tables(modsx_ctx *c) {
   const int PS = 41;
   std::vector<float> m(PS * PS);
-  circular_gauss_mask(m.data(), PS, PS / 3.0f);  // EstimateDominantAnglesFunctor ctor, synth-detection.cpp:757-762
+  OriTables ot;
   {
-    // the pixels that can vote (mask > 0; all lie inside the 1-pixel frame the gradient needs), raster order, as indices
-    // into k_orientation's 44-column patch
-    const int PSP = 44;
-    std::vector<unsigned short> idx;
-    std::vector<float> w;
-    for (int r = 1; r < PS - 1; r++)
-      for (int q = 1; q < PS - 1; q++)
-        if (m[r * PS + q] > 0) { idx.push_back((unsigned short)(r * PSP + q)); w.push_back(m[r * PS + q]); }
-    for (int r = 0; r < PS; r++)
-      for (int q = 0; q < PS; q++)
-        if ((r == 0 || q == 0 || r == PS - 1 || q == PS - 1) && m[r * PS + q] > 0) {
-          set_error("orientation mask reaches the patch frame");
-          return MODSX_ERR_ARG;
-        }
-    if ((int)idx.size() > ORI_NV) { set_error("orientation voting list exceeds ORI_NV"); return MODSX_ERR_ARG; }
-    while ((int)idx.size() < ORI_NV) { idx.push_back((unsigned short)(PSP + 1)); w.push_back(0.f); }
-    {   // k_orientation's lane l takes the CONTIGUOUS list elements [PER_L l, PER_L (l + 1)) and reads table entry lane + 64 q
-      constexpr int PER_L = ORI_NV / 64;
-      std::vector<unsigned short> idx2(ORI_NV);
-      std::vector<float> w2(ORI_NV);
-      for (int l = 0; l < 64; l++)
-        for (int q = 0; q < PER_L; q++) { idx2[l + 64 * q] = idx[PER_L * l + q]; w2[l + 64 * q] = w[PER_L * l + q]; }
-      idx.swap(idx2); w.swap(w2);
-    }
+    const int rc = orientation_tables_host(ot);
+    if (rc != MODSX_OK) return rc;
     MX_HIP(hipMalloc(&c->dOriMask, ORI_NV * 4));
     MX_HIP(hipMalloc(&c->dOriIdx, ORI_NV * 2));
-    MX_HIP(hipMemcpy(c->dOriMask, w.data(), ORI_NV * 4, hipMemcpyHostToDevice));
-    MX_HIP(hipMemcpy(c->dOriIdx, idx.data(), ORI_NV * 2, hipMemcpyHostToDevice));
+    MX_HIP(hipMemcpy(c->dOriMask, ot.wLanes.data(), ORI_NV * 4, hipMemcpyHostToDevice));
+    MX_HIP(hipMemcpy(c->dOriIdx, ot.idxLanes.data(), ORI_NV * 2, hipMemcpyHostToDevice));
   }
   MX_HIP(hipMalloc(&c->dSiftMask, PS * PS * 4));
   circular_gauss_mask(m.data(), PS, 0);          // SIFTDescriptor ctor / DescribeRegions, siftdesc.h:87
@@ -298,21 +318,18 @@ static int upload_tables(modsx_ctx *c) {
   MX_HIP(hipMalloc(&c->dAtan, 256 * 8));
   MX_HIP(hipMemcpy(c->dAtan, atan_lut_host(), 256 * 8, hipMemcpyHostToDevice));
   {
-    // What the gradient stages need of atan2LUTff's angle is a function of it: the histogram bin (orientation) and the
-    // fractional SIFT orientation bin (description).  The angle takes 8 x 256 values (kmath.hpp: atan2lut_case / _value) and
-    // 0 in the special case (entry 2048), so both functions are tabulated here with the kernels' own expressions.
-    std::vector<unsigned char> obin(ATAN_CASES);
+    // What the gradient stages need of atan2LUTff's angle is a function of it: the histogram bin (orientation:
+    // orientation_tables_host) and the fractional SIFT orientation bin (description).  The angle takes 8 x 256 values (kmath.hpp:
+    // atan2lut_case / _value) and 0 in the special case (entry 2048), so both functions are tabulated with the kernels' own expressions.
     std::vector<float> so(ATAN_CASES);
     const double *L = atan_lut_host();
-    const float PIf = float(M_PI);
     const double TWO_PI = 6.28318530718;
     for (int e = 0; e < ATAN_CASES; e++) {
       const float ori = e < 2048 ? atan2lut_value(L, e >> 8, e & 255) : 0.f;
-      obin[e] = (unsigned char)(int)(36 * (ori / PIf + 1.0f) / 2.0f);          // synth-detection.cpp:781-786 as in k_orientation
       so[e] = (float)((double)8.0f * ((double)ori + TWO_PI) / TWO_PI);         // siftdesc.cpp:103-110 as in k_describe
     }
     MX_HIP(hipMalloc(&c->dOriBinTab, ATAN_CASES));
-    MX_HIP(hipMemcpy(c->dOriBinTab, obin.data(), ATAN_CASES, hipMemcpyHostToDevice));
+    MX_HIP(hipMemcpy(c->dOriBinTab, ot.binTab.data(), ATAN_CASES, hipMemcpyHostToDevice));
     MX_HIP(hipMalloc(&c->dSiftOTab, ATAN_CASES * 4));
     MX_HIP(hipMemcpy(c->dSiftOTab, so.data(), ATAN_CASES * 4, hipMemcpyHostToDevice));
   }
@@ -471,6 +488,15 @@ static bool ori_prefilter_on() {
 // measurement hook (modsx_debug_orientation_counts): orientation jobs launched, and regions left out because their reprojection
 // is certain to drop them, by every context of the process since the last reset
 static std::atomic<unsigned long long> g_oriLaunched{0}, g_oriSkipped{0};
+// measurement hook (modsx_debug_orientation_launches): launches of the two instances of k_orientation, bin table in LDS / in
+// global memory, by every context of the process since the last reset
+static std::atomic<unsigned long long> g_oriLaunchLds{0}, g_oriLaunchGlobal{0};
+void orientation_launches(unsigned long long *ldsTable, unsigned long long *globalTable, bool reset) {
+  const unsigned long long a = reset ? g_oriLaunchLds.exchange(0) : g_oriLaunchLds.load();
+  const unsigned long long b = reset ? g_oriLaunchGlobal.exchange(0) : g_oriLaunchGlobal.load();
+  if (ldsTable) *ldsTable = a;
+  if (globalTable) *globalTable = b;
+}
 void orientation_counts(unsigned long long *launched, unsigned long long *skipped, bool reset) {
   if (launched) *launched = reset ? g_oriLaunched.exchange(0) : g_oriLaunched.load();
   else if (reset) g_oriLaunched.store(0);
@@ -547,6 +573,7 @@ int detect_orientation_batch(modsx_ctx *c, const modsx_image *const *imgs, int n
     res = hres;
     MX_HIP(ctx_copy(c, c->oriJobs.p, c->hOri.p, nj * sizeof(OriJob), hipMemcpyHostToDevice));
     ProfScope ps(c, K_ORIENT, (double)nj * 41 * 41 * 4);
+    (orientation_lds_table((int)nj) ? g_oriLaunchLds : g_oriLaunchGlobal).fetch_add(1, std::memory_order_relaxed);
     launch_orientation(s, (OriJob *)c->oriJobs.p, (float *)c->oriOut.p, (int)nj, (ImgRef *)c->imgRefs.p, c->dOriIdx,
                        c->dOriMask, c->dOriBinTab, doHalfSIFT, th, maxA);
     MX_HIP(ctx_copy(c, hres, c->oriOut.p, nj * oriB, hipMemcpyDeviceToHost));

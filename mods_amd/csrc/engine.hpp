@@ -238,9 +238,22 @@ bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, cons
                      float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean);
 constexpr int ATAN_CASES = 2048 + 64;   // 8 x 256 (sign / octant bits, table index) values of atan2LUTff's angle + the special case (entry 2048), padded
 constexpr int ORI_NV = 1344;   // entries of the orientation kernel's voting-pixel list (1245 under the mask, padded to 64 lanes x 21)
+constexpr int ORI_PSP = 44;    // row stride of the orientation kernel's padded 41 x 41 patch: what the voting list indexes
+// fewer regions than two rounds of wavefronts over the chip: k_orientation reads the bin table from a copy in LDS, otherwise
+// where it lies in global memory (kernels_orient.hip)
+constexpr int ORI_LDS_TABLE_BELOW = 2 * 256 * 16;
+inline bool orientation_lds_table(int n) { return n < ORI_LDS_TABLE_BELOW; }
 void launch_orientation(hipStream_t s, const OriJob *jobs, float *out, int n, const ImgRef *imgs,
                         const unsigned short *maskIdx, const float *maskW,
                         const unsigned char *binTab, int doHalf, double th, int maxAngles);
+// The host-built tables of k_orientation (engine.hip): what upload_tables copies to the device and modsx_orientation_tables shows.
+struct OriTables {
+  std::vector<unsigned char> binTab;                 // ATAN_CASES: histogram bin of atan2LUT case code * 256 + idx, [2048] the special case
+  std::vector<unsigned short> idxRaster, idxLanes;   // ORI_NV: r * ORI_PSP + q of the voting pixels in raster order / as uploaded
+  std::vector<float> wRaster, wLanes;                // ORI_NV: their mask values (0 in the padding)
+  int nReal = 0;                                     // voting pixels before the padding
+};
+int orientation_tables_host(OriTables &t);           // MODSX_OK, or MODSX_ERR_ARG with the error text set
 void launch_trunc_u8(hipStream_t s, const float *src, uint8_t *dst, size_t n);
 size_t mser_sort_blocks(const int *rows, int n);
 void launch_mser_sort(hipStream_t s, const uint8_t *const *u8, const int *rows, const int *cols, const size_t *ordOfs, int n, int *blockHist,

@@ -42,6 +42,7 @@ int reproject_regions_box(modsx_region *regs, int n, const double *H, int orig_w
 // drop[i] = 1: reproject_regions_box removes region i whatever rotation is applied to its shape first (engine.hip)
 void reproject_certain_drop(const modsx_region *regs, int n, const double *H, int orig_w, int orig_h, double boxk, unsigned char *drop);
 void orientation_counts(unsigned long long *launched, unsigned long long *skipped, bool reset);
+void orientation_launches(unsigned long long *ldsTable, unsigned long long *globalTable, bool reset);
 // The descriptor classes one step carries (modsx_pair_params / modsx_ladder_step n_desc, desc_types, desc_ratios resolved):
 // `Descriptors=` and `FGINNThreshold=` of a [DetectorN] section.  half(): the step orients with doHalfSIFT = true
 // (imagerepresentation.cpp:693-706, 1259-1264).

@@ -12,7 +12,7 @@
 
 namespace mx {
 
-constexpr int PS = 41, PSP = 44;   // PSP: padded row stride so rows start 16-byte aligned in LDS
+constexpr int PS = 41, PSP = ORI_PSP;   // PSP: padded row stride (44) so rows start 16-byte aligned in LDS
 constexpr int ORI_B = 21;          // taps of a patch row in flight per lane
 
 // LDS_TABLE: the launch is too small to fill the device (a lone pair of few views): every wavefront then runs alone on its SIMD,
@@ -236,7 +236,7 @@ void launch_orientation(hipStream_t s, const OriJob *jobs, float *out, int n, co
                           int maxAngles) {
   if (n <= 0) return;
   // fewer regions than two rounds of wavefronts over the chip: the launch is latency, not residency
-  if (n < 2 * 256 * 16)
+  if (orientation_lds_table(n))
     MX_DUP(K_ORIENT) hipLaunchKernelGGL(k_orientation<true>, dim3(8 * ((n + 7) / 8)), dim3(64), 0, s, jobs, out, n, imgs, maskIdx, maskW, binTab, doHalf, th,
                        maxAngles);
   else
