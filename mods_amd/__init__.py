@@ -305,7 +305,7 @@ def _err():
     return lib().modsx_last_error().decode()
 
 
-def _liop_patch_rows(patches):
+def _patch_rows(patches):
     patches = np.ascontiguousarray(patches, np.float32)
     if patches.ndim == 2 and patches.shape == (41, 41):
         patches = patches[None]
@@ -817,7 +817,7 @@ class Context(object):
 
     def liop_patches(self, patches, patch_size=41):
         """vl_liopdesc_process on [n][41][41] float32 patches (finite values) -> [n][144] float32."""
-        patches = _liop_patch_rows(patches)
+        patches = _patch_rows(patches)
         desc = np.zeros((len(patches), LIOP_DIM), np.float32)
         _check(lib().modsx_liop_patches(self._c(), _p(patches), len(patches), int(patch_size), _p(desc)), "liop_patches")
         return desc
@@ -843,7 +843,7 @@ class Context(object):
     def debug_liop(self, patches, patch_size=41):
         """dict(desc [n][144], path [n] (0: no tie group across a bin cut, 1: the reference's quicksort was replayed), perm [n][673]
         = measurement pixel of every rank, the permutation the spatial bins were cut from)."""
-        patches = _liop_patch_rows(patches)
+        patches = _patch_rows(patches)
         n = len(patches)
         desc = np.zeros((n, LIOP_DIM), np.float32)
         path, perm = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), LIOP_PIXELS), np.int32)
@@ -854,7 +854,7 @@ class Context(object):
     def surf_patches(self, patches, mr_size=5.1962, patch_size=41):
         """The SURF functor (OpenSURF U-SURF-64 of the fixed point of scale patch_size / mr_size) on [n][41][41] float32 patches
         (finite values) -> [n][64] float32; a row of NaN where every response is zero."""
-        patches = _liop_patch_rows(patches)
+        patches = _patch_rows(patches)
         desc = np.zeros((len(patches), SURF_DIM), np.float32)
         _check(lib().modsx_surf_patches(self._c(), _p(patches), len(patches), int(patch_size), C.c_double(mr_size), _p(desc)),
                "surf_patches")
@@ -883,18 +883,21 @@ class Context(object):
         """describe_regions_surf into a device pointer to [n][64] float32 (4-byte aligned)."""
         return self.describe_regions_surf(img, regs, mr_size, patch_size, fast, photo_norm, out_ptr=out_ptr)
 
+    def _counters(self, fn_name, names):
+        v = (C.c_long * len(names))()
+        n = _check(getattr(lib(), fn_name)(self._c(), v, len(names)), fn_name[len("modsx_"):])
+        assert n == len(names), n
+        return dict(zip(names, (int(x) for x in v)))
+
     def surf_counters(self):
         """dict of SURF_COUNTERS: SURF work of this context since it was created (cumulative)."""
-        v = (C.c_long * len(SURF_COUNTERS))()
-        n = _check(lib().modsx_surf_counters(self._c(), v, len(SURF_COUNTERS)), "surf_counters")
-        assert n == len(SURF_COUNTERS), n
-        return dict(zip(SURF_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_surf_counters", SURF_COUNTERS)
 
     # ---- DAISY (engine_daisy.hip) ----
     def daisy_patches(self, patches, rad=15, radq=3, thq=8, histq=8, nrm_type=0, patch_size=41):
         """The DAISY functor (libdaisy's descriptor of the patch centre at orientation 0) on [n][41][41] float32 patches ->
         [n][(radq * thq + 1) * 8] float32.  nrm_type: 0 partial, 1 full, 2 sift."""
-        patches = _liop_patch_rows(patches)
+        patches = _patch_rows(patches)
         desc = np.zeros((len(patches), (int(radq) * int(thq) + 1) * int(histq)), np.float32)
         _check(lib().modsx_daisy_patches(self._c(), _p(patches), len(patches), int(patch_size), int(rad), int(radq), int(thq), int(histq),
                                          int(nrm_type), _p(desc)), "daisy_patches")
@@ -928,17 +931,11 @@ class Context(object):
 
     def daisy_counters(self):
         """dict of DAISY_COUNTERS: DAISY work of this context since it was created (cumulative)."""
-        v = (C.c_long * len(DAISY_COUNTERS))()
-        n = _check(lib().modsx_daisy_counters(self._c(), v, len(DAISY_COUNTERS)), "daisy_counters")
-        assert n == len(DAISY_COUNTERS), n
-        return dict(zip(DAISY_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_daisy_counters", DAISY_COUNTERS)
 
     def liop_counters(self):
         """dict of LIOP_COUNTERS: LIOP work of this context since it was created (cumulative)."""
-        v = (C.c_long * len(LIOP_COUNTERS))()
-        n = _check(lib().modsx_liop_counters(self._c(), v, len(LIOP_COUNTERS)), "liop_counters")
-        assert n == len(LIOP_COUNTERS), n
-        return dict(zip(LIOP_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_liop_counters", LIOP_COUNTERS)
 
     # ---- raw SIFT histograms, the f32 SIFT norm and DSP-SIFT (engine_dsp.hip) ----
     def describe_regions_raw(self, img, regs, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1, out_ptr=None):
@@ -986,25 +983,16 @@ class Context(object):
 
     def dsp_counters(self):
         """dict of DSP_COUNTERS: DSP-SIFT work of this context since it was created (cumulative)."""
-        v = (C.c_long * len(DSP_COUNTERS))()
-        n = _check(lib().modsx_dsp_counters(self._c(), v, len(DSP_COUNTERS)), "dsp_counters")
-        assert n == len(DSP_COUNTERS), n
-        return dict(zip(DSP_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_dsp_counters", DSP_COUNTERS)
 
     def describe_counters(self):
         """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative)."""
-        v = (C.c_long * len(DESCRIBE_COUNTERS))()
-        n = _check(lib().modsx_describe_counters(self._c(), v, len(DESCRIBE_COUNTERS)), "describe_counters")
-        assert n == len(DESCRIBE_COUNTERS), n
-        return dict(zip(DESCRIBE_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_describe_counters", DESCRIBE_COUNTERS)
 
     def detect_counters(self):
         """dict of DETECT_COUNTERS: what the pyramid and the extrema scan launched on this context since it was created (the
         last_* entries describe its last scan / candidate set)."""
-        v = (C.c_long * len(DETECT_COUNTERS))()
-        n = _check(lib().modsx_detect_counters(self._c(), v, len(DETECT_COUNTERS)), "detect_counters")
-        assert n == len(DETECT_COUNTERS), n
-        return dict(zip(DETECT_COUNTERS, (int(x) for x in v)))
+        return self._counters("modsx_detect_counters", DETECT_COUNTERS)
 
     def debug_pyramids(self, images, params):
         """modsx_debug_pyramids: the pyramids of a batch of Images (sizes may differ) -> per image a list of (blurs, resps) per

@@ -1505,57 +1505,59 @@ int modsx_profile(modsx_ctx *ctx, int enable) {
   return MODSX_OK;
 }
 
-// ---- normalised patches and LIOP (engine_liop.hip) ----
-#define LIOP_ARGS(fn, bad)                                                                                       \
+// ---- the descriptors of normalised patches: their common argument check, call and counter read-out ----
+#define PATCH_ARGS(fn, bad)                                                                                      \
   do {                                                                                                           \
     if (n < 0 || (bad)) { mx::set_error(fn ": bad argument"); return MODSX_ERR_ARG; }                            \
     if (patchSize != 41) { mx::set_error(fn ": patchSize must be 41"); return MODSX_ERR_ARG; }                   \
   } while (0)
+// the engine call on the context's device; n rows on success
+#define RETURN_ROWS(call)          \
+  do {                             \
+    hipSetDevice(ctx->dev);        \
+    const int rc = (call);         \
+    return rc ? rc : n;            \
+  } while (0)
+static int read_counters(const char *fn, const long *counters, int len, long *out, int n) {
+  if (n < 0 || (n > 0 && !out)) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n && q < len; q++) out[q] = counters[q];
+  return len;
+}
+
+// ---- normalised patches and LIOP (engine_liop.hip) ----
 int modsx_extract_patches(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
                           int fast_extraction, int photoNorm, float *patches) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_extract_patches", !regs || !patches);
-  hipSetDevice(ctx->dev);
-  const int rc = extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, patches, false);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_extract_patches", !regs || !patches);
+  RETURN_ROWS(extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, patches, false));
 }
 int modsx_extract_patches_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                  int patchSize, int fast_extraction, int photoNorm, void *dev_patches) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_extract_patches_device", !regs || !dev_patches || ((uintptr_t)dev_patches & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_patches, true);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_extract_patches_device", !regs || !dev_patches || ((uintptr_t)dev_patches & 3));
+  RETURN_ROWS(extract_patches(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_patches, true));
 }
 int modsx_liop_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc) {
   NEED(ctx);
-  LIOP_ARGS("modsx_liop_patches", !patches || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = liop_patches(ctx, patches, n, patchSize, desc, false, nullptr, nullptr);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_liop_patches", !patches || !desc);
+  RETURN_ROWS(liop_patches(ctx, patches, n, patchSize, desc, false, nullptr, nullptr));
 }
 int modsx_liop_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, void *dev_desc) {
   NEED(ctx);
-  LIOP_ARGS("modsx_liop_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = liop_patches(ctx, (const float *)dev_patches, n, patchSize, (float *)dev_desc, true, nullptr, nullptr);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_liop_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
+  RETURN_ROWS(liop_patches(ctx, (const float *)dev_patches, n, patchSize, (float *)dev_desc, true, nullptr, nullptr));
 }
 int modsx_describe_regions_liop(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                 int patchSize, int fast_extraction, int photoNorm, float *desc) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_liop", !regs || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_liop", !regs || !desc);
+  RETURN_ROWS(describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false));
 }
 int modsx_describe_regions_liop_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                        int patchSize, int fast_extraction, int photoNorm, void *dev_desc) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_liop_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_liop_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  RETURN_ROWS(describe_regions_liop(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true));
 }
 int modsx_liop_tables(int patchSize, int *pixels, double *sx, double *sy, int cap) {
   if (cap < 0) { mx::set_error("modsx_liop_tables: bad argument"); return MODSX_ERR_ARG; }
@@ -1563,41 +1565,31 @@ int modsx_liop_tables(int patchSize, int *pixels, double *sx, double *sy, int ca
 }
 int modsx_debug_liop(modsx_ctx *ctx, const float *patches, int n, int patchSize, float *desc, int *path, int *perm) {
   NEED(ctx);
-  LIOP_ARGS("modsx_debug_liop", !patches || !desc || !path || !perm);
-  hipSetDevice(ctx->dev);
-  const int rc = liop_patches(ctx, patches, n, patchSize, desc, false, path, perm);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_debug_liop", !patches || !desc || !path || !perm);
+  RETURN_ROWS(liop_patches(ctx, patches, n, patchSize, desc, false, path, perm));
 }
 int modsx_liop_counters(modsx_ctx *ctx, long *out, int n) {
   NEED(ctx);
-  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_liop_counters: bad argument"); return MODSX_ERR_ARG; }
-  for (int q = 0; q < n && q < 4; q++) out[q] = ctx->liopCounters[q];
-  return 4;
+  return read_counters("modsx_liop_counters", ctx->liopCounters, 4, out, n);
 }
 
 // ---- raw SIFT histograms, the f32 SIFT norm and DSP-SIFT (engine_dsp.hip) ----
 int modsx_describe_regions_raw(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
                                int fast_extraction, int photoNorm, float *hist) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_raw", !regs || !hist);
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, hist, false);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_raw", !regs || !hist);
+  RETURN_ROWS(describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, hist, false));
 }
 int modsx_describe_regions_raw_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                       int patchSize, int fast_extraction, int photoNorm, void *dev_hist) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_raw_device", !regs || !dev_hist || ((uintptr_t)dev_hist & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_hist, true);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_raw_device", !regs || !dev_hist || ((uintptr_t)dev_hist & 3));
+  RETURN_ROWS(describe_regions_raw(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_hist, true));
 }
 int modsx_sift_norm_rows(modsx_ctx *ctx, const float *rows, int n, double maxBinValue, float *out) {
   NEED(ctx);
   if (n < 0 || !rows || !out) { mx::set_error("modsx_sift_norm_rows: bad argument"); return MODSX_ERR_ARG; }
-  hipSetDevice(ctx->dev);
-  const int rc = sift_norm_rows(ctx, rows, n, maxBinValue, out, false);
-  return rc ? rc : n;
+  RETURN_ROWS(sift_norm_rows(ctx, rows, n, maxBinValue, out, false));
 }
 int modsx_sift_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, double maxBinValue, void *dev_out) {
   NEED(ctx);
@@ -1605,87 +1597,69 @@ int modsx_sift_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, dou
     mx::set_error("modsx_sift_norm_rows_device: bad argument");
     return MODSX_ERR_ARG;
   }
-  hipSetDevice(ctx->dev);
-  const int rc = sift_norm_rows(ctx, (const float *)dev_rows, n, maxBinValue, (float *)dev_out, true);
-  return rc ? rc : n;
+  RETURN_ROWS(sift_norm_rows(ctx, (const float *)dev_rows, n, maxBinValue, (float *)dev_out, true));
 }
 int modsx_describe_regions_dspsift(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                    int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef, double endCoef,
                                    double maxBinValue, float *desc) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_dspsift", !regs || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
-                                          endCoef, maxBinValue, desc, false);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_dspsift", !regs || !desc);
+  RETURN_ROWS(describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
+                                          endCoef, maxBinValue, desc, false));
 }
 int modsx_describe_regions_dspsift_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                           int patchSize, int fast_extraction, int photoNorm, int numScales, double startCoef,
                                           double endCoef, double maxBinValue, void *dev_desc) {
   NEED(ctx); NEED(img);
-  LIOP_ARGS("modsx_describe_regions_dspsift_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
-                                          endCoef, maxBinValue, (float *)dev_desc, true);
-  return rc ? rc : n;
+  PATCH_ARGS("modsx_describe_regions_dspsift_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
+  RETURN_ROWS(describe_regions_dspsift(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, numScales, startCoef,
+                                          endCoef, maxBinValue, (float *)dev_desc, true));
 }
 int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n) {
   NEED(ctx);
-  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_dsp_counters: bad argument"); return MODSX_ERR_ARG; }
-  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->dspCounters[q];
-  return 3;
+  return read_counters("modsx_dsp_counters", ctx->dspCounters, 3, out, n);
 }
 
 // ---- SURF (engine_surf.hip) ----
 #define SURF_ARGS(fn, bad)                                                \
   do {                                                                    \
-    LIOP_ARGS(fn, bad);                                                   \
+    PATCH_ARGS(fn, bad);                                                   \
     if (surf_check_args(fn, patchSize, mrSize)) return MODSX_ERR_ARG;        \
   } while (0)
 int modsx_surf_patches(modsx_ctx *ctx, const float *patches, int n, int patchSize, double mrSize, float *desc) {
   NEED(ctx);
   SURF_ARGS("modsx_surf_patches", !patches || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = surf_patches(ctx, patches, n, mrSize, desc, false);
-  return rc ? rc : n;
+  RETURN_ROWS(surf_patches(ctx, patches, n, mrSize, desc, false));
 }
 int modsx_surf_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, double mrSize, void *dev_desc) {
   NEED(ctx);
   SURF_ARGS("modsx_surf_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = surf_patches(ctx, (const float *)dev_patches, n, mrSize, (float *)dev_desc, true);
-  return rc ? rc : n;
+  RETURN_ROWS(surf_patches(ctx, (const float *)dev_patches, n, mrSize, (float *)dev_desc, true));
 }
 int modsx_describe_regions_surf(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                 int patchSize, int fast_extraction, int photoNorm, float *desc) {
   NEED(ctx); NEED(img);
   SURF_ARGS("modsx_describe_regions_surf", !regs || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false);
-  return rc ? rc : n;
+  RETURN_ROWS(describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, desc, false));
 }
 int modsx_describe_regions_surf_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                        int patchSize, int fast_extraction, int photoNorm, void *dev_desc) {
   NEED(ctx); NEED(img);
   SURF_ARGS("modsx_describe_regions_surf_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true);
-  return rc ? rc : n;
+  RETURN_ROWS(describe_regions_surf(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, (float *)dev_desc, true));
 }
 int modsx_surf_tables(int patchSize, double mrSize, int *sample_x24, int *sample_y24, float *w1, float *w2, int *haar_size) {
   return surf_tables(patchSize, mrSize, sample_x24, sample_y24, w1, w2, haar_size);
 }
 int modsx_surf_counters(modsx_ctx *ctx, long *out, int n) {
   NEED(ctx);
-  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_surf_counters: bad argument"); return MODSX_ERR_ARG; }
-  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->surfCounters[q];
-  return 3;
+  return read_counters("modsx_surf_counters", ctx->surfCounters, 3, out, n);
 }
 
 // ---- DAISY (engine_daisy.hip) ----
 #define DAISY_ARGS(fn, bad)                                                                           \
   do {                                                                                                \
-    LIOP_ARGS(fn, bad);                                                                               \
+    PATCH_ARGS(fn, bad);                                                                               \
     if (daisy_check_args(fn, patchSize, rad, radq, thq, histq, nrm_type)) return MODSX_ERR_ARG;      \
   } while (0)
 int modsx_daisy_dim(int radq, int thq, int histq) { return daisy_dim(radq, thq, histq); }
@@ -1693,36 +1667,28 @@ int modsx_daisy_patches(modsx_ctx *ctx, const float *patches, int n, int patchSi
                         float *desc) {
   NEED(ctx);
   DAISY_ARGS("modsx_daisy_patches", !patches || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = daisy_patches(ctx, patches, n, rad, radq, thq, nrm_type, desc, false);
-  return rc ? rc : n;
+  RETURN_ROWS(daisy_patches(ctx, patches, n, rad, radq, thq, nrm_type, desc, false));
 }
 int modsx_daisy_patches_device(modsx_ctx *ctx, const void *dev_patches, int n, int patchSize, int rad, int radq, int thq, int histq,
                                int nrm_type, void *dev_desc) {
   NEED(ctx);
   DAISY_ARGS("modsx_daisy_patches_device", !dev_patches || !dev_desc || (((uintptr_t)dev_patches | (uintptr_t)dev_desc) & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = daisy_patches(ctx, (const float *)dev_patches, n, rad, radq, thq, nrm_type, (float *)dev_desc, true);
-  return rc ? rc : n;
+  RETURN_ROWS(daisy_patches(ctx, (const float *)dev_patches, n, rad, radq, thq, nrm_type, (float *)dev_desc, true));
 }
 int modsx_describe_regions_daisy(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize,
                                  int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq, int nrm_type, float *desc) {
   NEED(ctx); NEED(img);
   DAISY_ARGS("modsx_describe_regions_daisy", !regs || !desc);
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type, desc,
-                                        false);
-  return rc ? rc : n;
+  RETURN_ROWS(describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type, desc,
+                                        false));
 }
 int modsx_describe_regions_daisy_device(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
                                         int patchSize, int fast_extraction, int photoNorm, int rad, int radq, int thq, int histq,
                                         int nrm_type, void *dev_desc) {
   NEED(ctx); NEED(img);
   DAISY_ARGS("modsx_describe_regions_daisy_device", !regs || !dev_desc || ((uintptr_t)dev_desc & 3));
-  hipSetDevice(ctx->dev);
-  const int rc = describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type,
-                                        (float *)dev_desc, true);
-  return rc ? rc : n;
+  RETURN_ROWS(describe_regions_daisy(ctx, img, regs, n, mrSize, patchSize, fast_extraction, photoNorm, rad, radq, thq, nrm_type,
+                                        (float *)dev_desc, true));
 }
 int modsx_daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *kos8, float *zin8, int *fsz, float *taps, int *selected,
                        int *state, int *base, float *w) {
@@ -1730,9 +1696,7 @@ int modsx_daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *
 }
 int modsx_daisy_counters(modsx_ctx *ctx, long *out, int n) {
   NEED(ctx);
-  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_daisy_counters: bad argument"); return MODSX_ERR_ARG; }
-  for (int q = 0; q < n && q < 3; q++) out[q] = ctx->daisyCounters[q];
-  return 3;
+  return read_counters("modsx_daisy_counters", ctx->daisyCounters, 3, out, n);
 }
 
 int modsx_kernel_stats(modsx_ctx *ctx, double *ms, double *work, long *launches, int n) {

@@ -417,12 +417,11 @@ void ctx_destroy(modsx_ctx *c) {
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) for (int sd = 0; sd < 2; sd++) c->descCls[d][t][sd].release();
   for (int t = 0; t < 4; t++) c->halfDesc[t].release();
   c->candSort.release(); c->candOut.release();
-  c->liopTab.release(); c->liopPatches.release(); c->liopOut.release(); c->liopDbg.release(); c->liopCnt.release();
+  c->patchBuf.release(); c->patchOut.release();
+  c->liopTab.release(); c->liopDbg.release(); c->liopCnt.release();
   c->dspRows.release();
   for (DevBuf &b : c->surfTab) b.release();
-  c->surfOut.release();
   for (DevBuf &b : c->daisyTab) b.release();
-  c->daisyOut.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();
   hipFree(c->dSmmMask); hipFree(c->dOriMask); hipFree(c->dOriIdx); hipFree(c->dSiftMask); hipFree(c->dSiftMaskIdx); hipFree(c->dAtan); hipFree(c->dOriBinTab); hipFree(c->dSiftOTab); hipFree(c->dSiftBins);

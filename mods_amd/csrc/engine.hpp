@@ -478,24 +478,26 @@ struct modsx_ctx {
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
   double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search: packing, k_f32_topk + k_f32_merge
-  // LIOP (engine_liop.hip): the measurement pixels + sample table (built at the first LIOP call), the patches of one sub-batch
-  // (at most 64 MiB), descriptors / patches / debug rows on their way to the host, the exact-path counter word
-  mx::DevBuf liopTab, liopPatches, liopOut, liopDbg, liopCnt;
+  // the patch descriptors LIOP, SURF and DAISY (engine_patchdesc.hip): the patches of one sub-batch (at most 64 MiB), and the
+  // descriptors (or the patches of modsx_extract_patches) on their way to a host caller.  Calls are serialised and copy their rows
+  // out before they return, so one of each serves all of them
+  mx::DevBuf patchBuf, patchOut;
+  // LIOP (engine_liop.hip): the measurement pixels + sample table (built at the first LIOP call), debug rows on their way to the
+  // host, the exact-path counter word
+  mx::DevBuf liopTab, liopDbg, liopCnt;
   long liopCounters[4] = {0, 0, 0, 0};   // modsx_liop_counters: calls, regions, regions on the exact path, sub-batches
   // DSP-SIFT (engine_dsp.hip): rows on their way from / to the host
   mx::DevBuf dspRows;
   long dspCounters[3] = {0, 0, 0};       // modsx_dsp_counters: calls, regions, scale passes launched
-  // SURF (engine_surf.hip): the tables of the mrSize values seen last (a slot is refilled round robin), descriptors on their way
-  // to the host; patches pass through liopPatches
+  // SURF (engine_surf.hip): the tables of the mrSize values seen last (a slot is refilled round robin)
   static constexpr int SURF_TABS = 4;
-  mx::DevBuf surfTab[SURF_TABS], surfOut;
+  mx::DevBuf surfTab[SURF_TABS];
   double surfTabMr[SURF_TABS] = {0, 0, 0, 0};   // 0: the slot is empty (mrSize is positive)
   int surfTabNext = 0;
   long surfCounters[3] = {0, 0, 0};      // modsx_surf_counters: calls, patches, sub-batches
-  // DAISY (engine_daisy.hip): the tables of the (rad, radq, thq) triples seen last (a slot is refilled round robin), descriptors
-  // on their way to the host; patches pass through liopPatches
+  // DAISY (engine_daisy.hip): the tables of the (rad, radq, thq) triples seen last (a slot is refilled round robin)
   static constexpr int DAISY_TABS = 4;
-  mx::DevBuf daisyTab[DAISY_TABS], daisyOut;
+  mx::DevBuf daisyTab[DAISY_TABS];
   int daisyTabKey[DAISY_TABS] = {0, 0, 0, 0};   // rad << 16 | radq << 8 | thq; 0: the slot is empty
   int daisyTabNext = 0;
   long daisyCounters[3] = {0, 0, 0};     // modsx_daisy_counters: calls, patches, sub-batches

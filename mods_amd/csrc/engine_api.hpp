@@ -72,6 +72,22 @@ struct DescTail {
 };
 int describe_batch_tail(modsx_ctx *c, const modsx_image *img, const std::vector<modsx_region> &regs, double mrSize, int patchSize,
                         int fast, int photoNorm, const DescTail &tail);
+// The descriptors that are one kernel per normalised 41 x 41 patch (engine_patchdesc.hip).  launch() runs the kernel on s over nb
+// patch rows: `first` is the index of the first of them within the call, out the output base (the rows' own when jobs is null,
+// the call's when the jobs carry their output rows).  batchEnv names the variable that sets the patches per sub-batch.
+struct PatchDesc {
+  int dim;                  // descriptor width in floats
+  const char *batchEnv;
+  void (*launch)(void *self, hipStream_t s, const float *patches, int nb, int first, float *out, const DescJob *jobs);
+  void *self;
+};
+// Both enqueue on c->stream and add their sub-batches to *subBatches; inside CtxBusy, n > 0.  The caller then runs patch_sync (the
+// call's one wait and error check), books its counters, and patch_fetch copies the staged rows to a host caller
+int patchdesc_patches(modsx_ctx *c, const PatchDesc &d, const float *patches, int n, float *desc, bool onDevice, long *subBatches);
+int patchdesc_regions(modsx_ctx *c, const PatchDesc &d, const modsx_image *img, const modsx_region *regs, int n, double mrSize,
+                      int patchSize, int fast, int photoNorm, float *desc, bool onDevice, long *subBatches);
+int patch_sync(modsx_ctx *c);
+int patch_fetch(modsx_ctx *c, float *rows, size_t floats, bool onDevice);
 // LIOP and the normalised patches (engine_liop.hip).  out / patches: host pointers, or device pointers (4-byte aligned) when
 // onDevice; dbgPath [n] / dbgPerm [n][673] (host, optional): modsx_debug_liop
 int liop_tables(int patchSize, int *pixels, double *sx, double *sy, int cap);

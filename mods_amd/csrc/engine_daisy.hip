@@ -4,23 +4,19 @@
 //     layer directions, the grid points and their bilinear weights constants of (rad, radq, thq): daisy_tables builds them on the
 //     host with the reference's f32 / f64 expressions and libm's expf, cos and sin (the reference's object imports expf and
 //     sincos); the device copy is cached per context and per triple;
-//   * patches come from the description front end unchanged, as for LIOP and SURF: the patch-out form of k_describe as the last
-//     launch of a chunk, through the context's patch buffer of at most 64 MiB in sub-batches (MODSX_DAISY_BATCH = patches per
-//     sub-batch, read once per process), each followed by k_daisy.
+//   * patches take the route of every patch descriptor (engine_patchdesc.hip): caller-supplied rows, or the description front
+//     end with the patch-out form of k_describe, in sub-batches (MODSX_DAISY_BATCH = patches per sub-batch), each followed by k_daisy.
 // mrSize only sizes the measurement window: the DAISY point and its grid do not depend on it.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <string>
-#include <vector>
 #include "engine_api.hpp"
 
 namespace mx {
 
-constexpr int DAISY_SIDE = 41, DAISY_NPX = DAISY_SIDE * DAISY_SIDE, DAISY_HISTQ = 8;
-constexpr size_t DAISY_PATCH_B = (size_t)DAISY_NPX * 4, DAISY_BUF_B = (size_t)64 << 20;
+constexpr int DAISY_SIDE = 41, DAISY_HISTQ = 8;
 enum { DAISY_SKIPPED = 0, DAISY_ZEROED = 1, DAISY_SAMPLED = 2 };
 
 int daisy_check_args(const char *fn, int patchSize, int rad, int radq, int thq, int histq, int nrmType) {
@@ -177,84 +173,45 @@ static int ensure_table(modsx_ctx *c, int rad, int radq, int thq, const DaisyTab
   return MODSX_OK;
 }
 
-// patches per sub-batch: what fits 64 MiB, or MODSX_DAISY_BATCH (1 .. that many), read once per process
-static int daisy_batch() {
-  static const int b = [] {
-    const long full = (long)(DAISY_BUF_B / DAISY_PATCH_B);
-    const char *e = getenv("MODSX_DAISY_BATCH");
-    const long v = e ? atol(e) : full;
-    return (int)std::min(std::max(v, 1L), full);
-  }();
-  return b;
+struct DaisyRun { const DaisyTab *tab; int nrmType; };
+static void run_daisy(void *self, hipStream_t s, const float *patches, int nb, int first, float *out, const DescJob *jobs) {
+  const DaisyRun *r = (const DaisyRun *)self;
+  launch_daisy(s, patches, nb, out, jobs, r->tab, r->nrmType);
 }
+static PatchDesc daisy_desc(DaisyRun *r, int radq, int thq) { return {(radq * thq + 1) * DAISY_HISTQ, "MODSX_DAISY_BATCH", run_daisy, r}; }
 
-static int book_call(modsx_ctx *c, int n, long subBatches) {
-  MX_HIP(hipStreamSynchronize(c->stream));
-  MX_HIP(hipGetLastError());
+static int finish(modsx_ctx *c, const PatchDesc &d, int n, long subBatches, float *desc, bool onDevice) {
+  const int rc = patch_sync(c);
+  if (rc) return rc;
   c->daisyCounters[0]++; c->daisyCounters[1] += n; c->daisyCounters[2] += subBatches;
-  return MODSX_OK;
+  return patch_fetch(c, desc, (size_t)n * d.dim, onDevice);
 }
 
 // ---- DAISY of patches ----
 int daisy_patches(modsx_ctx *c, const float *patches, int n, int rad, int radq, int thq, int nrmType, float *desc, bool onDevice) {
   if (n == 0) return MODSX_OK;
   CtxBusy busy(c);
-  const DaisyTab *tab = nullptr;
-  int rc = ensure_table(c, rad, radq, thq, &tab);
+  DaisyRun r = {nullptr, nrmType};
+  int rc = ensure_table(c, rad, radq, thq, &r.tab);
   if (rc) return rc;
-  const int dim = (radq * thq + 1) * DAISY_HISTQ;
+  const PatchDesc d = daisy_desc(&r, radq, thq);
   long subBatches = 0;
-  if (onDevice) {
-    // rows that already live in HBM are read where they are
-    launch_daisy(c->stream, patches, n, desc, nullptr, tab, nrmType);
-    subBatches = 1;
-  } else {
-    const int B = std::min(daisy_batch(), n);
-    if (!c->liopPatches.ensure((size_t)B * DAISY_PATCH_B) || !c->daisyOut.ensure((size_t)n * dim * 4)) return MODSX_ERR_NOMEM;
-    for (int j0 = 0; j0 < n; j0 += B, subBatches++) {
-      const int nb = std::min(B, n - j0);
-      MX_HIP(hipMemcpyAsync(c->liopPatches.p, patches + (size_t)j0 * DAISY_NPX, (size_t)nb * DAISY_PATCH_B, hipMemcpyHostToDevice, c->stream));
-      launch_daisy(c->stream, (const float *)c->liopPatches.p, nb, (float *)c->daisyOut.p + (size_t)j0 * dim, nullptr, tab, nrmType);
-    }
-  }
-  if ((rc = book_call(c, n, subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, c->daisyOut.p, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
-  return MODSX_OK;
+  if ((rc = patchdesc_patches(c, d, patches, n, desc, onDevice, &subBatches))) return rc;
+  return finish(c, d, n, subBatches, desc, onDevice);
 }
 
 // ---- regions -> DAISY ----
-struct DaisyTail { float *out; const DaisyTab *tab; int nrmType; long subBatches; };
-static int tail_daisy(modsx_ctx *c, void *self, const DescJob *jobs, int n, const float *grid, const int *needTab, const float *coordTab,
-                      int photoNorm) {
-  DaisyTail *dt = (DaisyTail *)self;
-  const int B = std::min(daisy_batch(), n);
-  if (!c->liopPatches.ensure((size_t)B * DAISY_PATCH_B)) return MODSX_ERR_NOMEM;
-  // the launches of a stream run in order: sub-batch k + 1 overwrites the buffer after k_daisy of sub-batch k has read it
-  for (int j0 = 0; j0 < n; j0 += B, dt->subBatches++) {
-    const int nb = std::min(B, n - j0);
-    launch_describe_patch(c->stream, jobs + j0, nb, (const ImgRef *)c->imgRefs.p, grid, needTab, coordTab, c->dSiftMaskIdx, c->nSiftMask,
-                          photoNorm, (float *)c->liopPatches.p, 0);
-    launch_daisy(c->stream, (const float *)c->liopPatches.p, nb, dt->out, jobs + j0, dt->tab, dt->nrmType);
-  }
-  return MODSX_OK;
-}
-
 int describe_regions_daisy(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                            int photoNorm, int rad, int radq, int thq, int nrmType, float *desc, bool onDevice) {
   if (n == 0) return MODSX_OK;
   CtxBusy busy(c);
-  DaisyTail dt = {desc, nullptr, nrmType, 0};
-  int rc = ensure_table(c, rad, radq, thq, &dt.tab);
+  DaisyRun r = {nullptr, nrmType};
+  int rc = ensure_table(c, rad, radq, thq, &r.tab);
   if (rc) return rc;
-  const size_t bytes = (size_t)n * (radq * thq + 1) * DAISY_HISTQ * 4;
-  if (!onDevice) { if (!c->daisyOut.ensure(bytes)) return MODSX_ERR_NOMEM; dt.out = (float *)c->daisyOut.p; }
-  const std::vector<modsx_region> v(regs, regs + n);
-  const DescTail tail = {tail_daisy, &dt};
-  rc = describe_batch_tail(c, img, v, mrSize, patchSize, fast, photoNorm, tail);
-  if (rc) return rc;
-  if ((rc = book_call(c, n, dt.subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, dt.out, bytes, hipMemcpyDeviceToHost));
-  return MODSX_OK;
+  const PatchDesc d = daisy_desc(&r, radq, thq);
+  long subBatches = 0;
+  if ((rc = patchdesc_regions(c, d, img, regs, n, mrSize, patchSize, fast, photoNorm, desc, onDevice, &subBatches))) return rc;
+  return finish(c, d, n, subBatches, desc, onDevice);
 }
 
 }  // namespace mx

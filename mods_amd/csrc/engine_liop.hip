@@ -4,14 +4,11 @@
 //     builds them, once per context;
 //   * patches come from the description front end unchanged: the windows, the chunk planner (describe_plan.cpp) and the sampling
 //     and blur launches of describe_batch, with the patch-out form of k_describe as the last launch (DescTail);
-//   * a LIOP call passes its patches through a per-context buffer of at most 64 MiB: sub-batches of a chunk's jobs, patch-out
-//     launch then k_liop (MODSX_LIOP_BATCH = patches per sub-batch, read once per process).
+//   * a LIOP call takes the route of every patch descriptor (engine_patchdesc.hip): sub-batches of caller-supplied rows or of a
+//     chunk's jobs, patch-out launch then k_liop (MODSX_LIOP_BATCH = patches per sub-batch).
 // LIOP has no parameters of its own: the ini's neighbours / bins / radius / threshold keys never reach VLFeat.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
 #include <string>
 #include <vector>
 #include "engine_api.hpp"
@@ -19,7 +16,7 @@
 namespace mx {
 
 constexpr int LIOP_SIDE = 41, LIOP_NPX = LIOP_SIDE * LIOP_SIDE, LIOP_N = MODSX_LIOP_PIXELS, LIOP_DIM = MODSX_LIOP_DIM;
-constexpr size_t LIOP_PATCH_B = (size_t)LIOP_NPX * 4, LIOP_BUF_B = (size_t)64 << 20;
+constexpr size_t LIOP_PATCH_B = (size_t)LIOP_NPX * 4;
 constexpr size_t LIOP_TAB_SAMPLES = ((size_t)LIOP_N * 2 + 7) & ~(size_t)7;      // byte offset of the sample table behind the pixels
 
 // vl_liopdesc_new(4, 6, 6.0f, 41): the measurement pixels (raster order, the x == 0 && y == 0 skip of liop.c:355) and the four
@@ -83,30 +80,36 @@ static int ensure_tables(modsx_ctx *c) {
 static const unsigned short *tab_pixels(modsx_ctx *c) { return (const unsigned short *)c->liopTab.p; }
 static const LiopSample *tab_samples(modsx_ctx *c) { return (const LiopSample *)((const char *)c->liopTab.p + LIOP_TAB_SAMPLES); }
 
-// patches per sub-batch: what fits 64 MiB, or MODSX_LIOP_BATCH (1 .. that many), read once per process
-static int liop_batch() {
-  static const int b = [] {
-    const long full = (long)(LIOP_BUF_B / LIOP_PATCH_B);
-    const char *e = getenv("MODSX_LIOP_BATCH");
-    const long v = e ? atol(e) : full;
-    return (int)std::min(std::max(v, 1L), full);
-  }();
-  return b;
-}
-
 static int zero_counter(modsx_ctx *c) {
   if (!c->liopCnt.ensure(16)) return MODSX_ERR_NOMEM;
   MX_HIP(hipMemsetAsync(c->liopCnt.p, 0, 16, c->stream));
   return MODSX_OK;
 }
-static int book_call(modsx_ctx *c, int n, long subBatches) {
+// the exact-path counter rides the call's one wait; then the call is booked and a host caller gets its rows
+static int finish(modsx_ctx *c, int n, long subBatches, float *desc, bool onDevice) {
   unsigned cnt = 0;
   MX_HIP(hipMemcpyAsync(&cnt, c->liopCnt.p, 4, hipMemcpyDeviceToHost, c->stream));
-  MX_HIP(hipStreamSynchronize(c->stream));
-  MX_HIP(hipGetLastError());
+  const int rc = patch_sync(c);
+  if (rc) return rc;
   c->liopCounters[0]++; c->liopCounters[1] += n; c->liopCounters[2] += (long)cnt; c->liopCounters[3] += subBatches;
+  return patch_fetch(c, desc, (size_t)n * LIOP_DIM, onDevice);
+}
+
+struct LiopRun { const unsigned short *pixels; const LiopSample *samples; unsigned *cnt; int *dPath, *dPerm; };
+static void run_liop(void *self, hipStream_t s, const float *patches, int nb, int first, float *out, const DescJob *jobs) {
+  const LiopRun *r = (const LiopRun *)self;
+  launch_liop(s, patches, nb, out, jobs, r->pixels, r->samples, r->cnt, r->dPath ? r->dPath + first : nullptr,
+              r->dPerm ? r->dPerm + (size_t)first * LIOP_N : nullptr);
+}
+// the tables and a zeroed exact-path counter on the device: what every LIOP call starts with
+static int liop_begin(modsx_ctx *c, LiopRun *r) {
+  int rc = ensure_tables(c);
+  if (rc) return rc;
+  if ((rc = zero_counter(c))) return rc;
+  *r = {tab_pixels(c), tab_samples(c), (unsigned *)c->liopCnt.p, nullptr, nullptr};
   return MODSX_OK;
 }
+static PatchDesc liop_desc(LiopRun *r) { return {LIOP_DIM, "MODSX_LIOP_BATCH", run_liop, r}; }
 
 // ---- the normalised patches ----
 static int tail_patches(modsx_ctx *c, void *self, const DescJob *jobs, int n, const float *grid, const int *needTab, const float *coordTab,
@@ -123,7 +126,7 @@ int extract_patches(modsx_ctx *c, const modsx_image *img, const modsx_region *re
   CtxBusy busy(c);
   const size_t bytes = (size_t)n * LIOP_PATCH_B;
   float *dst = patches;
-  if (!onDevice) { if (!c->liopOut.ensure(bytes)) return MODSX_ERR_NOMEM; dst = (float *)c->liopOut.p; }
+  if (!onDevice) { if (!c->patchOut.ensure(bytes)) return MODSX_ERR_NOMEM; dst = (float *)c->patchOut.p; }
   const std::vector<modsx_region> v(regs, regs + n);
   const DescTail tail = {tail_patches, dst};
   int rc = describe_batch_tail(c, img, v, mrSize, patchSize, fast, photoNorm, tail);
@@ -137,73 +140,33 @@ int liop_patches(modsx_ctx *c, const float *patches, int n, int patchSize, float
   if (patchSize != LIOP_SIDE) { set_error("modsx_liop_patches: patchSize must be 41"); return MODSX_ERR_ARG; }
   if (n == 0) return MODSX_OK;
   CtxBusy busy(c);
-  int rc = ensure_tables(c);
+  LiopRun r;
+  int rc = liop_begin(c, &r);
   if (rc) return rc;
-  if ((rc = zero_counter(c))) return rc;
-  const bool dbg = dbgPath || dbgPerm;
-  int *dPath = nullptr, *dPerm = nullptr;
-  if (dbg) {
+  if (dbgPath || dbgPerm) {
     if (!c->liopDbg.ensure((size_t)n * (1 + LIOP_N) * 4)) return MODSX_ERR_NOMEM;
-    dPath = (int *)c->liopDbg.p; dPerm = dPath + n;
+    r.dPath = (int *)c->liopDbg.p; r.dPerm = r.dPath + n;
   }
   long subBatches = 0;
-  if (onDevice) {
-    // rows that already live in HBM are read where they are
-    launch_liop(c->stream, patches, n, desc, nullptr, tab_pixels(c), tab_samples(c), (unsigned *)c->liopCnt.p, dPath, dPerm);
-    subBatches = 1;
-  } else {
-    const int B = std::min(liop_batch(), n);
-    if (!c->liopPatches.ensure((size_t)B * LIOP_PATCH_B) || !c->liopOut.ensure((size_t)n * LIOP_DIM * 4)) return MODSX_ERR_NOMEM;
-    for (int j0 = 0; j0 < n; j0 += B, subBatches++) {
-      const int nb = std::min(B, n - j0);
-      MX_HIP(hipMemcpyAsync(c->liopPatches.p, patches + (size_t)j0 * LIOP_NPX, (size_t)nb * LIOP_PATCH_B, hipMemcpyHostToDevice, c->stream));
-      launch_liop(c->stream, (const float *)c->liopPatches.p, nb, (float *)c->liopOut.p + (size_t)j0 * LIOP_DIM, nullptr, tab_pixels(c),
-                  tab_samples(c), (unsigned *)c->liopCnt.p, dPath ? dPath + j0 : nullptr, dPerm ? dPerm + (size_t)j0 * LIOP_N : nullptr);
-    }
-  }
-  if ((rc = book_call(c, n, subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, c->liopOut.p, (size_t)n * LIOP_DIM * 4, hipMemcpyDeviceToHost));
-  if (dbgPath) MX_HIP(hipMemcpy(dbgPath, dPath, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (dbgPerm) MX_HIP(hipMemcpy(dbgPerm, dPerm, (size_t)n * LIOP_N * 4, hipMemcpyDeviceToHost));
+  if ((rc = patchdesc_patches(c, liop_desc(&r), patches, n, desc, onDevice, &subBatches))) return rc;
+  if ((rc = finish(c, n, subBatches, desc, onDevice))) return rc;
+  if (dbgPath) MX_HIP(hipMemcpy(dbgPath, r.dPath, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (dbgPerm) MX_HIP(hipMemcpy(dbgPerm, r.dPerm, (size_t)n * LIOP_N * 4, hipMemcpyDeviceToHost));
   return MODSX_OK;
 }
 
 // ---- regions -> LIOP ----
-struct LiopTail { float *out; long subBatches; };
-static int tail_liop(modsx_ctx *c, void *self, const DescJob *jobs, int n, const float *grid, const int *needTab, const float *coordTab,
-                     int photoNorm) {
-  LiopTail *lt = (LiopTail *)self;
-  const int B = std::min(liop_batch(), n);
-  if (!c->liopPatches.ensure((size_t)B * LIOP_PATCH_B)) return MODSX_ERR_NOMEM;
-  // the launches of a stream run in order: sub-batch k + 1 overwrites the buffer after k_liop of sub-batch k has read it
-  for (int j0 = 0; j0 < n; j0 += B, lt->subBatches++) {
-    const int nb = std::min(B, n - j0);
-    launch_describe_patch(c->stream, jobs + j0, nb, (const ImgRef *)c->imgRefs.p, grid, needTab, coordTab, c->dSiftMaskIdx, c->nSiftMask,
-                          photoNorm, (float *)c->liopPatches.p, 0);
-    launch_liop(c->stream, (const float *)c->liopPatches.p, nb, lt->out, jobs + j0, tab_pixels(c), tab_samples(c),
-                (unsigned *)c->liopCnt.p, nullptr, nullptr);
-  }
-  return MODSX_OK;
-}
-
 int describe_regions_liop(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                           int photoNorm, float *desc, bool onDevice) {
   if (patchSize != LIOP_SIDE) { set_error("modsx_describe_regions_liop: patchSize must be 41"); return MODSX_ERR_ARG; }
   if (n == 0) return MODSX_OK;
   CtxBusy busy(c);
-  int rc = ensure_tables(c);
+  LiopRun r;
+  int rc = liop_begin(c, &r);
   if (rc) return rc;
-  if ((rc = zero_counter(c))) return rc;
-  const size_t bytes = (size_t)n * LIOP_DIM * 4;
-  LiopTail lt = {desc, 0};
-  if (!onDevice) { if (!c->liopOut.ensure(bytes)) return MODSX_ERR_NOMEM; lt.out = (float *)c->liopOut.p; }
-  const std::vector<modsx_region> v(regs, regs + n);
-  const DescTail tail = {tail_liop, &lt};
-  rc = describe_batch_tail(c, img, v, mrSize, patchSize, fast, photoNorm, tail);
-  if (rc) return rc;
-  if ((rc = book_call(c, n, lt.subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, lt.out, bytes, hipMemcpyDeviceToHost));
-  return MODSX_OK;
+  long subBatches = 0;
+  if ((rc = patchdesc_regions(c, liop_desc(&r), img, regs, n, mrSize, patchSize, fast, photoNorm, desc, onDevice, &subBatches))) return rc;
+  return finish(c, n, subBatches, desc, onDevice);
 }
 
 }  // namespace mx

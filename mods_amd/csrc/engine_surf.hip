@@ -4,22 +4,17 @@
 //     every gaussian weight of Surf::getDescriptor(true) a constant of (patchSize, mrSize): surf_tables builds them on the host
 //     with the reference's f32 / f64 expressions and libm's expf (the overload the reference's object imports); the device copy
 //     is cached per context and per mrSize;
-//   * patches come from the description front end unchanged, as for LIOP (engine_liop.hip): the patch-out form of k_describe
-//     as the last launch of a chunk, through the context's patch buffer of at most 64 MiB in sub-batches (MODSX_SURF_BATCH =
-//     patches per sub-batch, read once per process), each followed by k_surf.
+//   * patches take the route of every patch descriptor (engine_patchdesc.hip): caller-supplied rows, or the description front
+//     end with the patch-out form of k_describe, in sub-batches (MODSX_SURF_BATCH = patches per sub-batch), each followed by k_surf.
 // mrSize is used twice, as the reference uses it: for the measurement window and for the scale of the point.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <algorithm>
 #include <string>
-#include <vector>
 #include "engine_api.hpp"
 
 namespace mx {
 
-constexpr int SURF_SIDE = 41, SURF_NPX = SURF_SIDE * SURF_SIDE, SURF_DIM = MODSX_SURF_DIM;
-constexpr size_t SURF_PATCH_B = (size_t)SURF_NPX * 4, SURF_BUF_B = (size_t)64 << 20;
+constexpr int SURF_SIDE = 41, SURF_DIM = MODSX_SURF_DIM;
 constexpr double SURF_MAX_SCALE = 1024.0;      // modsx.h: patchSize / mrSize above this is refused
 
 // fRound, opensurf/utils.h:58-61
@@ -91,22 +86,16 @@ static int ensure_table(modsx_ctx *c, double mrSize, const SurfTab **out) {
   return MODSX_OK;
 }
 
-// patches per sub-batch: what fits 64 MiB, or MODSX_SURF_BATCH (1 .. that many), read once per process
-static int surf_batch() {
-  static const int b = [] {
-    const long full = (long)(SURF_BUF_B / SURF_PATCH_B);
-    const char *e = getenv("MODSX_SURF_BATCH");
-    const long v = e ? atol(e) : full;
-    return (int)std::min(std::max(v, 1L), full);
-  }();
-  return b;
+static void run_surf(void *self, hipStream_t s, const float *patches, int nb, int first, float *out, const DescJob *jobs) {
+  launch_surf(s, patches, nb, out, jobs, (const SurfTab *)self);
 }
+static PatchDesc surf_desc(const SurfTab *tab) { return {SURF_DIM, "MODSX_SURF_BATCH", run_surf, (void *)tab}; }
 
-static int book_call(modsx_ctx *c, int n, long subBatches) {
-  MX_HIP(hipStreamSynchronize(c->stream));
-  MX_HIP(hipGetLastError());
+static int finish(modsx_ctx *c, int n, long subBatches, float *desc, bool onDevice) {
+  const int rc = patch_sync(c);
+  if (rc) return rc;
   c->surfCounters[0]++; c->surfCounters[1] += n; c->surfCounters[2] += subBatches;
-  return MODSX_OK;
+  return patch_fetch(c, desc, (size_t)n * SURF_DIM, onDevice);
 }
 
 // ---- SURF of patches ----
@@ -117,57 +106,21 @@ int surf_patches(modsx_ctx *c, const float *patches, int n, double mrSize, float
   int rc = ensure_table(c, mrSize, &tab);
   if (rc) return rc;
   long subBatches = 0;
-  if (onDevice) {
-    // rows that already live in HBM are read where they are
-    launch_surf(c->stream, patches, n, desc, nullptr, tab);
-    subBatches = 1;
-  } else {
-    const int B = std::min(surf_batch(), n);
-    if (!c->liopPatches.ensure((size_t)B * SURF_PATCH_B) || !c->surfOut.ensure((size_t)n * SURF_DIM * 4)) return MODSX_ERR_NOMEM;
-    for (int j0 = 0; j0 < n; j0 += B, subBatches++) {
-      const int nb = std::min(B, n - j0);
-      MX_HIP(hipMemcpyAsync(c->liopPatches.p, patches + (size_t)j0 * SURF_NPX, (size_t)nb * SURF_PATCH_B, hipMemcpyHostToDevice, c->stream));
-      launch_surf(c->stream, (const float *)c->liopPatches.p, nb, (float *)c->surfOut.p + (size_t)j0 * SURF_DIM, nullptr, tab);
-    }
-  }
-  if ((rc = book_call(c, n, subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, c->surfOut.p, (size_t)n * SURF_DIM * 4, hipMemcpyDeviceToHost));
-  return MODSX_OK;
+  if ((rc = patchdesc_patches(c, surf_desc(tab), patches, n, desc, onDevice, &subBatches))) return rc;
+  return finish(c, n, subBatches, desc, onDevice);
 }
 
 // ---- regions -> SURF ----
-struct SurfTail { float *out; const SurfTab *tab; long subBatches; };
-static int tail_surf(modsx_ctx *c, void *self, const DescJob *jobs, int n, const float *grid, const int *needTab, const float *coordTab,
-                     int photoNorm) {
-  SurfTail *st = (SurfTail *)self;
-  const int B = std::min(surf_batch(), n);
-  if (!c->liopPatches.ensure((size_t)B * SURF_PATCH_B)) return MODSX_ERR_NOMEM;
-  // the launches of a stream run in order: sub-batch k + 1 overwrites the buffer after k_surf of sub-batch k has read it
-  for (int j0 = 0; j0 < n; j0 += B, st->subBatches++) {
-    const int nb = std::min(B, n - j0);
-    launch_describe_patch(c->stream, jobs + j0, nb, (const ImgRef *)c->imgRefs.p, grid, needTab, coordTab, c->dSiftMaskIdx, c->nSiftMask,
-                          photoNorm, (float *)c->liopPatches.p, 0);
-    launch_surf(c->stream, (const float *)c->liopPatches.p, nb, st->out, jobs + j0, st->tab);
-  }
-  return MODSX_OK;
-}
-
 int describe_regions_surf(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                           int photoNorm, float *desc, bool onDevice) {
   if (n == 0) return MODSX_OK;
   CtxBusy busy(c);
-  SurfTail st = {desc, nullptr, 0};
-  int rc = ensure_table(c, mrSize, &st.tab);
+  const SurfTab *tab = nullptr;
+  int rc = ensure_table(c, mrSize, &tab);
   if (rc) return rc;
-  const size_t bytes = (size_t)n * SURF_DIM * 4;
-  if (!onDevice) { if (!c->surfOut.ensure(bytes)) return MODSX_ERR_NOMEM; st.out = (float *)c->surfOut.p; }
-  const std::vector<modsx_region> v(regs, regs + n);
-  const DescTail tail = {tail_surf, &st};
-  rc = describe_batch_tail(c, img, v, mrSize, patchSize, fast, photoNorm, tail);
-  if (rc) return rc;
-  if ((rc = book_call(c, n, st.subBatches))) return rc;
-  if (!onDevice) MX_HIP(hipMemcpy(desc, st.out, bytes, hipMemcpyDeviceToHost));
-  return MODSX_OK;
+  long subBatches = 0;
+  if ((rc = patchdesc_regions(c, surf_desc(tab), img, regs, n, mrSize, patchSize, fast, photoNorm, desc, onDevice, &subBatches))) return rc;
+  return finish(c, n, subBatches, desc, onDevice);
 }
 
 }  // namespace mx

@@ -18,7 +18,7 @@ from tests import describe_cases as DC
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "daisy_batch_child.py")
+CHILD = os.path.join(ROOT, "tests", "patchdesc_batch_child.py")
 CHILD_TIMEOUT_S = 120          # import + context creation + two calls; what tests/test_gpu_surf.py allows such a child
 SIZES = (1, 2, 3)              # one workgroup per patch: larger counts repeat the same work
 DEFAULT = Cs.PARAMS[0]
@@ -169,7 +169,7 @@ def test_sub_batches_of_four_in_a_child(ctx, modsx, image, daisy_regions, oracle
     inp, outp = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
     np.savez(inp, image=DC.image(), regs=np.frombuffer(np.ascontiguousarray(regs, modsx.REGION).tobytes(), np.uint8), mr_size=mr,
              params=np.array(P), nrm_type=nrm)
-    p = subprocess.run([sys.executable, CHILD, inp, outp], env=dict(os.environ, MODSX_DAISY_BATCH="4"), timeout=CHILD_TIMEOUT_S,
+    p = subprocess.run([sys.executable, CHILD, "daisy", inp, outp], env=dict(os.environ, MODSX_DAISY_BATCH="4"), timeout=CHILD_TIMEOUT_S,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     err = p.stderr.decode(errors="replace")[-1500:]
     if p.returncode < 0 or p.returncode in (134, 139):

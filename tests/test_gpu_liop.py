@@ -23,7 +23,7 @@ from tests import describe_cases as DC
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHILD = os.path.join(ROOT, "tests", "liop_batch_child.py")
+CHILD = os.path.join(ROOT, "tests", "patchdesc_batch_child.py")
 CHILD_TIMEOUT_S = 120          # import + context creation + two calls; the floor tests/test_gpu_describe_chunks.py uses for such a child
 SIZES = (1, 2, 3, 63, 64, 65)
 
@@ -250,7 +250,7 @@ def test_sub_batches_of_four_in_a_child(ctx, modsx, image, liop_regions, liop_re
     inp, outp = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
     np.savez(inp, image=DC.image(), regs=np.frombuffer(np.ascontiguousarray(liop_regions, modsx.REGION).tobytes(), np.uint8),
              mr_size=DC.MR_SIZE)
-    p = subprocess.run([sys.executable, CHILD, inp, outp], env=dict(os.environ, MODSX_LIOP_BATCH="4"), timeout=CHILD_TIMEOUT_S,
+    p = subprocess.run([sys.executable, CHILD, "liop", inp, outp], env=dict(os.environ, MODSX_LIOP_BATCH="4"), timeout=CHILD_TIMEOUT_S,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     err = p.stderr.decode(errors="replace")[-1500:]
     if p.returncode < 0 or p.returncode in (134, 139):
