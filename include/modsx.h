@@ -1079,6 +1079,56 @@ int modsx_daisy_tables(int rad, int radq, int thq, int histq, float *k5, float *
  * sub-batches (launches of the DAISY kernel).  Fills out[0 .. min(n, 3) - 1], returns 3. */
 int modsx_daisy_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- The SURF detector (OpenSURF FastHessian) ------------------------------------------------------------------------------
+ * The "SURF" detector branch of the reference (imagerepresentation.cpp:1046-1076): Integral() of the view / 255, then
+ * FastHessian(int_img, ipts, octaves, intervals, init_sample, thres).getIpoints() (opensurf/fasthessian.cpp, integral.cpp,
+ * integral.h, responselayer.h), bit for bit: the integral image with the reference's order of f32 adds, 4 + 2 (octaves - 1) box
+ * filter response layers (filters 9, 15, 21, 27 | 39, 51 | 75, 99 | 147, 195 | 291, 387), the 3 x 3 x 3 extremum test across layers
+ * of different density (read through the integer quotient of the layer WIDTHS, as getResponse does) and the sub-pixel step in
+ * f64.  Points come out in the reference's push order: octave, interval, raster position of the sparsest layer.
+ *   inverse   interpolateStep calls cvInvert(H, H_inv, CV_SVD); here the 3 x 3 inverse is the closed-form adjugate over the
+ *             determinant in f64 with a fixed order of operations, all zeros where the determinant is 0 or not finite (the point
+ *             then stays at its grid position).  This is the one step whose parity with a real OpenCV is not pinned.
+ *   params    normalised as FastHessian::saveParameters does: octaves outside 1..4 give 5, intervals outside 1..4 give 4 (nothing
+ *             reads it afterwards), init_sample outside 1..6 gives 2, thresh < 0 (or NaN) gives 0.0004f.
+ *   refusals  MODSX_ERR_ARG with a message, before any launch: a null pointer, n_imgs < 0, an image for which a layer the
+ *             parameters ask for has width or height 0 (cols / init_sample / 2^(octaves - 1) == 0, or rows likewise: the
+ *             reference's assert aborts there).  n_imgs == 0 succeeds.  Pixels must be finite.
+ * No orientation is assigned (the branch calls no getOrientation): keypoints carry the frame of orientation 0.  SURF is no
+ * detector of the ladder, of modsx_rep or of the sharded path. */
+#define MODSX_DET_SURF 6                 /* detector_type DET_SURF, detectors/structures.hpp */
+#define MODSX_SURFDET_MAX_LAYERS 12
+typedef struct modsx_surfdet_params {
+  int octaves, intervals, init_sample;   /* the [SURF] section of the config files: 4, 4, 2 */
+  float thresh;                          /* 0.0004 */
+} modsx_surfdet_params;
+/* out: malloc'd (modsx_free) keypoints as the branch fills det_kp: x, y, s = the Ipoint's f32 x, y, scale widened to double,
+ * a11 = cos(0.0), a12 = sin(0.0), a21 = -sin(0.0) (that is -0.0), a22 = cos(0.0), every other field 0.  Returns their number. */
+int modsx_detect_surf(modsx_ctx *ctx, const modsx_image *img, const modsx_surfdet_params *par, modsx_keypoint **out);
+/* The same for n_imgs images of any sizes with shared launches: out = the keypoints of image 0, then image 1, ...;
+ * counts[i] = the number of image i.  Returns the total.  Each image's list equals what modsx_detect_surf gives for it. */
+int modsx_detect_surf_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_surfdet_params *par,
+                            modsx_keypoint **out, int *counts);
+/* host only: regions of SURF keypoints as the branch leaves them -- type = MODSX_DET_SURF, det_kp as given (no scaling and no
+ * rectification: the branch does none), img_id, id = index, the rest as modsx_detect_affine_regions leaves it.  Returns n. */
+int modsx_surf_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out);
+/* host only: the layer table the kernels would build for a rows x cols image, layers [MODSX_SURFDET_MAX_LAYERS][4] = (width,
+ * height, step, filter) (may be NULL).  Returns the number of layers, or MODSX_ERR_ARG as above. */
+int modsx_surfdet_geometry(int rows, int cols, const modsx_surfdet_params *par, int *layers);
+/* host only: *out = the parameters as saveParameters stores them */
+int modsx_surfdet_normalise(const modsx_surfdet_params *par, modsx_surfdet_params *out);
+/* Stage tap of one image.  integral [rows][cols]; layers as modsx_surfdet_geometry; resp (f32) / lap (u8): every plane, one after
+ * the other in layer order; the raw extrema in push order, the first cap_ext of them: ext [cap_ext][4] = (octave, interval, r, c
+ * of the t layer), dD [.][3] = (dx, dy, ds), H [.][6] = (dxx, dxy, dxs, dyy, dys, dss), x [.][3] = (xc, xr, xi), accepted [.],
+ * laplacian [.]; *n_ext = how many there are (call again with a larger cap_ext when it exceeds cap_ext).  Returns the number of
+ * layers. */
+int modsx_debug_surfdet(modsx_ctx *ctx, const modsx_image *img, const modsx_surfdet_params *par, float *integral, int *layers, float *resp,
+                        unsigned char *lap, int *ext, double *dD, double *H, double *x, int *accepted, int *laplacian, int cap_ext,
+                        int *n_ext);
+/* SURF detector work of this context since modsx_create, cumulative (measurement hook): calls that launched, images, extrema
+ * found, points accepted, regrows of the point buffer.  Fills out[0 .. min(n, 5) - 1], returns 5. */
+int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n);
+
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel
  * class, GPU milliseconds, launch count and algorithmic work (bytes; flops for the matcher).  Classes in order:

@@ -36,6 +36,15 @@ class HessAffParams(C.Structure):
                 ("affInitialSigma", C.c_float), ("doBaumberg", C.c_int), ("detectorType", C.c_int)]
 
 
+class SurfDetParams(C.Structure):
+    """modsx_surfdet_params: the [SURF] section of the config files"""
+    _fields_ = [("octaves", C.c_int), ("intervals", C.c_int), ("init_sample", C.c_int), ("thresh", C.c_float)]
+
+
+def surfdet_params(octaves=4, intervals=4, init_sample=2, thresh=0.0004):
+    return SurfDetParams(int(octaves), int(intervals), int(init_sample), float(thresh))
+
+
 class MserParams(C.Structure):
     _fields_ = [("min_size", C.c_int), ("max_area", C.c_double), ("min_margin", C.c_double), ("relative", C.c_int),
                 ("mode", C.c_int), ("reg_number", C.c_int), ("rel_threshold", C.c_float), ("rel_reg_number", C.c_float)]
@@ -126,6 +135,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_describe_regions_dspsift", "modsx_describe_regions_dspsift_device", "modsx_dsp_counters",
            "modsx_surf_patches", "modsx_surf_patches_device", "modsx_describe_regions_surf", "modsx_describe_regions_surf_device",
            "modsx_surf_tables", "modsx_surf_counters",
+           "modsx_detect_surf", "modsx_detect_surf_batch", "modsx_surf_regions", "modsx_surfdet_geometry", "modsx_surfdet_normalise",
+           "modsx_debug_surfdet", "modsx_surfdet_counters",
            "modsx_daisy_dim", "modsx_daisy_patches", "modsx_daisy_patches_device", "modsx_describe_regions_daisy",
            "modsx_describe_regions_daisy_device", "modsx_daisy_tables", "modsx_daisy_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -150,6 +161,9 @@ DSP_COUNTERS = ("calls", "regions", "scale_passes")
 # include/modsx.h: modsx_surf_counters, in its order
 SURF_COUNTERS = ("calls", "patches", "sub_batches")
 SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
+# include/modsx.h: modsx_surfdet_counters, in its order
+SURFDET_COUNTERS = ("calls", "images", "extrema", "accepted", "regrows")
+DET_SURF, SURFDET_MAX_LAYERS = 6, 12      # include/modsx.h: MODSX_DET_SURF, MODSX_SURFDET_MAX_LAYERS
 # include/modsx.h: modsx_daisy_counters, in its order
 DAISY_COUNTERS = ("calls", "patches", "sub_batches")
 DAISY_MAX_DIM, DAISY_MAX_TAPS = 200, 51      # include/modsx.h: MODSX_DAISY_MAX_DIM, MODSX_DAISY_MAX_TAPS
@@ -293,6 +307,13 @@ def lib():
         L.modsx_daisy_patches_device.argtypes = L.modsx_daisy_patches.argtypes
         L.modsx_describe_regions_daisy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double] + [C.c_int] * 8 + [C.c_void_p]
         L.modsx_describe_regions_daisy_device.argtypes = L.modsx_describe_regions_daisy.argtypes
+        L.modsx_detect_surf.argtypes = [C.c_void_p] * 4
+        L.modsx_detect_surf_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_surf_regions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_surfdet_geometry.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.modsx_surfdet_normalise.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_debug_surfdet.argtypes = [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
+        L.modsx_surfdet_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_daisy_tables.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9
         L.modsx_daisy_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
@@ -435,6 +456,30 @@ def detect_affine_regions(kps, img_id=0, det_type=0):
     out = np.zeros(len(kps), REGION)
     _check(lib().modsx_detect_affine_regions(_p(kps), len(kps), img_id, det_type, _p(out)), "detect_affine_regions")
     return out
+
+
+def surf_regions(kps, img_id=0):
+    """Regions of SURF keypoints as the reference's SURF branch leaves them: type DET_SURF, det_kp as given (no device needed)."""
+    kps = np.ascontiguousarray(kps, KEYPOINT)
+    out = np.zeros(len(kps), REGION)
+    _check(lib().modsx_surf_regions(_p(kps), len(kps), int(img_id), _p(out)), "surf_regions")
+    return out
+
+
+def surfdet_normalise(params):
+    """The parameters as FastHessian::saveParameters stores them (no device needed)."""
+    out = SurfDetParams()
+    _check(lib().modsx_surfdet_normalise(C.byref(params), C.byref(out)), "surfdet_normalise")
+    return out
+
+
+def surfdet_geometry(rows, cols, params=None):
+    """[n][4] int32 (width, height, step, filter): the response layers the SURF detector builds for a rows x cols image; raises
+    where the library refuses the image (no device needed)."""
+    params = params or surfdet_params()
+    layers = np.zeros((SURFDET_MAX_LAYERS, 4), np.int32)
+    n = _check(lib().modsx_surfdet_geometry(int(rows), int(cols), C.byref(params), _p(layers)), "surfdet_geometry")
+    return layers[:n].copy()
 
 
 def reproject_regions(regs, H, w, h):
@@ -882,6 +927,56 @@ class Context(object):
     def describe_regions_surf_device(self, img, regs, out_ptr, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1):
         """describe_regions_surf into a device pointer to [n][64] float32 (4-byte aligned)."""
         return self.describe_regions_surf(img, regs, mr_size, patch_size, fast, photo_norm, out_ptr=out_ptr)
+
+    # ---- the SURF detector (engine_surfdet.hip) ----
+    def detect_surf(self, img, params=None):
+        """OpenSURF's FastHessian on the image: KEYPOINT records in the reference's push order (x, y, s and the frame of
+        orientation 0)."""
+        params = params or surfdet_params()
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_surf(self._c(), C.c_void_p(img.h), C.byref(params), C.byref(out)), "detect_surf")
+        return _take(out, n, KEYPOINT)
+
+    def detect_surf_batch(self, imgs, params=None):
+        """detect_surf of several images (any sizes) with shared launches: a list of KEYPOINT arrays."""
+        params = params or surfdet_params()
+        ptrs = (C.c_void_p * max(1, len(imgs)))(*[im.h for im in imgs])
+        counts = np.zeros(max(1, len(imgs)), np.int32)
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_surf_batch(self._c(), ptrs, len(imgs), C.byref(params), C.byref(out), _p(counts)),
+                   "detect_surf_batch")
+        allk = _take(out, n, KEYPOINT)
+        ends = np.cumsum(counts[:len(imgs)])
+        return [allk[e - k:e].copy() for e, k in zip(ends, counts[:len(imgs)])]
+
+    def debug_surfdet(self, img, params=None):
+        """modsx_debug_surfdet: dict(layers [n][4], integral, resp / lap: lists of planes, extrema [m][4] (o, i, r, c), dD [m][3],
+        H [m][6], x [m][3], accepted [m], laplacian [m]) -- the stages of detect_surf for one image."""
+        params = params or surfdet_params()
+        layers = surfdet_geometry(img.rows, img.cols, params)
+        sizes = layers[:, 0].astype(np.int64) * layers[:, 1]
+        integral = np.zeros((img.rows, img.cols), np.float32)
+        resp, lap = np.zeros(int(sizes.sum()), np.float32), np.zeros(int(sizes.sum()), np.uint8)
+        lay = np.zeros((SURFDET_MAX_LAYERS, 4), np.int32)
+        cap = 4096
+        while True:
+            ext, dD, H, x = np.zeros((cap, 4), np.int32), np.zeros((cap, 3)), np.zeros((cap, 6)), np.zeros((cap, 3))
+            acc, lp = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+            n_ext = C.c_int(0)
+            nl = _check(lib().modsx_debug_surfdet(self._c(), C.c_void_p(img.h), C.byref(params), _p(integral), _p(lay), _p(resp), _p(lap),
+                                                  _p(ext), _p(dD), _p(H), _p(x), _p(acc), _p(lp), cap, C.byref(n_ext)), "debug_surfdet")
+            if n_ext.value <= cap:
+                break
+            cap = n_ext.value
+        assert nl == len(layers) and np.array_equal(lay[:nl], layers)
+        m, ofs = n_ext.value, np.concatenate([[0], np.cumsum(sizes)])
+        plane = lambda a, k: a[ofs[k]:ofs[k + 1]].reshape(layers[k, 1], layers[k, 0])      # noqa: E731
+        return dict(layers=layers, integral=integral, resp=[plane(resp, k) for k in range(nl)], lap=[plane(lap, k) for k in range(nl)],
+                    extrema=ext[:m], dD=dD[:m], H=H[:m], x=x[:m], accepted=acc[:m].astype(bool), laplacian=lp[:m])
+
+    def surfdet_counters(self):
+        """dict of SURFDET_COUNTERS: SURF detector work of this context since it was created (cumulative)."""
+        return self._counters("modsx_surfdet_counters", SURFDET_COUNTERS)
 
     def _counters(self, fn_name, names):
         v = (C.c_long * len(names))()

@@ -1656,6 +1656,57 @@ int modsx_surf_counters(modsx_ctx *ctx, long *out, int n) {
   return read_counters("modsx_surf_counters", ctx->surfCounters, 3, out, n);
 }
 
+// ---- the SURF detector (engine_surfdet.hip) ----
+int modsx_surfdet_normalise(const modsx_surfdet_params *par, modsx_surfdet_params *out) {
+  NEED(par); NEED(out);
+  *out = surfdet_normalise(*par);
+  return MODSX_OK;
+}
+int modsx_surfdet_geometry(int rows, int cols, const modsx_surfdet_params *par, int *layers) {
+  NEED(par);
+  return surfdet_geometry("modsx_surfdet_geometry", rows, cols, *par, layers);
+}
+int modsx_surf_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out) {
+  if (n < 0 || (n > 0 && (!kps || !out))) { mx::set_error("modsx_surf_regions: bad argument"); return MODSX_ERR_ARG; }
+  surf_regions(kps, n, img_id, out);
+  return n;
+}
+int modsx_detect_surf_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_surfdet_params *par,
+                            modsx_keypoint **out, int *counts) {
+  NEED(ctx); NEED(par); NEED(out);
+  if (n_imgs < 0 || (n_imgs > 0 && (!imgs || !counts))) { mx::set_error("modsx_detect_surf_batch: bad argument"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n_imgs; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  std::vector<std::vector<modsx_keypoint>> k(n_imgs);
+  const int rc = detect_surf_batch(ctx, imgs, n_imgs, *par, k.data());
+  if (rc) return rc;
+  std::vector<modsx_keypoint> all;
+  for (int i = 0; i < n_imgs; i++) { counts[i] = (int)k[i].size(); all.insert(all.end(), k[i].begin(), k[i].end()); }
+  *out = to_malloc(all);
+  return (int)all.size();
+}
+int modsx_detect_surf(modsx_ctx *ctx, const modsx_image *img, const modsx_surfdet_params *par, modsx_keypoint **out) {
+  NEED(ctx); NEED(img); NEED(par); NEED(out);
+  int count = 0;
+  const modsx_image *imgs[1] = {img};
+  return modsx_detect_surf_batch(ctx, imgs, 1, par, out, &count);
+}
+int modsx_debug_surfdet(modsx_ctx *ctx, const modsx_image *img, const modsx_surfdet_params *par, float *integral, int *layers, float *resp,
+                        unsigned char *lap, int *ext, double *dD, double *H, double *x, int *accepted, int *laplacian, int cap_ext,
+                        int *n_ext) {
+  NEED(ctx); NEED(img); NEED(par); NEED(integral); NEED(layers); NEED(resp); NEED(lap); NEED(n_ext);
+  if (cap_ext < 0 || (cap_ext > 0 && (!ext || !dD || !H || !x || !accepted || !laplacian))) {
+    mx::set_error("modsx_debug_surfdet: bad argument");
+    return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  return debug_surfdet(ctx, img, *par, integral, layers, resp, lap, ext, dD, H, x, accepted, laplacian, cap_ext, n_ext);
+}
+int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  return read_counters("modsx_surfdet_counters", ctx->sdCounters, 5, out, n);
+}
+
 // ---- DAISY (engine_daisy.hip) ----
 #define DAISY_ARGS(fn, bad)                                                                           \
   do {                                                                                                \

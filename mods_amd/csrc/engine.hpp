@@ -380,6 +380,28 @@ struct DaisyTab {
   float taps[4 * DAISY_TAP_ROW];
 };
 void launch_daisy(hipStream_t s, const float *patches, int n, float *out, const DescJob *jobs, const DaisyTab *tab, int nrmType);
+// The SURF detector (kernels_surfdet.hip; OpenSURF's FastHessian on a whole view).  Every kernel reads a job table in device memory,
+// one SdJob per image, and finds its (job, part) through a table of workgroup runs, so a view set is one launch set.
+constexpr int SD_MAX_LAYERS = MODSX_SURFDET_MAX_LAYERS, SD_ROWS_PER_WG = 16, SD_TILE = 256;
+struct SdLayer { int w, h, step, filter; unsigned long long ofs; };   // ofs: the plane's offset in the response (f32) and laplacian (u8) arenas
+struct SdJob { const float *src; float *integ; int rows, cols, nLayers, pad; SdLayer L[SD_MAX_LAYERS]; };
+// a run of workgroups that starts at workgroup blk0: 16 rows / 64 columns of image `job` (a, b unused), SD_TILE pixels of its layer a, or
+// SD_TILE raster positions of the t layer of (octave a, interval b)
+struct SdSeg { int job, a, b, blk0; };
+struct SdPoint { float x, y, scale; int laplacian; };                  // an Ipoint as getIpoints pushes it
+struct SdExt { int job, o, i, r, c, accepted, laplacian, pad; double dD[3], H[6], x[3]; };   // modsx_debug_surfdet: one raw extremum
+void launch_surfdet_integral(hipStream_t s, const SdJob *jobs, const SdSeg *rowSegs, int nRowSegs, int rowBlocks, const SdSeg *colSegs,
+                             int nColSegs, int colBlocks);
+void launch_surfdet_responses(hipStream_t s, const SdJob *jobs, const SdSeg *segs, int nsegs, int blocks, float *resp, unsigned char *lap);
+// the first pass over the t layers (flags [tiles][SD_TILE]: bit 0 extremum, bit 1 accepted; counts [tiles] int2), then the exclusive
+// scan (offs [tiles + 1] int2; jobStart [nj + 1] int2 = offs at tile0[j])
+void launch_surfdet_scan(hipStream_t s, const SdJob *jobs, const SdSeg *segs, int nsegs, int tiles, const float *resp,
+                         const unsigned char *lap, float thresh, unsigned char *flags, int *counts, int *offs, const int *tile0, int nj,
+                         int *jobStart);
+// the second pass: points [capPts] and / or ext [capExt] in push order (either may be null)
+void launch_surfdet_emit(hipStream_t s, const SdJob *jobs, const SdSeg *segs, int nsegs, int tiles, const float *resp,
+                         const unsigned char *lap, const unsigned char *flags, const int *offs, SdPoint *points, int capPts, SdExt *ext,
+                         int capExt);
 // the patch-out form of k_describe (kernels_describe.hip): [slot][1681] f32, slot = outIdx (patchByOutIdx) or the job's index
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -501,6 +523,11 @@ struct modsx_ctx {
   int daisyTabKey[DAISY_TABS] = {0, 0, 0, 0};   // rad << 16 | radq << 8 | thq; 0: the slot is empty
   int daisyTabNext = 0;
   long daisyCounters[3] = {0, 0, 0};     // modsx_daisy_counters: calls, patches, sub-batches
+  // the SURF detector (engine_surfdet.hip): integral images, response and laplacian planes, the scan's flags / counts / offsets, the
+  // job and run tables, the points (and, for the debug tap, the raw extrema) of one launch set
+  mx::DevBuf sdInteg, sdResp, sdLap, sdFlags, sdCounts, sdTab, sdPoints, sdExt;
+  mx::PinBuf sdHost, sdBack;
+  long sdCounters[5] = {0, 0, 0, 0, 0};  // modsx_surfdet_counters: calls, images, extrema found, points accepted, buffer regrows
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

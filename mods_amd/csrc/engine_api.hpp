@@ -112,6 +112,16 @@ int surf_check_args(const char *fn, int patchSize, double mrSize);
 int surf_patches(modsx_ctx *c, const float *patches, int n, double mrSize, float *desc, bool onDevice);
 int describe_regions_surf(modsx_ctx *c, const modsx_image *img, const modsx_region *regs, int n, double mrSize, int patchSize, int fast,
                           int photoNorm, float *desc, bool onDevice);
+// The SURF detector (engine_surfdet.hip).  surfdet_normalise: saveParameters; surfdet_geometry: layers [12][4] (may be null) = (width,
+// height, step, filter), returns their number or MODSX_ERR_ARG for a layer of width or height 0; surfdet_check: the refusals of the
+// entries that need no device; fn names the entry in the error text.  out [n]: the keypoints of every image in push order
+modsx_surfdet_params surfdet_normalise(const modsx_surfdet_params &p);
+int surfdet_geometry(const char *fn, int rows, int cols, const modsx_surfdet_params &par, int *layers);
+int surfdet_check(const char *fn, const modsx_image *const *imgs, int n, const modsx_surfdet_params &par);
+void surf_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out);
+int detect_surf_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_surfdet_params &par, std::vector<modsx_keypoint> *out);
+int debug_surfdet(modsx_ctx *c, const modsx_image *img, const modsx_surfdet_params &par, float *integral, int *layers, float *resp,
+                  unsigned char *lap, int *ext, double *dD, double *H, double *x, int *accepted, int *laplacian, int capExt, int *nExt);
 // DAISY (engine_daisy.hip).  patches [n][41][41] f32 / desc [n][(radq * thq + 1) * 8] f32: host pointers, or device pointers
 // (4-byte aligned) when onDevice.  daisy_check_args: the refusals that need no device (patchSize, rad, radq, thq, histq, nrmType),
 // made by the entries of capi.hip before they call in here; fn names the entry in the error text
