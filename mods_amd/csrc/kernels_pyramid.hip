@@ -41,6 +41,13 @@ MX_D int find_job(const int *tile0, int nj, int t) {
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));   // two f32 lanes of the packed ALU (v_pk_mul_f32 / v_pk_add_f32)
+// Four floats that are only dword-aligned, in the global address space: a level plane's rows start at any dword (odd widths),
+// and gfx950 moves such a vector with one global_load_dwordx4 / global_store_dwordx4.
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef f4 f4u __attribute__((aligned(4)));
+typedef const f4u __attribute__((address_space(1))) *gcf4u_p;
+typedef f4u __attribute__((address_space(1))) *gf4u_p;
+typedef float __attribute__((address_space(1))) *gfloat_p;
 
 // Vector issue is what the pipeline's concurrent streams compete for, so both filter passes run on the packed f32 ALU: two
 // outputs per instruction, each with the operand order and rounding of the scalar form (no contraction, IEEE mul and add).
@@ -65,25 +72,49 @@ __global__ __launch_bounds__(256) void k_blur_hess(BlurBatch batch) {
   __shared__ __attribute__((aligned(16))) float tmp[sh * TMP_W];
   float *blr = src;
   const int tid = threadIdx.x;
-  // stage 1: clamped input tile
+  // stage 1: clamped input tile.  One item is one 4-column group of one row pair (rows 2 lp, 2 lp + 1 of the tile): the two rows'
+  // four floats each, written as the two 16-byte pair-interleaved vectors stage 2 reads.  A pair-row holds SW columns; stage 2
+  // never reads the sw .. SW - 1 padding.  A group whose four columns all lie in [0, cols - 1] takes one 16-byte load per row:
+  // gy is clamped into [0, rows - 1] and gx0 >= 0, gx0 + 3 <= cols - 1, so the four floats are elements gy cols + gx0 .. + 3 of
+  // the rows x cols plane -- inside it whatever the plane's alignment.  Any other group (a view's left / right edge) takes the
+  // eight clamped scalar loads; the choice is per lane, and a wavefront without a border group skips that side.
   {   // all loads of a thread are issued before the first LDS write: one memory round trip for the tile
-    constexpr int PER = (sh * sw + 255) / 256;
-    float t[PER];
+    constexpr int NG = SW / 4, NI = (sh / 2) * NG, PER = (NI + 255) / 256;
+    const gcfloat_p P = as_global(jb.src);
+    f4 t0[PER], t1[PER];
 #pragma unroll
     for (int u = 0; u < PER; u++) {
-      const int i = tid + 256 * u, ii = i < sh * sw ? i : sh * sw - 1;
-      const int ly = ii / sw, lx = ii - ly * sw;
-      int gy = ty0 - 1 - R + ly, gx = tx0 - 1 - R + lx;
-      gy = gy < 0 ? 0 : (gy > rows - 1 ? rows - 1 : gy);
-      gx = gx < 0 ? 0 : (gx > cols - 1 ? cols - 1 : gx);
-      // 32-bit element offset from the job's (wave-uniform) plane: one 24-bit multiply-add, the load in the scalar base + vector
+      const int i = tid + 256 * u, ii = i < NI ? i : NI - 1;
+      const int lp = ii / NG, g = ii - lp * NG;
+      int gy0 = ty0 - 1 - R + 2 * lp, gy1 = gy0 + 1;
+      gy0 = gy0 < 0 ? 0 : (gy0 > rows - 1 ? rows - 1 : gy0);
+      gy1 = gy1 < 0 ? 0 : (gy1 > rows - 1 ? rows - 1 : gy1);
+      const int gx0 = tx0 - 1 - R + 4 * g;
+      // 32-bit element offset from the job's (wave-uniform) plane: one 24-bit multiply per row, the load in the scalar base + vector
       // offset form (a level is far below 2^24 px per side and 2^30 px in all, capi.hip image_size_ok)
-      t[u] = as_global(jb.src)[__umul24((unsigned)gy, (unsigned)cols) + (unsigned)gx];
+      const unsigned o0 = __umul24((unsigned)gy0, (unsigned)cols), o1 = __umul24((unsigned)gy1, (unsigned)cols);
+      if (gx0 >= 0 && gx0 + 3 <= cols - 1) {
+        t0[u] = *reinterpret_cast<gcf4u_p>(P + (o0 + (unsigned)gx0));
+        t1[u] = *reinterpret_cast<gcf4u_p>(P + (o1 + (unsigned)gx0));
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          int gx = gx0 + q;
+          gx = gx < 0 ? 0 : (gx > cols - 1 ? cols - 1 : gx);
+          t0[u][q] = P[o0 + (unsigned)gx];
+          t1[u][q] = P[o1 + (unsigned)gx];
+        }
+      }
     }
 #pragma unroll
     for (int u = 0; u < PER; u++) {
       const int i = tid + 256 * u;
-      if (i < sh * sw) { const int ly = i / sw, lx = i - ly * sw; src[(ly >> 1) * (2 * SW) + 2 * lx + (ly & 1)] = t[u]; }
+      if (i < NI) {
+        const int lp = i / NG, g = i - lp * NG;
+        float4 *D = reinterpret_cast<float4 *>(src + lp * (2 * SW) + 8 * g);
+        D[0] = make_float4(t0[u].x, t1[u].x, t0[u].y, t1[u].y);
+        D[1] = make_float4(t0[u].z, t1[u].z, t0[u].w, t1[u].w);
+      }
     }
   }
   __syncthreads();
@@ -132,6 +163,7 @@ __global__ __launch_bounds__(256) void k_blur_hess(BlurBatch batch) {
   __syncthreads();
   // stage 4: write blur and response
   const float norm2 = jb.norm * jb.norm;
+#ifdef MODSX_BLUR_SCALAR_STORE   // tuning build: the one-pixel-per-thread store, to price the 4-pixel form below
   for (int i = tid; i < TH * TW; i += 256) {
     const int ly = i / TW, lx = i - ly * TW;
     const int gy = ty0 + ly, gx = tx0 + lx;
@@ -153,6 +185,51 @@ __global__ __launch_bounds__(256) void k_blur_hess(BlurBatch batch) {
       jb.resp[gofs] = o;
     }
   }
+#else
+  // A thread takes four neighbouring outputs of one row: the 3 x 6 window of blr as a 16-byte and an 8-byte LDS read per row
+  // (TMP_W and lx are multiples of 4), the four responses by the expression and border test of k_hessian, and one 16-byte store
+  // per plane when the four pixels exist (gx + 3 < cols: elements gofs .. gofs + 3 of row gy), per pixel otherwise.
+  for (int i = tid; i < TH * (TW / 4); i += 256) {
+    const int ly = i / (TW / 4), lx = 4 * (i - ly * (TW / 4));
+    const int gy = ty0 + ly, gx = tx0 + lx;
+    if (gy >= rows || gx >= cols) continue;
+    float w[3][6];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const float *B = blr + (ly + r) * TMP_W + lx;   // window column c is tile column lx - 1 + c
+      const float4 a = *reinterpret_cast<const float4 *>(B);
+      const float2 b = *reinterpret_cast<const float2 *>(B + 4);
+      w[r][0] = a.x; w[r][1] = a.y; w[r][2] = a.z; w[r][3] = a.w; w[r][4] = b.x; w[r][5] = b.y;
+    }
+    const unsigned gofs = __umul24((unsigned)gy, (unsigned)cols) + (unsigned)gx;
+    const gfloat_p blurp = (gfloat_p)jb.blur, respp = (gfloat_p)jb.resp;   // resp may be null: offset only where it is stored
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    if (jb.resp) {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        if (gy >= 1 && gy < rows - 1 && gx + q >= 1 && gx + q < cols - 1) {
+          const float v11 = w[0][q], v12 = w[0][q + 1], v13 = w[0][q + 2];
+          const float v21 = w[1][q], v22 = w[1][q + 1], v23 = w[1][q + 2];
+          const float v31 = w[2][q], v32 = w[2][q + 1], v33 = w[2][q + 2];
+          float Lxx = (v21 - 2 * v22 + v23);
+          float Lyy = (v12 - 2 * v22 + v32);
+          float Lxy = (v13 - v11 + v31 - v33) / 4.0f;
+          o[q] = (Lxx * Lyy - Lxy * Lxy) * norm2;
+        }
+    }
+    if (gx + 3 < cols) {
+      *reinterpret_cast<gf4u_p>(blurp + gofs) = (f4){w[1][1], w[1][2], w[1][3], w[1][4]};
+      if (jb.resp) *reinterpret_cast<gf4u_p>(respp + gofs) = (f4){o[0], o[1], o[2], o[3]};
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        if (gx + q < cols) {
+          blurp[gofs + q] = w[1][q + 1];
+          if (jb.resp) respp[gofs + q] = o[q];
+        }
+    }
+  }
+#endif
 }
 
 // HessianResponse of an existing level (first level of octaves >= 1), pyramid.cpp:223-281
@@ -203,31 +280,53 @@ MX_D float resize_half_px(const float *src, int sr, int sc, int dx, int dy) {
   return out;
 }
 // First level of an octave >= 1: the 2 x 2 resize and, in the same launch, the Hessian response of the resized level
-// (HessianResponse, pyramid.cpp:223-281; the expression of k_hessian) -- a thread forms the 3 x 3 resized values its
-// response needs itself (the same f32 values its neighbours store), which saves a launch per octave.
+// (HessianResponse, pyramid.cpp:223-281; the expression of k_hessian), which saves a launch per octave.  A workgroup owns a
+// 64 x RESIZE_TH tile of the destination (a thread two pixels, one above the other).  With a response it first parks the resized
+// values of the tile and its one-pixel ring in LDS, each formed once by resize_half_px (1.24 values per output instead of the
+// 9 a pixel on its own would form); ring entries outside the destination are neither formed nor read: the response is 0 on the
+// border.  Jobs without a response form and store their pixels directly.
+constexpr int RESIZE_TH = 8, RESIZE_LW = 64 + 2;
 __global__ __launch_bounds__(256) void k_resize_half(ResizeBatch batch) {
   const int ji = find_job(batch.tile0, batch.nj, blockIdx.x);
   const ResizeJob jb = batch.j[ji];
   const int lt = blockIdx.x - batch.tile0[ji], ntx = (jb.dcols + 63) / 64;
-  const int dx = (lt % ntx) * 64 + (threadIdx.x & 63), dy = (lt / ntx) * 4 + (threadIdx.x >> 6);
-  if (dx >= jb.dcols || dy >= jb.drows) return;
+  const int tx0 = (lt % ntx) * 64, ty0 = (lt / ntx) * RESIZE_TH;
+  const int lx = threadIdx.x & 63, ly = 2 * (threadIdx.x >> 6);
+  const int dx = tx0 + lx;
   const int sr = jb.srows, sc = jb.scols, rows = jb.drows, cols = jb.dcols;
-  const float v22 = resize_half_px(jb.src, sr, sc, dx, dy);
-  jb.dst[(size_t)dy * cols + dx] = v22;
-  if (!jb.resp) return;
-  float o = 0.f;
-  if (dy >= 1 && dy < rows - 1 && dx >= 1 && dx < cols - 1) {
-    const float v11 = resize_half_px(jb.src, sr, sc, dx - 1, dy - 1), v12 = resize_half_px(jb.src, sr, sc, dx, dy - 1),
-                v13 = resize_half_px(jb.src, sr, sc, dx + 1, dy - 1);
-    const float v21 = resize_half_px(jb.src, sr, sc, dx - 1, dy), v23 = resize_half_px(jb.src, sr, sc, dx + 1, dy);
-    const float v31 = resize_half_px(jb.src, sr, sc, dx - 1, dy + 1), v32 = resize_half_px(jb.src, sr, sc, dx, dy + 1),
-                v33 = resize_half_px(jb.src, sr, sc, dx + 1, dy + 1);
-    float Lxx = (v21 - 2 * v22 + v23);
-    float Lyy = (v12 - 2 * v22 + v32);
-    float Lxy = (v13 - v11 + v31 - v33) / 4.0f;
-    o = (Lxx * Lyy - Lxy * Lxy) * (jb.norm * jb.norm);
+  if (!jb.resp) {   // (uniform over the workgroup)
+    for (int k = 0; k < 2; k++) {
+      const int dy = ty0 + ly + k;
+      if (dx < cols && dy < rows) jb.dst[(size_t)dy * cols + dx] = resize_half_px(jb.src, sr, sc, dx, dy);
+    }
+    return;
   }
-  jb.resp[(size_t)dy * cols + dx] = o;
+  __shared__ float v[(RESIZE_TH + 2) * RESIZE_LW];   // v[ry][rx] = resized pixel (ty0 - 1 + ry, tx0 - 1 + rx)
+  for (int i = threadIdx.x; i < (RESIZE_TH + 2) * RESIZE_LW; i += 256) {
+    const int ry = i / RESIZE_LW, rx = i - ry * RESIZE_LW;
+    const int y = ty0 - 1 + ry, x = tx0 - 1 + rx;
+    if (y >= 0 && y < rows && x >= 0 && x < cols) v[i] = resize_half_px(jb.src, sr, sc, x, y);
+  }
+  __syncthreads();
+  if (dx >= cols) return;
+  for (int k = 0; k < 2; k++) {
+    const int dy = ty0 + ly + k;
+    if (dy >= rows) break;
+    const float *B = v + (ly + k + 1) * RESIZE_LW + (lx + 1);
+    const float v22 = B[0];
+    jb.dst[(size_t)dy * cols + dx] = v22;
+    float o = 0.f;
+    if (dy >= 1 && dy < rows - 1 && dx >= 1 && dx < cols - 1) {
+      const float v11 = B[-RESIZE_LW - 1], v12 = B[-RESIZE_LW], v13 = B[-RESIZE_LW + 1];
+      const float v21 = B[-1], v23 = B[1];
+      const float v31 = B[RESIZE_LW - 1], v32 = B[RESIZE_LW], v33 = B[RESIZE_LW + 1];
+      float Lxx = (v21 - 2 * v22 + v23);
+      float Lyy = (v12 - 2 * v22 + v32);
+      float Lxy = (v13 - v11 + v31 - v33) / 4.0f;
+      o = (Lxx * Lyy - Lxy * Lxy) * (jb.norm * jb.norm);
+    }
+    jb.resp[(size_t)dy * cols + dx] = o;
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -600,7 +699,7 @@ bool launch_resize_half(hipStream_t s, const ResizeBatch &bin, int nj, int, int)
   ResizeBatch b = bin;
   b.nj = nj;
   int t = 0;
-  for (int i = 0; i < nj; i++) { b.tile0[i] = t; t += ((b.j[i].dcols + 63) / 64) * ((b.j[i].drows + 3) / 4); }
+  for (int i = 0; i < nj; i++) { b.tile0[i] = t; t += ((b.j[i].dcols + 63) / 64) * ((b.j[i].drows + RESIZE_TH - 1) / RESIZE_TH); }
   b.tile0[nj] = t;
   if (t > 0) MX_DUP(K_RESIZE) hipLaunchKernelGGL(k_resize_half, dim3(t), dim3(256), 0, s, b);
   return t > 0;
