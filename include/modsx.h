@@ -422,6 +422,14 @@ int modsx_debug_scan_levels(modsx_ctx *ctx, const float *resps, const float *blu
                             const modsx_hessaff_params *par, modsx_candidate **cands, int *n_cands, modsx_sskp **out);
 int modsx_debug_detect_scalespace_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n, const modsx_hessaff_params *par,
                                         modsx_sskp **out, int *counts);
+/* The device half of DetectMSERs in the view loop, for one launch set of 1 <= n <= 32 views (views_host[i]: rows[i] x cols[i]
+ * f32 on the host, any rows, cols >= 1, sizes may differ; copied to device scratch as they are): the views go through the
+ * function the loop itself calls -- u8 truncation, (unsigned char)float as x86 evaluates it, and the stable counting sort by grey
+ * level, device sort on -- and come back as downloaded.  u8 and order receive view after view (rows x cols bytes / ints each;
+ * order = the offsets (r + 1) * (cols + 2) + c + 1 of the view's pixels by (grey level, raster position)), start the n x 257
+ * level starts (start[257 i + l] = pixels of view i below level l, [257 i + 256] = its pixels).  MODSX_ERR_ARG for anything else */
+int modsx_debug_mser_front(modsx_ctx *ctx, const float *const *views_host, const int *rows, const int *cols, int n,
+                           unsigned char *u8, int *start, int *order);
 /* orientation jobs launched by the pair and view pipelines of this process, and regions they left out of the orientation launch
  * because modsx_debug_reproject_certain_drop flags them, since the last reset (measurement hook; MODSX_ORI_PREFILTER=0 in the
  * environment launches them all).  modsx_detect_orientation itself never leaves a region out */

@@ -125,7 +125,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
            "modsx_match_regions_hamming", "modsx_debug_hamming_geometry",
            "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
-           "modsx_debug_detect_scalespace_batch",
+           "modsx_debug_detect_scalespace_batch", "modsx_debug_mser_front",
            "modsx_match_fginn_f32", "modsx_match_fginn_f32_device", "modsx_match_regions_f32", "modsx_debug_match_fginn_f32",
            "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass",
            "modsx_extract_patches", "modsx_extract_patches_device", "modsx_liop_patches", "modsx_liop_patches_device",
@@ -169,6 +169,7 @@ DAISY_COUNTERS = ("calls", "patches", "sub_batches")
 DAISY_MAX_DIM, DAISY_MAX_TAPS = 200, 51      # include/modsx.h: MODSX_DAISY_MAX_DIM, MODSX_DAISY_MAX_TAPS
 DAISY_NRM_PARTIAL, DAISY_NRM_FULL, DAISY_NRM_SIFT = 0, 1, 2
 DAISY_SKIPPED, DAISY_ZEROED, DAISY_SAMPLED = 0, 1, 2     # modsx_daisy_tables: the state of a grid point
+MAXB = 32                             # csrc/engine.hpp: MODSX_MAXB, the views / images of one launch set
 KP_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s")
 KERNEL_CLASSES = ["blur_hess", "hessian", "resize", "nms_localize", "baumberg", "orientation", "patch_sample",
                   "blur_rows", "describe", "match_fginn", "gray", "warp_affine", "view_blur", "blur_cols", "match_sweep1", "match_db"]
@@ -237,6 +238,7 @@ def lib():
         L.modsx_debug_scan_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_debug_detect_scalespace_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_mser_front.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_debug_describe_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_debug_baumberg_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -1411,6 +1413,27 @@ class Context(object):
         n = _check(lib().modsx_detect_msers(self._c(), C.c_void_p(img.h), C.byref(params), C.c_double(tilt),
                                             C.c_double(zoom), C.byref(out)), "detect_msers")
         return _take(out, n, KEYPOINT)
+
+    def debug_mser_front(self, views):
+        """modsx_debug_mser_front: the device half of the MSER view loop (u8 truncation, bin sort, block layout, one download)
+        for ONE launch set of f32 views (2-d arrays, any sizes from 1 x 1, at most 32) -> per view (u8 [rows, cols], start [257]
+        int32, order [rows * cols] int32: padded offsets (r + 1) * (cols + 2) + c + 1 by grey level, raster order in a level)."""
+        views = [np.ascontiguousarray(v, np.float32) for v in views]
+        n = len(views)
+        if any(v.ndim != 2 for v in views):
+            raise ValueError("debug_mser_front: 2-d views are expected")
+        ptrs = (C.c_void_p * max(1, n))(*[v.ctypes.data for v in views])
+        rows = np.array([v.shape[0] for v in views] or [0], np.int32)
+        cols = np.array([v.shape[1] for v in views] or [0], np.int32)
+        npx = [v.size for v in views]
+        u8, order = np.zeros(max(1, sum(npx)), np.uint8), np.zeros(max(1, sum(npx)), np.int32)
+        start = np.zeros((max(1, n), 257), np.int32)
+        _check(lib().modsx_debug_mser_front(self._c(), ptrs, _p(rows), _p(cols), n, _p(u8), _p(start), _p(order)), "debug_mser_front")
+        out, at = [], 0
+        for i, v in enumerate(views):
+            out.append((u8[at:at + npx[i]].reshape(v.shape), start[i], order[at:at + npx[i]]))
+            at += npx[i]
+        return out
 
     def match_ladder(self, img1, img2, steps, params, min_matches=10, comm=None):
         """steps: list of (views, match_ratio[, detector[, descs]]); descs = [(descriptor type, FGINN ratio), ...] is the

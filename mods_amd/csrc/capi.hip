@@ -1467,6 +1467,45 @@ extern "C" __attribute__((visibility("default"))) int modsx_debug_msers_views_u8
   return (int)total;
 }
 
+// The device half of the MSER view loop on its own (test aid): the n f32 views go to the context's view scratch as they are --
+// no modsx_image_upload, which refuses images of one row or one column -- and through mser_front, the function the view loop
+// calls, with the device sort on.
+int modsx_debug_mser_front(modsx_ctx *ctx, const float *const *views_host, const int *rows, const int *cols, int n,
+                           unsigned char *u8, int *start, int *order) {
+  NEED(ctx); NEED(views_host); NEED(rows); NEED(cols); NEED(u8); NEED(start); NEED(order);
+  if (n < 1 || n > mx::MAXB) { mx::set_error("modsx_debug_mser_front: 1 .. 32 views"); return MODSX_ERR_ARG; }
+  size_t npxAll = 0;
+  for (int i = 0; i < n; i++) {
+    // the sorted offsets (r + 1) * (cols + 2) + c + 1 and the level starts are ints
+    if (!views_host[i] || rows[i] < 1 || cols[i] < 1 || ((size_t)rows[i] + 2) * ((size_t)cols[i] + 2) > 0x7fffffffu) {
+      mx::set_error("modsx_debug_mser_front: bad view"); return MODSX_ERR_ARG;
+    }
+    npxAll += (size_t)rows[i] * cols[i];
+  }
+  if (npxAll > 0x7fffffffu) { mx::set_error("modsx_debug_mser_front: too many pixels"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  CtxBusy busy(ctx);
+  const float *dv[mx::MAXB];
+  for (int i = 0; i < n; i++) {
+    const size_t b = (size_t)rows[i] * cols[i] * 4;
+    if (!ctx->viewImg[i].ensure(b)) return MODSX_ERR_NOMEM;
+    MX_HIP(hipMemcpyAsync(ctx->viewImg[i].p, views_host[i], b, hipMemcpyHostToDevice, ctx->stream));
+    dv[i] = (const float *)ctx->viewImg[i].p;
+  }
+  mx::MserFront mf;
+  const int rc = mx::mser_front(ctx, dv, rows, cols, n, true, mf);
+  if (rc) return rc;
+  size_t at = 0;
+  for (int i = 0; i < n; i++) {
+    const size_t npx = (size_t)rows[i] * cols[i];
+    memcpy(u8 + at, mf.u8[i], npx);
+    memcpy(order + at, mf.order[i], npx * 4);
+    memcpy(start + (size_t)i * 257, mf.start[i], 257 * 4);
+    at += npx;
+  }
+  return MODSX_OK;
+}
+
 int modsx_save_regions(const char *path, const modsx_region_class *classes, int nclasses) {
   if (!path || !classes || nclasses <= 0) { mx::set_error("modsx_save_regions: bad argument"); return MODSX_ERR_ARG; }
   for (int i = 0; i < nclasses; i++) {

@@ -346,6 +346,10 @@ int detect_msers_host(const uint8_t *u8, int rows, int cols, const modsx_mser_pa
 int detect_msers_views(const uint8_t *const *u8, const int *rows, const int *cols, int n, const modsx_mser_params &par,
                        const double *tilts, const double *zooms, std::vector<modsx_keypoint> *out, const int *const *devOrder = nullptr,
                        const int *const *devStart = nullptr);
+// engine_views.hip: u8 truncation (+ bin sort with devSort) of the n <= MAXB views of a launch set on the device and the one
+// download of the block; per view the host pointers into c->hMser that detect_msers_views takes
+struct MserFront { const uint8_t *u8[MAXB]; const int *order[MAXB], *start[MAXB]; };
+int mser_front(modsx_ctx *c, const float *const *dview, const int *rows, const int *cols, int n, bool devSort, MserFront &out);
 // fn(0) .. fn(n - 1) on the process-wide host worker pool (MODSX_HOST_THREADS, default min(hardware threads, 64)) + the caller
 void host_parallel_for(int n, const std::function<void(int)> &fn, bool light = false);
 void host_light_pool(bool on);   // this thread's short host loops may use the pool regardless of the sets in flight

@@ -289,6 +289,44 @@ int synth_view(modsx_ctx *c, const modsx_image *gray, const modsx_view &v, modsx
   return MODSX_OK;
 }
 
+// The MSER front end of one launch set, DetectAffineRegions(temp_img1, temp_kp1, det_par.MSERParam, DET_MSER, DetectMSERs),
+// imagerepresentation.cpp:1037, up to the component trees: the u8 truncation of every view (dview[i]: rows[i] x cols[i] floats on
+// the device) and, with devSort, the bin sort of every view -- the pixel offsets per grey level in raster order that the tree walks
+// -- in ONE block [u8 views | start: n x 257 ints | order: all views' pixels, ints] of c->misc (view i's bytes at a multiple of 64,
+// start and order at multiples of 256; the sort's blockHist scratch behind the block, on the device only), ONE download of that
+// block into c->hMser and the wait for it.  out: per view the host pointers into c->hMser (order / start null without devSort: the
+// host sorts), valid until the context's next set.
+int mser_front(modsx_ctx *c, const float *const *dview, const int *rows, const int *cols, int n, bool devSort, MserFront &out) {
+  if (n < 1 || n > MAXB) { set_error("mser_front: batch size"); return MODSX_ERR_ARG; }
+  size_t ofs[MAXB + 1], tot = 0, ordOfs[MAXB], npxAll = 0;
+  for (int i = 0; i < n; i++) {
+    ofs[i] = tot; tot += ((size_t)rows[i] * cols[i] + 63) & ~(size_t)63;
+    ordOfs[i] = npxAll; npxAll += (size_t)rows[i] * cols[i];
+  }
+  const size_t oStart = (tot + 255) & ~(size_t)255, oOrder = oStart + (((size_t)n * 257 * 4 + 255) & ~(size_t)255);
+  const size_t blockB = devSort ? oOrder + npxAll * 4 : tot;
+  const size_t histB = devSort ? mser_sort_blocks(rows, n) * 256 * 4 : 0;
+  if (!c->misc.ensure(((blockB + 255) & ~(size_t)255) + histB + 64) || !c->hMser.ensure(blockB + 64)) return MODSX_ERR_NOMEM;
+  char *base = (char *)c->misc.p;
+  for (int i = 0; i < n; i++) launch_trunc_u8(c->stream, dview[i], (uint8_t *)base + ofs[i], (size_t)rows[i] * cols[i]);
+  if (devSort) {
+    const uint8_t *du8[MAXB];
+    for (int i = 0; i < n; i++) du8[i] = (const uint8_t *)base + ofs[i];
+    launch_mser_sort(c->stream, du8, rows, cols, ordOfs, n, (int *)(base + ((blockB + 255) & ~(size_t)255)), (int *)(base + oStart), (int *)(base + oOrder));
+  }
+  if (ctx_copy(c, c->hMser.p, c->misc.p, blockB, hipMemcpyDeviceToHost) != hipSuccess || ctx_sync(c) != hipSuccess) {
+    set_error("MSER view download failed");
+    return MODSX_ERR_DEVICE;
+  }
+  const char *hb = (const char *)c->hMser.p;
+  for (int i = 0; i < n; i++) {
+    out.u8[i] = (const uint8_t *)hb + ofs[i];
+    out.order[i] = devSort ? (const int *)(hb + oOrder) + ordOfs[i] : nullptr;
+    out.start[i] = devSort ? (const int *)(hb + oStart) + (size_t)i * 257 : nullptr;
+  }
+  return MODSX_OK;
+}
+
 // The per-view loop over ITEMS = (source image, view) pairs, any mix of images in one launch set (the view-sharded path
 // batches the views a rank owns of several images / pairs: at world 8 a rank holds ~4 views per image, and launch sets of 4
 // views leave the device mostly idle).  Output regions carry img_id = view index (0 for the identity view) and ids local to
@@ -355,44 +393,16 @@ int detect_describe_items(modsx_ctx *c, const modsx_image *const *itemImg, const
     if (!rc) {
       if (pp.detector == MODSX_DET_MSER) {
         // DetectAffineRegions(temp_img1, temp_kp1, det_par.MSERParam, DET_MSER, DetectMSERs), imagerepresentation.cpp:1037:
-        // u8 truncation of every view on the device, one D2H of bytes, the component trees on host threads' time
-        // all views of the set in one buffer, ONE download; the 2 n (view, polarity) trees then run on the host pool
-        // ... and the bin sort of every view (the pixel offsets per grey level in raster order that the component tree walks) on the
-        // device too: bytes + sorted offsets + level starts in ONE block, one download (MODSX_MSER_DEVICE_SORT=0: the host sorts)
+        // u8 truncation and bin sort of every view on the device, one download (mser_front; MODSX_MSER_DEVICE_SORT=0: the host
+        // sorts); the 2 n (view, polarity) component trees then run on the host pool
         static const bool devSort = !(getenv("MODSX_MSER_DEVICE_SORT") && !atoi(getenv("MODSX_MSER_DEVICE_SORT")));
-        size_t ofs[MAXB + 1], tot = 0, ordOfs[MAXB], npxAll = 0;
+        const float *dv[MAXB];
         int vr[MAXB], vc[MAXB];
-        for (int i = 0; i < n; i++) {
-          ofs[i] = tot; tot += ((size_t)cimg[i]->rows * cimg[i]->cols + 63) & ~(size_t)63;
-          vr[i] = cimg[i]->rows; vc[i] = cimg[i]->cols;
-          ordOfs[i] = npxAll; npxAll += (size_t)vr[i] * vc[i];
-        }
-        // layout of the block: [u8 views | start: n x 257 ints | order: npxAll ints]; blockHist behind it on the device only
-        const size_t oStart = (tot + 255) & ~(size_t)255, oOrder = oStart + (((size_t)n * 257 * 4 + 255) & ~(size_t)255);
-        const size_t blockB = devSort ? oOrder + npxAll * 4 : tot;
-        const size_t histB = devSort ? mser_sort_blocks(vr, n) * 256 * 4 : 0;
-        if (!c->misc.ensure(((blockB + 255) & ~(size_t)255) + histB + 64) || !c->hMser.ensure(blockB + 64)) rc = MODSX_ERR_NOMEM;
-        for (int i = 0; i < n && !rc; i++)
-          launch_trunc_u8(c->stream, cimg[i]->d, (uint8_t *)c->misc.p + ofs[i], (size_t)vr[i] * vc[i]);
-        if (!rc && devSort) {
-          const uint8_t *du8[MAXB];
-          for (int i = 0; i < n; i++) du8[i] = (const uint8_t *)c->misc.p + ofs[i];
-          char *base = (char *)c->misc.p;
-          launch_mser_sort(c->stream, du8, vr, vc, ordOfs, n, (int *)(base + ((blockB + 255) & ~(size_t)255)), (int *)(base + oStart), (int *)(base + oOrder));
-        }
-        if (!rc && (ctx_copy(c, c->hMser.p, c->misc.p, blockB, hipMemcpyDeviceToHost) != hipSuccess ||
-                    ctx_sync(c) != hipSuccess)) { set_error("MSER view download failed"); rc = MODSX_ERR_DEVICE; }
+        for (int i = 0; i < n; i++) { dv[i] = cimg[i]->d; vr[i] = cimg[i]->rows; vc[i] = cimg[i]->cols; }
+        MserFront mf;
+        rc = mser_front(c, dv, vr, vc, n, devSort, mf);
         const double tdl = tnow();
-        if (!rc) {
-          const uint8_t *src[MAXB];
-          const int *ho[MAXB], *hs[MAXB];
-          for (int i = 0; i < n; i++) {
-            src[i] = (const uint8_t *)c->hMser.p + ofs[i];
-            ho[i] = (const int *)((const char *)c->hMser.p + oOrder) + ordOfs[i];
-            hs[i] = (const int *)((const char *)c->hMser.p + oStart) + (size_t)i * 257;
-          }
-          rc = detect_msers_views(src, vr, vc, n, pp.mser, tilts, zooms, kps, devSort ? ho : nullptr, devSort ? hs : nullptr);
-        }
+        if (!rc) rc = detect_msers_views(mf.u8, vr, vc, n, pp.mser, tilts, zooms, kps, devSort ? mf.order : nullptr, devSort ? mf.start : nullptr);
         if (tim) fprintf(stderr, "  mser set of %d views: u8 + download %.2f ms, component trees %.2f ms\n", n, tdl - t1, tnow() - tdl);
       } else rc = detect_keypoints_batch(c, cimg, n, pp.det, tilts, zooms, kps);
     }

@@ -748,15 +748,21 @@ void launch_nms(hipStream_t s, const NmsBatch &b, const NmsJob *jobs, const int 
   hipLaunchKernelGGL(k_nms_localize, dim3(nTiles), dim3(256), 0, s, b, jobs, tilePrefix, tileJob, queue, qcount, qcap, counter + 1);
   hipLaunchKernelGGL(k_nms_refine, dim3(NMS_REFINE_BLOCKS, NMS_QUEUES), dim3(256), 0, s, b, jobs, queue, qcount, qcap, out, counter, cap);
 }
-// *ptr = (unsigned char)*in_ptr of DetectMSERs (extrema.cpp:401-403): f32 -> u8 by truncation, 4 pixels per thread
+// *ptr = (unsigned char)*in_ptr of DetectMSERs (extrema.cpp:401-403; the oracle's oracle_mser.cpp:348) as x86 evaluates it: cvttss2si
+// truncates toward zero into int32 and the low byte is kept (-1 -> 255, -300 -> 212, 300 -> 44, 2147483520 -> 128); everything
+// outside [-2^31, 2^31) -- 2^31, 1e30, both infinities, NaN -- converts to 0x80000000, byte 0.  Stated in full here: the cast
+// (uint8_t)v is undefined outside 0 .. 255, and gfx950 compiled it to the saturating v_cvt_i32_f32 with no byte mask in the packed
+// word below: 255 at and above 2^31, and the high bits of a negative or large pixel OR-ed into the later pixels of its group of 4.
+MX_D unsigned trunc_u8(float v) { return (v >= -2147483648.f && v < 2147483648.f) ? (unsigned)(int)v & 255u : 0u; }
+// 4 pixels per thread; the float4 body and the scalar tail apply the same rule
 __global__ void k_trunc_u8(const float *src, uint8_t *dst, size_t n) {
   const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i + 3 < n) {
     const float4 v = *reinterpret_cast<const float4 *>(src + i);
-    const unsigned p = (unsigned)(uint8_t)v.x | ((unsigned)(uint8_t)v.y << 8) | ((unsigned)(uint8_t)v.z << 16) | ((unsigned)(uint8_t)v.w << 24);
+    const unsigned p = trunc_u8(v.x) | (trunc_u8(v.y) << 8) | (trunc_u8(v.z) << 16) | (trunc_u8(v.w) << 24);
     *reinterpret_cast<unsigned *>(dst + i) = p;
   } else {
-    for (size_t k = i; k < n; k++) dst[k] = (uint8_t)src[k];
+    for (size_t k = i; k < n; k++) dst[k] = (uint8_t)trunc_u8(src[k]);
   }
 }
 void launch_trunc_u8(hipStream_t s, const float *src, uint8_t *dst, size_t n) {
