@@ -43,6 +43,9 @@ enum { MODSX_DET_HESSIAN = 0, MODSX_DET_DOG = 1, MODSX_DET_HARRIS = 2, MODSX_DET
  * L2 distance unchanged, so the matcher needs no second layout. */
 enum { MODSX_DESC_SIFT = 0, MODSX_DESC_ROOT_SIFT = 1, MODSX_DESC_HALF_SIFT = 2, MODSX_DESC_HALF_ROOT_SIFT = 3 };
 #define MODSX_MAX_DESC 4   /* descriptor classes one step can carry (the four SIFT-family types above) */
+/* The real-valued descriptor classes of a stored representation (modsx_rep_append_f32 and what follows it).  They share the
+ * namespace of modsx_rep_class_sel::desc_type; every entry that takes the types 0..3 alone goes on refusing them. */
+enum { MODSX_DESC_CAFFE = 8, MODSX_DESC_DAISY = 9, MODSX_DESC_LIOP = 10, MODSX_DESC_MROGH = 11, MODSX_DESC_SURF = 12 };
 /* ScaleSpaceDetector point types, affinedetectors/pyramid.h:32-36 */
 enum { MODSX_HESSIAN_DARK = 0, MODSX_HESSIAN_BRIGHT = 1, MODSX_HESSIAN_SADDLE = 2 };
 
@@ -755,7 +758,9 @@ int modsx_rep_match_fginn(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep
  *   The contexts take groups of up to 4 partners off a shared counter; a group costs one matcher launch set per class (problems
  * with an empty side are left out), verification runs on helper threads as in modsx_match_pairs_views.  A database attached
  * to the contexts applies to the RootSIFT classes (modsx_set_fginn_db; all contexts the same database, or none).  A partner
- * without regions gives the zeroed result with H = -1 and n_regions1 set.  Returns n. */
+ * without regions gives the zeroed result with H = -1 and n_regions1 set.  Returns n.
+ *   Float classes (MODSX_DESC_CAFFE .. MODSX_DESC_SURF, see modsx_rep_append_f32 below) are taken in classes[] as well and are part
+ * of "every class" when n_classes == 0; modsx_rep_class_rank gives the order of all classes. */
 typedef struct { int detector, desc_type; double ratio; } modsx_rep_class_sel;
 int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
                      const modsx_rep_class_sel *classes, int n_classes, const modsx_pair_params *par, modsx_pair_result *results);
@@ -1009,8 +1014,8 @@ int modsx_dsp_counters(modsx_ctx *ctx, long *out, int n);
  * the patch and 28 of the 64 entries are identically zero.  A patch whose responses are all zero (a patch of zeros, or any patch
  * when the rounded scale is 0, mrSize > 82) has length 0 and gives a row of 64 NaN, as the reference does; sign and payload of
  * those NaN are unspecified.  Patch values must be finite.
- * SURF is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder, of modsx_rep or of the sharded
- * path; the rows go to modsx_match_regions_f32 at dim 64 (finite rows only).  The detector (FastHessian) and getOrientation are
+ * SURF is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder or of the sharded path; the rows
+ * go to modsx_match_regions_f32 at dim 64 or into a stored representation (modsx_rep_describe_append), finite rows only.  The detector (FastHessian) and getOrientation are
  * not part of this library.
  * Every entry: n < 0, patchSize != 41, a null pointer, an mrSize that is not finite and positive, or an mrSize below
  * patchSize / 1024 (scale above 1024: beyond it the reference's int sample coordinates and the int squares inside its gaussian
@@ -1052,8 +1057,8 @@ int modsx_surf_counters(modsx_ctx *ctx, long *out, int n);
  * sin on the host, as the reference's do.  A grid point outside [0, 40) on either axis, or one whose integer part is 39 or more,
  * gives 8 zeros: at rad = 20, radq = 3, thq = 8 those are histograms 17 and 19.  A patch without gradients gives a row of zeros.
  * Rows of patches with non-finite values are unspecified.
- * DAISY is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder, of modsx_rep or of the sharded
- * path; the rows go to modsx_match_regions_f32 at their width.
+ * DAISY is no descriptor class of modsx_describe_regions (desc_type stays 0..3), of the ladder or of the sharded path; the rows
+ * go to modsx_match_regions_f32 at their width or into a stored representation (modsx_rep_describe_append).
  * Accepted: patchSize == 41, histq == 8, 1 <= thq <= 8, 1 <= radq <= 3, 1 <= rad <= 20 (no grid point then leaves [0, 40]),
  * nrm_type 0 .. 2.  Every entry: anything else, n < 0 or a null pointer is MODSX_ERR_ARG with a message, before anything is
  * launched, and the context stays usable; n == 0 succeeds and writes nothing.  The _device forms take DEVICE pointers, 4-byte
@@ -1103,7 +1108,7 @@ int modsx_daisy_counters(modsx_ctx *ctx, long *out, int n);
  *             parameters ask for has width or height 0 (cols / init_sample / 2^(octaves - 1) == 0, or rows likewise: the
  *             reference's assert aborts there).  n_imgs == 0 succeeds.  Pixels must be finite.
  * No orientation is assigned (the branch calls no getOrientation): keypoints carry the frame of orientation 0.  SURF is no
- * detector of the ladder, of modsx_rep or of the sharded path. */
+ * detector of the ladder, of modsx_rep_add_views or of the sharded path; a stored representation has float classes for it. */
 #define MODSX_DET_SURF 6                 /* detector_type DET_SURF, detectors/structures.hpp */
 #define MODSX_SURFDET_MAX_LAYERS 12
 typedef struct modsx_surfdet_params {
@@ -1136,6 +1141,64 @@ int modsx_debug_surfdet(modsx_ctx *ctx, const modsx_image *img, const modsx_surf
 /* SURF detector work of this context since modsx_create, cumulative (measurement hook): calls that launched, images, extrema
  * found, points accepted, regrows of the point buffer.  Fills out[0 .. min(n, 5) - 1], returns 5. */
 int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n);
+
+/* ---- float descriptor classes of a stored representation (engine_reps_f32.hip) -------------------------------------------
+ * A modsx_rep also holds one class per (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF}) x (float descriptor
+ * type MODSX_DESC_CAFFE .. MODSX_DESC_SURF), as RegionVectorMap[det][desc] does for any descriptor name.  Widths: CAFFE any
+ * dim % 4 == 0 in [4, MODSX_FGINN32_MAX_DIM] (learned vectors), DAISY a width modsx_daisy_dim can return, LIOP 144, MROGH 192,
+ * SURF 64; CAFFE and MROGH rows come from the caller only.  A class fixes its width at its first append; a later append of
+ * another width is MODSX_ERR_ARG.
+ *   Stored form.  A class keeps its rows in the row form of the f32 matcher (the kernel width DK floats per row, zero behind
+ * dim, 16-byte aligned) padded with zero rows to a multiple of 256 rows, and the positions reproj_kp.x, y of its regions as
+ * [n][2] f64 in HBM: the form both the query side and the train side of a match read, so no stored match packs anything.  An
+ * append writes its rows behind the old ones; the buffer starts at MODSX_REP_F32_FIRST_ROWS rows and grows x4, copying the
+ * old rows once.  Values must be finite with |x| <= 1e17 (the matcher's contract): host rows are checked on the host, rows of
+ * a device extractor through the flag word of the kernel that stores them.  An append that fails leaves the class as it was.
+ * A class holds at most 2 000 000 regions.  The u8 classes and every entry that takes them are unchanged. */
+#define MODSX_REP_F32_FIRST_ROWS 4096
+/* LoadRegions for a float class: n regions and their dense [n][dim] f32 rows, ids as given.  Returns n.  MODSX_ERR_ARG: a
+ * detector or type that names no float class, a width the type does not have or the class does not hold, an invalid value,
+ * more than 2 000 000 regions in the class. */
+int modsx_rep_append_f32(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const float *rows,
+                         int dim, int n);
+/* Describes the caller's (oriented) regions of one view image with the class's extractor -- MODSX_DESC_SURF, MODSX_DESC_LIOP
+ * or MODSX_DESC_DAISY (CAFFE and MROGH are refused) -- and appends regions and rows; the rows stay on the device from the
+ * extractor's kernel to the class.  They are bit for bit what modsx_describe_regions_surf / _liop / _daisy return for the same
+ * arguments.  daisy_par = {rad, radq, thq, histq, nrm_type} for DAISY, NULL otherwise.  A region list that gives an invalid
+ * row (SURF's NaN rows) is MODSX_ERR_ARG and leaves the class unchanged.  Returns n. */
+int modsx_rep_describe_append(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_image *img,
+                              const modsx_region *regs, int n, double mrSize, int patchSize, int fast_extraction, int photoNorm,
+                              const int *daisy_par);
+/* The regions and dense [n][dim] f32 rows of one float class as malloc'd copies (modsx_free), and its width (0 while the class
+ * is empty); any pointer may be NULL.  Returns n. */
+int modsx_rep_class_f32(modsx_ctx *ctx, const modsx_rep *rep, int detector, int desc_type, modsx_region **regs, float **rows, int *dim);
+/* Stage tap: the MatchFlannFGINN records of one float class, rep1 the queries, rep2 the trains -- what modsx_match_fginn_f32
+ * returns for the same rows and the positions reproj_kp.x, y of rep2's regions. */
+int modsx_rep_match_fginn_f32(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep *rep2, int detector, int desc_type, double ratio,
+                              double contradDist, int nn, modsx_tentative **out);
+/* Stage tap of the grouped launch set: the class of rep1 against that class of 1 <= G <= 4 partners in ONE launch set (one
+ * search launch and one merge launch for all partners, one copy of every partner's four nearest keys, the host's walk, ONE
+ * resolve launch for the walks of all partners that are still open, one copy back).  outs[g] (modsx_free) / counts[g]: partner
+ * g's records, those of modsx_rep_match_fginn_f32(rep1, reps2[g]).  Partners with an empty class are left out of the launches.
+ * Returns G. */
+int modsx_rep_match_group_f32(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int detector, int desc_type,
+                              double ratio, double contradDist, int nn, modsx_tentative **outs, int *counts);
+/* modsx_match_reps also takes float classes in classes[]; with n_classes == 0 it includes every float class that is non-empty
+ * in rep1, with par->match_ratio.  A float class costs one grouped launch set per group of partners.  The database
+ * attachment applies to RootSIFT only.  Classes are concatenated in std::map order of the reference's names -- descriptor
+ * CAFFE, DAISY, HalfRootSIFT, HalfSIFT, LIOP, MROGH, RootSIFT, SIFT, SURF, then detector HessianAffine, MSER, SURF -- and the
+ * region indices of a result refer to that concatenation.
+ * host only: the position of a class in that order, -1 when there is no such descriptor type or detector. */
+int modsx_rep_class_rank(int detector, int desc_type);
+/* host only, no context: the train axis of the grouped launch set for n1 queries against G <= 4 partners of n2[g] rows.
+ * geometry[4] = {tile length, kernel width DK, query blocks gx, splits in all}; per_problem [G][3] = {tiles, splits, tiles per
+ * split} (zeros for an empty partner); splits [cap][3] = {partner, first tile, end tile} of the first min(cap, splits) splits
+ * in launch order (may be NULL with cap 0).  Returns the number of splits.  Every partner with n2 >= 1 has the S and tiles per
+ * split modsx_debug_fginn32_geometry(n1, n2[g], dim, 0) gives it alone, whatever shares the launch. */
+int modsx_debug_fginn32_group_geometry(int n1, const int *n2, int G, int dim, int *geometry, int *per_problem, int *splits, int cap);
+/* cumulative on this context: grouped launch sets, problems in them, queries sent to resolve, resolve launches.  Fills
+ * out[0 .. min(n, 4) - 1], returns 4. */
+int modsx_fginn32_group_counters(modsx_ctx *ctx, long *out, int n);
 
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel

@@ -122,6 +122,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
            "modsx_rep_match_fginn", "modsx_match_reps", "modsx_match_one_to_many",
+           "modsx_rep_append_f32", "modsx_rep_describe_append", "modsx_rep_class_f32", "modsx_rep_match_fginn_f32",
+           "modsx_rep_match_group_f32", "modsx_rep_class_rank", "modsx_debug_fginn32_group_geometry",
+           "modsx_fginn32_group_counters",
            "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
            "modsx_match_regions_hamming", "modsx_debug_hamming_geometry",
            "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
@@ -164,6 +167,10 @@ SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
 # include/modsx.h: modsx_surfdet_counters, in its order
 SURFDET_COUNTERS = ("calls", "images", "extrema", "accepted", "regrows")
 DET_SURF, SURFDET_MAX_LAYERS = 6, 12      # include/modsx.h: MODSX_DET_SURF, MODSX_SURFDET_MAX_LAYERS
+DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, MODSX_DET_MSER
+# include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
+DESC_CAFFE, DESC_DAISY, DESC_LIOP, DESC_MROGH, DESC_SURF = 8, 9, 10, 11, 12
+REP_F32_FIRST_ROWS = 4096
 # include/modsx.h: modsx_daisy_counters, in its order
 DAISY_COUNTERS = ("calls", "patches", "sub_batches")
 DAISY_MAX_DIM, DAISY_MAX_TAPS = 200, 51      # include/modsx.h: MODSX_DAISY_MAX_DIM, MODSX_DAISY_MAX_TAPS
@@ -258,6 +265,18 @@ def lib():
         L.modsx_rep_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.modsx_rep_match_fginn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                             C.c_void_p]
+        L.modsx_rep_append_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.modsx_rep_describe_append.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                                C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_rep_class_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_rep_match_fginn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                C.c_void_p]
+        L.modsx_rep_match_group_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                C.c_int, C.c_void_p, C.c_void_p]
+        L.modsx_rep_class_rank.argtypes = [C.c_int, C.c_int]
+        L.modsx_debug_fginn32_group_geometry.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_int]
+        L.modsx_fginn32_group_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_match_reps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p]
         L.modsx_match_one_to_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -716,6 +735,38 @@ class Rep(object):
 
     def count(self, detector=0, desc_type=1):
         return _check(lib().modsx_rep_class(self.ctx.h, self.h, int(detector), int(desc_type), None, None), "rep_class")
+
+    # ---- float classes (DESC_CAFFE .. DESC_SURF; detector DET_HESSIAN, DET_MSER or DET_SURF) ----
+    def append_f32(self, regs, rows, detector=0, desc_type=DESC_CAFFE, ctx=None):
+        """LoadRegions for a float class: regions (REGION records) and their dense [n][dim] float32 rows.  Returns n."""
+        regs = np.ascontiguousarray(regs, REGION)
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or len(rows) != len(regs):
+            raise ValueError("rep.append_f32: [n][dim] rows for n regions are expected")
+        return _check(lib().modsx_rep_append_f32((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs), _p(rows),
+                                                 rows.shape[1], len(regs)), "rep_append_f32")
+
+    def describe_append(self, img, regs, detector=0, desc_type=DESC_SURF, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1,
+                        daisy_par=None, ctx=None):
+        """Describes the (oriented) regions of one view image with the class's extractor (DESC_SURF, DESC_LIOP, DESC_DAISY) and
+        appends regions and rows; daisy_par = (rad, radq, thq, histq, nrm_type) for DAISY.  Returns n."""
+        regs = np.ascontiguousarray(regs, REGION)
+        dp = None if daisy_par is None else np.ascontiguousarray(daisy_par, np.int32)
+        if dp is not None and dp.shape != (5,):
+            raise ValueError("rep.describe_append: daisy_par = (rad, radq, thq, histq, nrm_type)")
+        return _check(lib().modsx_rep_describe_append((ctx or self.ctx).h, self.h, int(detector), int(desc_type), C.c_void_p(img.h),
+                                                      _p(regs), len(regs), C.c_double(mr_size), int(patch_size), int(fast),
+                                                      int(photo_norm), None if dp is None else _p(dp)), "rep_describe_append")
+
+    def class_f32(self, detector=0, desc_type=DESC_CAFFE):
+        """(regions, dense [n][dim] float32 rows) of one float class; dim = 0 while the class is empty."""
+        regs, rows, dim = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        n = _check(lib().modsx_rep_class_f32(self.ctx.h, self.h, int(detector), int(desc_type), C.byref(regs), C.byref(rows),
+                                             C.byref(dim)), "rep_class_f32")
+        return _take(regs, n, REGION), _take(rows, n * dim.value, np.dtype(np.float32)).reshape(n, dim.value)
+
+    def count_f32(self, detector=0, desc_type=DESC_CAFFE):
+        return _check(lib().modsx_rep_class_f32(self.ctx.h, self.h, int(detector), int(desc_type), None, None, None), "rep_class_f32")
 
     def free(self):
         if self.h:
@@ -1330,6 +1381,29 @@ class Context(object):
                                                C.c_double(contrad_dist), int(nn), C.byref(out)), "rep_match_fginn")
         return _take(out, n, TENT)
 
+    def rep_match_fginn_f32(self, rep1, rep2, detector=0, desc_type=DESC_CAFFE, ratio=0.8, contrad_dist=30.0, nn=50):
+        """MatchFlannFGINN of one float class of two stored representations: rep1 the queries, rep2 the trains."""
+        out = C.c_void_p()
+        n = _check(lib().modsx_rep_match_fginn_f32(self.h, rep1.h, rep2.h, int(detector), int(desc_type), C.c_double(ratio),
+                                                   C.c_double(contrad_dist), int(nn), C.byref(out)), "rep_match_fginn_f32")
+        return _take(out, n, TENT)
+
+    def rep_match_group_f32(self, rep1, reps2, detector=0, desc_type=DESC_CAFFE, ratio=0.8, contrad_dist=30.0, nn=50):
+        """The grouped launch set: one float class of rep1 against that class of 1..4 partners; a list of TENT arrays."""
+        G = len(reps2)
+        rarr = (C.c_void_p * max(1, G))(*[r.h for r in reps2])
+        outs = (C.c_void_p * max(1, G))()
+        counts = (C.c_int * max(1, G))()
+        _check(lib().modsx_rep_match_group_f32(self.h, rep1.h, rarr, G, int(detector), int(desc_type), C.c_double(ratio),
+                                               C.c_double(contrad_dist), int(nn), outs, counts), "rep_match_group_f32")
+        return [_take(C.c_void_p(outs[g]), counts[g], TENT) for g in range(G)]
+
+    def fginn32_group_counters(self):
+        """dict(launch_sets, problems, resolve_queries, resolve_launches) of the grouped f32 matcher on this context, cumulative."""
+        out = np.zeros(4, np.int64)
+        _check(lib().modsx_fginn32_group_counters(self.h, _p(out), 4), "fginn32_group_counters")
+        return dict(zip(("launch_sets", "problems", "resolve_queries", "resolve_launches"), (int(x) for x in out)))
+
     def match_pair_views(self, img1, img2, views, params):
         arr = _view_array(views)
         res = PairResult()
@@ -1567,6 +1641,26 @@ def fginn32_geometry(n1, n2, dim, splits=0):
     geo = np.zeros(6, np.int32)
     _check(lib().modsx_debug_fginn32_geometry(int(n1), int(n2), int(dim), int(splits), _p(geo)), "fginn32_geometry")
     return dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo)))
+
+
+def rep_class_rank(detector, desc_type):
+    """The position of a class in the order match_reps concatenates the classes in (descriptor name, then detector name, as the
+    reference's std::map walks them); -1 when there is no such class (host only)."""
+    return int(lib().modsx_rep_class_rank(int(detector), int(desc_type)))
+
+
+def fginn32_group_geometry(n1, n2, dim):
+    """The train axis of the grouped f32 search for n1 queries against len(n2) <= 4 partners of n2[g] rows (host only): dict(tile,
+    DK, gx, splits = [(partner, first tile, end tile), ...] in launch order, per_problem = [(tiles, splits, tiles per split), ...])."""
+    n2 = np.ascontiguousarray(n2, np.int32)
+    geo, per = np.zeros(4, np.int32), np.zeros((max(1, len(n2)), 3), np.int32)
+    total = _check(lib().modsx_debug_fginn32_group_geometry(int(n1), _p(n2), len(n2), int(dim), _p(geo), _p(per), None, 0),
+                   "fginn32_group_geometry")
+    sp = np.zeros((max(1, total), 3), np.int32)
+    _check(lib().modsx_debug_fginn32_group_geometry(int(n1), _p(n2), len(n2), int(dim), _p(geo), _p(per), _p(sp), total),
+           "fginn32_group_geometry")
+    return dict(tile=int(geo[0]), DK=int(geo[1]), gx=int(geo[2]), splits=[tuple(int(v) for v in r) for r in sp[:total]],
+                per_problem=[tuple(int(v) for v in r) for r in per[:len(n2)]])
 
 
 def fginn32_dpass(d0, ratio):

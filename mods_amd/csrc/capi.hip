@@ -881,10 +881,10 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
 // ---- stored representations: one against many (engine_reps.hip) ---------------------------------------------------------------
 // One round of MatchImgReps + verification of rep1 against n partners: the contexts take groups of up to MATCH_MAXB partners off
 // a shared counter, a group costs one matcher launch set per class of sel; every partner's tentatives (tents[i], the classes of
-// sel replaced, the others kept) are verified over the classes `present` marks, on helper threads while the contexts go on.
+// sel replaced, the others kept) are verified over the ordered class list `present`, on helper threads while the contexts go on.
 // results[i] must own nothing or the arrays of an earlier round (released here).  The round is over when it returns.
 static int reps_round(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
-                      const modsx_rep_class_sel *sel, int nsel, unsigned present, const modsx_pair_params &pp, mx::RepTents *tents,
+                      const modsx_rep_class_sel *sel, int nsel, const mx::RepClassList &present, const modsx_pair_params &pp, mx::RepTents *tents,
                       modsx_pair_result *results) {
   std::atomic<int> next(0), failed(0);
   std::string firstErr;
@@ -968,36 +968,41 @@ int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, c
                      const modsx_rep_class_sel *classes, int n_classes, const modsx_pair_params *par, modsx_pair_result *results) {
   { const int rc = reps_contexts_ok(ctxs, n_ctx, "modsx_match_reps"); if (rc) return rc; }
   NEED(rep1); NEED(par);
-  if (n < 0 || n_classes < 0 || n_classes > 8 || (n > 0 && (!reps2 || !results)) || (n_classes > 0 && !classes)) {
+  if (n < 0 || n_classes < 0 || n_classes > mx::REP_CLASSES_MAX || (n > 0 && (!reps2 || !results)) || (n_classes > 0 && !classes)) {
     mx::set_error("modsx_match_reps: bad argument");
     return MODSX_ERR_ARG;
   }
   for (int i = 0; i < n; i++) NEED(reps2[i]);
   for (int i = 0; i <= n; i++)
     if ((i ? reps2[i - 1] : rep1)->dev != ctxs[0]->dev) { mx::set_error("modsx_match_reps: a representation lives on another device than the contexts"); return MODSX_ERR_ARG; }
-  modsx_rep_class_sel sel[8];
+  modsx_rep_class_sel sel[mx::REP_CLASSES_MAX];
   int nsel = 0;
-  unsigned present = 0;
+  mx::RepClassList present;      // the classes that are verified, in the order GetCorresponcesVector concatenates them
   if (n_classes > 0) {
     for (int k = 0; k < n_classes; k++) {
       int det;
-      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det)) { mx::set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
-      if (present >> (det * 4 + classes[k].desc_type) & 1) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
-      present |= 1u << (det * 4 + classes[k].desc_type);
+      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det) && !mx::rep_class_f32_ok(classes[k].detector, classes[k].desc_type, &det)) {
+        mx::set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG;
+      }
+      if (present.has(det, classes[k].desc_type)) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
+      present.add(det, classes[k].desc_type);
       sel[nsel++] = classes[k];
     }
   } else {
     mx::DescSet ds;
     { const int rd = mx::resolve_descs(*par, nullptr, ds); if (rd) return rd; }
-    present = 0xff;
-    for (int t = 3; t >= 0; t--)
-      for (int d = 0; d < 2; d++) {
-        if (rep1->slot[d][t].regs.empty()) continue;       // no queries: no partner has tentatives in this class
-        double ratio = par->match_ratio;
-        for (int j = 0; j < ds.n; j++) if (ds.type[j] == t && ds.ratio[j] > 0) ratio = ds.ratio[j];
-        sel[nsel].detector = d ? MODSX_DET_MSER : MODSX_DET_HESSIAN; sel[nsel].desc_type = t; sel[nsel].ratio = ratio;
-        nsel++;
-      }
+    static const int detOf[3] = {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF};
+    mx::rep_classes_u8(present);
+    for (int t = MODSX_DESC_CAFFE; t <= MODSX_DESC_SURF; t++) for (int d = 0; d < 3; d++) present.add(d, t);
+    for (int i = 0; i < present.n; i++) {
+      const int d = present.k[i].det, t = present.k[i].type;
+      const bool f32 = t >= MODSX_DESC_CAFFE;
+      if (f32 ? rep1->fslot[d][t - MODSX_DESC_CAFFE].regs.empty() : rep1->slot[d][t].regs.empty()) continue;   // no queries: no partner has tentatives in this class
+      double ratio = par->match_ratio;
+      for (int j = 0; j < ds.n && !f32; j++) if (ds.type[j] == t && ds.ratio[j] > 0) ratio = ds.ratio[j];
+      sel[nsel].detector = detOf[d]; sel[nsel].desc_type = t; sel[nsel].ratio = ratio;
+      nsel++;
+    }
   }
   for (int i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
   if (n == 0) return 0;
@@ -1025,6 +1030,8 @@ int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
   std::vector<modsx_rep *> reps((size_t)n + 1, nullptr);
   for (auto &r : reps) r = modsx_rep_create(ctxs[0]);
   std::vector<mx::RepTents> tents((size_t)n);
+  mx::RepClassList u8Classes;      // the ladder carries the SIFT-family classes only
+  mx::rep_classes_u8(u8Classes);
   int rc = MODSX_OK, step = 0;
   bool reached = false;
   for (; step < nsteps && !reached && !rc; step++) {
@@ -1059,7 +1066,7 @@ int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
     if (rc) break;
     modsx_rep_class_sel sel[MODSX_MAX_DESC];
     for (int j = 0; j < ds.n; j++) { sel[j].detector = steps[step].detector == MODSX_DET_MSER ? MODSX_DET_MSER : MODSX_DET_HESSIAN; sel[j].desc_type = ds.type[j]; sel[j].ratio = ds.ratio[j]; }
-    rc = reps_round(ctxs, n_ctx, reps[0], reps.data() + 1, n, sel, ds.n, 0xff, *par, tents.data(), results);
+    rc = reps_round(ctxs, n_ctx, reps[0], reps.data() + 1, n, sel, ds.n, u8Classes, *par, tents.data(), results);
     if (rc) break;
     for (int i = 0; i < n; i++) reached = reached || results[i].n_verified >= min_matches;
   }

@@ -419,7 +419,7 @@ void ctx_destroy(modsx_ctx *c) {
   c->candSort.release(); c->candOut.release();
   c->patchBuf.release(); c->patchOut.release();
   c->liopTab.release(); c->liopDbg.release(); c->liopCnt.release();
-  c->dspRows.release();
+  c->dspRows.release(); c->repStage.release();
   for (DevBuf &b : c->surfTab) b.release();
   for (DevBuf *b : {&c->sdInteg, &c->sdResp, &c->sdLap, &c->sdFlags, &c->sdCounts, &c->sdTab, &c->sdPoints, &c->sdExt}) b->release();
   c->sdHost.release(); c->sdBack.release();

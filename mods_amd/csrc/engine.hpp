@@ -354,6 +354,31 @@ Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work);
 void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, int n1, const float *d2, int n2, void *work,
                          void *flagAndTop4, hipEvent_t *ev = nullptr);
 void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work);
+// The grouped form: np <= MATCH_MAXB problems share one stored query side (rows of DK floats, padded to whole workgroups); problem p
+// has its own stored trains (zero rows up to a multiple of 256) and positions.  This is the whole table of the launch set, passed
+// to the kernels by value.  Train axis: problem p owns the splits [first[p], first[p + 1]) of tps[p] whole tiles each.  Resolve:
+// problem p owns the open entries [ubeg[p], uend[p]) and the workgroups [rfirst[p], rfirst[p + 1]) = its blocks of 256 entries x
+// its splits.  Entries of first / rfirst behind np hold the total, so that no workgroup selects an unused problem.
+struct F32Group {
+  const float *trains[MATCH_MAXB];
+  const double *pos[MATCH_MAXB];
+  int n2[MATCH_MAXB], ntiles[MATCH_MAXB], tps[MATCH_MAXB], S[MATCH_MAXB];
+  int first[MATCH_MAXB + 1];
+  int ubeg[MATCH_MAXB], uend[MATCH_MAXB], rfirst[MATCH_MAXB + 1];
+  int np, gx, DK, tile;
+};
+// n2[0..G): every problem's trains; problems with n2 == 0 are left out (prob[k] = the caller's index of table problem k).  Every
+// problem is cut as fginn32_geometry cuts it alone (about 2048 / gx splits, at most one per tile): its S and tps, whatever G is.
+int fginn32_kernel_width(int dim);
+int fginn32_group_geometry(int n1, const int *n2, int G, int dim, F32Group &g, int *prob);
+// keys: [first[np]][n1][4]; top4: [np][n1][4]
+void launch_fginn32_group_topk(hipStream_t s, const F32Group &g, const float *queries, int n1, unsigned long long *keys,
+                               unsigned long long *top4);
+// open / closed: uend[np - 1] entries sorted by problem, closed = {all ones, 0} on entry; g.ubeg / uend / rfirst are set
+void launch_fginn32_group_resolve(hipStream_t s, const F32Group &g, const float *queries, const F32Open *open, double contrDistSq,
+                                  F32Closed *closed);
+// dst: n rows of DK floats at their place in a stored slot; *flag |= bit for a value outside the matcher's contract
+void launch_fginn32_pack_rows(hipStream_t s, const float *src, int n, int dim, int DK, float *dst, unsigned *flag, unsigned bit);
 // LIOP (kernels_liop.hip).  One neighbour sample of a measurement pixel: floor and fraction of neighSamplesX / Y (liop.c:376-395,
 // 503-507), built by the host with libm (engine_liop.hip: liop_tables)
 struct LiopSample { double wx, wy; int ix, iy; };
@@ -528,6 +553,10 @@ struct modsx_ctx {
   mx::DevBuf sdInteg, sdResp, sdLap, sdFlags, sdCounts, sdTab, sdPoints, sdExt;
   mx::PinBuf sdHost, sdBack;
   long sdCounters[5] = {0, 0, 0, 0, 0};  // modsx_surfdet_counters: calls, images, extrema found, points accepted, buffer regrows
+  // float classes of stored representations (engine_reps_f32.hip): dense rows of a device extractor on their way into a slot, and
+  // modsx_fginn32_group_counters: grouped launch sets, problems in them, queries sent to resolve, resolve launches
+  mx::DevBuf repStage;
+  long f32GroupCounters[4] = {0, 0, 0, 0};
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

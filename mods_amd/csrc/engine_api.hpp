@@ -252,6 +252,7 @@ int match_regions_hamming(modsx_ctx *c, const modsx_region *regs1, const void *d
 // counters [4] = {queries sent to resolve, of those closed by the count, records, validity flag}
 struct Fginn32Tap { int splits, stageMask; unsigned long long *top4; unsigned char *stage; int *geometry; int *counters; };
 float fginn32_dpass(float d0, double rsq);
+bool fginn32_rows_ok(const float *f, size_t n);     // every value finite with |x| <= 1e17
 int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, int nn);
 int fginn32_geometry_report(int n1, int n2, int dim, int splits, int *geo6);
 int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
@@ -268,9 +269,10 @@ inline const DbSet *fginn_db_for(const modsx_ctx *c, int descType) { return desc
 // The region list a tentative's indices refer to: the per-class lists of one image in the order GetCorresponcesVector walks
 // the classes (descriptor name, then detector name), as segments -- two descriptor classes of one detector share their
 // regions, so the concatenation is never materialised.
+constexpr int REP_CLASSES_MAX = 2 * MODSX_MAX_DESC + 3 * 5;   // the u8 classes and the float classes of a stored representation
 struct RegList {
-  const modsx_region *p[2 * MODSX_MAX_DESC];
-  size_t end[2 * MODSX_MAX_DESC];   // running end index of every segment
+  const modsx_region *p[REP_CLASSES_MAX];
+  size_t end[REP_CLASSES_MAX];   // running end index of every segment
   int n = 0;
   void clear() { n = 0; }
   void add(const modsx_region *q, size_t cnt) { p[n] = q; end[n] = (n ? end[n - 1] : 0) + cnt; n++; }
@@ -314,14 +316,47 @@ struct RepSlot {
   size_t cap = (size_t)1 << 16;     // regions `desc` has room for (grows x4)
   DevBuf desc, pack;
 };
+// One float class of a stored representation (engine_reps_f32.hip): the host region list (and its positions), the rows in the matcher's form
+// (kernels_fginn32.hip: DK floats per row, zero columns behind dim, zero rows up to the capacity, which is a multiple of 256) and
+// the regions' reproj_kp as [n][2] f64.  dim is fixed by the first append that succeeds.
+constexpr size_t REP_F32_FIRST_ROWS = 4096;      // MODSX_REP_F32_FIRST_ROWS: the first capacity of a float slot (grows x4)
+struct RepSlotF {
+  std::vector<modsx_region> regs;
+  std::vector<double> hpos;      // reproj_kp.x, y of regs, dense: what the host's walk reads
+  int dim = 0, DK = 0;
+  size_t cap = 0;                // rows the buffers have room for, each of capDK floats
+  int capDK = 0;
+  DevBuf rows, pos;
+};
 // the tentatives of every class's last match against one partner (CorrespondencesMapMap[desc][det])
-struct RepTents { std::vector<modsx_tentative> t[2][4]; };
-bool rep_class_ok(int detector, int desc_type, int *det);
+struct RepTents { std::vector<modsx_tentative> t[2][4], f[3][5]; };
+// A class by its slot: det 0 = HessianAffine, 1 = MSER, 2 = SURF; type = MODSX_DESC_* (0..3: u8 slots, det 0..1 only; 8..12: float
+// slots).  A RepClassList is sorted by rep_class_rank: the order GetCorresponcesVector("All", "All") concatenates the classes in.
+struct RepClassId { int det, type; };
+struct RepClassList {
+  int n = 0;
+  RepClassId k[REP_CLASSES_MAX];
+  bool has(int det, int type) const { for (int i = 0; i < n; i++) if (k[i].det == det && k[i].type == type) return true; return false; }
+  void add(int det, int type);      // keeps the order
+};
+int rep_class_rank(int detector, int desc_type);                 // -1: no such class
+bool rep_class_ok(int detector, int desc_type, int *det);        // a u8 class
+bool rep_class_f32_ok(int detector, int desc_type, int *det);    // a float class
+void rep_classes_u8(RepClassList &l);                            // the eight u8 classes
 int rep_add_views(modsx_ctx *c, modsx_rep *rep, const modsx_image *img, const modsx_ladder_step &st, const modsx_pair_params &pp);
 int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, const modsx_rep_class_sel *sel, int nsel,
                      const modsx_pair_params &pp, RepTents *const *tents);
-void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, unsigned present, const RepTents &tents, modsx_pair_result *res,
-                      int dev, VerifyTask &task);
+void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepClassList &classes, const RepTents &tents,
+                      modsx_pair_result *res, int dev, VerifyTask &task);
+// float classes (engine_reps_f32.hip); det = the slot index rep_class_f32_ok gives
+int rep_append_f32(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const float *rows, int dim, int n);
+int rep_describe_append(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_image *img, const modsx_region *regs, int n,
+                        double mrSize, int patchSize, int fast, int photoNorm, const int *daisyPar);
+int rep_class_f32(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, float **rows, int *dim);
+// MatchFlannFGINN of one float class for G <= MATCH_MAXB partners in one grouped launch set; outs[g]: partner g's records
+int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
+                         double ratio, double contradDist, int nn, std::vector<modsx_tentative> *outs);
+void rep_free_f32(modsx_rep *rep);
 bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u);   // false: a value that is not one of the integers 0..255
 int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_image *const *imgs2, int G,
                      const modsx_pair_params &pp, modsx_pair_result *res, std::vector<VerifyTask> *deferred = nullptr);
@@ -366,4 +401,5 @@ int loransac_h(const double *pts, const double *laf1, const double *laf2, int T,
                double *Hraw, unsigned char *inl, unsigned char *keep, int *data_out, int error_type = 0);
 }  // namespace mx
 
-struct modsx_rep { int dev; mx::RepSlot slot[2][4]; };   // slot[det][type]: det 0 = HessianAffine, 1 = MSER; type = MODSX_DESC_*
+// slot[det][type]: det 0 = HessianAffine, 1 = MSER; type = MODSX_DESC_* 0..3.  fslot[det][type - MODSX_DESC_CAFFE]: det 2 = SURF
+struct modsx_rep { int dev; mx::RepSlot slot[2][4]; mx::RepSlotF fslot[3][5]; };

@@ -8,7 +8,8 @@
 // regions' reprojected positions: what the train half of k_match_pack writes depends on the trains alone, so it is written once,
 // when the slot changes, and every match that takes the slot as its train side starts from it (kernels_match.hip
 // launch_match_pack_trains, MatchProblem::packed).  A representation is changed by one thread at a time; otherwise it is
-// read-only and any context of its device may match against it, also at the same time.
+// read-only and any context of its device may match against it, also at the same time.  The float classes (SURF, LIOP, DAISY,
+// MROGH, learned vectors) and their grouped search are engine_reps_f32.hip; reps_match_group and reps_verify_task take both kinds.
 #include <math.h>
 #include <algorithm>
 #include "engine_api.hpp"
@@ -91,8 +92,16 @@ int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const
   if (G < 1 || G > MATCH_MAXB) { set_error("reps_match_group: group size"); return MODSX_ERR_ARG; }
   for (int s = 0; s < nsel; s++) {
     int det;
-    if (!rep_class_ok(sel[s].detector, sel[s].desc_type, &det)) { set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
     const int type = sel[s].desc_type;
+    if (rep_class_f32_ok(sel[s].detector, type, &det)) {
+      // a float class: one grouped launch set of the f32 matcher (engine_reps_f32.hip)
+      std::vector<modsx_tentative> out[MATCH_MAXB];
+      const int rc = reps_f32_match_group(c, "modsx_match_reps", rep1, reps2, G, det, type, sel[s].ratio, pp.contradDist, pp.nn, out);
+      if (rc) return rc;
+      for (int g = 0; g < G; g++) tents[g]->f[det][type - MODSX_DESC_CAFFE] = std::move(out[g]);
+      continue;
+    }
+    if (!rep_class_ok(sel[s].detector, type, &det)) { set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
     const RepSlot &q = rep1->slot[det][type];
     const uint8_t *d1[MATCH_MAXB], *d2[MATCH_MAXB];
     const double *pos[MATCH_MAXB];
@@ -119,28 +128,29 @@ int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const
   return MODSX_OK;
 }
 
-// GetCorresponcesVector("All", "All") over the classes `present` marks (bit det * 4 + type) that are non-empty in either
-// representation, in map order: the region lists as segments of the representations' own vectors (which must outlive the task),
-// the tentatives re-based onto their concatenation.  res is reset to the zeroed result with H = -1.
-void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, unsigned present, const RepTents &tents, modsx_pair_result *res,
-                      int dev, VerifyTask &task) {
+// GetCorresponcesVector("All", "All") over the classes of `classes` (in map order: rep_class_rank) that are non-empty in either
+// representation: the region lists as segments of the representations' own vectors (which must outlive the task), the tentatives
+// re-based onto their concatenation.  res is reset to the zeroed result with H = -1.
+void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepClassList &classes, const RepTents &tents,
+                      modsx_pair_result *res, int dev, VerifyTask &task) {
   memset(res, 0, sizeof *res);
   for (int i = 0; i < 9; i++) res->H[i] = -1;
   task.l1.clear(); task.l2.clear(); task.own.clear(); task.tents.clear();
-  for (int t = 3; t >= 0; t--)
-    for (int d = 0; d < 2; d++) {
-      if (!(present >> (d * 4 + t) & 1)) continue;
-      const RepSlot &a = rep1->slot[d][t], &b = rep2->slot[d][t];
-      if (a.regs.empty() && b.regs.empty()) continue;
-      const int o1 = (int)task.l1.size(), o2 = (int)task.l2.size();
-      task.l1.add(a.regs); task.l2.add(b.regs);
-      for (modsx_tentative tt : tents.t[d][t]) {
-        tt.q += o1; tt.t0 += o2;
-        if (tt.t1 >= 0) tt.t1 += o2;
-        if (tt.tj >= 0) tt.tj += o2;
-        task.tents.push_back(tt);
-      }
+  for (int i = 0; i < classes.n; i++) {
+    const int d = classes.k[i].det, t = classes.k[i].type, ft = t - MODSX_DESC_CAFFE;
+    const bool f32 = t >= MODSX_DESC_CAFFE;
+    const std::vector<modsx_region> &a = f32 ? rep1->fslot[d][ft].regs : rep1->slot[d][t].regs;
+    const std::vector<modsx_region> &b = f32 ? rep2->fslot[d][ft].regs : rep2->slot[d][t].regs;
+    if (a.empty() && b.empty()) continue;
+    const int o1 = (int)task.l1.size(), o2 = (int)task.l2.size();
+    task.l1.add(a); task.l2.add(b);
+    for (modsx_tentative tt : f32 ? tents.f[d][ft] : tents.t[d][t]) {
+      tt.q += o1; tt.t0 += o2;
+      if (tt.t1 >= 0) tt.t1 += o2;
+      if (tt.tj >= 0) tt.tj += o2;
+      task.tents.push_back(tt);
     }
+  }
   res->n_regions1 = (int)task.l1.size();
   res->n_regions2 = (int)task.l2.size();
   task.res = res; task.dev = dev;
@@ -163,6 +173,7 @@ void modsx_rep_free(modsx_ctx *ctx, modsx_rep *rep) {
   if (!rep) return;
   hipSetDevice(ctx ? ctx->dev : rep->dev);
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) { rep->slot[d][t].desc.release(); rep->slot[d][t].pack.release(); }
+  rep_free_f32(rep);
   delete rep;
 }
 

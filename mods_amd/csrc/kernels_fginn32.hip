@@ -43,6 +43,20 @@
 //   k_f32_resolve<256>      182     38    32768        0      2
 //   k_f32_pack               14     24        0        0      8
 //   k_f32_merge              26     22        0        0      8
+//   k_f32g_topk<32>          82     26    16384        0      5
+//   k_f32g_topk<64>         113     26    16384        0      4
+//   k_f32g_topk<128>        174     26    16384        0      2
+//   k_f32g_topk<192>        144     28    28672        0      3
+//   k_f32g_topk<256>        180     27    32768        0      2
+//   k_f32g_resolve<32>       84     34    16384        0      5
+//   k_f32g_resolve<64>      114     34    16384        0      4
+//   k_f32g_resolve<128>     254     34    16384        0      2
+//   k_f32g_resolve<192>     147     34    28672        0      3
+//   k_f32g_resolve<256>     184     34    32768        0      2
+//   k_f32g_merge             26     25        0        0      8
+// The k_f32g_* kernels are the grouped form (stored representations, engine_reps_f32.hip): the same f32_sweep<DK> body, with the
+// problem of a workgroup, its trains and its tile range selected from a by-value table of at most four problems (F32Group).  The
+// selection is scalar compares on constant indices: it adds SGPRs, no VGPR at DK <= 128, and nothing inside the sweep loop.
 // Per (query, train) the sweep loop of k_f32_topk<DK> issues 100 / 195 / 387 / 551 / 744 vector instructions at DK = 32 / 64 / 128 /
 // 192 / 256 and DK / 4 ds_read_b128; at DK = 128 that is 96 v_sub_f32, 96 v_mul_f32, 103 v_add_f32, 28 v_pk_add_f32, 16 v_pk_mul_f32
 // and 48 for the key and its branch-free insertion (measured times 9.9).
@@ -311,6 +325,155 @@ void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, 
   const Fginn32Work w = fginn32_work(g, n1, work);
   static_assert(sizeof(F32Closed) == 16 && sizeof(F32Open) == 24, "record sizes");
   F32_BY_WIDTH(g, launch_resolve, s, g, w, nu, n2, pos, contrDistSq);
+}
+
+// ---- the grouped form: up to MATCH_MAXB problems, one stored query side, stored trains (engine_reps_f32.hip) ----------------------
+
+int fginn32_group_geometry(int n1, const int *n2, int G, int dim, F32Group &g, int *prob) {
+  g = F32Group();
+  g.DK = fginn32_kernel_width(dim);
+  g.tile = f32_tile_trains(g.DK);
+  g.gx = std::max(1, (n1 + 255) / 256);
+  for (int i = 0; i < G; i++) {
+    if (n2[i] <= 0) continue;
+    const int p = g.np++;
+    prob[p] = i;
+    g.n2[p] = n2[i];
+    g.ntiles[p] = (n2[i] + g.tile - 1) / g.tile;
+  }
+  const long total = (2048 + g.gx - 1) / g.gx;
+  int first = 0;
+  for (int p = 0; p < g.np; p++) {
+    // every problem is cut as it would be alone (fginn32_geometry): at most one split per tile; then no empty split
+    const int S = (int)std::min<long>(total, g.ntiles[p]);
+    g.tps[p] = (g.ntiles[p] + S - 1) / S;
+    g.S[p] = (g.ntiles[p] + g.tps[p] - 1) / g.tps[p];
+    g.first[p] = first;
+    first += g.S[p];
+  }
+  for (int p = g.np; p <= MATCH_MAXB; p++) g.first[p] = first;
+  return first;
+}
+
+// element p of a by-value table: compares and selects on constant indices, so the table stays in scalar registers
+template <class T>
+__device__ __forceinline__ T f32g_pick(const T *a, int p) {
+  T v = a[0];
+  if (p == 1) v = a[1];
+  if (p == 2) v = a[2];
+  if (p == 3) v = a[3];
+  return v;
+}
+static_assert(MATCH_MAXB == 4, "f32g_pick and the problem search below are written for four problems");
+
+// keys: [splits][n1][4].  Workgroup (x, y) sweeps split y -- tiles of ONE problem -- for the queries of block x; train indices are
+// the problem's own
+template <int DK>
+__global__ __launch_bounds__(256) void k_f32g_topk(const float *__restrict__ queries, int n1, const F32Group g,
+                                                   unsigned long long *__restrict__ keys) {
+  F32_SWEEP_LDS(DK);
+  const int q = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  const int p = (y >= g.first[1]) + (y >= g.first[2]) + (y >= g.first[3]);
+  const int tps = f32g_pick(g.tps, p), ntiles = f32g_pick(g.ntiles, p);
+  const int t0 = (y - f32g_pick(g.first, p)) * tps, t1 = min(ntiles, t0 + tps);
+  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
+  f32_sweep<DK>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(f32g_pick(g.trains, p)), f32g_pick(g.n2, p),
+                t0, t1, tile, part, [&](float d, int idx) {
+    const unsigned long long key = f32_key(d, idx);
+    if (key < k3) {
+      k3 = min(k3, max(k2, key));
+      k2 = min(k2, max(k1, key));
+      k1 = min(k1, max(k0, key));
+      k0 = min(k0, key);
+    }
+  });
+  if (q < n1) {
+    unsigned long long *o = keys + ((size_t)y * n1 + q) * 4;
+    o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
+  }
+}
+
+// top4[p][q] = the four smallest keys of query q over the splits of problem p = blockIdx.y
+__global__ __launch_bounds__(256) void k_f32g_merge(const unsigned long long *__restrict__ keys, int n1, const F32Group g,
+                                                    unsigned long long *__restrict__ top4) {
+  const int q = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+  if (q >= n1) return;
+  const int s0 = f32g_pick(g.first, p), s1 = s0 + f32g_pick(g.S, p);
+  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
+  for (int s = s0; s < s1; s++) {
+    const unsigned long long *k = keys + ((size_t)s * n1 + q) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const unsigned long long key = k[e];
+      k3 = min(k3, max(k2, key));
+      k2 = min(k2, max(k1, key));
+      k1 = min(k1, max(k0, key));
+      k0 = min(k0, key);
+    }
+  }
+  unsigned long long *o = top4 + ((size_t)p * n1 + q) * 4;
+  o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
+}
+
+// k_f32_resolve for the open walks of every problem at once: workgroup x belongs to one problem, one block of 256 of its open
+// entries and one of its splits
+template <int DK>
+__global__ __launch_bounds__(256) void k_f32g_resolve(const float *__restrict__ queries, const F32Open *__restrict__ open, const F32Group g,
+                                                      double contrDistSq, F32Closed *__restrict__ closed) {
+  F32_SWEEP_LDS(DK);
+  const int x = blockIdx.x;
+  const int p = (x >= g.rfirst[1]) + (x >= g.rfirst[2]) + (x >= g.rfirst[3]);
+  const int S = f32g_pick(g.S, p), local = x - f32g_pick(g.rfirst, p), ub = local / S, sp = local - ub * S;
+  const int tps = f32g_pick(g.tps, p), ntiles = f32g_pick(g.ntiles, p);
+  const int t0 = sp * tps, t1 = min(ntiles, t0 + tps);
+  const int u = f32g_pick(g.ubeg, p) + ub * 256 + threadIdx.x;
+  const bool live = u < f32g_pick(g.uend, p);
+  const double *__restrict__ pos = f32g_pick(g.pos, p);
+  F32Open o;
+  o.klast = F32_NONE; o.q = 0; o.t0 = 0; o.dpass = 0.f; o.pad = 0;
+  if (live) o = open[u];
+  const double px = pos[2 * (size_t)o.t0], py = pos[2 * (size_t)o.t0 + 1];
+  unsigned long long kterm = F32_NONE;
+  unsigned cnt = 0;
+  f32_sweep<DK>(live ? queries + (size_t)o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(f32g_pick(g.trains, p)), f32g_pick(g.n2, p),
+                t0, t1, tile, part, [&](float d, int idx) {
+    const unsigned long long key = f32_key(d, idx);
+    const double dx = px - pos[2 * (size_t)idx], dy = py - pos[2 * (size_t)idx + 1];
+    const bool terminal = d >= o.dpass || dx * dx + dy * dy > contrDistSq;
+    if (key > o.klast) {
+      if (terminal) kterm = min(kterm, key);
+      else cnt++;
+    }
+  });
+  if (live) {
+    if (kterm != F32_NONE) atomicMin(&closed[u].kterm, kterm);
+    if (cnt) atomicAdd(&closed[u].cnt, cnt);
+  }
+}
+
+template <int DK>
+static void launch_group_topk(hipStream_t s, const F32Group &g, const float *queries, int n1, unsigned long long *keys) {
+  hipLaunchKernelGGL(k_f32g_topk<DK>, dim3(g.gx, g.first[g.np]), dim3(256), 0, s, queries, n1, g, keys);
+}
+template <int DK>
+static void launch_group_resolve(hipStream_t s, const F32Group &g, const float *queries, const F32Open *open, double cd2, F32Closed *closed) {
+  hipLaunchKernelGGL(k_f32g_resolve<DK>, dim3(g.rfirst[g.np]), dim3(256), 0, s, queries, open, g, cd2, closed);
+}
+
+void launch_fginn32_group_topk(hipStream_t s, const F32Group &g, const float *queries, int n1, unsigned long long *keys,
+                               unsigned long long *top4) {
+  F32_BY_WIDTH(g, launch_group_topk, s, g, queries, n1, keys);
+  hipLaunchKernelGGL(k_f32g_merge, dim3(g.gx, g.np), dim3(256), 0, s, keys, n1, g, top4);
+}
+
+void launch_fginn32_group_resolve(hipStream_t s, const F32Group &g, const float *queries, const F32Open *open, double contrDistSq,
+                                  F32Closed *closed) {
+  F32_BY_WIDTH(g, launch_group_resolve, s, g, queries, open, contrDistSq, closed);
+}
+
+void launch_fginn32_pack_rows(hipStream_t s, const float *src, int n, int dim, int DK, float *dst, unsigned *flag, unsigned bit) {
+  hipLaunchKernelGGL(k_f32_pack, dim3((unsigned)(((size_t)n * (DK / 4) + 255) / 256)), dim3(256), 0, s, src, n, dim, DK, n, (float4 *)dst,
+                     flag, bit);
 }
 
 }  // namespace mx
