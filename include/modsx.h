@@ -236,8 +236,9 @@ int modsx_detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, in
  *                                            detectors/mser/extrema/extrema.h:11, extrema.cpp:284-473 (doOnNormal)
  * MSER+ (sub_type 21) then MSER- (sub_type 20) of one view: x, y = centroid, A = covariance^(1/2), s = 1,
  * response = margin.  The view is truncated to u8 on the device; the component tree itself is sequential host code
- * (as in the reference).  PARITY UNPINNED (the reference's MSER sources cannot be built in this image): checked against
- * an independent CPU restatement only.  *out is malloc'd (modsx_free).  Returns the number of keypoints. */
+ * (as in the reference).  Parity is pinned: tests/test_mser_ref_cpu.py and tests/test_gpu_mser_ref.py compare these entry points bit
+ * for bit with the reference's own MSER sources, compiled in place for the tests (images of 64 pixels and more; smaller ones are
+ * checked against the independent CPU restatement only).  *out is malloc'd (modsx_free).  Returns the number of keypoints. */
 void modsx_default_mser_params(modsx_mser_params *p);
 int modsx_detect_msers(modsx_ctx *ctx, const modsx_image *img, const modsx_mser_params *par, double tilt, double zoom,
                        modsx_keypoint **out);

@@ -23,7 +23,11 @@
 // Known deviations: the packed counters of the reference overflow their 15-bit size field when components of more than
 // 32767 pixels are merged before promotion (impossible for min_size <= 8191); AffineKeypoint::octave_number and
 // pyramid_scale are uninitialised stack values in the reference and 0 here; thresholds at level 255, for which the
-// reference never builds a boundary and would dereference NULL, are skipped.
+// reference never builds a boundary and would dereference NULL, are skipped (for min_margin >= 0 none can occur: pos + margin <= 255
+// leaves thresh = pos + margin / 2 = 255 only to a margin of 0); a region that is stable at threshold 0 -- relative margins, or
+// min_margin < 1, on an image that holds grey 0 (MSER+) or 255 (MSER-) -- gets its key here, where the reference fills nothing
+// (boundary.cpp marks with `thresh` in a picture cleared to 0) and ends the process on the NaN covariance; an image of fewer than
+// min(10000, min_size) pixels gives no keys here and a fault in the reference (its root label is never upgraded to a region).
 #include <emmintrin.h>
 #include <math.h>
 #include <stdint.h>

@@ -1,6 +1,7 @@
 /* oracle_mser.cpp -- TEST INFRASTRUCTURE ONLY: CPU restatement of the reference's MSER detector (SURVEY.md rows
- * E1, E2).  PARITY UNPINNED: the reference's MSER sources include OpenCV through detectors/helpers.h, cannot be
- * compiled in this image, and ship no golden vectors; this file follows the reference's own data structures step by
+ * E1, E2).  PINNED: the reference's MSER sources compile in place behind two stand-in OpenCV headers (oracle/Makefile,
+ * _ref/libmser_ref.so) and tests/test_mser_ref_cpu.py holds this file to them bit for bit, for images of 64 pixels and more (the
+ * reference faults on tiny ones; below that this file is the only check).  It follows the reference's own data structures step by
  * step (tagged label words, packed minimal regions, per-level pixel/border histograms) so that the product's
  * independent implementation (mods_amd/csrc/mser.cpp, plain union-find) can be cross-checked against it.
  *
@@ -337,8 +338,11 @@ extern "C" {
 /* DetectMSERs (doOnNormal), extrema.cpp:284-300, 393-468.  mode: orc detection_mode values as for the Hessian
  * detector.  Returns the number of keypoints (<= cap). */
 int orc_detect_msers(const float *img, int rows, int cols, int min_size, double max_area, double min_margin_par,
-                     int relative, int mode, int reg_number, double rel_threshold, double rel_reg_number, double tilt,
+                     int relative, int mode, int reg_number, double rel_threshold_par, double rel_reg_number_par, double tilt,
                      double zoom, orc_keypoint *out, int cap) {
+  /* ExtremaParams::rel_threshold and rel_reg_number are floats (extremaParams.h:68-70): 0.7 is 0.699999988 there, which moves
+   * floor(0.7 * 10) from 7 to 6 and the RELATIVE_TH probe below a tie at 70 % of the top margin */
+  const float rel_threshold = (float)rel_threshold_par, rel_reg_number = (float)rel_reg_number_par;
   if ((tilt > 2.0) || (zoom < 0.5)) reg_number = (int)floor(zoom * 2.0 * reg_number / tilt);
   const double min_margin = (mode != 0) ? 1.0 : min_margin_par;   /* FIXED_TH = 0 */
   Extrema E;

@@ -6,6 +6,7 @@ cpu_baseline leg of bench.py.  The product (mods_amd/) never imports this.
 import ctypes as C
 import os
 import subprocess
+import threading
 
 import numpy as np
 
@@ -37,16 +38,19 @@ class View(C.Structure):
                 ("doBlur", C.c_int)]
 
 
+_REF_MSER_SO = os.path.join(_HERE, "_ref", "libmser_ref.so")
+
+
 def build(force=False):
     so = os.path.join(_HERE, "liboracle.so")
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".cpp", ".hpp", ".h", ".c"))]
     stale = (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference/degensac"):
-        ref = os.path.join(_HERE, "_ref", "libdegensac_ref.so")
-        if force or not os.path.exists(ref):
-            subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    # the reference's own degensac and MSER, compiled in place where its sources are (`make ref` builds what is missing of the two)
+    want = [(os.path.join(_HERE, "_ref", "libdegensac_ref.so"), "/root/reference/degensac"), (_REF_MSER_SO, "/root/reference/detectors/mser")]
+    if any(os.path.isdir(src) and (force or not os.path.exists(lib_)) for lib_, src in want):
+        subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     return so
 
 
@@ -324,7 +328,10 @@ def ref_available():
 
 def detect_msers(img, min_size=30, max_area=0.05, min_margin=8.0, relative=0, mode=0, reg_number=500, rel_threshold=-1.0,
                  rel_reg_number=-1.0, tilt=1.0, zoom=1.0):
-    """DetectMSERs (extrema.cpp:284-473, doOnNormal); defaults = [MSER] of config_iter_mods_cviu.ini.  PARITY UNPINNED."""
+    """DetectMSERs (extrema.cpp:284-473, doOnNormal); defaults = [MSER] of config_iter_mods_cviu.ini.
+    The restatement (oracle_mser.cpp).  PINNED to the reference's own sources by tests/test_mser_ref_cpu.py (detect_msers_ref
+    below, bit for bit on the nine fields DetectMSERs sets) for images of 64 pixels and more.  NOT pinned: images under 64
+    pixels, which the reference cannot be handed, and the OpenCV-backed view synthesis that runs in front of MSER."""
     img = _f32(img)
     cap = 1 << 16
     while True:
@@ -336,6 +343,68 @@ def detect_msers(img, min_size=30, max_area=0.05, min_margin=8.0, relative=0, mo
         if n <= cap:
             return out[:n].copy()
         cap = n
+
+
+# ---- the reference's own MSER (oracle/_ref/libmser_ref.so: detectors/mser compiled in place, oracle/ref_mser_shim.cpp) ----
+# The reference faults (SIGSEGV) on tiny images: every image tried with fewer than 30 pixels at the default min_size = 30 did, and
+# every one tried with 30 or more ran.  64 is a MARGIN over that observed line of 30, not a measured quantity: nothing smaller is
+# handed to the reference, so images under 64 pixels are the one MSER input class that stays checked against the restatement
+# (detect_msers) alone.
+# The cause behind that line, read from the code and then measured (84 x 1 at min_size 85 faults, at 84 it runs; 10 x 10 at 101
+# faults, at 100 it runs): an image of fewer than min(10000, min_size) pixels never upgrades a component to a region, the root
+# label is still a packed counter when GetExtrema (getExtrema.cpp:428-434) casts it to a t_region pointer and dereferences it.
+# Such a call is refused below as well, whatever the image's size.
+REF_MSER_MIN_PIXELS = 64
+# the reference keeps its state in file-level statics (labels_ptr, g_cols, ...): one call at a time, whatever the thread
+_ref_mser_lock = threading.Lock()
+_ref_mser_lib = None
+
+
+def ref_mser_available():
+    build()
+    return os.path.exists(_REF_MSER_SO)
+
+
+def detect_msers_ref(img, min_size=30, max_area=0.05, min_margin=8.0, relative=0, mode=0, reg_number=500, rel_threshold=-1.0,
+                     rel_reg_number=-1.0, tilt=1.0, zoom=1.0):
+    """The reference's DetectMSERs (5-argument overload, extrema.cpp:284-473) on f32 pixels: its own (unsigned char) conversion,
+    component tree, stability selection, boundaries, ellipses and export.  Same keywords and defaults as detect_msers.
+    -> KEYPOINT records; octave_number and pyramid_scale, which the reference never writes, are zero."""
+    global _ref_mser_lib
+    img = _f32(img)
+    if img.ndim != 2:
+        raise ValueError("detect_msers_ref: a 2-d image is expected")
+    if img.size < REF_MSER_MIN_PIXELS:
+        raise ValueError("detect_msers_ref: the reference faults on tiny images; %d x %d is under the %d-pixel margin"
+                         % (img.shape[0], img.shape[1], REF_MSER_MIN_PIXELS))
+    if img.size < min(10000, int(min_size)):
+        raise ValueError("detect_msers_ref: the reference faults when the image (%d pixels) is smaller than min(10000, min_size = %d)"
+                         % (img.size, int(min_size)))
+    with _ref_mser_lock:
+        if _ref_mser_lib is None:
+            if not ref_mser_available():
+                raise RuntimeError("oracle/_ref/libmser_ref.so is not built: run `make -C oracle ref` where the reference is")
+            L = C.CDLL(_REF_MSER_SO)
+            L.refmser_detect.restype = C.c_int
+            L.refmser_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                         C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int]
+            _ref_mser_lib = L
+        cap = 1 << 12
+        while True:
+            out9 = np.zeros((cap, 9), np.float64)
+            n = _ref_mser_lib.refmser_detect(_p(img), img.shape[0], img.shape[1], int(relative), int(min_size), float(max_area),
+                                             float(min_margin), int(mode), float(rel_threshold), int(reg_number),
+                                             float(rel_reg_number), float(tilt), float(zoom), _p(out9), cap)
+            if n <= cap:
+                break
+            cap = n
+    out = np.zeros(n, KEYPOINT)
+    for i, f in enumerate(MSER_FIELDS):
+        out[f] = out9[:n, i]
+    return out
+
+
+MSER_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s", "response", "sub_type")    # what DetectMSERs sets, in the shim's order
 
 
 def loransac_h(pts, laf1, laf2, err_threshold=3.0, confidence=0.99, max_samples=100000, lo=1, hlaf_coef=12.0,

@@ -187,3 +187,10 @@ def need_ref(oracle):
     carried to the GPU box with the snapshot).  On a GPU box a missing build is an ERROR, not a skip: a green run must mean that
     the comparisons were made."""
     assert oracle.ref_available(), "oracle/_ref is not built: run `make -C oracle ref` where /root/reference exists"
+
+
+def need_mser_ref(oracle):
+    """The MSER comparisons are made against the reference's own extrema sources (oracle/_ref/libmser_ref.so, built from
+    /root/reference in place and carried to the GPU box with the snapshot).  The same rule as need_ref: where the comparison is
+    expected, a missing build is an ERROR, not a skip -- a green run must mean that the comparisons were made."""
+    assert oracle.ref_mser_available(), "oracle/_ref/libmser_ref.so is not built: run `make -C oracle ref` where /root/reference exists"

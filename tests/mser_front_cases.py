@@ -4,7 +4,8 @@ mser_front in engine_views.hip) and of the grey ingest (k_gray_u8 / k_gray_f32),
 The models restate the operations, not the kernels:
   trunc_u8_model   (unsigned char)float as x86 evaluates it (cvttss2si, low byte), DetectMSERs' `*ptr = (unsigned char)*in_ptr`
                    (extrema.cpp:401-403) and the oracle's oracle_mser.cpp:348; tests/test_mser_front_cases_cpu.py pins it to the
-                   oracle as built
+                   oracle as built, and tests/test_mser_ref_cpu.py to that very line of the reference as built (the reference on
+                   f32 pixels == the reference on this model's bytes, at every planted value)
   bin_sort_model   the stable counting sort by grey level that the component tree walks (sortPixels.cpp:76-125): 257 level starts
                    and the pixels' padded offsets (r + 1) * (cols + 2) + c + 1
   gray_model       the 3-channel ingest, f32(f64(f32(B + G)) * k + f64(R) * k) with the f64 constant k = 1. / 3.0

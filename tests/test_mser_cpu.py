@@ -1,6 +1,10 @@
-"""MSER.  PARITY UNPINNED: the reference's MSER sources cannot be compiled here, so the product
-(mods_amd/csrc/mser.cpp, array union-find) is checked against the independent restatement that follows the reference's own
-data structures (oracle/oracle_mser.cpp), plus properties that hold for any correct MSER."""
+"""MSER: the product (mods_amd/csrc/mser.cpp, array union-find) against the independent restatement that
+follows the reference's own data structures (oracle/oracle_mser.cpp), plus properties that hold for any correct MSER.
+
+PINNED: tests/test_mser_ref_cpu.py compares both the product and the restatement, bit for bit, with the reference's own MSER
+sources (compiled in place into oracle/_ref/libmser_ref.so) on these images and parameter sets and on many more.  NOT pinned: images
+under 64 pixels, which the reference cannot be handed (it faults on tiny images) -- the 1 x 37 and 23 x 1 images below stay with the
+restatement alone -- and the OpenCV-backed view synthesis that runs in front of MSER."""
 import numpy as np
 import pytest
 
