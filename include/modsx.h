@@ -46,6 +46,10 @@ enum { MODSX_DESC_SIFT = 0, MODSX_DESC_ROOT_SIFT = 1, MODSX_DESC_HALF_SIFT = 2, 
 /* The real-valued descriptor classes of a stored representation (modsx_rep_append_f32 and what follows it).  They share the
  * namespace of modsx_rep_class_sel::desc_type; every entry that takes the types 0..3 alone goes on refusing them. */
 enum { MODSX_DESC_CAFFE = 8, MODSX_DESC_DAISY = 9, MODSX_DESC_LIOP = 10, MODSX_DESC_MROGH = 11, MODSX_DESC_SURF = 12 };
+/* The binary descriptor classes of a stored representation (modsx_rep_append_bin and what follows it), in the same namespace;
+ * 4..7 and 13..15 stay unassigned.  Every entry that takes the types 0..3 alone, or 8..12, goes on refusing them. */
+enum { MODSX_DESC_BRISK = 16, MODSX_DESC_FREAK = 17, MODSX_DESC_ORB = 18 };
+enum { MODSX_DET_ORB = 4 };   /* detector_type DET_ORB, detectors/structures.hpp:20: a detector of binary classes only */
 /* ScaleSpaceDetector point types, affinedetectors/pyramid.h:32-36 */
 enum { MODSX_HESSIAN_DARK = 0, MODSX_HESSIAN_BRIGHT = 1, MODSX_HESSIAN_SADDLE = 2 };
 
@@ -761,7 +765,9 @@ int modsx_rep_match_fginn(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep
  * to the contexts applies to the RootSIFT classes (modsx_set_fginn_db; all contexts the same database, or none).  A partner
  * without regions gives the zeroed result with H = -1 and n_regions1 set.  Returns n.
  *   Float classes (MODSX_DESC_CAFFE .. MODSX_DESC_SURF, see modsx_rep_append_f32 below) are taken in classes[] as well and are part
- * of "every class" when n_classes == 0; modsx_rep_class_rank gives the order of all classes. */
+ * of "every class" when n_classes == 0; modsx_rep_class_rank gives the order of all classes.
+ *   Binary classes (MODSX_DESC_BRISK .. MODSX_DESC_ORB, see modsx_rep_append_bin below) are taken in classes[] only.  For a binary
+ * class the `ratio` field is the class's DistanceThreshold (MatchFLANNDistance), not an FGINN ratio. */
 typedef struct { int detector, desc_type; double ratio; } modsx_rep_class_sel;
 int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
                      const modsx_rep_class_sel *classes, int n_classes, const modsx_pair_params *par, modsx_pair_result *results);
@@ -1200,6 +1206,69 @@ int modsx_debug_fginn32_group_geometry(int n1, const int *n2, int G, int dim, in
 /* cumulative on this context: grouped launch sets, problems in them, queries sent to resolve, resolve launches.  Fills
  * out[0 .. min(n, 4) - 1], returns 4. */
 int modsx_fginn32_group_counters(modsx_ctx *ctx, long *out, int n);
+
+/* ---- binary descriptor classes of a stored representation (engine_reps_bin.hip) ------------------------------------------
+ * A modsx_rep also holds one class per (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_ORB, MODSX_DET_SURF}) x
+ * (binary descriptor type MODSX_DESC_BRISK, MODSX_DESC_FREAK, MODSX_DESC_ORB): the classes MatchImgReps matches with
+ * MatchFLANNDistance (see modsx_match_hamming for the search and the record rule).  A class takes any width
+ * 1 <= nbytes <= MODSX_HAMMING_MAX_BYTES and fixes it at its first append; a later append of another width is MODSX_ERR_ARG.
+ * The library does not extract such descriptors: the rows come from the caller, e.g. from modsx_load_regions.
+ *   Stored form.  A class keeps its rows exactly as the pack kernel of the Hamming search writes them: WK dwords per row (WK =
+ * the kernel width, ceil(nbytes / 4) rounded up to 1, 2, 4, 8 or 16), zero behind nbytes, the array 16-byte aligned, zero rows
+ * up to the capacity.  The capacity is a multiple of 1024 rows -- whole 256-query workgroups and whole train tiles at every WK --
+ * so the same buffer is the query side and the train side of any match and nothing is packed at match time.  An append packs
+ * its rows behind the old ones; the buffer starts at MODSX_REP_BIN_FIRST_ROWS rows and grows x4, copying the old rows once.
+ * The search never visits a row at or behind the class's count, so a zero padding row is never a neighbour.  An append that
+ * fails leaves the class as it was; a class that is still empty afterwards keeps no buffer.  A class holds at most 2 000 000
+ * regions.  The u8 and float classes and every entry that takes them are unchanged. */
+#define MODSX_REP_BIN_FIRST_ROWS 4096
+/* LoadRegions for a binary class: n regions and their dense [n][nbytes] rows, ids as given.  dtype 0 = u8, 1 = f32 holding the
+ * integers 0..255; anything else is MODSX_ERR_ARG (the rule of modsx_match_hamming).  Returns n; n == 0 is a no-op that returns
+ * 0.  MODSX_ERR_ARG: a detector or type that names no binary class, nbytes outside 1..64 or another width than the class holds,
+ * an invalid value, more than 2 000 000 regions in the class, a representation on another device. */
+int modsx_rep_append_bin(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const void *desc,
+                         int nbytes, int dtype, int n);
+/* The same from dense [n][nbytes] u8 rows that already live in HBM (any alignment); the regions come from the host. */
+int modsx_rep_append_bin_device(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs,
+                                const void *dev_desc_u8, int nbytes, int n);
+/* The regions and dense [n][nbytes] u8 rows of one binary class as malloc'd copies (modsx_free), and its width (0 while the
+ * class is empty); any pointer may be NULL.  Returns n. */
+int modsx_rep_class_bin(modsx_ctx *ctx, const modsx_rep *rep, int detector, int desc_type, modsx_region **regs, unsigned char **desc_u8,
+                        int *nbytes);
+/* Stage tap: the MatchFLANNDistance records of one binary class, rep1 the queries, rep2 the trains -- what
+ * modsx_match_hamming_device returns for the same rows. */
+int modsx_rep_match_hamming(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep *rep2, int detector, int desc_type,
+                            double distanceThreshold, modsx_tentative **out);
+/* Stage tap of the grouped launch set: the class of rep1 against that class of 1 <= G <= 4 partners in ONE launch set (one
+ * search launch and one merge launch for all partners, one copy of G x n1 x 16 bytes back; the Hamming search has no walk and no
+ * resolve pass).  outs[g] (modsx_free) / counts[g]: partner g's records, those of modsx_rep_match_hamming(rep1, reps2[g]).
+ * Partners with an empty class give 0 records and are left out of the launches.  Returns G.
+ *   Refusals of both taps and of modsx_match_reps for a binary class, all MODSX_ERR_ARG before any launch: a train class of
+ * exactly one region in ANY partner (the reference reads a second neighbour that was never written), distanceThreshold <= 0 or
+ * not finite, widths that differ between the two representations, a (detector, type) pair that names no binary class, a
+ * representation on another device, G outside 1..4. */
+int modsx_rep_match_group_hamming(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int detector,
+                                  int desc_type, double distanceThreshold, modsx_tentative **outs, int *counts);
+/* modsx_match_reps takes binary classes in classes[], with the class's DistanceThreshold in the `ratio` field.  With
+ * n_classes == 0 binary classes are NOT included: modsx_pair_params has no distance threshold, and the reference matches a class
+ * only if its section gives one.  A binary class costs one grouped launch set per group of partners; the pair tail is that of
+ * modsx_match_regions_hamming (DuplicateFiltering with key = ratio, NaN from 0 / 0 as it is there, then LORANSACFiltering).
+ * Classes are concatenated in the order of modsx_rep_class_order.
+ * host only: the position of a class in the std::map order of the reference's names over every (descriptor, detector) name pair
+ * -- descriptor BRISK, CAFFE, DAISY, FREAK, HalfRootSIFT, HalfSIFT, LIOP, MROGH, ORB, RootSIFT, SIFT, SURF, then detector
+ * HessianAffine, MSER, ORB, SURF: 4 x the descriptor's place + the detector's -- or -1 for a pair that names no class of a
+ * representation.  modsx_rep_class_rank is unchanged and does not know the binary classes; on the 27 classes it knows, the two
+ * functions agree in relative order. */
+int modsx_rep_class_order(int detector, int desc_type);
+/* host only, no context: the table the grouped launch set would use for n1 queries against G <= 4 partners of n2[g] rows of
+ * nbytes bytes.  geometry[4] = {tile length in trains, kernel width WK, query blocks, splits in all}; per_problem [G][3] =
+ * {tiles, splits, tiles per split} (zeros for an empty partner); splits [cap][3] = {partner, first tile, end tile} of the first
+ * min(cap, splits) splits in launch order (may be NULL with cap 0).  Returns the number of splits.  Every partner with rows has
+ * the S and tiles per split modsx_debug_hamming_geometry(n1, n2[g], nbytes, 0) gives it alone, whatever shares the launch. */
+int modsx_debug_hamming_group_geometry(int n1, const int *n2, int G, int nbytes, int *geometry, int *per_problem, int *splits, int cap);
+/* cumulative on this context: grouped launch sets, problems in them, rows packed by appends, pack launches issued at match time
+ * (0 for stored matches).  Fills out[0 .. min(n, 4) - 1], returns 4. */
+int modsx_hamming_group_counters(modsx_ctx *ctx, long *out, int n);
 
 /* Measurement hooks (no reference counterpart; the reference only keeps wall-clock TimeLog, structures.hpp:51-74).
  * modsx_profile(ctx, 1) brackets every kernel launch with HIP events on the ctx stream and accumulates, per kernel

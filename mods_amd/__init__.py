@@ -125,6 +125,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_rep_append_f32", "modsx_rep_describe_append", "modsx_rep_class_f32", "modsx_rep_match_fginn_f32",
            "modsx_rep_match_group_f32", "modsx_rep_class_rank", "modsx_debug_fginn32_group_geometry",
            "modsx_fginn32_group_counters",
+           "modsx_rep_append_bin", "modsx_rep_append_bin_device", "modsx_rep_class_bin", "modsx_rep_match_hamming",
+           "modsx_rep_match_group_hamming", "modsx_rep_class_order", "modsx_debug_hamming_group_geometry",
+           "modsx_hamming_group_counters",
            "modsx_match_hamming", "modsx_match_hamming_device", "modsx_hamming_tentatives", "modsx_debug_match_hamming",
            "modsx_match_regions_hamming", "modsx_debug_hamming_geometry",
            "modsx_blur_geometry", "modsx_detect_counters", "modsx_debug_pyramids", "modsx_debug_scan_levels",
@@ -171,6 +174,12 @@ DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, 
 # include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
 DESC_CAFFE, DESC_DAISY, DESC_LIOP, DESC_MROGH, DESC_SURF = 8, 9, 10, 11, 12
 REP_F32_FIRST_ROWS = 4096
+# include/modsx.h: the binary descriptor classes of a stored representation, their own detector, the first capacity in rows
+DET_ORB = 4
+DESC_BRISK, DESC_FREAK, DESC_ORB = 16, 17, 18
+REP_BIN_FIRST_ROWS = 4096
+# include/modsx.h: modsx_hamming_group_counters, in its order
+HAMMING_GROUP_COUNTERS = ("launch_sets", "problems", "rows_packed", "match_pack_launches")
 # include/modsx.h: modsx_daisy_counters, in its order
 DAISY_COUNTERS = ("calls", "patches", "sub_batches")
 DAISY_MAX_DIM, DAISY_MAX_TAPS = 200, 51      # include/modsx.h: MODSX_DAISY_MAX_DIM, MODSX_DAISY_MAX_TAPS
@@ -277,6 +286,16 @@ def lib():
         L.modsx_debug_fginn32_group_geometry.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_int]
         L.modsx_fginn32_group_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_rep_append_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.modsx_rep_append_bin_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.modsx_rep_class_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_rep_match_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.modsx_rep_match_group_hamming.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                                    C.c_void_p]
+        L.modsx_rep_class_order.argtypes = [C.c_int, C.c_int]
+        L.modsx_debug_hamming_group_geometry.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_int]
+        L.modsx_hamming_group_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_match_reps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p]
         L.modsx_match_one_to_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -767,6 +786,39 @@ class Rep(object):
 
     def count_f32(self, detector=0, desc_type=DESC_CAFFE):
         return _check(lib().modsx_rep_class_f32(self.ctx.h, self.h, int(detector), int(desc_type), None, None, None), "rep_class_f32")
+
+    # ---- binary classes (DESC_BRISK, DESC_FREAK, DESC_ORB; detector DET_HESSIAN, DET_MSER, DET_ORB or DET_SURF) ----
+    def append_bin(self, regs, rows, detector=DET_ORB, desc_type=DESC_ORB, ctx=None, dtype=None):
+        """LoadRegions for a binary class: regions (REGION records) and their dense [n][nbytes] rows (uint8, or anything convertible
+        to float32 holding the integers 0..255).  dtype overrides the dtype code handed to the library.  Returns n."""
+        regs = np.ascontiguousarray(regs, REGION)
+        d = np.ascontiguousarray(rows)
+        if d.dtype != np.uint8:
+            d = np.ascontiguousarray(d, np.float32)
+        if d.ndim != 2 or len(d) != len(regs):
+            raise ValueError("rep.append_bin: [n][nbytes] rows for n regions are expected")
+        code = (0 if d.dtype == np.uint8 else 1) if dtype is None else int(dtype)
+        return _check(lib().modsx_rep_append_bin((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs), _p(d),
+                                                 d.shape[1], code, len(regs)), "rep_append_bin")
+
+    def append_bin_device(self, regs, dev_ptr, nbytes, detector=DET_ORB, desc_type=DESC_ORB, ctx=None):
+        """The same from dense [n][nbytes] uint8 rows in HBM at address dev_ptr (any alignment); the regions come from the host."""
+        regs = np.ascontiguousarray(regs, REGION)
+        return _check(lib().modsx_rep_append_bin_device((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs),
+                                                        C.c_void_p(dev_ptr), int(nbytes), len(regs)), "rep_append_bin_device")
+
+    def regions_bin(self, detector=DET_ORB, desc_type=DESC_ORB, want_desc=True):
+        """(regions, dense [n][nbytes] uint8 rows) of one binary class, nbytes = 0 while it is empty; want_desc=False: the regions."""
+        regs, rows, nb = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        n = _check(lib().modsx_rep_class_bin(self.ctx.h, self.h, int(detector), int(desc_type), C.byref(regs),
+                                             C.byref(rows) if want_desc else None, C.byref(nb)), "rep_class_bin")
+        r = _take(regs, n, REGION)
+        if not want_desc:
+            return r
+        return r, _take(rows, n * nb.value, np.dtype(np.uint8)).reshape(n, nb.value)
+
+    def count_bin(self, detector=DET_ORB, desc_type=DESC_ORB):
+        return _check(lib().modsx_rep_class_bin(self.ctx.h, self.h, int(detector), int(desc_type), None, None, None), "rep_class_bin")
 
     def free(self):
         if self.h:
@@ -1404,6 +1456,30 @@ class Context(object):
         _check(lib().modsx_fginn32_group_counters(self.h, _p(out), 4), "fginn32_group_counters")
         return dict(zip(("launch_sets", "problems", "resolve_queries", "resolve_launches"), (int(x) for x in out)))
 
+    def rep_match_hamming(self, rep1, rep2, detector=DET_ORB, desc_type=DESC_ORB, distance_threshold=64.0):
+        """MatchFLANNDistance of one binary class of two stored representations: rep1 the queries, rep2 the trains."""
+        out = C.c_void_p()
+        n = _check(lib().modsx_rep_match_hamming(self.h, rep1.h, rep2.h, int(detector), int(desc_type), C.c_double(distance_threshold),
+                                                 C.byref(out)), "rep_match_hamming")
+        return _take(out, n, TENT)
+
+    def rep_match_group_hamming(self, rep1, reps2, detector=DET_ORB, desc_type=DESC_ORB, distance_threshold=64.0):
+        """The grouped launch set: one binary class of rep1 against that class of 1..4 partners; a list of TENT arrays."""
+        G = len(reps2)
+        rarr = (C.c_void_p * max(1, G))(*[r.h for r in reps2])
+        outs = (C.c_void_p * max(1, G))()
+        counts = (C.c_int * max(1, G))()
+        _check(lib().modsx_rep_match_group_hamming(self.h, rep1.h, rarr, G, int(detector), int(desc_type),
+                                                   C.c_double(distance_threshold), outs, counts), "rep_match_group_hamming")
+        return [_take(C.c_void_p(outs[g]), counts[g], TENT) for g in range(G)]
+
+    def hamming_group_counters(self):
+        """dict of HAMMING_GROUP_COUNTERS: grouped Hamming launch sets, problems in them, rows packed by appends and pack launches
+        issued at match time (none for stored matches) on this context, cumulative."""
+        out = np.zeros(4, np.int64)
+        _check(lib().modsx_hamming_group_counters(self.h, _p(out), 4), "hamming_group_counters")
+        return dict(zip(HAMMING_GROUP_COUNTERS, (int(x) for x in out)))
+
     def match_pair_views(self, img1, img2, views, params):
         arr = _view_array(views)
         res = PairResult()
@@ -1660,6 +1736,27 @@ def fginn32_group_geometry(n1, n2, dim):
     _check(lib().modsx_debug_fginn32_group_geometry(int(n1), _p(n2), len(n2), int(dim), _p(geo), _p(per), _p(sp), total),
            "fginn32_group_geometry")
     return dict(tile=int(geo[0]), DK=int(geo[1]), gx=int(geo[2]), splits=[tuple(int(v) for v in r) for r in sp[:total]],
+                per_problem=[tuple(int(v) for v in r) for r in per[:len(n2)]])
+
+
+def rep_class_order(detector, desc_type):
+    """The position of a class in the order match_reps concatenates ALL kinds of classes in, the binary ones included: 4 x the
+    place of the descriptor's name + the place of the detector's name among the reference's names; -1 when a representation has
+    no such class (host only)."""
+    return int(lib().modsx_rep_class_order(int(detector), int(desc_type)))
+
+
+def hamming_group_geometry(n1, n2, nbytes):
+    """The table of the grouped Hamming search for n1 queries against len(n2) <= 4 partners of n2[g] rows (host only): dict(tile,
+    WK, gx, splits = [(partner, first tile, end tile), ...] in launch order, per_problem = [(tiles, splits, tiles per split), ...])."""
+    n2 = np.ascontiguousarray(n2, np.int32)
+    geo, per = np.zeros(4, np.int32), np.zeros((max(1, len(n2)), 3), np.int32)
+    total = _check(lib().modsx_debug_hamming_group_geometry(int(n1), _p(n2), len(n2), int(nbytes), _p(geo), _p(per), None, 0),
+                   "hamming_group_geometry")
+    sp = np.zeros((max(1, total), 3), np.int32)
+    _check(lib().modsx_debug_hamming_group_geometry(int(n1), _p(n2), len(n2), int(nbytes), _p(geo), _p(per), _p(sp), total),
+           "hamming_group_geometry")
+    return dict(tile=int(geo[0]), WK=int(geo[1]), gx=int(geo[2]), splits=[tuple(int(v) for v in r) for r in sp[:total]],
                 per_problem=[tuple(int(v) for v in r) for r in per[:len(n2)]])
 
 
@@ -1930,7 +2027,9 @@ def match_pairs_views(ctxs, imgs1, imgs2, views, params, arrays=True):
 
 def match_reps(ctxs, rep1, reps2, params, classes=None, arrays=True):
     """modsx_match_reps: MatchImgReps + verification of rep1 against every representation of reps2 over several contexts.
-    classes = [(detector, descriptor type, ratio), ...]; None: every non-empty class with the ratio params gives its descriptor."""
+    classes = [(detector, descriptor type, ratio), ...]; None: every non-empty class with the ratio params gives its descriptor.
+    For a binary class (DESC_BRISK, DESC_FREAK, DESC_ORB) `ratio` is its DistanceThreshold; binary classes are matched only when
+    they are listed."""
     n = len(reps2)
     carr = (C.c_void_p * max(1, len(ctxs)))(*[c.h for c in ctxs])
     rarr = (C.c_void_p * max(1, n))(*[r.h for r in reps2])

@@ -981,10 +981,16 @@ int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, c
   if (n_classes > 0) {
     for (int k = 0; k < n_classes; k++) {
       int det;
-      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det) && !mx::rep_class_f32_ok(classes[k].detector, classes[k].desc_type, &det)) {
+      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det) && !mx::rep_class_f32_ok(classes[k].detector, classes[k].desc_type, &det) &&
+          !mx::rep_class_bin_ok(classes[k].detector, classes[k].desc_type, &det)) {
         mx::set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG;
       }
       if (present.has(det, classes[k].desc_type)) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
+      if (classes[k].desc_type >= MODSX_DESC_BRISK) {
+        // a binary class: `ratio` is its DistanceThreshold; every partner is checked before any group is launched
+        const int rc = mx::reps_bin_check("modsx_match_reps", ctxs[0], rep1, reps2, n, det, classes[k].desc_type, classes[k].ratio);
+        if (rc) return rc;
+      }
       present.add(det, classes[k].desc_type);
       sel[nsel++] = classes[k];
     }

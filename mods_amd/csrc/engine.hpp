@@ -341,6 +341,24 @@ HammingGeo hamming_geometry(int n1, int n2, int W, int splits);   // splits = 0:
 size_t hamming_workspace_bytes(const HammingGeo &g, int n1);
 void launch_hamming(hipStream_t s, const HammingGeo &g, const uint8_t *d1, int n1, const uint8_t *d2, int n2, int nbytes, void *work,
                     int *nn2, hipEvent_t *ev = nullptr);             // ev: three events, around the packing and the search launches
+// The grouped form: np <= MATCH_MAXB problems share one stored query side; problem p has its own stored trains (rows of WK dwords,
+// zero rows up to a multiple of 1024 rows: whole tiles at every WK).  This is the whole table of the launch set, passed to the
+// kernels by value.  Problem p owns the splits [first[p], first[p + 1]) of tps[p] whole tiles each; entries of first behind np
+// hold the total, so that no workgroup selects an unused problem.
+struct HamGroup {
+  const uint32_t *trains[MATCH_MAXB];
+  int n2[MATCH_MAXB], ntiles[MATCH_MAXB], tps[MATCH_MAXB], S[MATCH_MAXB];
+  int first[MATCH_MAXB + 1];
+  int np, gx, WK, tile;
+};
+int hamming_kernel_width(int W);
+// n2[0..G): every problem's trains; problems with n2 == 0 are left out (prob[k] = the caller's index of table problem k).  Every
+// problem is cut as hamming_geometry(n1, n2, W, 0) cuts it alone: its S and tps, whatever G is.  Returns the splits in all.
+int hamming_group_geometry(int n1, const int *n2, int G, int W, HamGroup &g, int *prob);
+// part: [first[np]][n1][2] keys; nn2: [np][n1][4] ints
+void launch_hamming_group(hipStream_t s, const HamGroup &g, const uint32_t *queries, int n1, unsigned long long *part, int *nn2);
+// dst: n rows of WK dwords at their place in a stored class, from dense [n][nbytes] u8 rows of any alignment
+void launch_hamming_pack_rows(hipStream_t s, const uint8_t *src, int n, int nbytes, int WK, uint32_t *dst);
 // FGINN matching of f32 rows of any width (kernels_fginn32.hip).  DK = the kernel width dim rounds up to; tile = trains per LDS
 // tile; the train axis is cut into S splits of tilesPerSplit tiles; gx x S workgroups of k_f32_topk.
 struct Fginn32Geo { int dim, DK, tile, ntiles, tilesPerSplit, S, gx; };
@@ -557,6 +575,9 @@ struct modsx_ctx {
   // modsx_fginn32_group_counters: grouped launch sets, problems in them, queries sent to resolve, resolve launches
   mx::DevBuf repStage;
   long f32GroupCounters[4] = {0, 0, 0, 0};
+  // binary classes (engine_reps_bin.hip), modsx_hamming_group_counters: grouped launch sets, problems in them, rows packed by
+  // appends, pack launches issued at match time (stored matches issue none)
+  long hamGroupCounters[4] = {0, 0, 0, 0};
   int busyDepth = 0;           // nesting of mx::CtxBusy on this context (its driving thread only)
   int shardLane = 0;           // lane of the rank's communicator this context issues its collectives on (engine_shard.hip)
   modsx_ctx *peer = nullptr;   // second stream + buffers, created on demand: the two images of a multi-view pair run side by side

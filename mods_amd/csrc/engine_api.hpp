@@ -269,7 +269,7 @@ inline const DbSet *fginn_db_for(const modsx_ctx *c, int descType) { return desc
 // The region list a tentative's indices refer to: the per-class lists of one image in the order GetCorresponcesVector walks
 // the classes (descriptor name, then detector name), as segments -- two descriptor classes of one detector share their
 // regions, so the concatenation is never materialised.
-constexpr int REP_CLASSES_MAX = 2 * MODSX_MAX_DESC + 3 * 5;   // the u8 classes and the float classes of a stored representation
+constexpr int REP_CLASSES_MAX = 2 * MODSX_MAX_DESC + 3 * 5 + 4 * 3;   // the u8, the float and the binary classes of a stored representation
 struct RegList {
   const modsx_region *p[REP_CLASSES_MAX];
   size_t end[REP_CLASSES_MAX];   // running end index of every segment
@@ -328,10 +328,22 @@ struct RepSlotF {
   int capDK = 0;
   DevBuf rows, pos;
 };
+// One binary class of a stored representation (engine_reps_bin.hip): the host region list and the rows exactly as k_hamming_pack
+// writes them (kernels_hamming.hip: WK dwords per row, zero behind nbytes, zero rows up to the capacity, which is a multiple of
+// 1024 rows: whole workgroups of queries and whole train tiles at every WK).  nbytes is fixed by the first append that succeeds.
+constexpr size_t REP_BIN_FIRST_ROWS = 4096;      // MODSX_REP_BIN_FIRST_ROWS: the first capacity of a binary slot (grows x4)
+struct RepSlotB {
+  std::vector<modsx_region> regs;
+  int nbytes = 0, WK = 0;
+  size_t cap = 0;                // rows the buffer has room for, each of capWK dwords
+  int capWK = 0;
+  DevBuf rows;
+};
 // the tentatives of every class's last match against one partner (CorrespondencesMapMap[desc][det])
-struct RepTents { std::vector<modsx_tentative> t[2][4], f[3][5]; };
-// A class by its slot: det 0 = HessianAffine, 1 = MSER, 2 = SURF; type = MODSX_DESC_* (0..3: u8 slots, det 0..1 only; 8..12: float
-// slots).  A RepClassList is sorted by rep_class_rank: the order GetCorresponcesVector("All", "All") concatenates the classes in.
+struct RepTents { std::vector<modsx_tentative> t[2][4], f[3][5], b[4][3]; };
+// A class by its slot; type = MODSX_DESC_*.  0..3: u8 slots, det 0 = HessianAffine, 1 = MSER; 8..12: float slots, det 2 = SURF as
+// well; 16..18: binary slots, det 0 = HessianAffine, 1 = MSER, 2 = ORB, 3 = SURF.  A RepClassList is sorted by rep_slot_order: the
+// order GetCorresponcesVector("All", "All") concatenates the classes in.
 struct RepClassId { int det, type; };
 struct RepClassList {
   int n = 0;
@@ -357,6 +369,22 @@ int rep_class_f32(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_r
 int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
                          double ratio, double contradDist, int nn, std::vector<modsx_tentative> *outs);
 void rep_free_f32(modsx_rep *rep);
+// binary classes (engine_reps_bin.hip); det = the slot index rep_class_bin_ok gives
+bool rep_class_bin_ok(int detector, int desc_type, int *det);    // a binary class
+int rep_class_order(int detector, int desc_type);                // over every class a representation can hold; -1: no such class
+int rep_slot_order(int det, int type);                           // the same by slot (RepClassId)
+const std::vector<modsx_region> &rep_slot_regions(const modsx_rep *rep, int det, int type);      // of any kind of class
+int rep_append_bin(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const uint8_t *rows, bool onDevice,
+                   int nbytes, int n, const char *fn);
+int rep_class_bin(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, unsigned char **rows, int *nbytes);
+// what every stored Hamming match refuses before any launch, over n partners: another device, widths that differ, a train class
+// of exactly one region, a threshold that is not positive and finite
+int reps_bin_check(const char *fn, const modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int n, int det, int type,
+                   double distanceThreshold);
+// MatchFLANNDistance of one binary class for G <= MATCH_MAXB partners in one grouped launch set; outs[g]: partner g's records
+int reps_bin_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
+                         double distanceThreshold, std::vector<modsx_tentative> *outs);
+void rep_free_bin(modsx_rep *rep);
 bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u);   // false: a value that is not one of the integers 0..255
 int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_image *const *imgs2, int G,
                      const modsx_pair_params &pp, modsx_pair_result *res, std::vector<VerifyTask> *deferred = nullptr);
@@ -401,5 +429,6 @@ int loransac_h(const double *pts, const double *laf1, const double *laf2, int T,
                double *Hraw, unsigned char *inl, unsigned char *keep, int *data_out, int error_type = 0);
 }  // namespace mx
 
-// slot[det][type]: det 0 = HessianAffine, 1 = MSER; type = MODSX_DESC_* 0..3.  fslot[det][type - MODSX_DESC_CAFFE]: det 2 = SURF
-struct modsx_rep { int dev; mx::RepSlot slot[2][4]; mx::RepSlotF fslot[3][5]; };
+// slot[det][type]: det 0 = HessianAffine, 1 = MSER; type = MODSX_DESC_* 0..3.  fslot[det][type - MODSX_DESC_CAFFE]: det 2 = SURF.
+// bslot[det][type - MODSX_DESC_BRISK]: det 0 = HessianAffine, 1 = MSER, 2 = ORB, 3 = SURF
+struct modsx_rep { int dev; mx::RepSlot slot[2][4]; mx::RepSlotF fslot[3][5]; mx::RepSlotB bslot[4][3]; };

@@ -70,6 +70,7 @@ int hamming_search_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t
     for (int i = 0; i < 3; i++) hipEventDestroy(ev[i]);
   }
   MX_HIP(e);
+  c->hamGroupCounters[3] += 2;      // both sides were packed for this call (modsx_hamming_group_counters)
   memcpy(nn2, c->hMatch.p, rowB);
   return MODSX_OK;
 }

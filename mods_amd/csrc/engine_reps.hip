@@ -9,7 +9,8 @@
 // when the slot changes, and every match that takes the slot as its train side starts from it (kernels_match.hip
 // launch_match_pack_trains, MatchProblem::packed).  A representation is changed by one thread at a time; otherwise it is
 // read-only and any context of its device may match against it, also at the same time.  The float classes (SURF, LIOP, DAISY,
-// MROGH, learned vectors) and their grouped search are engine_reps_f32.hip; reps_match_group and reps_verify_task take both kinds.
+// MROGH, learned vectors) and their grouped search are engine_reps_f32.hip, the binary classes (ORB, BRISK, FREAK) and theirs
+// engine_reps_bin.hip; reps_match_group and reps_verify_task take all three kinds.
 #include <math.h>
 #include <algorithm>
 #include "engine_api.hpp"
@@ -101,6 +102,14 @@ int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const
       for (int g = 0; g < G; g++) tents[g]->f[det][type - MODSX_DESC_CAFFE] = std::move(out[g]);
       continue;
     }
+    if (rep_class_bin_ok(sel[s].detector, type, &det)) {
+      // a binary class: one grouped launch set of the Hamming search (engine_reps_bin.hip); `ratio` is its DistanceThreshold
+      std::vector<modsx_tentative> out[MATCH_MAXB];
+      const int rc = reps_bin_match_group(c, "modsx_match_reps", rep1, reps2, G, det, type, sel[s].ratio, out);
+      if (rc) return rc;
+      for (int g = 0; g < G; g++) tents[g]->b[det][type - MODSX_DESC_BRISK] = std::move(out[g]);
+      continue;
+    }
     if (!rep_class_ok(sel[s].detector, type, &det)) { set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
     const RepSlot &q = rep1->slot[det][type];
     const uint8_t *d1[MATCH_MAXB], *d2[MATCH_MAXB];
@@ -137,14 +146,14 @@ void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepCla
   for (int i = 0; i < 9; i++) res->H[i] = -1;
   task.l1.clear(); task.l2.clear(); task.own.clear(); task.tents.clear();
   for (int i = 0; i < classes.n; i++) {
-    const int d = classes.k[i].det, t = classes.k[i].type, ft = t - MODSX_DESC_CAFFE;
-    const bool f32 = t >= MODSX_DESC_CAFFE;
-    const std::vector<modsx_region> &a = f32 ? rep1->fslot[d][ft].regs : rep1->slot[d][t].regs;
-    const std::vector<modsx_region> &b = f32 ? rep2->fslot[d][ft].regs : rep2->slot[d][t].regs;
+    const int d = classes.k[i].det, t = classes.k[i].type;
+    const std::vector<modsx_region> &a = rep_slot_regions(rep1, d, t), &b = rep_slot_regions(rep2, d, t);
     if (a.empty() && b.empty()) continue;
     const int o1 = (int)task.l1.size(), o2 = (int)task.l2.size();
     task.l1.add(a); task.l2.add(b);
-    for (modsx_tentative tt : f32 ? tents.f[d][ft] : tents.t[d][t]) {
+    const std::vector<modsx_tentative> &mine = t >= MODSX_DESC_BRISK ? tents.b[d][t - MODSX_DESC_BRISK] :
+                                               t >= MODSX_DESC_CAFFE ? tents.f[d][t - MODSX_DESC_CAFFE] : tents.t[d][t];
+    for (modsx_tentative tt : mine) {
       tt.q += o1; tt.t0 += o2;
       if (tt.t1 >= 0) tt.t1 += o2;
       if (tt.tj >= 0) tt.tj += o2;
@@ -174,6 +183,7 @@ void modsx_rep_free(modsx_ctx *ctx, modsx_rep *rep) {
   hipSetDevice(ctx ? ctx->dev : rep->dev);
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) { rep->slot[d][t].desc.release(); rep->slot[d][t].pack.release(); }
   rep_free_f32(rep);
+  rep_free_bin(rep);
   delete rep;
 }
 

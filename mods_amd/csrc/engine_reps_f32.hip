@@ -42,7 +42,7 @@ bool rep_class_f32_ok(int detector, int desc_type, int *det) {
 }
 void RepClassList::add(int det, int type) {
   int at = n;
-  while (at > 0 && slot_rank(k[at - 1].det, k[at - 1].type) > slot_rank(det, type)) { k[at] = k[at - 1]; at--; }
+  while (at > 0 && rep_slot_order(k[at - 1].det, k[at - 1].type) > rep_slot_order(det, type)) { k[at] = k[at - 1]; at--; }
   k[at] = {det, type};
   n++;
 }

@@ -32,6 +32,15 @@
 //   k_hamming_2nn<16>       44     25     4096        0      8
 //   k_hamming_pack          11     24        0        0      8
 //   k_hamming_merge         14     16        0        0      8
+//   k_hamg_2nn<1>           18     27     4096        0      8
+//   k_hamg_2nn<2>           22     27     4096        0      8
+//   k_hamg_2nn<4>           32     27     4096        0      8
+//   k_hamg_2nn<8>           52     27     4096        0      8
+//   k_hamg_2nn<16>          44     25     4096        0      8
+//   k_hamg_merge            14     19        0        0      8
+// k_hamg_* are the grouped form at the end of the file: up to four problems of one stored query side in one launch, the sweep
+// (ham_sweep) shared with k_hamming_2nn.  k_hamg_2nn asks for eight waves per SIMD in its launch bounds: without that the compiler
+// gives the <16> instance 92 VGPRs (occupancy 5) where the same loop in k_hamming_2nn<16> takes 44.
 // i.e. eight workgroups of 256 per CU (the 32-wave cap), 32 KiB of the CU's 160 KiB LDS.  Per (query, train) k_hamming_2nn<8>
 // issues 2 WK + 3.75 vector instructions (WK v_xor_b32, WK v_bcnt_u32_b32, v_lshl_or_b32, v_max_u32, v_min_u32, half a v_min3_u32,
 // a quarter of a v_mov_b32) and WK / 4 ds_read_b128 (measured times 9.8).
@@ -90,14 +99,14 @@ __device__ __forceinline__ unsigned long long ham_key64(unsigned k) {
   return k == HAM_NONE ? ~0ull : ((unsigned long long)(k >> HAM_IDX_BITS) << 32) | (k & ((1u << HAM_IDX_BITS) - 1));
 }
 
-// part: [S][n1][2] keys.  Split blockIdx.y sweeps the tiles [y * tilesPerSplit, ...) of `trains` (ntiles whole tiles, zero rows
-// behind row n2 - 1, which the sweep never visits).
+// The sweep both search kernels share.  Query q's WK dwords go into VGPRs (zeros for q >= n1); the tiles [t0, t1) of `trains` (whole
+// tiles, zero rows behind row n2 - 1, which the sweep never visits: jn = min(T, n2 - base)) pass through `tile`; k1 <= k2 leave as
+// the two smallest 32-bit keys met, HAM_NONE where there is none.
 template <int WK>
-__global__ __launch_bounds__(256) void k_hamming_2nn(const uint32_t *__restrict__ queries, int n1, const uint4 *__restrict__ trains,
-                                                     int n2, int ntiles, int tilesPerSplit, unsigned long long *__restrict__ part) {
+__device__ __forceinline__ void ham_sweep(const uint32_t *__restrict__ queries, int q, int n1, const uint4 *__restrict__ trains, int n2,
+                                          int t0, int t1, uint32_t *tile, unsigned &k1, unsigned &k2) {
   constexpr int T = HAM_TILE_DWORDS / WK;
-  __shared__ __attribute__((aligned(16))) uint32_t tile[HAM_TILE_DWORDS];
-  const int tid = threadIdx.x, q = blockIdx.x * 256 + tid;
+  const int tid = threadIdx.x;
   uint32_t a[WK];
 #pragma unroll
   for (int w = 0; w < WK; w++) a[w] = 0;
@@ -111,8 +120,7 @@ __global__ __launch_bounds__(256) void k_hamming_2nn(const uint32_t *__restrict_
       for (int w = 0; w < WK; w++) a[w] = queries[(size_t)q * WK + w];
     }
   }
-  const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
-  unsigned k1 = HAM_NONE, k2 = HAM_NONE;
+  k1 = HAM_NONE; k2 = HAM_NONE;
   uint4 nxt = trains[(size_t)t0 * 256 + tid];
   for (int t = t0; t < t1; t++) {
     __syncthreads();                                   // the previous tile is no longer read
@@ -130,6 +138,18 @@ __global__ __launch_bounds__(256) void k_hamming_2nn(const uint32_t *__restrict_
       k1 = min(k1, key);
     }
   }
+}
+
+// part: [S][n1][2] keys.  Split blockIdx.y sweeps the tiles [y * tilesPerSplit, ...) of `trains` (ntiles whole tiles, zero rows
+// behind row n2 - 1, which the sweep never visits).
+template <int WK>
+__global__ __launch_bounds__(256) void k_hamming_2nn(const uint32_t *__restrict__ queries, int n1, const uint4 *__restrict__ trains,
+                                                     int n2, int ntiles, int tilesPerSplit, unsigned long long *__restrict__ part) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[HAM_TILE_DWORDS];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
+  unsigned k1, k2;
+  ham_sweep<WK>(queries, q, n1, trains, n2, t0, t1, tile, k1, k2);
   if (q < n1) {
     unsigned long long *o = part + ((size_t)blockIdx.y * n1 + q) * 2;
     o[0] = ham_key64(k1);
@@ -184,6 +204,104 @@ void launch_hamming(hipStream_t s, const HammingGeo &g, const uint8_t *d1, int n
   }
   hipLaunchKernelGGL(k_hamming_merge, dim3(g.gx), dim3(256), 0, s, part, n1, g.S, (int4 *)nn2);
   if (ev) hipEventRecord(ev[2], s);
+}
+
+// ---- the grouped form: up to MATCH_MAXB problems, one stored query side, stored trains (engine_reps_bin.hip) ------------------------
+
+// Every problem is cut as hamming_geometry(n1, n2, W, 0) cuts it alone, whatever shares the launch; problems without trains are
+// left out (prob[k] = the caller's index of table problem k).  Returns the splits of the whole group.
+int hamming_group_geometry(int n1, const int *n2, int G, int W, HamGroup &g, int *prob) {
+  g = HamGroup();
+  g.WK = hamming_kernel_width(W);
+  g.tile = HAM_TILE_DWORDS / g.WK;
+  g.gx = std::max(1, (n1 + 255) / 256);
+  int first = 0;
+  for (int i = 0; i < G; i++) {
+    if (n2[i] <= 0) continue;
+    const HammingGeo one = hamming_geometry(n1, n2[i], W, 0);
+    const int p = g.np++;
+    prob[p] = i;
+    g.n2[p] = n2[i]; g.ntiles[p] = one.ntiles; g.tps[p] = one.tilesPerSplit; g.S[p] = one.S;
+    g.first[p] = first;
+    first += one.S;
+  }
+  for (int p = g.np; p <= MATCH_MAXB; p++) g.first[p] = first;
+  return first;
+}
+
+// element p of a by-value table: compares and selects on constant indices, so the table stays in scalar registers
+template <class T>
+__device__ __forceinline__ T hamg_pick(const T *a, int p) {
+  T v = a[0];
+  if (p == 1) v = a[1];
+  if (p == 2) v = a[2];
+  if (p == 3) v = a[3];
+  return v;
+}
+static_assert(MATCH_MAXB == 4, "hamg_pick and the problem search below are written for four problems");
+
+// part: [splits of the group][n1][2] keys.  Workgroup (x, y) sweeps split y -- whole tiles of ONE problem -- for the queries of
+// block x; the keys carry the problem's own train index
+template <int WK>
+__global__ __launch_bounds__(256, 8) void k_hamg_2nn(const uint32_t *__restrict__ queries, int n1, const HamGroup g,
+                                                  unsigned long long *__restrict__ part) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[HAM_TILE_DWORDS];
+  const int q = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  const int p = (y >= g.first[1]) + (y >= g.first[2]) + (y >= g.first[3]);
+  const int tps = hamg_pick(g.tps, p);
+  const int t0 = (y - hamg_pick(g.first, p)) * tps, t1 = min(hamg_pick(g.ntiles, p), t0 + tps);
+  unsigned k1, k2;
+  ham_sweep<WK>(queries, q, n1, reinterpret_cast<const uint4 *>(hamg_pick(g.trains, p)), hamg_pick(g.n2, p), t0, t1, tile, k1, k2);
+  if (q < n1) {
+    unsigned long long *o = part + ((size_t)y * n1 + q) * 2;
+    o[0] = ham_key64(k1);
+    o[1] = ham_key64(k2);
+  }
+}
+
+// nn2[p][q] = {first, d(first), second, d(second)} of query q over the splits of problem p = blockIdx.y
+__global__ __launch_bounds__(256) void k_hamg_merge(const unsigned long long *__restrict__ part, int n1, const HamGroup g,
+                                                    int4 *__restrict__ nn2) {
+  const int q = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+  if (q >= n1) return;
+  const int s0 = hamg_pick(g.first, p), s1 = s0 + hamg_pick(g.S, p);
+  unsigned long long k1 = ~0ull, k2 = ~0ull;
+  for (int s = s0; s < s1; s++) {
+    const unsigned long long *k = part + ((size_t)s * n1 + q) * 2;
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      const unsigned long long key = k[e];
+      k2 = min(k2, max(k1, key));
+      k1 = min(k1, key);
+    }
+  }
+  int4 r;
+  r.x = k1 == ~0ull ? -1 : (int)(k1 & 0xffffffffu); r.y = k1 == ~0ull ? -1 : (int)(k1 >> 32);
+  r.z = k2 == ~0ull ? -1 : (int)(k2 & 0xffffffffu); r.w = k2 == ~0ull ? -1 : (int)(k2 >> 32);
+  nn2[(size_t)p * n1 + q] = r;
+}
+
+template <int WK>
+static void launch_group_2nn(hipStream_t s, const HamGroup &g, const uint32_t *q, int n1, unsigned long long *part) {
+  hipLaunchKernelGGL(k_hamg_2nn<WK>, dim3(g.gx, g.first[g.np]), dim3(256), 0, s, q, n1, g, part);
+}
+
+// queries: n1 stored rows of g.WK dwords; g.trains[p]: problem p's stored rows (whole tiles, zero behind n2[p]); part:
+// [g.first[g.np]][n1][2] keys; nn2: [g.np][n1] int4.  n1 >= 1, g.np >= 1
+void launch_hamming_group(hipStream_t s, const HamGroup &g, const uint32_t *queries, int n1, unsigned long long *part, int *nn2) {
+  switch (g.WK) {
+    case 1: launch_group_2nn<1>(s, g, queries, n1, part); break;
+    case 2: launch_group_2nn<2>(s, g, queries, n1, part); break;
+    case 4: launch_group_2nn<4>(s, g, queries, n1, part); break;
+    case 8: launch_group_2nn<8>(s, g, queries, n1, part); break;
+    default: launch_group_2nn<16>(s, g, queries, n1, part); break;
+  }
+  hipLaunchKernelGGL(k_hamg_merge, dim3(g.gx, g.np), dim3(256), 0, s, part, n1, g, (int4 *)nn2);
+}
+
+// dst: n rows of WK dwords at their place in a stored class (k_hamming_pack on a destination offset; nothing behind them is written)
+void launch_hamming_pack_rows(hipStream_t s, const uint8_t *src, int n, int nbytes, int WK, uint32_t *dst) {
+  hipLaunchKernelGGL(k_hamming_pack, dim3((unsigned)(((size_t)n * WK + 255) / 256)), dim3(256), 0, s, src, n, nbytes, WK, n, dst);
 }
 
 }  // namespace mx
