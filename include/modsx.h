@@ -1149,6 +1149,56 @@ int modsx_debug_surfdet(modsx_ctx *ctx, const modsx_image *img, const modsx_surf
  * found, points accepted, regrows of the point buffer.  Fills out[0 .. min(n, 5) - 1], returns 5. */
 int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- external affine adaptation: DetectAffineShape (synth-detection.cpp:922-1074) on a caller's regions ------------------
+ * Baumberg iteration on the view image itself for a finished region list: what SynthDetectDescribeKeypoints runs
+ * (imagerepresentation.cpp:1226-1236) in every detector branch that sets doExternalAffineAdaptation -- SURF with doBaumberg = 1
+ * (imagerepresentation.cpp:1048), ORB, FAST, STAR, BRISK, KAZE, FOCI, SFOP, WAVE, WASH, TILDE-plugin.  Per region, bit for bit:
+ *   lx, ly    (float)det_kp.x, (float)det_kp.y on img (no pyramid, no pixelDistance)
+ *   ratio     (float)(det_kp.s / (double)1.6f): the function's own constant, formed on the host in f64; no parameter replaces it
+ *   border    interpolateCheckBorders(cols, rows, lx, ly, (float)a11 .. (float)a22, res, res) with res = (int)(2 * 5.0 * ratio)
+ *             (truncated toward zero) and the region's OWN matrix: a region that fails is dropped without an iteration
+ *   loop      from the identity (the input matrix takes part in the border test only), the AFF_BMBRG_SMM body of findAffineShape
+ *             on the kernels of modsx_detect_affine_keypoints, one launch per call on the context's stream
+ *   output    the converged regions in input order, det_kp.a11 .. a22 = the f32 shape widened to double, every other field as
+ *             given; NaN, negative discriminant, anisotropy above 6 and the iteration limit drop the region.
+ * The reference function ends without a return statement; these entries return the number of output regions.
+ * Defaults (modsx_default_affshape_params): AffineShapeParams(), detectors/affinedetectors/affine.h:52-63 -- maxIterations 16
+ * (:54), convergenceThreshold 0.05 (:56), smmWindowSize 19 (:58), affBmbrgMethod AFF_BMBRG_SMM (:61).
+ * Refusals, MODSX_ERR_ARG with a message and before any launch: a null pointer or a negative count; smmWindowSize even or
+ * outside 3..19; affBmbrgMethod other than 0 (AFF_BMBRG_HESSIAN needs cv::SVD and is built nowhere in this library); an image
+ * below 4 x 4; a region whose x, y, s or matrix entries are not finite, or with |10 * ratio| >= 2^31 (the reference's conversion
+ * to int is undefined there).  maxIterations has no upper limit: the kernels loop to it and keep no per-iteration storage.
+ * Parameters and regions are checked first; then n == 0 or maxIterations <= 0 gives 0 regions (*out an empty array) without a
+ * launch and without a look at the context or the image.  Pixels must be finite. */
+typedef struct modsx_affshape_params {
+  int maxIterations;            /* 16 */
+  int smmWindowSize;            /* 19 */
+  float convergenceThreshold;   /* 0.05 */
+  int affBmbrgMethod;           /* 0 = AFF_BMBRG_SMM; 1 = AFF_BMBRG_HESSIAN is refused */
+} modsx_affshape_params;
+void modsx_default_affshape_params(modsx_affshape_params *p);
+/* out: malloc'd (modsx_free).  Returns the number of regions. */
+int modsx_detect_affine_shape(modsx_ctx *ctx, const modsx_image *img, const modsx_region *in, int n,
+                              const modsx_affshape_params *par, modsx_region **out);
+/* The same for n_imgs images in one launch: in = the counts[0] regions of image 0, then those of image 1, ...; out likewise with
+ * out_counts[i] regions of image i.  Returns the total.  Each image's list equals what modsx_detect_affine_shape gives for it. */
+int modsx_detect_affine_shape_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_region *in,
+                                    const int *counts, const modsx_affshape_params *par, modsx_region **out, int *out_counts);
+/* Test entry: the same job list and launch, reported per INPUT region -- border [.] = the up-front test, u [.][4] / ok / iters as
+ * modsx_debug_baumberg reports them (the state and the loop counter when the loop was left; identity, ok = 0 and iters = -1 for
+ * a border-refused region; identity, 0, 0 and no launch with maxIterations <= 0).  variant: -1 = what the entries above launch
+ * (modsx_debug_baumberg_variant), 0..3 as modsx_debug_baumberg_geometry; geometry [4] = that of the launch over the regions
+ * that passed the border test.  Returns the number of regions launched. */
+int modsx_debug_affine_shape(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_region *in, const int *counts,
+                             const modsx_affshape_params *par, int variant, unsigned char *border, float *u, int *ok, int *iters,
+                             int *geometry);
+/* host only: ratio [n], res [n] (the truncated window argument) and border [n] (1 = refused) of every region on a cols x rows
+ * image; any of the three may be NULL.  Returns n, or MODSX_ERR_ARG for a region or an image the entries above refuse. */
+int modsx_affshape_jobs(const modsx_region *in, int n, int cols, int rows, float *ratio, int *res, unsigned char *border);
+/* External adaptation work of this context since modsx_create, cumulative (measurement hook): calls, regions in, regions the
+ * border test refused, regions launched, regions converged, launches.  Fills out[0 .. min(n, 6) - 1], returns 6. */
+int modsx_affshape_counters(modsx_ctx *ctx, long *out, int n);
+
 /* ---- float descriptor classes of a stored representation (engine_reps_f32.hip) -------------------------------------------
  * A modsx_rep also holds one class per (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF}) x (float descriptor
  * type MODSX_DESC_CAFFE .. MODSX_DESC_SURF), as RegionVectorMap[det][desc] does for any descriptor name.  Widths: CAFFE any

@@ -45,6 +45,12 @@ def surfdet_params(octaves=4, intervals=4, init_sample=2, thresh=0.0004):
     return SurfDetParams(int(octaves), int(intervals), int(init_sample), float(thresh))
 
 
+class AffShapeParams(C.Structure):
+    """modsx_affshape_params: the fields of AffineShapeParams that DetectAffineShape reads"""
+    _fields_ = [("maxIterations", C.c_int), ("smmWindowSize", C.c_int), ("convergenceThreshold", C.c_float),
+                ("affBmbrgMethod", C.c_int)]
+
+
 class MserParams(C.Structure):
     _fields_ = [("min_size", C.c_int), ("max_area", C.c_double), ("min_margin", C.c_double), ("relative", C.c_int),
                 ("mode", C.c_int), ("reg_number", C.c_int), ("rel_threshold", C.c_float), ("rel_reg_number", C.c_float)]
@@ -143,6 +149,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_surf_tables", "modsx_surf_counters",
            "modsx_detect_surf", "modsx_detect_surf_batch", "modsx_surf_regions", "modsx_surfdet_geometry", "modsx_surfdet_normalise",
            "modsx_debug_surfdet", "modsx_surfdet_counters",
+           "modsx_default_affshape_params", "modsx_detect_affine_shape", "modsx_detect_affine_shape_batch",
+           "modsx_debug_affine_shape", "modsx_affshape_jobs", "modsx_affshape_counters",
            "modsx_daisy_dim", "modsx_daisy_patches", "modsx_daisy_patches_device", "modsx_describe_regions_daisy",
            "modsx_describe_regions_daisy_device", "modsx_daisy_tables", "modsx_daisy_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -169,6 +177,8 @@ SURF_COUNTERS = ("calls", "patches", "sub_batches")
 SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
 # include/modsx.h: modsx_surfdet_counters, in its order
 SURFDET_COUNTERS = ("calls", "images", "extrema", "accepted", "regrows")
+# include/modsx.h: modsx_affshape_counters, in its order
+AFFSHAPE_COUNTERS = ("calls", "regions", "border_refused", "launched", "converged", "launches")
 DET_SURF, SURFDET_MAX_LAYERS = 6, 12      # include/modsx.h: MODSX_DET_SURF, MODSX_SURFDET_MAX_LAYERS
 DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, MODSX_DET_MSER
 # include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
@@ -355,6 +365,13 @@ def lib():
         L.modsx_debug_surfdet.argtypes = [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
         L.modsx_surfdet_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_daisy_tables.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9
+        L.modsx_default_affshape_params.restype = None
+        L.modsx_default_affshape_params.argtypes = [C.c_void_p]
+        L.modsx_detect_affine_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.modsx_detect_affine_shape_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.modsx_debug_affine_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.modsx_affshape_jobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_affshape_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_daisy_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -504,6 +521,28 @@ def surf_regions(kps, img_id=0):
     out = np.zeros(len(kps), REGION)
     _check(lib().modsx_surf_regions(_p(kps), len(kps), int(img_id), _p(out)), "surf_regions")
     return out
+
+
+def default_affshape_params(**kw):
+    """AffineShapeParams() as DetectAffineShape reads it: maxIterations 16, smmWindowSize 19, convergenceThreshold 0.05, SMM."""
+    p = AffShapeParams()
+    lib().modsx_default_affshape_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def affshape_jobs(regs, cols, rows):
+    """dict(ratio [n] f32, res [n] i32, border [n] bool): what DetectAffineShape forms on the host for every region of a cols x rows
+    image -- (float)(s / (double)1.6f), the truncated window argument (int)(10.0 * ratio) and the up-front border test with the
+    region's own matrix (no device needed); raises for regions or images the library refuses."""
+    regs = np.ascontiguousarray(regs, REGION)
+    n = len(regs)
+    ratio, res, border = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+    _check(lib().modsx_affshape_jobs(_p(regs), n, int(cols), int(rows), _p(ratio), _p(res), _p(border)), "affshape_jobs")
+    return dict(ratio=ratio[:n], res=res[:n], border=border[:n].astype(bool))
 
 
 def surfdet_normalise(params):
@@ -1078,6 +1117,56 @@ class Context(object):
         plane = lambda a, k: a[ofs[k]:ofs[k + 1]].reshape(layers[k, 1], layers[k, 0])      # noqa: E731
         return dict(layers=layers, integral=integral, resp=[plane(resp, k) for k in range(nl)], lap=[plane(lap, k) for k in range(nl)],
                     extrema=ext[:m], dD=dD[:m], H=H[:m], x=x[:m], accepted=acc[:m].astype(bool), laplacian=lp[:m])
+
+    # ---- external affine adaptation (engine_detect.hip: DetectAffineShape) ----
+    def detect_affine_shape(self, img, regs, params=None):
+        """DetectAffineShape on a finished region list: the regions whose Baumberg iteration on the image converges, in input
+        order, det_kp.a11 .. a22 replaced by the shape found (every other field as given)."""
+        params = params or default_affshape_params()
+        regs = np.ascontiguousarray(regs, REGION)
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_affine_shape(self._c(), C.c_void_p(img.h), _p(regs), len(regs), C.byref(params), C.byref(out)),
+                   "detect_affine_shape")
+        return _take(out, n, REGION)
+
+    @staticmethod
+    def _affshape_lists(imgs, regs):
+        assert len(imgs) == len(regs)
+        regs = [np.ascontiguousarray(r, REGION) for r in regs]
+        ptrs = (C.c_void_p * max(1, len(imgs)))(*[im.h for im in imgs])
+        counts = np.array([len(r) for r in regs] + [0], np.int32)
+        flat = np.concatenate(regs + [np.zeros(0, REGION)]) if regs else np.zeros(0, REGION)
+        return ptrs, counts, np.ascontiguousarray(flat, REGION)
+
+    def detect_affine_shape_batch(self, imgs, regs, params=None):
+        """detect_affine_shape of several images (any sizes; regs: one REGION array per image) in one launch: a list of REGION arrays."""
+        params = params or default_affshape_params()
+        ptrs, counts, flat = self._affshape_lists(imgs, regs)
+        out_counts = np.zeros(len(imgs) + 1, np.int32)
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_affine_shape_batch(self._c(), ptrs, len(imgs), _p(flat), _p(counts), C.byref(params), C.byref(out),
+                                                         _p(out_counts)), "detect_affine_shape_batch")
+        allr = _take(out, n, REGION)
+        ends = np.cumsum(out_counts[:len(imgs)])
+        return [allr[e - k:e].copy() for e, k in zip(ends, out_counts[:len(imgs)])]
+
+    def debug_affine_shape(self, imgs, regs, params=None, variant=-1):
+        """modsx_debug_affine_shape: the launch of detect_affine_shape_batch reported per INPUT region (image 0's, then image 1's,
+        ...) -> dict(border bool [n], u [n, 4] f32, ok, iters (-1 for a border-refused region), geometry, launched).  variant -1 =
+        the production rule, 0..3 as baumberg_geometry."""
+        params = params or default_affshape_params()
+        ptrs, counts, flat = self._affshape_lists(imgs, regs)
+        n = len(flat)
+        border, u = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 4), np.float32)
+        ok, iters, geo = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(4, np.int32)
+        launched = _check(lib().modsx_debug_affine_shape(self._c(), ptrs, len(imgs), _p(flat), _p(counts), C.byref(params), int(variant),
+                                                         _p(border), _p(u), _p(ok), _p(iters), _p(geo)), "debug_affine_shape")
+        return dict(border=border[:n].astype(bool), u=u[:n], ok=ok[:n], iters=iters[:n],
+                    geometry=dict(zip(BAUMBERG_GEOMETRY, (int(x) for x in geo))), launched=launched)
+
+    def affshape_counters(self):
+        """dict of AFFSHAPE_COUNTERS: external affine adaptation work of this context since it was created (cumulative)."""
+        return self._counters("modsx_affshape_counters", AFFSHAPE_COUNTERS)
 
     def surfdet_counters(self):
         """dict of SURFDET_COUNTERS: SURF detector work of this context since it was created (cumulative)."""

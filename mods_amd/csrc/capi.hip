@@ -1759,8 +1759,87 @@ int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n) {
   return read_counters("modsx_surfdet_counters", ctx->sdCounters, 5, out, n);
 }
 
+// ---- external affine adaptation, DetectAffineShape (engine_detect.hip) ----
+void modsx_default_affshape_params(modsx_affshape_params *p) {
+  if (!p) return;
+  // AffineShapeParams(), detectors/affinedetectors/affine.h:52-63
+  p->maxIterations = 16;            // :54
+  p->smmWindowSize = 19;            // :58
+  p->convergenceThreshold = 0.05f;  // :56
+  p->affBmbrgMethod = 0;            // :61 AFF_BMBRG_SMM
+}
+int modsx_affshape_jobs(const modsx_region *in, int n, int cols, int rows, float *ratio, int *res, unsigned char *border) {
+  return affshape_jobs("modsx_affshape_jobs", in, n, cols, rows, ratio, res, border);
+}
+// what the three entries check before they look at the context: the parameters, the counts and every region's values (against
+// the images where they are given); total = the regions in all
+static int affshape_args(const char *fn, const modsx_image *const *imgs, int n_imgs, const modsx_region *in, const int *counts,
+                         const modsx_affshape_params *par, long *total) {
+  if (!par) { mx::set_error(std::string(fn) + ": null argument: par"); return MODSX_ERR_ARG; }
+  int rc = affshape_check(fn, *par);
+  if (rc) return rc;
+  if (n_imgs < 0 || (n_imgs > 0 && !counts)) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  *total = 0;
+  for (int i = 0; i < n_imgs; i++) {
+    if (counts[i] < 0 || (counts[i] > 0 && !in)) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+    const modsx_image *im = imgs ? imgs[i] : nullptr;
+    rc = affshape_jobs(fn, in + *total, counts[i], im ? im->cols : 4, im ? im->rows : 4, nullptr, nullptr, nullptr);
+    if (rc < 0) return rc;
+    *total += counts[i];
+  }
+  return MODSX_OK;
+}
+int modsx_detect_affine_shape_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_region *in, const int *counts,
+                                    const modsx_affshape_params *par, modsx_region **out, int *out_counts) {
+  const char *fn = "modsx_detect_affine_shape_batch";
+  NEED(out);
+  long total = 0;
+  int rc = affshape_args(fn, imgs, n_imgs, in, counts, par, &total);
+  if (rc) return rc;
+  if (n_imgs > 0 && !out_counts) { mx::set_error(std::string(fn) + ": null argument: out_counts"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n_imgs; i++) out_counts[i] = 0;
+  std::vector<modsx_region> all;
+  if (total == 0 || par->maxIterations <= 0) { *out = to_malloc(all); return 0; }
+  NEED(ctx); NEED(imgs);
+  for (int i = 0; i < n_imgs; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  std::vector<std::vector<modsx_region>> r(n_imgs);
+  rc = affine_shape_batch(ctx, fn, imgs, n_imgs, in, counts, *par, -1, r.data(), nullptr);
+  if (rc < 0) return rc;
+  for (int i = 0; i < n_imgs; i++) { out_counts[i] = (int)r[i].size(); all.insert(all.end(), r[i].begin(), r[i].end()); }
+  *out = to_malloc(all);
+  return (int)all.size();
+}
+int modsx_detect_affine_shape(modsx_ctx *ctx, const modsx_image *img, const modsx_region *in, int n, const modsx_affshape_params *par,
+                              modsx_region **out) {
+  int count = 0;
+  const modsx_image *imgs[1] = {img};
+  if (n < 0) { mx::set_error("modsx_detect_affine_shape: bad argument"); return MODSX_ERR_ARG; }
+  return modsx_detect_affine_shape_batch(ctx, imgs, 1, in, &n, par, out, &count);
+}
+int modsx_debug_affine_shape(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_region *in, const int *counts,
+                             const modsx_affshape_params *par, int variant, unsigned char *border, float *u, int *ok, int *iters,
+                             int *geometry) {
+  const char *fn = "modsx_debug_affine_shape";
+  NEED(ctx); NEED(geometry);
+  long total = 0;
+  int rc = affshape_args(fn, imgs, n_imgs, in, counts, par, &total);
+  if (rc) return rc;
+  if (n_imgs > 0) NEED(imgs);
+  for (int i = 0; i < n_imgs; i++) NEED(imgs[i]);
+  if (total > 0 && (!border || !u || !ok || !iters)) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  if (variant < -1 || variant > 3) { mx::set_error(std::string(fn) + ": variant must be -1 .. 3"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  const AffShapeReport rep = {border, u, ok, iters, geometry};
+  return affine_shape_batch(ctx, fn, imgs, n_imgs, in, counts, *par, variant, nullptr, &rep);
+}
+int modsx_affshape_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  return read_counters("modsx_affshape_counters", ctx->affshapeCounters, 6, out, n);
+}
+
 // ---- DAISY (engine_daisy.hip) ----
-#define DAISY_ARGS(fn, bad)                                                                           \
+#define DAISY_ARGS(fn, bad)                                                                          \
   do {                                                                                                \
     PATCH_ARGS(fn, bad);                                                                               \
     if (daisy_check_args(fn, patchSize, rad, radq, thq, histq, nrm_type)) return MODSX_ERR_ARG;      \

@@ -61,6 +61,8 @@ struct Candidate {
 };
 
 // Baumberg: one wave per scale-space keypoint
+// external form (launch_baumberg_external, DetectAffineShape on a caller's regions): blur = the view image, x, y = the position in
+// it, s = the RATIO the window steps by (formed by the host in f64), pixelDistance is not read
 struct AffJob {
   const float *blur;  // prevBlur level
   int rows, cols;
@@ -236,6 +238,8 @@ constexpr int BAUM_RANGES = 8, BAUM_COUNTER_STRIDE = 32, BAUM_QUEUE_BYTES = BAUM
 MX_HD int baum_range_start(int n, int r) { return (int)(((long long)n * r) / BAUM_RANGES); }   // range r = keypoints start(r) .. start(r + 1)
 bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
                      float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean);
+bool launch_baumberg_external(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                              float convTh, int variant, int chunk, int resident, unsigned *queue, bool queueClean);
 constexpr int ATAN_CASES = 2048 + 64;   // 8 x 256 (sign / octant bits, table index) values of atan2LUTff's angle + the special case (entry 2048), padded
 constexpr int ORI_NV = 1344;   // entries of the orientation kernel's voting-pixel list (1245 under the mask, padded to 64 lanes x 21)
 constexpr int ORI_PSP = 44;    // row stride of the orientation kernel's padded 41 x 41 patch: what the voting list indexes
@@ -571,6 +575,9 @@ struct modsx_ctx {
   mx::DevBuf sdInteg, sdResp, sdLap, sdFlags, sdCounts, sdTab, sdPoints, sdExt;
   mx::PinBuf sdHost, sdBack;
   long sdCounters[5] = {0, 0, 0, 0, 0};  // modsx_surfdet_counters: calls, images, extrema found, points accepted, buffer regrows
+  // external affine adaptation (engine_detect.hip: affine_shape_batch), modsx_affshape_counters: calls, regions in, regions the
+  // border test refused, regions launched, regions converged, launches
+  long affshapeCounters[6] = {0, 0, 0, 0, 0, 0};
   // float classes of stored representations (engine_reps_f32.hip): dense rows of a device extractor on their way into a slot, and
   // modsx_fginn32_group_counters: grouped launch sets, problems in them, queries sent to resolve, resolve launches
   mx::DevBuf repStage;

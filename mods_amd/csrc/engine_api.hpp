@@ -29,6 +29,16 @@ int debug_scan_levels(modsx_ctx *c, const float *resps, const float *blurs, int 
 int debug_baumberg_geometry(modsx_ctx *c, int n, int W, int variant, int chunk, int *geo);
 int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, const int *planeOf, const float *xyspd, int n,
                    const modsx_hessaff_params &p, int variant, int chunk, float *u, int *ok, int *iters, int *geo, int *handedOut);
+// DetectAffineShape (synth-detection.cpp:922-1074) on a caller's regions (engine_detect.hip).  affshape_check / affshape_jobs: the
+// refusals and the per-region host work that need no device (ratio, truncated window argument, up-front border test; each output
+// optional); fn names the entry in the error text.  affine_shape_batch: in = the regions of image 0, then image 1, ... (counts per
+// image); variant -1 = the production rule; out (optional) [nImgs]: the converged regions of every image; rep (optional): the
+// per-INPUT-region report of modsx_debug_affine_shape.  Returns the number of regions launched or a negative status.
+struct AffShapeReport { unsigned char *border; float *u; int *ok; int *iters; int *geo; };
+int affshape_check(const char *fn, const modsx_affshape_params &p);
+int affshape_jobs(const char *fn, const modsx_region *in, int n, int cols, int rows, float *ratio, int *res, unsigned char *border);
+int affine_shape_batch(modsx_ctx *c, const char *fn, const modsx_image *const *imgs, int nImgs, const modsx_region *in, const int *counts,
+                       const modsx_affshape_params &p, int variant, std::vector<modsx_region> *out, const AffShapeReport *rep);
 void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out);
 // reproj (optional, one entry per image): what the caller's reproject_regions will be called with.  A region that
 // reproject_certain_drop flags for it is treated like one at the view's border: no orientation job and no output entry,

@@ -688,6 +688,149 @@ int debug_baumberg(modsx_ctx *c, const modsx_image *const *planes, int nplanes, 
   return MODSX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// External affine adaptation: DetectAffineShape (synth-detection.cpp:922-1074) on a caller's regions
+// ------------------------------------------------------------------------------------------------
+int affshape_check(const char *fn, const modsx_affshape_params &p) {
+  if (p.smmWindowSize < 3 || p.smmWindowSize > 19 || !(p.smmWindowSize & 1)) {
+    set_error(std::string(fn) + ": smmWindowSize must be odd and in 3..19"); return MODSX_ERR_ARG;
+  }
+  if (p.affBmbrgMethod != 0) {
+    set_error(std::string(fn) + ": affBmbrgMethod must be 0 (AFF_BMBRG_SMM); AFF_BMBRG_HESSIAN needs cv::SVD and is not built");
+    return MODSX_ERR_ARG;
+  }
+  if (!std::isfinite(p.convergenceThreshold)) { set_error(std::string(fn) + ": convergenceThreshold must be finite"); return MODSX_ERR_ARG; }
+  return MODSX_OK;
+}
+
+// The host's share of a region (synth-detection.cpp:949-964).  ratio: `float ratio = det_kp.s / initialSigma` with s a double and
+// initialSigma the function's `const float 1.6` -- an f64 division rounded once; the window argument `2*5.0*ratio` is the double
+// 10.0 * ratio, which the int parameter of interpolateCheckBorders truncates.
+int affshape_jobs(const char *fn, const modsx_region *in, int n, int cols, int rows, float *ratio, int *res, unsigned char *border) {
+  if (n < 0 || (n > 0 && !in)) { set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  if (rows < 4 || cols < 4) { set_error(std::string(fn) + ": images must be at least 4 x 4"); return MODSX_ERR_ARG; }
+  const float initialSigma = 1.6f;
+  for (int k = 0; k < n; k++) {
+    const modsx_keypoint &q = in[k].det_kp;
+    if (!std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.s) || !std::isfinite(q.a11) || !std::isfinite(q.a12) ||
+        !std::isfinite(q.a21) || !std::isfinite(q.a22)) {
+      set_error(std::string(fn) + ": region " + std::to_string(k) + " has a non-finite x, y, s or matrix entry"); return MODSX_ERR_ARG;
+    }
+    const float r = (float)(q.s / (double)initialSigma);
+    const double w = 2 * 5.0 * r;
+    if (!(fabs(w) < 2147483648.0)) {
+      set_error(std::string(fn) + ": region " + std::to_string(k) + ": |10 * s / 1.6| must be below 2^31"); return MODSX_ERR_ARG;
+    }
+    const int rs = (int)w;
+    if (ratio) ratio[k] = r;
+    if (res) res[k] = rs;
+    if (border) border[k] = check_borders_host(cols, rows, (float)q.x, (float)q.y, (float)q.a11, (float)q.a12, (float)q.a21, (float)q.a22, rs, rs) ? 1 : 0;
+  }
+  return n;
+}
+
+int affine_shape_batch(modsx_ctx *c, const char *fn, const modsx_image *const *imgs, int nImgs, const modsx_region *in, const int *counts,
+                       const modsx_affshape_params &p, int variant, std::vector<modsx_region> *out, const AffShapeReport *rep) {
+  int rc = affshape_check(fn, p);
+  if (rc) return rc;
+  const int W = p.smmWindowSize;
+  if (variant < 0) variant = baumberg_production_variant(W);
+  size_t total = 0;
+  for (int i = 0; i < nImgs; i++) {
+    if (!imgs[i] || !imgs[i]->d || counts[i] < 0) { set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+    total += (size_t)counts[i];
+  }
+  if (total > (size_t)1 << 28) { set_error(std::string(fn) + ": too many regions"); return MODSX_ERR_ARG; }
+  std::vector<float> ratio(total);
+  std::vector<unsigned char> border(total);
+  {
+    size_t k = 0;
+    for (int i = 0; i < nImgs; k += (size_t)counts[i], i++) {
+      rc = affshape_jobs(fn, in + k, counts[i], imgs[i]->cols, imgs[i]->rows, ratio.data() + k, nullptr, border.data() + k);
+      if (rc < 0) return rc;
+    }
+  }
+  size_t launched = 0;
+  for (size_t k = 0; k < total; k++) launched += !border[k];
+  const BaumGeo g = baumberg_geometry((int)launched, W, variant, 0, baum_resident(c));
+  if (g.kernel < 0) {
+    if (variant == 3 && W == 19 && !baum_resident(c)) {
+      set_error(std::string(fn) + ": the occupancy query that sizes the queue form's grid failed (MODSX_BAUMBERG_QUEUE=0 runs the static chunks)");
+      return MODSX_ERR_DEVICE;
+    }
+    set_error(std::string(fn) + ": no kernel for this window size / variant"); return MODSX_ERR_ARG;
+  }
+  if (rep && rep->geo) { rep->geo[0] = g.kernel; rep->geo[1] = g.chunk; rep->geo[2] = g.nchunks; rep->geo[3] = g.grid; }
+  if (out) for (int i = 0; i < nImgs; i++) out[i].clear();
+  if (rep)
+    for (size_t k = 0; k < total; k++) {
+      if (rep->border) rep->border[k] = border[k];
+      if (rep->u) { rep->u[4 * k] = 1.f; rep->u[4 * k + 1] = 0.f; rep->u[4 * k + 2] = 0.f; rep->u[4 * k + 3] = 1.f; }
+      if (rep->ok) rep->ok[k] = 0;
+      if (rep->iters) rep->iters[k] = border[k] ? -1 : 0;
+    }
+  c->affshapeCounters[0]++;
+  c->affshapeCounters[1] += (long)total;
+  c->affshapeCounters[2] += (long)(total - launched);
+  if (!launched || p.maxIterations <= 0) return (int)launched;   // the reference's loop does not run: nothing converges
+  rc = ensure_smm_mask(c, W);
+  if (rc) return rc;
+  CtxBusy busy(c);
+  if (!c->hAff.ensure(launched * sizeof(AffJob) + launched * sizeof(AffOut))) return MODSX_ERR_NOMEM;
+  if (!c->affJobs.ensure(launched * sizeof(AffJob)) || !c->affOut.ensure(launched * sizeof(AffOut))) return MODSX_ERR_NOMEM;
+  if (!c->counter.ensure(COUNTER_BYTES)) return MODSX_ERR_NOMEM;
+  AffJob *hj = (AffJob *)c->hAff.p;
+  AffOut *ho = (AffOut *)((char *)c->hAff.p + launched * sizeof(AffJob));
+  {
+    size_t k = 0, j = 0;
+    for (int i = 0; i < nImgs; i++)
+      for (int r = 0; r < counts[i]; r++, k++) {
+        if (border[k]) continue;
+        AffJob &a = hj[j++];
+        a.blur = imgs[i]->d; a.rows = imgs[i]->rows; a.cols = imgs[i]->cols;
+        a.x = (float)in[k].det_kp.x; a.y = (float)in[k].det_kp.y; a.s = ratio[k]; a.pixelDistance = 1.f;
+      }
+  }
+  hipStream_t s = c->stream;
+  MX_HIP(ctx_copy(c, c->affJobs.p, hj, launched * sizeof(AffJob), hipMemcpyHostToDevice));
+  if (rep) MX_HIP(hipMemsetAsync(c->affOut.p, 0xFF, launched * sizeof(AffOut), s));   // the test entry: a job no wavefront wrote shows iters == -1
+  {
+    ProfScope ps(c, K_BAUMBERG, (double)launched * W * W * 4 * 2);
+    // no scan has filled the counter block for this launch: the launcher zeroes the queue's counters itself.  A later detection
+    // call starts with scan_extrema's fill of the whole block, so what this launch leaves in them is never read
+    if (!launch_baumberg_external(s, (AffJob *)c->affJobs.p, (AffOut *)c->affOut.p, (int)launched, c->dSmmMask, W, p.maxIterations,
+                                  p.convergenceThreshold, variant, 0, baum_resident(c), baum_queue(c), false)) {
+      MX_HIP(hipGetLastError());
+      set_error(std::string(fn) + ": nothing was launched"); return MODSX_ERR_INTERNAL;
+    }
+  }
+  MX_HIP(hipGetLastError());
+  MX_HIP(ctx_copy(c, ho, c->affOut.p, launched * sizeof(AffOut), hipMemcpyDeviceToHost));
+  MX_HIP(ctx_sync(c));
+  c->affshapeCounters[3] += (long)launched;
+  c->affshapeCounters[5]++;
+  {
+    size_t k = 0, j = 0;
+    for (int i = 0; i < nImgs; i++)
+      for (int r = 0; r < counts[i]; r++, k++) {
+        if (border[k]) continue;
+        const AffOut &a = ho[j++];
+        if (rep) {
+          if (rep->u) { rep->u[4 * k] = a.u11; rep->u[4 * k + 1] = a.u12; rep->u[4 * k + 2] = a.u21; rep->u[4 * k + 3] = a.u22; }
+          if (rep->ok) rep->ok[k] = a.ok;
+          if (rep->iters) rep->iters[k] = a.iters;
+        }
+        if (!a.ok) continue;
+        c->affshapeCounters[4]++;
+        if (!out) continue;
+        out[i].push_back(in[k]);
+        modsx_keypoint &q = out[i].back().det_kp;
+        q.a11 = (double)a.u11; q.a12 = (double)a.u12; q.a21 = (double)a.u21; q.a22 = (double)a.u22;
+      }
+  }
+  return (int)launched;
+}
+
 // AffineDetector::prepareKeysForExport, scale-space-detector.hpp:118-198
 static void prepare_keys_for_export(std::vector<modsx_keypoint> &keys, const modsx_hessaff_params &p) {
   if (keys.empty() || p.mode == MODSX_FIXED_TH) return;

@@ -46,10 +46,19 @@ MX_D void inv_sqrt_wave(int lane, float &a, float &b, float &c, float &l1, float
   c = float(t * t * x + r * r * z);
 }
 
+// The two forms of a job (engine.hpp AffJob), chosen at compile time.  Scale-space form, what detection launches: x, y, s are image
+// coordinates of a keypoint of a pyramid level, and the kernel forms the position in the level and the window's step there
+// (affine.cpp:33-35).  EXTERNAL form, DetectAffineShape (synth-detection.cpp:949-950) on a caller's regions: the plane is the view
+// itself and the job carries the position and the ratio as they are used -- the host formed the ratio in f64 from the region's
+// double scale, which no f32 division here reproduces -- so neither pixelDistance nor affInitialSigma is read.  The form decides
+// these three values where a job is taken (AFF_JOB_POS / AFF_JOB_RATIO below); every line after that serves both.
+#define AFF_JOB_POS(v, jb) (EXTERNAL ? (v) : (v) / (jb).pixelDistance)
+#define AFF_JOB_RATIO(jb) (EXTERNAL ? (jb).s : (jb).s / (affInitialSigma * (jb).pixelDistance))
+
 // WT = window size when known at compile time (19, the default smmWindowSize), 0 = use the argument: the row / column of a
 // pixel is an integer division by W, done once per keypoint (the LDS offsets of a pixel's four gradient neighbours do not
 // change between iterations)
-template <int WT>
+template <int WT, bool EXTERNAL = false>
 __global__ __launch_bounds__(64) void k_baumberg(const AffJob *jobs, AffOut *out, int n, const float *mask, int Warg,
                                                  int maxIter, float convTh, float affInitialSigma) {
   const int W = WT ? WT : Warg;
@@ -90,8 +99,8 @@ __global__ __launch_bounds__(64) void k_baumberg(const AffJob *jobs, AffOut *out
   }
   float u11 = 1.0f, u12 = 0.0f, u21 = 0.0f, u22 = 1.0f, l1 = 1.0f, l2 = 1.0f;
   float era = 0.0f, erb = 0.0f;
-  const float lx = jb.x / jb.pixelDistance, ly = jb.y / jb.pixelDistance;
-  const float ratio = jb.s / (affInitialSigma * jb.pixelDistance);
+  const float lx = AFF_JOB_POS(jb.x, jb), ly = AFF_JOB_POS(jb.y, jb);
+  const float ratio = AFF_JOB_RATIO(jb);
   const gcfloat_p img = as_global(jb.blur);
   int ok = 0, l = 0;
   __syncthreads();
@@ -240,7 +249,7 @@ __device__ unsigned long long g_btrace[16];
 // NO WAVEFRONT EVER WAITS FOR ANOTHER: there is no spin loop and no flag, nothing depends on another wavefront being resident or
 // having run, and every loop ends because a counter passed the end of its range or because maxIter was reached.  That makes the
 // launch safe when the other streams of the pipeline hold part of the chip: a wavefront dispatched late finds what is left.
-template <int K, bool QUEUE>
+template <int K, bool QUEUE, bool EXTERNAL = false>
 __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffOut *out, int n, const float *mask, int chunk,
                                                         int nchunks, int maxIter, float convTh, float affInitialSigma,
                                                         unsigned *queue) {
@@ -320,8 +329,8 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
             const int cand = lo + (int)got + (rank - done);
             kidx = cand;
             const AffJob sj = jobs[cand];
-            ratio = sj.s / (affInitialSigma * sj.pixelDistance);
-            slx = sj.x / sj.pixelDistance; sly = sj.y / sj.pixelDistance;
+            ratio = AFF_JOB_RATIO(sj);
+            slx = AFF_JOB_POS(sj.x, sj); sly = AFF_JOB_POS(sj.y, sj);
             scols = sj.cols; srows = sj.rows;
             u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f; l1 = 1.0f; l2 = 1.0f; era = 0.0f; erb = 0.0f;
             ok = 0; it = 0;
@@ -338,8 +347,8 @@ __global__ __launch_bounds__(64) void k_baumberg_stream(const AffJob *jobs, AffO
         if (want && cand < end) {
           kidx = cand;
           const AffJob sj = jobs[cand];
-          ratio = sj.s / (affInitialSigma * sj.pixelDistance);
-          slx = sj.x / sj.pixelDistance; sly = sj.y / sj.pixelDistance;
+          ratio = AFF_JOB_RATIO(sj);
+          slx = AFF_JOB_POS(sj.x, sj); sly = AFF_JOB_POS(sj.y, sj);
           scols = sj.cols; srows = sj.rows;
           u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f; l1 = 1.0f; l2 = 1.0f; era = 0.0f; erb = 0.0f;
           ok = 0; it = 0;
@@ -621,25 +630,37 @@ BaumGeo baumberg_geometry(int n, int W, int variant, int chunk, int resident) {
 // queue: the BAUM_RANGES counters of the queue form (BAUM_QUEUE_BYTES, device memory); queueClean: they are zero and nothing on
 // the stream writes them before this launch, otherwise the launcher fills them first.  false: there is no such launch (or the
 // queue form was asked for without its counters) and nothing was launched
-bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
-                     float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean) {
+template <bool EXTERNAL>
+static bool launch_baumberg_form(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                                 float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue,
+                                 bool queueClean) {
   if (n <= 0) return true;
   constexpr int K = MODSX_BAUMBERG_K;
   const BaumGeo g = baumberg_geometry(n, W, variant, chunk, resident);
   if (g.kernel == 0) {
-    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL((k_baumberg_stream<K, false>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks,
-                       maxIter, convTh, affInitialSigma, (unsigned *)nullptr);
+    MX_DUP(K_BAUMBERG) hipLaunchKernelGGL((k_baumberg_stream<K, false, EXTERNAL>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk,
+                       g.nchunks, maxIter, convTh, affInitialSigma, (unsigned *)nullptr);
   } else if (g.kernel == 3 && queue) {
     MX_DUP(K_BAUMBERG) {
       if (!queueClean && hipMemsetAsync(queue, 0, BAUM_QUEUE_BYTES, s) != hipSuccess) return false;   // (the caller reads the runtime's error)
       queueClean = false;
-      hipLaunchKernelGGL((k_baumberg_stream<K, true>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks, maxIter,
+      hipLaunchKernelGGL((k_baumberg_stream<K, true, EXTERNAL>), dim3(g.grid), dim3(64), 0, s, jobs, out, n, mask, g.chunk, g.nchunks, maxIter,
                          convTh, affInitialSigma, queue);
     }
-  } else if (g.kernel == 1) hipLaunchKernelGGL(k_baumberg<19>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
-  else if (g.kernel == 2) hipLaunchKernelGGL(k_baumberg<0>, dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
+  } else if (g.kernel == 1) hipLaunchKernelGGL((k_baumberg<19, EXTERNAL>), dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
+  else if (g.kernel == 2) hipLaunchKernelGGL((k_baumberg<0, EXTERNAL>), dim3(n), dim3(64), 0, s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma);
   else return false;
   return true;
+}
+bool launch_baumberg(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                     float convTh, float affInitialSigma, int variant, int chunk, int resident, unsigned *queue, bool queueClean) {
+  return launch_baumberg_form<false>(s, jobs, out, n, mask, W, maxIter, convTh, affInitialSigma, variant, chunk, resident, queue, queueClean);
+}
+// The same launch for jobs in the external form (AFF_JOB_POS / AFF_JOB_RATIO): the same geometry rule and kernels; there is no
+// initial sigma to pass, the jobs carry their ratio
+bool launch_baumberg_external(hipStream_t s, const AffJob *jobs, AffOut *out, int n, const float *mask, int W, int maxIter,
+                              float convTh, int variant, int chunk, int resident, unsigned *queue, bool queueClean) {
+  return launch_baumberg_form<true>(s, jobs, out, n, mask, W, maxIter, convTh, 0.f, variant, chunk, resident, queue, queueClean);
 }
 
 }  // namespace mx
