@@ -447,6 +447,30 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
  * in global memory.  modsx_detect_orientation and the pipelines count alike; a call with no region to orient launches nothing.
  * Either pointer may be NULL.  Returns 0 */
 int modsx_debug_orientation_launches(unsigned long long *lds_table, unsigned long long *global_table, int reset);
+/* view synthesis by every context of this process since the last reset (measurement hook): *views_fused the non-identity views
+ * that went source image -> view in the one fused launch, *groups the groups of shared rotations they formed (views of one
+ * launch set whose source image, sizes and inverse rotation match bit for bit are rotated once; MODSX_VIEWS_SHARE_ROT=0 in the
+ * environment makes every view a group of its own), *rotated_pixels the sum of w_rot x h_rot over those groups.  Any pointer may
+ * be NULL.  Returns 0 */
+int modsx_debug_views_counters(unsigned long long *views_fused, unsigned long long *groups, unsigned long long *rotated_pixels,
+                               int reset);
+/* host only (no device, no context): the plan of one view of a rows x cols image.  geometry[8] = {is_identity, w_rot, h_rot,
+ * out_cols, out_rows, kx, ky, kind}, kind = 2: the fused launch, 1: rotate + blur fused and a second launch for the tilt,
+ * 0: one launch per stage (what the environment of the process selects; an identity view has kind 0); rinv[6] / winv[6]
+ * (optional) = the inverse maps of the rotation and of the tilt / zoom as the kernels receive them.  Returns 0 or an error */
+int modsx_debug_view_plan(int rows, int cols, const modsx_view *view, int *geometry, double *rinv, double *winv);
+/* host only: the grouping rule of the fused launch on n views given by their plans.  source[i] tells source images apart,
+ * dims[5 i ..] = {source rows, source cols, h_rot, w_rot, kind}, rinv[6 i ..] the inverse rotation.  cap <= 0: the built-in
+ * cap.  group[i] = the view's group in job-table order, -1 for a view that does not take the fused launch (kind != 2);
+ * order[n] = the views in job-table order; totals[5] = {views fused, groups, tiles, rotated pixels, rotated pixels without
+ * sharing}.  Returns 0 or an error */
+int modsx_debug_views_groups(const int *source, const int *dims, const double *rinv, int n, int cap, int *group, int *order,
+                             long long *totals);
+/* the n <= 32 (image, view) items synthesised as ONE launch set, the way the view loops of the pipelines do it (measurement and
+ * test hook; modsx_synth_view is the same for n = 1).  out[i]: a new image handle (modsx_image_free); is_identity[i] = 1: the
+ * handle aliases imgs[i].  Returns 0 or an error (no handle is left behind then) */
+int modsx_debug_synth_views(modsx_ctx *ctx, const modsx_image *const *imgs, const modsx_view *views, int n, modsx_image **out,
+                            int *is_identity);
 /* host only: the tables the orientation kernel reads, built by the function that fills a context's copies.
  * bin_table [2049]: the histogram bin (int)(36 * (angle / pi + 1) / 2) of the atan2LUTff angle of case code * 256 + idx, code =
  * (x > 0) << 2 | (y > 0) << 1 | (|x| > |y|), idx = (int)(255 * small / big) clamped to 0 .. 255; entry 2048 is the special case

@@ -124,6 +124,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
            "modsx_debug_orientation_counts", "modsx_debug_orientation_launches", "modsx_orientation_tables",
            "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
+           "modsx_debug_views_counters", "modsx_debug_view_plan", "modsx_debug_views_groups", "modsx_debug_synth_views",
            "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
            "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
            "modsx_rep_create", "modsx_rep_free", "modsx_rep_add_views", "modsx_rep_append", "modsx_rep_class",
@@ -257,6 +258,10 @@ def lib():
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_orientation_tables.argtypes = [C.c_void_p] * 6
+        L.modsx_debug_views_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_view_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_views_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_debug_synth_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.modsx_blur_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_detect_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_pyramids.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong,
@@ -1390,6 +1395,22 @@ class Context(object):
         out.rows, out.cols = _image_dims(h)
         return out, H.reshape(3, 3), bool(ident.value)
 
+    def synth_views(self, imgs, views):
+        """modsx_debug_synth_views: the (image, view) items as ONE launch set (at most MAXB).  -> [(Image, is_identity)]; an
+        identity view's Image aliases its source.  Free every Image."""
+        n = len(views)
+        assert n == len(imgs)
+        hs = (C.c_void_p * n)(*[im.h for im in imgs])
+        out = (C.c_void_p * n)()
+        ident = (C.c_int * n)()
+        _check(lib().modsx_debug_synth_views(self._c(), hs, _view_array(views), n, out, ident), "synth_views")
+        res = []
+        for i in range(n):
+            im = Image(self, out[i], 0, 0)
+            im.rows, im.cols = _image_dims(out[i])
+            res.append((im, bool(ident[i])))
+        return res
+
     def detect_describe_views(self, img, views, params, view_begin=0, view_step=1, want_desc=True, dev_desc=None,
                               dev_cap=0, want_counts=False):
         arr = _view_array(views)
@@ -1931,6 +1952,43 @@ def orientation_launches(reset=False):
     a, b = C.c_ulonglong(), C.c_ulonglong()
     lib().modsx_debug_orientation_launches(C.byref(a), C.byref(b), int(reset))
     return a.value, b.value
+
+
+def views_counters(reset=False):
+    """(views_fused, groups, rotated_pixels): non-identity views this process sent through the fused view kernel, the groups of
+    shared rotations they formed and the pixels those groups rotate (w_rot x h_rot per group), since the last reset."""
+    a, b, d = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+    lib().modsx_debug_views_counters(C.byref(a), C.byref(b), C.byref(d), int(reset))
+    return a.value, b.value, d.value
+
+
+VIEW_GROUP_CAP = 8      # csrc/engine.hpp: most views that share one rotated tile
+
+
+def view_plan(rows, cols, view):
+    """modsx_debug_view_plan (host only): dict(identity, w_rot, h_rot, cols, rows, kx, ky, kind, rinv [6] f64, winv [6] f64) of
+    one view of a rows x cols image; kind 2 = the fused launch."""
+    g = np.zeros(8, np.int32)
+    rinv, winv = np.zeros(6), np.zeros(6)
+    _check(lib().modsx_debug_view_plan(int(rows), int(cols), C.byref(view), _p(g), _p(rinv), _p(winv)), "view_plan")
+    return dict(identity=bool(g[0]), w_rot=int(g[1]), h_rot=int(g[2]), cols=int(g[3]), rows=int(g[4]), kx=int(g[5]), ky=int(g[6]),
+                kind=int(g[7]), rinv=rinv, winv=winv, src_rows=int(rows), src_cols=int(cols))
+
+
+def views_groups(plans, sources=None, cap=0):
+    """modsx_debug_views_groups (host only): the grouping rule of the fused view launch on the non-identity views `plans`
+    (dicts as view_plan returns them; sources[i]: which source image view i is of, default all 0).
+    -> dict(group [n] (-1: not on the fused launch), order [n], views_fused, groups, tiles, rotated_pixels, rotated_pixels_alone)."""
+    n = len(plans)
+    assert not any(p["identity"] for p in plans), "identity views are not part of a launch set's job table"
+    src = np.ascontiguousarray(np.zeros(n, np.int32) if sources is None else sources, np.int32)
+    dims = np.ascontiguousarray([[p["src_rows"], p["src_cols"], p["h_rot"], p["w_rot"], p["kind"]] for p in plans], np.int32).reshape(n, 5)
+    rinv = np.ascontiguousarray([p["rinv"] for p in plans], np.float64).reshape(n, 6)
+    group, order = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
+    tot = np.zeros(5, np.int64)
+    _check(lib().modsx_debug_views_groups(_p(src), _p(dims), _p(rinv), n, int(cap), _p(group), _p(order), _p(tot)), "views_groups")
+    return dict(group=group[:n], order=order[:n], views_fused=int(tot[0]), groups=int(tot[1]), tiles=int(tot[2]),
+                rotated_pixels=int(tot[3]), rotated_pixels_alone=int(tot[4]))
 
 
 def orientation_tables():

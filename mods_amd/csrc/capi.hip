@@ -10,6 +10,7 @@
 #include <deque>
 #include "engine_api.hpp"
 #include "describe_plan.hpp"
+#include "views_plan.hpp"
 #include "describe_lanes.hpp"
 
 using namespace mx;
@@ -375,6 +376,56 @@ int modsx_debug_orientation_counts(unsigned long long *launched, unsigned long l
 int modsx_debug_orientation_launches(unsigned long long *lds_table, unsigned long long *global_table, int reset) {
   mx::orientation_launches(lds_table, global_table, reset != 0);
   return MODSX_OK;
+}
+
+int modsx_debug_views_counters(unsigned long long *views_fused, unsigned long long *groups, unsigned long long *rotated_pixels,
+                               int reset) {
+  mx::views_counters(views_fused, groups, rotated_pixels, reset != 0);
+  return MODSX_OK;
+}
+
+int modsx_debug_view_plan(int rows, int cols, const modsx_view *view, int *geometry, double *rinv, double *winv) {
+  if (rows < 1 || cols < 1 || !view || !geometry) { mx::set_error("modsx_debug_view_plan: bad argument"); return MODSX_ERR_ARG; }
+  static const bool separate = getenv("MODSX_VIEWS_SEPARATE") && atoi(getenv("MODSX_VIEWS_SEPARATE"));
+  mx::ViewPlan P;
+  const int rc = mx::plan_view(rows, cols, *view, P);
+  if (rc) return rc;
+  const int g[8] = {P.identity, P.w_rot, P.h_rot, P.ow, P.oh, P.kx, P.ky, P.identity ? 0 : mx::view_fused_kind(P, separate)};
+  for (int q = 0; q < 8; q++) geometry[q] = g[q];
+  for (int q = 0; q < 6; q++) {
+    if (rinv) rinv[q] = P.identity ? 0. : P.Rinv[q];
+    if (winv) winv[q] = P.identity ? 0. : P.Winv[q];
+  }
+  return MODSX_OK;
+}
+
+int modsx_debug_views_groups(const int *source, const int *dims, const double *rinv, int n, int cap, int *group, int *order,
+                             long long *totals) {
+  if (n < 0 || (n > 0 && (!source || !dims || !rinv || !group || !order)) || !totals) {
+    mx::set_error("modsx_debug_views_groups: bad argument"); return MODSX_ERR_ARG;
+  }
+  std::vector<mx::ViewPlan> plans(n);
+  std::vector<mx::ViewGroupIn> in(n);
+  for (int i = 0; i < n; i++) {
+    plans[i].h_rot = dims[5 * i + 2]; plans[i].w_rot = dims[5 * i + 3];
+    for (int q = 0; q < 6; q++) plans[i].Rinv[q] = rinv[6 * i + q];
+    in[i] = {(const void *)(uintptr_t)(source[i] + 1), dims[5 * i], dims[5 * i + 1], &plans[i], dims[5 * i + 4]};
+  }
+  mx::ViewGrouping g;
+  mx::group_views(in.data(), n, cap > 0 ? cap : mx::VIEW_GROUP_CAP, g);
+  for (int i = 0; i < n; i++) { group[i] = g.group[i]; order[i] = g.order[i]; }
+  totals[0] = g.nFused; totals[1] = g.nGroups; totals[2] = g.tiles; totals[3] = g.rotPx; totals[4] = g.rotPxAlone;
+  return MODSX_OK;
+}
+
+int modsx_debug_synth_views(modsx_ctx *ctx, const modsx_image *const *imgs, const modsx_view *views, int n, modsx_image **out,
+                            int *is_identity) {
+  NEED(ctx);
+  if (!imgs || !views || !out || !is_identity) { mx::set_error("modsx_debug_synth_views: null argument"); return MODSX_ERR_ARG; }
+  if (n < 1 || n > mx::MAXB) { mx::set_error("batch size"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  return synth_views_set(ctx, imgs, views, n, out, is_identity);
 }
 
 int modsx_orientation_tables(unsigned char *bin_table, unsigned short *index_raster, float *weight_raster,

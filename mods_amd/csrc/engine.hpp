@@ -130,6 +130,10 @@ struct ViewJob {
   int tileA, tileB;   // first 64 x 4 tile of this view in the rotated-image / output-image tile lists
   int tileF, fused;   // fused rotate + blur: first VF_TW x VF_TH tile of this view (views with a blur whose halo fits)
   int tileG, pad;     // rotate + blur + tilt in one launch (fused == 2: W is diagonal as well): first VF_TW x VF_TH tile of the ROTATED image
+  // fused == 2: the views that share this view's rotation (same src, sizes and R, bit for bit) lie next to each other in the job
+  // table and share tileG: one workgroup rotates a tile once for all of them
+  int grpFirst, grpCount;   // table index of the group's first view, views in the group (1 .. VIEW_GROUP_CAP)
+  int grpRx, grpRy;         // largest kx >> 1 / ky >> 1 of the group: the halo of the shared rotated tile
   double R[6], W[6];  // inverse maps of the two cv::warpAffine calls (f64, inverted on the host)
   double invW[2];     // 1 / W[0], 1 / W[4]: where a fused tile starts looking for its first output column / row (a hint, never the answer)
 };
@@ -285,6 +289,7 @@ void launch_harris_combine(hipStream_t s, const float *bxx, const float *byy, co
 void launch_views_warp(hipStream_t s, const ViewJob *jobs, int n, int tiles, int stage);
 void launch_views_blur(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int pass);
 constexpr int VF_TW = 128, VF_TH = 16, VF_RX = 32, VF_RY = 2;   // tile of the fused rotate + blur kernel and the largest halo it takes
+constexpr int VIEW_GROUP_CAP = 8;   // most views that share one rotated tile of k_views_fused (the shipped ladders need 4)
 void launch_views_rotblur(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int maxRx, int maxRy);
 void launch_views_fused(hipStream_t s, const ViewJob *jobs, int n, int tiles, const float *taps, int maxRx, int maxRy);
 size_t match_workspace_bytes(int n1, int n2);

@@ -149,6 +149,12 @@ int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt,
 // per-view loop: hipMalloc / hipFree synchronise the whole device, i.e. every other context's stream as well).
 int synth_view(modsx_ctx *c, const modsx_image *gray, const modsx_view &v, modsx_image **out, double *H, int *identity,
                int slot = -1);
+// n <= MAXB (image, view) items synthesised as one launch set (modsx_debug_synth_views); out[i] owns its pixels unless identity[i]
+int synth_views_set(modsx_ctx *c, const modsx_image *const *grays, const modsx_view *views, int n, modsx_image **out, int *identity);
+// views that took the fused kernel, the groups of shared rotations they formed, the pixels those groups rotate: every context
+// of the process since the last reset (modsx_debug_views_counters).  MODSX_VIEWS_SHARE_ROT=0: every view a group of its own.
+void views_counters(unsigned long long *viewsFused, unsigned long long *groups, unsigned long long *rotPx, bool reset);
+bool views_share_rotation();
 // the per-view loop over (source image, view) items: one launch set may mix the views of several images
 int detect_describe_items(modsx_ctx *c, const modsx_image *const *itemImg, const int *itemView, int nitems, const modsx_view *views,
                           const modsx_pair_params &pp, std::vector<modsx_region> &regs,

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <thread>
 #include "engine_api.hpp"
+#include "views_plan.hpp"
 
 namespace mx {
 
@@ -52,131 +53,30 @@ int set_vs_pars(const double *scale_set, int ns, const double *tilt_set, int nt,
   return n;
 }
 
-// cv::warpAffine inverts the forward 2x3 matrix in f64 before the pixel loop (imgwarp.cpp)
-static void invert_affine(const double *Min, double *M) {
-  for (int i = 0; i < 6; i++) M[i] = Min[i];
-  double D = M[0] * M[4] - M[1] * M[3];
-  D = D != 0 ? 1. / D : 0;
-  double A11 = M[4] * D, A22 = M[0] * D;
-  M[0] = A11; M[1] *= -D;
-  M[3] *= -D; M[4] = A22;
-  double b1 = -M[0] * M[2] - M[1] * M[5];
-  double b2 = -M[3] * M[2] - M[4] * M[5];
-  M[2] = b1; M[5] = b2;
+// measurement hook (modsx_debug_views_counters): views that took the fused kernel, the groups they formed and the pixels those
+// groups rotate (w_rot x h_rot per group), by every context of the process since the last reset
+static std::atomic<unsigned long long> g_viewsFused{0}, g_viewGroups{0}, g_viewRotPx{0};
+void views_counters(unsigned long long *viewsFused, unsigned long long *groups, unsigned long long *rotPx, bool reset) {
+  const unsigned long long a = reset ? g_viewsFused.exchange(0) : g_viewsFused.load();
+  const unsigned long long b = reset ? g_viewGroups.exchange(0) : g_viewGroups.load();
+  const unsigned long long d = reset ? g_viewRotPx.exchange(0) : g_viewRotPx.load();
+  if (viewsFused) *viewsFused = a;
+  if (groups) *groups = b;
+  if (rotPx) *rotPx = d;
 }
-
-// host half of GenerateSynthImageCorr (synth-detection.cpp:236-430) for one view: homography, sizes, the inverse maps of the
-// two warps and the anti-alias taps
-struct ViewPlan {
-  int identity = 0;
-  double H[9];
-  int w_rot = 0, h_rot = 0, ow = 0, oh = 0, doBlur = 0, kx = 1, ky = 1;
-  double Rinv[6], Winv[6];
-  std::vector<float> taps;   // kx taps, then ky taps
-};
-
-static int plan_view(const modsx_image *gray, const modsx_view &v, ViewPlan &P) {
-  double tilt = v.tilt;
-  const double phi = v.phi, zoom = v.zoom, InitSigma = v.InitSigma;
-  int zoomed = 0;
-  bool vertical_tilt = false;
-  if (tilt < 0) { tilt = -tilt; vertical_tilt = true; }
-  if (fabs(zoom - 1.0f) >= 0.05) zoomed = 1;
-  const int w = gray->cols, h = gray->rows;
-  int wS1 = (int)(w * zoom), hS1 = (int)(h * zoom);
-  double *H = P.H;
-  if ((fabs(tilt - 1.) <= 0.1) && (fabs(phi) <= 0.2) && (fabs(zoom - 1.) <= 0.1)) {  // original image, :278-289
-    const double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int i = 0; i < 9; i++) H[i] = E[i];
-    P.identity = 1;
-    P.ow = w; P.oh = h;
-    return MODSX_OK;
-  }
-  P.identity = 0;
-  double d, d2, w_new, h_new;
-  double kV = 1., kH = 1.;
-  if (zoomed) { kV = (double)w / (double)wS1; kH = (double)h / (double)hS1; }
-  const bool q1 = (phi >= 0) && (phi < M_PI / 2);
-  if (vertical_tilt) {
-    if (q1) {
-      w_new = floor((0.5 + cos(phi) * w + sin(phi) * h) / (kH));
-      h_new = floor((0.5 + sin(phi) * w + cos(phi) * h) / (tilt * kV));
-      H[0] = cos(phi) / kH; H[1] = sin(phi) / kH; H[2] = 0;
-      H[3] = -sin(phi) / (tilt * kV); H[4] = cos(phi) / (tilt * kV); H[5] = floor(0.5 + sin(phi) * w / (tilt * kV));
-    } else {
-      w_new = floor((0.5 - cos(phi) * w + sin(phi) * h) / (kH));
-      h_new = floor((0.5 + sin(phi) * w - cos(phi) * h) / (tilt * kV));
-      d = -floor(cos(phi) * w / kH);
-      d2 = floor(0.5 + (sin(phi) * w - cos(phi) * h) / (tilt * kV));
-      H[0] = cos(phi) / kH; H[1] = sin(phi) / kH; H[2] = d;
-      H[3] = -sin(phi) / (tilt * kV); H[4] = cos(phi) / (tilt * kV); H[5] = d2;
-    }
-  } else {
-    if (q1) {
-      w_new = floor((0.5 + cos(phi) * w + sin(phi) * h) / (tilt * kH));
-      h_new = floor((0.5 + sin(phi) * w + cos(phi) * h) / (kV));
-      H[0] = cos(phi) / (tilt * kH); H[1] = sin(phi) / (tilt * kH); H[2] = 0;
-      H[3] = -sin(phi) / kV; H[4] = cos(phi) / kV; H[5] = floor(0.5 + sin(phi) * w / kV);
-    } else {
-      w_new = floor((0.5 - cos(phi) * w + sin(phi) * h) / (tilt * kH));
-      h_new = floor((0.5 + sin(phi) * w - cos(phi) * h) / (kV));
-      d = -floor(cos(phi) * w / (tilt * kH));
-      d2 = floor(0.5 + (sin(phi) * w - cos(phi) * h) / kV);
-      H[0] = cos(phi) / (tilt * kH); H[1] = sin(phi) / (tilt * kH); H[2] = d;
-      H[3] = -sin(phi) / kV; H[4] = cos(phi) / kV; H[5] = d2;
-    }
-  }
-  H[6] = 0; H[7] = 0; H[8] = 1;
-  double sigma_aa_2 = zoomed ? InitSigma / (4.0 * zoom) : InitSigma / 2.0;
-  double sigma_aa = InitSigma * tilt / (2.0 * zoom);
-  double sigma_x = vertical_tilt ? sigma_aa_2 : sigma_aa, sigma_y = vertical_tilt ? sigma_aa : sigma_aa_2;
-  double R[6];
-  if (q1) {
-    P.w_rot = floor((0.5 + cos(phi) * w + sin(phi) * h));
-    P.h_rot = floor((0.5 + sin(phi) * w + cos(phi) * h));
-    R[0] = cos(phi); R[1] = sin(phi); R[2] = 0;
-    R[3] = -sin(phi); R[4] = cos(phi); R[5] = floor(0.5 + sin(phi) * w);
-  } else {
-    P.w_rot = floor((0.5 - cos(phi) * w + sin(phi) * h));
-    P.h_rot = floor((0.5 + sin(phi) * w - cos(phi) * h));
-    d = -floor(cos(phi) * w);
-    d2 = floor(0.5 + (sin(phi) * w - cos(phi) * h));
-    R[0] = cos(phi); R[1] = sin(phi); R[2] = d;
-    R[3] = -sin(phi); R[4] = cos(phi); R[5] = d2;
-  }
-  P.ow = (int)w_new; P.oh = (int)h_new;
-  if (P.w_rot <= 0 || P.h_rot <= 0 || P.ow <= 0 || P.oh <= 0) { set_error("degenerate synthesised view"); return MODSX_ERR_ARG; }
-  invert_affine(R, P.Rinv);
-  P.doBlur = v.doBlur;
-  P.taps.clear();
-  if (v.doBlur) {
-    int kx = floor(2.0 * 3.0 * sigma_x + 1.0);
-    if (kx % 2 == 0) kx++;
-    if (kx < 3) kx = 3;
-    int ky = floor(2.0 * 3.0 * sigma_y + 1.0);
-    if (ky % 2 == 0) ky++;
-    if (ky < 3) ky = 3;
-    if (P.h_rot == 1) ky = 1;
-    if (P.w_rot == 1) kx = 1;
-    std::vector<float> KX = gaussian_kernel(kx, std::max(sigma_x, 0.));
-    std::vector<float> KY = (ky == kx && fabs(sigma_x - sigma_y) < 2.220446049250313e-16) ? KX : gaussian_kernel(ky, std::max(sigma_y, 0.));
-    P.kx = kx; P.ky = ky;
-    P.taps = KX;
-    P.taps.insert(P.taps.end(), KY.begin(), KY.end());
-  }
-  double Wz[6] = {0, 0, 0, 0, 0, 0};
-  if (vertical_tilt) { Wz[0] = 1.0 / kH; Wz[4] = 1.0 / (tilt * kV); }
-  else { Wz[0] = 1.0 / (tilt * kH); Wz[4] = 1.0 / kV; }
-  invert_affine(Wz, P.Winv);
-  return MODSX_OK;
+bool views_share_rotation() {
+  static const bool on = !(getenv("MODSX_VIEWS_SHARE_ROT") && atoi(getenv("MODSX_VIEWS_SHARE_ROT")) == 0);
+  return on;
 }
 
 // Synthesises n views of `gray`: one launch for all views whose blur fits the fused kernel's tile and whose tilt / zoom map is
 // diagonal (every view plan_view makes with a blur of up to 2 VF_RX + 1 by 2 VF_RY + 1 taps), the separate launches (rotate,
-// blur rows, blur columns -- or rotate + blur --, tilt / zoom) for the rest.  Outputs go to dst[i] (device, P[i].ow x P[i].oh
+// blur rows, blur columns -- or rotate + blur --, tilt / zoom) for the rest.  Views of the fused launch that share a rotation
+// (group_views: the tilts of a ladder step have many angles in common) lie next to each other in the job table and share one
+// tile grid: a workgroup rotates a tile once for all of them.  Outputs go to dst[i] (device, P[i].ow x P[i].oh
 // floats; ignored for identity views).  No host wait: the job table and the taps travel through pinned staging that is only
 // rewritten after the caller's next synchronisation of the stream.  MODSX_VIEWS_SEPARATE=1 keeps every view on the separate
-// launches (measurements: the values are the same either way).
+// launches, MODSX_VIEWS_SHARE_ROT=0 makes every view a group of its own (measurements: the values are the same either way).
 static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, const ViewPlan *P, float *const *dst, int n) {
   static const bool separate = getenv("MODSX_VIEWS_SEPARATE") && atoi(getenv("MODSX_VIEWS_SEPARATE"));
   hipStream_t s = c->stream;
@@ -185,8 +85,18 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
   size_t rotFloats = 0, tmpFloats = 0;
   int tilesA = 0, tilesB = 0, tilesF = 0, tilesG = 0, maxRx = 0, maxRy = 0, maxRxG = 0, maxRyG = 0;
   double pxRot = 0, pxBlur = 0, pxFused = 0, pxTilt = 0;   // pixels moved through HBM by the four kinds of launch
+  std::vector<ViewGroupIn> gin;
+  std::vector<int> viewOf;      // gin[k] is view viewOf[k]
   for (int i = 0; i < n; i++) {
     if (P[i].identity) continue;
+    gin.push_back({grays[i]->d, grays[i]->rows, grays[i]->cols, &P[i], view_fused_kind(P[i], separate)});
+    viewOf.push_back(i);
+  }
+  ViewGrouping grp;
+  group_views(gin.data(), (int)gin.size(), views_share_rotation() ? VIEW_GROUP_CAP : 1, grp);
+  int curGroup = -1, grpFirst = 0, grpTile = 0;
+  for (int k : grp.order) {
+    const int i = viewOf[k];
     ViewJob j;
     memset(&j, 0, sizeof j);
     const modsx_image *gray = grays[i];
@@ -199,12 +109,18 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
     j.tileA = tilesA; j.tileB = tilesB; j.tileF = tilesF; j.tileG = tilesG;
     const double srcPx = (double)gray->rows * gray->cols, rotPx = (double)j.rrows * j.rcols, dstPx = (double)j.drows * j.dcols;
     // rotate + blur in LDS when the halo of the two filters fits the fused kernels' tile (every default view does); the tilt
-    // as well when its inverse map is diagonal with positive scales: tap origins monotone in x and y, independent of the other
-    j.fused = j.doBlur && (j.kx >> 1) <= VF_RX && (j.ky >> 1) <= VF_RY;
-    if (j.fused && !separate && j.W[1] == 0 && j.W[3] == 0 && j.W[0] > 0 && j.W[4] > 0) j.fused = 2;
+    // as well when its inverse map is diagonal with positive scales (view_fused_kind)
+    j.fused = gin[k].fused;
     const int tilesV = ((j.rcols + VF_TW - 1) / VF_TW) * ((j.rrows + VF_TH - 1) / VF_TH);
     if (j.fused == 2) {
-      tilesG += tilesV;
+      if (grp.group[k] != curGroup) {     // a group's first view opens the group's tile grid; the others share it
+        curGroup = grp.group[k]; grpFirst = (int)jobs.size(); grpTile = tilesG;
+        tilesG += tilesV;
+      }
+      j.tileG = grpTile; j.grpFirst = grpFirst;
+      ViewJob &f = jobs.size() > (size_t)grpFirst ? jobs[grpFirst] : j;
+      f.grpCount++;
+      f.grpRx = std::max(f.grpRx, j.kx >> 1); f.grpRy = std::max(f.grpRy, j.ky >> 1);
       maxRxG = std::max(maxRxG, j.kx >> 1); maxRyG = std::max(maxRyG, j.ky >> 1);
       j.invW[0] = 1.0 / j.W[0]; j.invW[1] = 1.0 / j.W[4];
       pxFused += srcPx + dstPx;
@@ -227,6 +143,10 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
     }
     jobs.push_back(j);
   }
+  // every member carries its group's size and halo (the kernel finds a group through its LAST member)
+  for (ViewJob &j : jobs)
+    if (j.fused == 2) { const ViewJob &f = jobs[j.grpFirst]; j.grpCount = f.grpCount; j.grpRx = f.grpRx; j.grpRy = f.grpRy; }
+  g_viewsFused += (unsigned long long)grp.nFused; g_viewGroups += (unsigned long long)grp.nGroups; g_viewRotPx += (unsigned long long)grp.rotPx;
   if (jobs.empty()) return MODSX_OK;
   const size_t jobB = jobs.size() * sizeof(ViewJob), tapB = std::max<size_t>(1, taps.size()) * 4;
   // the rotated planes of the views that are not fused end to end, the row-filtered planes of those that are not fused at all
@@ -272,7 +192,7 @@ static int synth_views_batch(modsx_ctx *c, const modsx_image *const *grays, cons
 int synth_view(modsx_ctx *c, const modsx_image *gray, const modsx_view &v, modsx_image **out, double *H, int *identity, int) {
   *out = nullptr;
   ViewPlan P;
-  int rc = plan_view(gray, v, P);
+  int rc = plan_view(gray->rows, gray->cols, v, P);
   if (rc) return rc;
   for (int i = 0; i < 9; i++) H[i] = P.H[i];
   *identity = P.identity;
@@ -287,6 +207,33 @@ int synth_view(modsx_ctx *c, const modsx_image *gray, const modsx_view &v, modsx
   if (rc) { hipFree(im->d); delete im; return rc; }
   *out = im;
   return MODSX_OK;
+}
+
+// modsx_debug_synth_views: the n <= MAXB views (grays[i], views[i]) as ONE launch set, the way the per-view loop synthesises
+// them; out[i] = a fresh image that owns its pixels (an identity view aliases its source)
+int synth_views_set(modsx_ctx *c, const modsx_image *const *grays, const modsx_view *views, int n, modsx_image **out, int *identity) {
+  if (n < 1 || n > MAXB) { set_error("synth_views_set: batch size"); return MODSX_ERR_ARG; }
+  ViewPlan plans[MAXB];
+  float *dst[MAXB];
+  int rc = MODSX_OK;
+  for (int i = 0; i < n; i++) out[i] = nullptr;
+  for (int i = 0; i < n && !rc; i++) {
+    rc = plan_view(grays[i]->rows, grays[i]->cols, views[i], plans[i]);
+    if (rc) break;
+    modsx_image *im = new modsx_image();
+    im->rows = plans[i].oh; im->cols = plans[i].ow;
+    im->owned = !plans[i].identity; im->d = plans[i].identity ? grays[i]->d : nullptr;
+    out[i] = im;
+    identity[i] = plans[i].identity;
+    if (!plans[i].identity && hipMalloc(&im->d, (size_t)im->rows * im->cols * 4) != hipSuccess) { im->d = nullptr; set_error("hipMalloc view"); rc = MODSX_ERR_NOMEM; }
+    dst[i] = im->d;
+  }
+  if (!rc) rc = synth_views_batch(c, grays, plans, dst, n);
+  if (!rc && ctx_sync(c) != hipSuccess) { set_error("view synthesis failed"); rc = MODSX_ERR_DEVICE; }
+  if (rc)
+    for (int i = 0; i < n; i++)
+      if (out[i]) { if (out[i]->owned && out[i]->d) hipFree(out[i]->d); delete out[i]; out[i] = nullptr; }
+  return rc;
 }
 
 // The MSER front end of one launch set, DetectAffineRegions(temp_img1, temp_kp1, det_par.MSERParam, DET_MSER, DetectMSERs),
@@ -365,7 +312,7 @@ int detect_describe_items(modsx_ctx *c, const modsx_image *const *itemImg, const
       const modsx_image *gray = itemImg[take[g0 + i]];
       gimg[i] = gray;
       const modsx_view &v = views[itemView[take[g0 + i]]];
-      rc = plan_view(gray, v, plans[i]);
+      rc = plan_view(gray->rows, gray->cols, v, plans[i]);
       if (rc) break;
       for (int q = 0; q < 9; q++) Hs[i][q] = plans[i].H[q];
       ident[i] = plans[i].identity;

@@ -305,13 +305,15 @@ __global__ __launch_bounds__(256) void k_views_rotblur(const ViewJob *jobs, int 
 // The second cv::warpAffine of a view (tilt / zoom) has a diagonal inverse map: output column x taps the blurred columns sx(x)
 // and sx(x) + 1 whatever the row, output row y the rows sy(y) and sy(y) + 1, and sx, sy are monotone.  At tilt t only 2 / t of
 // the blurred columns are ever read.  k_views_rotblur + k_views_warp filter all of them, write the blurred plane (4 - 5 x the
-// size of the output) and read it back; here a workgroup keeps its VF_TW x VF_TH tile of the blurred rotated image in LDS,
-// filters only the columns and rows some output pixel of the tile taps, and emits the output pixels whose (clamped) tap origin
-// lies in the tile.  Every value is the f32 the separate launches pass through memory: the rotation is warp_fetch, the filter
-// terms are vf_row_value / vf_col_value, the output is warp_fetch's expression read from the tile (warp_fetch_tile).
+// size of the output) and read it back; here a workgroup keeps its VF_TW x VF_TH tile of the rotated image in LDS, row-filters
+// only the columns some output pixel of the tile taps, forms the column-filtered value under each tap of an output pixel in
+// registers, and emits the output pixels whose (clamped) tap origin lies in the tile.  Every value is the f32 the separate
+// launches pass through memory: the rotation is warp_fetch, the filter terms are vf_row_value / vf_col_value, the output is
+// warp_fetch's expression over those values (warp_fetch_tile).  The rotated tile is left as it is, so the views of a launch
+// set that share the rotation (a ladder step's tilts have most angles in common) are served from one rotation of the tile.
 constexpr int VG_TS = VF_TW + 1;          // row stride of the row-filtered tile: the tile's columns and the one the taps sx + 1 reach
 constexpr int VG_HR = VF_TH + 2 * VF_RY + 1;   // most rows of the rotated tile
-constexpr int VG_TABS = VF_TW + 4 + VF_TH + 4;   // bytes of the tapped-column and tapped-row lists
+constexpr int VG_TABS = VF_TW + 4;        // bytes of the tapped-column list
 
 // tap origin of output column p (axis 0) / row p (axis 1) under a diagonal inverse map: warp_fetch's sx / sy
 MX_D int warp_tap0(const double *M, int axis, int p) {
@@ -332,27 +334,30 @@ MX_D int first_reaching(const double *M, int axis, int target, int n, int lim, d
   while (p < n && warp_tap0(M, axis, p) < target) p++;
   return p;
 }
-// warp_fetch on the blurred tile Bt (stride WW, origin (x0, y0) of the sh x sw rotated image): the same four products in the
-// same order and the same three branches; a tap inside the image is in the tile for every pixel the tile owns
-MX_D float warp_fetch_tile(const float *Bt, int WW, int x0, int y0, int sh, int sw, float cval, int adelta, int bdelta, int X0, int Y0) {
+// warp_fetch on the blurred tile whose origin is (x0, y0) of the sh x sw rotated image, B(r, c) = the blurred value at tile row r,
+// column c: the same four products in the same order and the same three branches; a tap inside the image is in the tile for
+// every pixel the tile owns
+template <class Blurred>
+MX_D float warp_fetch_tile(const Blurred &B, int x0, int y0, int sh, int sw, float cval, int adelta, int bdelta, int X0, int Y0) {
   const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
   int sx = X >> 5, sy = Y >> 5;
   sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
   sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
   const float fx = (float)(X & 31) * (1.f / 32), fy = (float)(Y & 31) * (1.f / 32);
   const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;
+  const int r = sy - y0, c = sx - x0;
   float out;
   if (sx >= 0 && sx < sw - 1 && sy >= 0 && sy < sh - 1) {
-    const float *S = Bt + (sy - y0) * WW + (sx - x0);
-    out = S[0] * w0 + S[1] * w1 + S[WW] * w2 + S[WW + 1] * w3;
+    const float s0 = B(r, c), s1 = B(r, c + 1), s2 = B(r + 1, c), s3 = B(r + 1, c + 1);
+    out = s0 * w0 + s1 * w1 + s2 * w2 + s3 * w3;
   } else if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
     out = cval;
   } else {
     const bool bx0 = sx >= 0 && sx < sw, bx1 = sx + 1 >= 0 && sx + 1 < sw, by0 = sy >= 0 && sy < sh, by1 = sy + 1 >= 0 && sy + 1 < sh;
-    const float v0 = (bx0 && by0) ? Bt[(sy - y0) * WW + (sx - x0)] : cval;
-    const float v1 = (bx1 && by0) ? Bt[(sy - y0) * WW + (sx + 1 - x0)] : cval;
-    const float v2 = (bx0 && by1) ? Bt[(sy + 1 - y0) * WW + (sx - x0)] : cval;
-    const float v3 = (bx1 && by1) ? Bt[(sy + 1 - y0) * WW + (sx + 1 - x0)] : cval;
+    const float v0 = (bx0 && by0) ? B(r, c) : cval;
+    const float v1 = (bx1 && by0) ? B(r, c + 1) : cval;
+    const float v2 = (bx0 && by1) ? B(r + 1, c) : cval;
+    const float v3 = (bx1 && by1) ? B(r + 1, c + 1) : cval;
     out = v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3;
   }
   return out;
@@ -364,111 +369,127 @@ struct FlatWalk {
   MX_D FlatWalk(int tid, int inner) : o(tid / inner), i(tid - (tid / inner) * inner), dq(256 / inner), dr(256 - (256 / inner) * inner), n(inner) {}
   MX_D void next() { o += dq; i += dr; if (i >= n) { i -= n; o++; } }
 };
+// row filter of one view of the group at its tapped columns: Wt = the group's rotated tile (stride WW, halo gRx x gRy), of
+// which the view reads the rows from dRy = gRy - Ry on; Tt row o = row y0 - Ry + o of the rotated image
 template <int N>
-MX_D void vg_rows(const float *Wt, float *Tt, const unsigned char *colTab, const float *kxT, int WW, int Rx, int tid, int nix, int yEnd, int nxRt) {
+MX_D void vg_rows(const float *Wt, float *Tt, const unsigned char *colTab, const float *kxT, int WW, int gRx, int dRy, int Rx, int tid, int nix,
+                  int yEnd, int nxRt) {
   constexpr int NK = N ? N : 1;
   float k[NK];
 #pragma unroll
   for (int q = 0; q < NK; q++) k[q] = N ? kxT[q] : 0.f;
   for (FlatWalk w(tid, nix); w.o < yEnd; w.next()) {
     const int lc = colTab[w.i];
-    if (lc != 255) Tt[w.o * VG_TS + lc] = vf_row_value<N>(Wt + w.o * WW + Rx, lc, k, kxT, Rx, nxRt);
+    if (lc != 255) Tt[w.o * VG_TS + lc] = vf_row_value<N>(Wt + (w.o + dRy) * WW + gRx, lc, k, kxT, Rx, nxRt);
   }
 }
+// column filter + tilt of one view: the blurred value under each of an output pixel's four taps is formed in registers, straight
+// from the row-filtered tile (vf_col_value, the call the blurred tile used to be filled by), so the rotated tile stays as it is
+// for the next view of the group
 template <int N>
-MX_D void vg_cols(const float *Tt, float *Bt, const unsigned char *colTab, const unsigned char *rowTab, const float *kyT, int WW, int Ry, int tid,
-                  int nix, int niy) {
+MX_D void vg_out(const float *Tt, const ViewJob &u, const float *kyT, int Ry, int tid, int x0, int y0, int xa, int ya, int nox, int noy) {
   constexpr int NK = N ? N : 1;
   float k[NK];
 #pragma unroll
   for (int q = 0; q < NK; q++) k[q] = N ? kyT[q] : 0.f;
-  for (FlatWalk w(tid, nix); w.o < niy; w.next()) {
-    const int lc = colTab[w.i], lr = rowTab[w.o];
-    if (lc != 255 && lr != 255) Bt[lr * WW + lc] = vf_col_value<N>(Tt + (lr + Ry) * VG_TS, lc, VG_TS, k, kyT, Ry);
+  const auto B = [&](int lr, int lc) { return vf_col_value<N>(Tt + (lr + Ry) * VG_TS, lc, VG_TS, k, kyT, Ry); };
+  for (FlatWalk w(tid, nox); w.o < noy; w.next()) {
+    const int x = xa + w.i, y = ya + w.o;
+    int ad, bd, X0, Y0;
+    warp_xterm(u.W, x, ad, bd);
+    warp_yterm(u.W, y, X0, Y0);
+    u.dst[(size_t)y * u.dcols + x] = warp_fetch_tile(B, x0, y0, u.rrows, u.rcols, 128.f, ad, bd, X0, Y0);
   }
 }
-__global__ __launch_bounds__(256) void k_views_fused(const ViewJob *jobs, int n, const float *taps, int wFloats, int tFloats) {
+// A workgroup takes one tile position of a GROUP of views that share a rotation (same source, sizes and R: engine_views.hip):
+// it rotates the tile once, with the widest halo of the group, and then runs the filters and the tilt of every view that owns
+// an output pixel there.  The value of the rotated image at a coordinate does not depend on which view asks for it.
+// (SGPRs held to what eight waves per SIMD allow: LDS admits eight workgroups per CU, and the kernel waits on the rotation's gathers)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_views_fused(const ViewJob *jobs, int n, const float *taps, int wFloats, int tFloats) {
   extern __shared__ float smem[];
-  const int j = find_view(jobs, n, blockIdx.x, 3);
-  const ViewJob &v = jobs[j];
-  const int Rx = v.kx >> 1, Ry = v.ky >> 1;
+  const ViewJob &last = jobs[find_view(jobs, n, blockIdx.x, 3)];     // the views of a group share tileG: the bisection ends at the last
+  const ViewJob *const grp = jobs + last.grpFirst;
+  const ViewJob &v = grp[0];                                          // what the group shares: src, sizes, R, tileG
+  const int cnt = min(last.grpCount, VIEW_GROUP_CAP), gRx = last.grpRx, gRy = last.grpRy;
   const int t = blockIdx.x - v.tileG, tx = (v.rcols + VF_TW - 1) / VF_TW;
   const int x0 = (t % tx) * VF_TW, y0 = (t / tx) * VF_TH;
   const int x1 = min(x0 + VF_TW, v.rcols), y1 = min(y0 + VF_TH, v.rrows);
+  const int tid = threadIdx.x;
   // Ownership: output pixel (x, y) belongs to the tile that holds (clamp(sx, 0, rcols - 1), clamp(sy, 0, rrows - 1)), so pixels
-  // whose taps fall outside the rotated image are written exactly once too.  Columns [xa, xb) x rows [ya, yb).
-  // (each of the four waves finds one of the four bounds)
-  __shared__ int own[4];
+  // whose taps fall outside the rotated image are written exactly once too.  Columns [xa, xb) x rows [ya, yb) per view.
+  // (each of the four waves finds one of the four bounds, view after view)
+  __shared__ int own[VIEW_GROUP_CAP][4];
   {
-    const int axis = threadIdx.x >> 7, upper = (threadIdx.x >> 6) & 1;
-    const int r = first_reaching(v.W, axis, axis ? (upper ? y1 : y0) : (upper ? x1 : x0), axis ? v.drows : v.dcols, axis ? v.rrows : v.rcols, v.invW[axis]);
-    if ((threadIdx.x & 63) == 0) own[threadIdx.x >> 6] = r;
+    const int axis = tid >> 7, upper = (tid >> 6) & 1;
+    for (int m = 0; m < cnt; m++) {
+      const ViewJob &u = grp[m];
+      const int r = first_reaching(u.W, axis, axis ? (upper ? y1 : y0) : (upper ? x1 : x0), axis ? u.drows : u.dcols, axis ? v.rrows : v.rcols, u.invW[axis]);
+      if ((tid & 63) == 0) own[m][tid >> 6] = r;
+    }
   }
   __syncthreads();
-  const int xa = own[0], xb = own[1], ya = own[2], yb = own[3];
-  const int nox = xb - xa, noy = yb - ya;
-  if (nox <= 0 || noy <= 0) return;
+  {
+    bool any = false;
+    for (int m = 0; m < cnt; m++) any = any || (own[m][1] > own[m][0] && own[m][3] > own[m][2]);
+    if (!any) return;
+  }
   // blurred pixels the taps of owned pixels can read: the tile and, inside the image, the column and row behind it
   const int colsB = x1 - x0 + (x1 < v.rcols ? 1 : 0), rowsB = y1 - y0 + (y1 < v.rrows ? 1 : 0);
-  const int xEnd = colsB + 2 * Rx, yEnd = rowsB + 2 * Ry;      // ... and what the two filters reach of the rotated image
-  const int WW = VF_TW + 2 * Rx + 1;
-  float *const Wt = smem, *const Tt = smem + wFloats;          // rotated tile (later the blurred one), row-filtered tile
-  unsigned char *const colTab = (unsigned char *)(smem + wFloats + tFloats), *const rowTab = colTab + VF_TW + 4;
-  const int tid = threadIdx.x;
-  // The columns to filter: every one of the tile when the owned pixels tap at least that many (a tilt below 2), else the two
-  // taps of each owned column; rows likewise.  255 = a tap outside the image (it reads cval, not a blurred value).
-  const bool denseX = 2 * nox >= colsB, denseY = 2 * noy >= rowsB;
-  const int nix = denseX ? colsB : 2 * nox, niy = denseY ? rowsB : 2 * noy;
+  const int WW = VF_TW + 2 * gRx + 1;
+  float *const Wt = smem, *const Tt = smem + wFloats;          // rotated tile of the group, row-filtered tile of one view
+  unsigned char *const colTab = (unsigned char *)(smem + wFloats + tFloats);
   {
     // cv::warpAffine's per-column and per-row terms of the rotation, tabulated once (they live where the row-filtered tile
     // goes afterwards); halo pixels outside the rotated image mirror it (BORDER_REFLECT_101 of the blur)
+    const int xEnd = colsB + 2 * gRx, yEnd = rowsB + 2 * gRy;  // what the two filters of the group reach of the rotated image
     int *const colAd = (int *)Tt, *const colBd = colAd + WW, *const rowX0 = colBd + WW, *const rowY0 = rowX0 + VG_HR;
     for (int i = tid; i < xEnd + yEnd; i += 256) {
-      if (i < xEnd) warp_xterm(v.R, reflect101(x0 - Rx + i, v.rcols), colAd[i], colBd[i]);
-      else warp_yterm(v.R, reflect101(y0 - Ry + i - xEnd, v.rrows), rowX0[i - xEnd], rowY0[i - xEnd]);
-    }
-    for (int i = tid; i < nix + niy; i += 256) {
-      if (i < nix) {
-        const int lc = denseX ? i : warp_tap0(v.W, 0, xa + (i >> 1)) + (i & 1) - x0;
-        colTab[i] = (unsigned char)(lc >= 0 && lc < colsB ? lc : 255);
-      } else {
-        const int q = i - nix, lr = denseY ? q : warp_tap0(v.W, 1, ya + (q >> 1)) + (q & 1) - y0;
-        rowTab[q] = (unsigned char)(lr >= 0 && lr < rowsB ? lr : 255);
-      }
+      if (i < xEnd) warp_xterm(v.R, reflect101(x0 - gRx + i, v.rcols), colAd[i], colBd[i]);
+      else warp_yterm(v.R, reflect101(y0 - gRy + i - xEnd, v.rrows), rowX0[i - xEnd], rowY0[i - xEnd]);
     }
     __syncthreads();
     for (FlatWalk w(tid, xEnd); w.o < yEnd; w.next())
       Wt[w.o * WW + w.i] = warp_fetch(v.src, v.srows, v.scols, 128.f, colAd[w.i], colBd[w.i], rowX0[w.o], rowY0[w.o]);
   }
   __syncthreads();
-  const float *kxT = taps + v.tapOfs, *kyT = kxT + v.kx;
-  const int nx = v.kx, ny = v.ky;
-  // wave-uniform tap counts: one switch per pass picks a fully unrolled body with the taps in registers (as k_views_rotblur)
-  switch (nx) {
-    case 1: vg_rows<1>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 3: vg_rows<3>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 5: vg_rows<5>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 7: vg_rows<7>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 9: vg_rows<9>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 11: vg_rows<11>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    case 13: vg_rows<13>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-    default: vg_rows<0>(Wt, Tt, colTab, kxT, WW, Rx, tid, nix, yEnd, nx); break;
-  }
-  __syncthreads();
-  // the blurred tile takes the place of the rotated one, which nothing reads any more
-  switch (ny) {
-    case 1: vg_cols<1>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
-    case 3: vg_cols<3>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
-    case 5: vg_cols<5>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
-    default: vg_cols<0>(Tt, Wt, colTab, rowTab, kyT, WW, Ry, tid, nix, niy); break;
-  }
-  __syncthreads();
-  for (FlatWalk w(tid, nox); w.o < noy; w.next()) {
-    const int x = xa + w.i, y = ya + w.o;
-    int ad, bd, X0, Y0;
-    warp_xterm(v.W, x, ad, bd);
-    warp_yterm(v.W, y, X0, Y0);
-    v.dst[(size_t)y * v.dcols + x] = warp_fetch_tile(Wt, WW, x0, y0, v.rrows, v.rcols, 128.f, ad, bd, X0, Y0);
+  for (int m = 0; m < cnt; m++) {
+    const int xa = own[m][0], xb = own[m][1], ya = own[m][2], yb = own[m][3];
+    const int nox = xb - xa, noy = yb - ya;
+    if (nox <= 0 || noy <= 0) continue;                        // (uniform: the whole workgroup skips the view)
+    const ViewJob &u = grp[m];
+    const int Rx = u.kx >> 1, Ry = u.ky >> 1;
+    const int yEnd = rowsB + 2 * Ry;
+    // The columns to filter: every one of the tile when the owned pixels tap at least that many (a tilt below 2), else the two
+    // taps of each owned column.  255 = a tap outside the image (it reads cval, not a blurred value).  All rows the column
+    // filter reaches are row-filtered.
+    const bool denseX = 2 * nox >= colsB;
+    const int nix = denseX ? colsB : 2 * nox;
+    for (int i = tid; i < nix; i += 256) {
+      const int lc = denseX ? i : warp_tap0(u.W, 0, xa + (i >> 1)) + (i & 1) - x0;
+      colTab[i] = (unsigned char)(lc >= 0 && lc < colsB ? lc : 255);
+    }
+    __syncthreads();
+    const float *kxT = taps + u.tapOfs, *kyT = kxT + u.kx;
+    const int nx = u.kx, ny = u.ky;
+    // wave-uniform tap counts: one switch per pass picks a fully unrolled body with the taps in registers (as k_views_rotblur)
+    switch (nx) {
+      case 1: vg_rows<1>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 3: vg_rows<3>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 5: vg_rows<5>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 7: vg_rows<7>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 9: vg_rows<9>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 11: vg_rows<11>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      case 13: vg_rows<13>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+      default: vg_rows<0>(Wt, Tt, colTab, kxT, WW, gRx, gRy - Ry, Rx, tid, nix, yEnd, nx); break;
+    }
+    __syncthreads();
+    switch (ny) {
+      case 1: vg_out<1>(Tt, u, kyT, Ry, tid, x0, y0, xa, ya, nox, noy); break;
+      case 3: vg_out<3>(Tt, u, kyT, Ry, tid, x0, y0, xa, ya, nox, noy); break;
+      case 5: vg_out<5>(Tt, u, kyT, Ry, tid, x0, y0, xa, ya, nox, noy); break;
+      default: vg_out<0>(Tt, u, kyT, Ry, tid, x0, y0, xa, ya, nox, noy); break;
+    }
+    __syncthreads();                                           // the next view overwrites the row-filtered tile and the column list
   }
 }
 
@@ -504,7 +525,7 @@ void launch_views_fused(hipStream_t s, const ViewJob *jobs, int n, int tiles, co
   if (tiles <= 0) return;
   const int wFloats = (VF_TH + 2 * maxRy + 1) * (VF_TW + 2 * maxRx + 1), tFloats = (VF_TH + 2 * maxRy + 1) * VG_TS;
   static_assert(2 * (VF_TW + 2 * VF_RX + 1) + 2 * VG_HR <= (VF_TH + 1) * VG_TS, "the rotation's column / row terms fit the row-filtered tile");
-  static_assert(VF_TW + 1 < 255 && VF_TH + 1 < 255, "tapped columns / rows are listed as bytes");
+  static_assert(VF_TW + 1 < 255, "tapped columns are listed as bytes");
   MX_DUP(K_VIEW_BLUR) hipLaunchKernelGGL(k_views_fused, dim3(tiles), dim3(256), (size_t)(wFloats + tFloats) * 4 + ((VG_TABS + 3) & ~3), s, jobs, n, taps,
                                          wFloats, tFloats);
 }
