@@ -1223,6 +1223,63 @@ int modsx_affshape_jobs(const modsx_region *in, int n, int cols, int rows, float
  * border test refused, regions launched, regions converged, launches.  Fills out[0 .. min(n, 6) - 1], returns 6. */
 int modsx_affshape_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- CLAHE on the device: the drivers' doCLAHE step (engine_clahe.hip, kernels_clahe.hip) ---------------------------------
+ * With `[Matching] doCLAHE` set every driver of the reference runs createCLAHE(), setClipLimit(4) and clahe->apply() on the
+ * 8-bit gray image before it builds the ImageRepresentation (mods.cpp:139-189, mods_multi.cpp:162-178 for the query and every
+ * partner, extract_features.cpp:92-103, export_descriptors.cpp:92-119).  These entries are that step on an uploaded image.
+ * Contract: CLAHE_Impl::apply of OpenCV 2.4.9, modules/imgproc/src/clahe.cpp, restated here (no OpenCV is linked or needed; the
+ * restatement is not pinned against an OpenCV build).  tx, ty = tiles_x, tiles_y; H = 256.
+ *   source    the u8 value of a pixel is saturate_cast<uchar>(v) of the gray f32 value: round to nearest even, clamp to 0 .. 255,
+ *             NaN -> 0.  A u8 upload is unchanged by it; a 3-channel upload has gone through (B + G + R) / 3.
+ *   tiles     cols % tx == 0 && rows % ty == 0: tile = cols / tx x rows / ty on the image.  Otherwise the LUT source is the
+ *             image padded with BORDER_REFLECT_101 by ty - rows % ty rows at the bottom and tx - cols % tx columns at the right
+ *             (a divisible side is padded by a whole ty / tx), tile = padded size / grid.  No padded copy is made.
+ *   scale     total = tileW * tileH; lutScale = (float)(H - 1) / total; clipLimit = clip_limit > 0 ?
+ *             max((int)(clip_limit * total / H), 1) : 0 in f64 (a product of INT_MAX or more gives INT_MAX: nothing is clipped)
+ *   per tile  hist[256] of the tile's ROI; with clipLimit > 0: clipped = sum max(hist[i] - clipLimit, 0), hist[i] =
+ *             min(hist[i], clipLimit), batch = clipped / H, residual = clipped - batch * H, hist[i] += batch, hist[i]++ for
+ *             i < residual; lut[i] = saturate_cast<uchar>((float)sum_i * lutScale) with the running int sum
+ *   per pixel tyf = (float)y / tileH - 0.5f, ty1 = floor(tyf), ya = tyf - ty1, ty2 = ty1 + 1, then ty1 = max(ty1, 0), ty2 =
+ *             min(ty2, ty - 1); the same in x; res = 0, res += lut[ty1, tx1][v] * ((1 - xa) * (1 - ya)), += lut[ty1, tx2][v] *
+ *             (xa * (1 - ya)), += lut[ty2, tx1][v] * ((1 - xa) * ya), += lut[ty2, tx2][v] * (xa * ya) in f32 without contraction;
+ *             dst = saturate_cast<uchar>(res), stored as f32: the integers 0 .. 255 that ImageRepresentation(img_clahe) holds.
+ * variant 1 is the rule of OpenCV 3.x / 4.x (restated from memory of those sources): the residual is spread with a step
+ * (step = max(H / residual, 1); for (i = 0; i < H && residual > 0; i += step, residual--) hist[i]++), txf = x * (1.0f / tileW)
+ * - 0.5f (and in y), res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya with xa1 = 1.0f - xa.
+ * Defaults (modsx_default_clahe_params): clip 4.0, 8 x 8 tiles, variant 0 -- what the drivers set (createCLAHE's own clip is 40).
+ * Refusals, MODSX_ERR_ARG with a message and before any launch: a null pointer; tiles_x or tiles_y < 1; tiles_x * tiles_y above
+ * MODSX_CLAHE_MAX_TILES (the LUT table of an image, tiles x 256 bytes, is staged in 64 KiB of LDS); clip_limit negative or not
+ * finite; variant other than 0 / 1; an output of another size than its input; an image whose pixels are not memory of the
+ * context's device; in a batch more than 65535 images, two outputs that share their pixels, an output that is another image's
+ * input.  Images are one-channel by construction (modsx_image_wrap_device takes nothing else).  Not here: 16-bit input, colour
+ * CLAHE; modsx_match_ladder / modsx_match_one_to_many do not equalise -- as in the reference the caller does it first. */
+#define MODSX_CLAHE_MAX_TILES 256
+typedef struct modsx_clahe_params {
+  double clip_limit;            /* 4.0 */
+  int tiles_x, tiles_y;         /* 8, 8 */
+  int variant;                  /* 0 = OpenCV 2.4.9 (the reference's), 1 = OpenCV 3.x / 4.x */
+} modsx_clahe_params;
+void modsx_default_clahe_params(modsx_clahe_params *p);
+/* out: an image of the same size; may be `in` itself (in place: the launches that read the image as LUT source are ordered
+ * before the pixel pass).  Three launches on the context's stream; returns after they have finished. */
+int modsx_image_clahe(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par, modsx_image *out);
+/* the same into a fresh handle (modsx_image_free); NULL on failure */
+modsx_image *modsx_image_clahe_new(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par);
+/* n images of ANY sizes in one launch set: three launches for the whole batch, from a device table of per-image geometry
+ * (mods_multi's loop over the partners).  out[i] may be in[i].  Every result equals that of a single call.  n == 0 is MODSX_OK. */
+int modsx_image_clahe_batch(modsx_ctx *ctx, const modsx_image *const *in, modsx_image *const *out, int n, const modsx_clahe_params *par);
+/* host only: what the launcher derives from the image size, from the function it calls itself.  out[0 .. 8] = tileW, tileH,
+ * padded cols, padded rows, clipLimit, the bits of lutScale (f32), row strips per tile of the histogram launch, tile rows per
+ * strip, workgroups of the pixel pass.  Strip rule: rows per strip = max(1, 4096 / tileW), raised so that a tile has at most
+ * 256 strips and never above tileH; pixel pass: one workgroup per 4096 consecutive pixels.  Sizes 1 .. 16384 per side, at most 64 Mpx.  Returns 9. */
+int modsx_clahe_geometry(int rows, int cols, const modsx_clahe_params *par, int *out);
+/* Test entry: the first two launches on `in`; hist [tiles][256] = the counts of every tile BEFORE clipping, lut [tiles][256] =
+ * the finished LUTs (either may be NULL), tiles in row-major order. */
+int modsx_debug_clahe(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par, int *hist, unsigned char *lut);
+/* CLAHE work of this context since modsx_create, cumulative: calls (a batch is one), images, tiles, histogram strips, pixels,
+ * launches.  Fills out[0 .. min(n, 6) - 1], returns 6. */
+int modsx_clahe_counters(modsx_ctx *ctx, long *out, int n);
+
 /* ---- float descriptor classes of a stored representation (engine_reps_f32.hip) -------------------------------------------
  * A modsx_rep also holds one class per (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF}) x (float descriptor
  * type MODSX_DESC_CAFFE .. MODSX_DESC_SURF), as RegionVectorMap[det][desc] does for any descriptor name.  Widths: CAFFE any

@@ -51,6 +51,11 @@ class AffShapeParams(C.Structure):
                 ("affBmbrgMethod", C.c_int)]
 
 
+class ClaheParams(C.Structure):
+    """modsx_clahe_params: cv::CLAHE's clip limit and tile grid, and which OpenCV's rule (0 = 2.4.9, 1 = 3.x / 4.x)"""
+    _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("variant", C.c_int)]
+
+
 class MserParams(C.Structure):
     _fields_ = [("min_size", C.c_int), ("max_area", C.c_double), ("min_margin", C.c_double), ("relative", C.c_int),
                 ("mode", C.c_int), ("reg_number", C.c_int), ("rel_threshold", C.c_float), ("rel_reg_number", C.c_float)]
@@ -152,6 +157,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_surfdet", "modsx_surfdet_counters",
            "modsx_default_affshape_params", "modsx_detect_affine_shape", "modsx_detect_affine_shape_batch",
            "modsx_debug_affine_shape", "modsx_affshape_jobs", "modsx_affshape_counters",
+           "modsx_default_clahe_params", "modsx_image_clahe", "modsx_image_clahe_new", "modsx_image_clahe_batch",
+           "modsx_clahe_geometry", "modsx_debug_clahe", "modsx_clahe_counters",
            "modsx_daisy_dim", "modsx_daisy_patches", "modsx_daisy_patches_device", "modsx_describe_regions_daisy",
            "modsx_describe_regions_daisy_device", "modsx_daisy_tables", "modsx_daisy_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -180,6 +187,10 @@ SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
 SURFDET_COUNTERS = ("calls", "images", "extrema", "accepted", "regrows")
 # include/modsx.h: modsx_affshape_counters, in its order
 AFFSHAPE_COUNTERS = ("calls", "regions", "border_refused", "launched", "converged", "launches")
+# include/modsx.h: modsx_clahe_counters and modsx_clahe_geometry, in their order
+CLAHE_COUNTERS = ("calls", "images", "tiles", "strips", "pixels", "launches")
+CLAHE_GEOMETRY = ("tile_w", "tile_h", "pad_cols", "pad_rows", "clip_limit", "lut_scale_bits", "strips", "strip_rows", "apply_blocks")
+CLAHE_MAX_TILES = 256                     # include/modsx.h: MODSX_CLAHE_MAX_TILES
 DET_SURF, SURFDET_MAX_LAYERS = 6, 12      # include/modsx.h: MODSX_DET_SURF, MODSX_SURFDET_MAX_LAYERS
 DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, MODSX_DET_MSER
 # include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
@@ -378,6 +389,16 @@ def lib():
         L.modsx_affshape_jobs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.modsx_affshape_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_daisy_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_default_clahe_params.restype = None
+        L.modsx_default_clahe_params.argtypes = [C.c_void_p]
+        L.modsx_image_clahe.argtypes = [C.c_void_p] * 4
+        L.modsx_image_clahe_new.restype = C.c_void_p
+        L.modsx_image_clahe_new.argtypes = [C.c_void_p] * 3
+        L.modsx_image_clahe_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.modsx_clahe_geometry.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.modsx_debug_clahe.argtypes = [C.c_void_p] * 5
+        L.modsx_clahe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_clahe_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -548,6 +569,27 @@ def affshape_jobs(regs, cols, rows):
     ratio, res, border = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
     _check(lib().modsx_affshape_jobs(_p(regs), n, int(cols), int(rows), _p(ratio), _p(res), _p(border)), "affshape_jobs")
     return dict(ratio=ratio[:n], res=res[:n], border=border[:n].astype(bool))
+
+
+def clahe_params(clip_limit=4.0, tiles=(8, 8), variant=0):
+    """modsx_clahe_params; tiles = (tiles_x, tiles_y) as cv::Size(width, height).  The defaults are what the drivers set."""
+    p = ClaheParams()
+    lib().modsx_default_clahe_params(C.byref(p))
+    p.clip_limit, p.tiles_x, p.tiles_y, p.variant = float(clip_limit), int(tiles[0]), int(tiles[1]), int(variant)
+    return p
+
+
+def clahe_geometry(rows, cols, clip_limit=4.0, tiles=(8, 8), variant=0):
+    """dict of CLAHE_GEOMETRY (and lut_scale as np.float32): the tile and padded size, clipLimit, lutScale, the histogram
+    launch's strips per tile / rows per strip and the pixel pass's workgroups for a rows x cols image, from the function the
+    launcher itself calls (no device needed); raises for what the library refuses."""
+    out = np.zeros(len(CLAHE_GEOMETRY), np.int32)
+    n = _check(lib().modsx_clahe_geometry(int(rows), int(cols), C.byref(clahe_params(clip_limit, tiles, variant)), _p(out)),
+               "clahe_geometry")
+    assert n == len(CLAHE_GEOMETRY), n
+    g = dict(zip(CLAHE_GEOMETRY, (int(x) for x in out)))
+    g["lut_scale"] = out[5:6].view(np.float32)[0]
+    return g
 
 
 def surfdet_normalise(params):
@@ -1172,6 +1214,50 @@ class Context(object):
     def affshape_counters(self):
         """dict of AFFSHAPE_COUNTERS: external affine adaptation work of this context since it was created (cumulative)."""
         return self._counters("modsx_affshape_counters", AFFSHAPE_COUNTERS)
+
+    # ---- CLAHE (engine_clahe.hip: the drivers' doCLAHE step) ----
+    def clahe(self, img, clip_limit=4.0, tiles=(8, 8), variant=0, out=None):
+        """cv::CLAHE::apply (clip 4, 8 x 8 as the drivers set it) on an uploaded image: a new Image, or `out` (same size; may be
+        img itself) filled and returned.  The result holds the integers 0..255 as f32."""
+        par = clahe_params(clip_limit, tiles, variant)
+        if out is None:
+            h = lib().modsx_image_clahe_new(self._c(), C.c_void_p(img.h), C.byref(par))
+            if not h:
+                raise RuntimeError("clahe failed: " + _err())
+            return Image(self, h, img.rows, img.cols)
+        _check(lib().modsx_image_clahe(self._c(), C.c_void_p(img.h), C.byref(par), C.c_void_p(out.h)), "clahe")
+        return out
+
+    def clahe_batch(self, imgs, clip_limit=4.0, tiles=(8, 8), variant=0, out=None):
+        """clahe of several images of any sizes in ONE launch set (three launches): out[i] (default: imgs[i], in place) is
+        filled; returns the list of outputs."""
+        out = list(imgs) if out is None else list(out)
+        assert len(out) == len(imgs)
+        n = len(imgs)
+        src = (C.c_void_p * max(1, n))(*[im.h for im in imgs])
+        dst = (C.c_void_p * max(1, n))(*[im.h for im in out])
+        _check(lib().modsx_image_clahe_batch(self._c(), src, dst, n, C.byref(clahe_params(clip_limit, tiles, variant))), "clahe_batch")
+        return out
+
+    def debug_clahe(self, img, clip_limit=4.0, tiles=(8, 8), variant=0):
+        """modsx_debug_clahe -> dict(hist [tiles][256] int32: the counts of every tile before clipping, lut [tiles][256] uint8),
+        tiles in row-major order."""
+        nt = int(tiles[0]) * int(tiles[1])
+        hist, lut = np.zeros((max(nt, 1), 256), np.int32), np.zeros((max(nt, 1), 256), np.uint8)
+        _check(lib().modsx_debug_clahe(self._c(), C.c_void_p(img.h), C.byref(clahe_params(clip_limit, tiles, variant)), _p(hist), _p(lut)),
+               "debug_clahe")
+        return dict(hist=hist, lut=lut)
+
+    def clahe_last_ms(self):
+        """(hist, lut, apply) HIP-event times in ms of the last clahe / clahe_batch / debug_clahe launches of this context, recorded
+        while profile(True) is on (zeros before)."""
+        ms = np.zeros(3, np.float64)
+        _check(lib().modsx_debug_clahe_last_ms(self._c(), _p(ms)), "clahe_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def clahe_counters(self):
+        """dict of CLAHE_COUNTERS: CLAHE work of this context since it was created (cumulative)."""
+        return self._counters("modsx_clahe_counters", CLAHE_COUNTERS)
 
     def surfdet_counters(self):
         """dict of SURFDET_COUNTERS: SURF detector work of this context since it was created (cumulative)."""

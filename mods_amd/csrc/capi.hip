@@ -1889,8 +1889,80 @@ int modsx_affshape_counters(modsx_ctx *ctx, long *out, int n) {
   return read_counters("modsx_affshape_counters", ctx->affshapeCounters, 6, out, n);
 }
 
+// ---- CLAHE (engine_clahe.hip) ----
+void modsx_default_clahe_params(modsx_clahe_params *p) {
+  if (!p) return;
+  // what every driver sets: createCLAHE(); setClipLimit(4), mods.cpp:139-189 (createCLAHE's own defaults: clip 40, 8 x 8 tiles)
+  p->clip_limit = 4.0;
+  p->tiles_x = 8; p->tiles_y = 8;
+  p->variant = 0;
+}
+int modsx_clahe_geometry(int rows, int cols, const modsx_clahe_params *par, int *out) {
+  NEED(par); NEED(out);
+  ClaheGeo g;
+  const int rc = clahe_geometry("modsx_clahe_geometry", rows, cols, *par, g);
+  if (rc) return rc;
+  int bits;
+  memcpy(&bits, &g.lutScale, 4);
+  const int v[9] = {g.tileW, g.tileH, g.padW, g.padH, g.clipLimit, bits, g.strips, g.stripRows, g.applyBlocks};
+  memcpy(out, v, sizeof v);
+  return 9;
+}
+int modsx_image_clahe_batch(modsx_ctx *ctx, const modsx_image *const *in, modsx_image *const *out, int n, const modsx_clahe_params *par) {
+  const char *fn = "modsx_image_clahe_batch";
+  NEED(par);
+  int rc = clahe_check(fn, *par);
+  if (rc) return rc;
+  if (n < 0) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  if (n == 0) return MODSX_OK;
+  NEED(ctx); NEED(in); NEED(out);
+  for (int i = 0; i < n; i++) { NEED(in[i]); NEED(out[i]); }
+  hipSetDevice(ctx->dev);
+  return clahe_batch(ctx, fn, in, out, n, *par, nullptr, nullptr);
+}
+int modsx_image_clahe(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par, modsx_image *out) {
+  const char *fn = "modsx_image_clahe";
+  NEED(par);
+  int rc = clahe_check(fn, *par);
+  if (rc) return rc;
+  NEED(ctx); NEED(in); NEED(out);
+  hipSetDevice(ctx->dev);
+  return clahe_batch(ctx, fn, &in, &out, 1, *par, nullptr, nullptr);
+}
+modsx_image *modsx_image_clahe_new(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par) {
+  const char *fn = "modsx_image_clahe_new";
+  if (!par || clahe_check(fn, *par)) { if (!par) mx::set_error(std::string(fn) + ": null argument: par"); return nullptr; }
+  if (!ctx || !in) { mx::set_error(std::string(fn) + ": null argument"); return nullptr; }
+  hipSetDevice(ctx->dev);
+  modsx_image *im = new modsx_image();
+  im->rows = in->rows; im->cols = in->cols; im->owned = true; im->d = nullptr;
+  if (hipMalloc(&im->d, (size_t)in->rows * in->cols * 4) != hipSuccess) { mx::set_error("hipMalloc image"); delete im; return nullptr; }
+  if (clahe_batch(ctx, fn, &in, &im, 1, *par, nullptr, nullptr) != MODSX_OK) { hipFree(im->d); delete im; return nullptr; }
+  return im;
+}
+int modsx_debug_clahe(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_params *par, int *hist, unsigned char *lut) {
+  const char *fn = "modsx_debug_clahe";
+  NEED(par);
+  int rc = clahe_check(fn, *par);
+  if (rc) return rc;
+  NEED(ctx); NEED(in);
+  hipSetDevice(ctx->dev);
+  return clahe_batch(ctx, fn, &in, nullptr, 1, *par, hist, lut);
+}
+// under modsx_profile(ctx, 1): HIP-event times in ms of the three launches of this context's last CLAHE call or batch --
+// k_clahe_hist, k_clahe_lut, k_clahe_apply (tools/bench_clahe.py)
+extern "C" __attribute__((visibility("default"))) int modsx_debug_clahe_last_ms(modsx_ctx *ctx, double *ms3) {
+  NEED(ctx); NEED(ms3);
+  for (int i = 0; i < 3; i++) ms3[i] = ctx->claheMs[i];
+  return MODSX_OK;
+}
+int modsx_clahe_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  return read_counters("modsx_clahe_counters", ctx->claheCounters, 6, out, n);
+}
+
 // ---- DAISY (engine_daisy.hip) ----
-#define DAISY_ARGS(fn, bad)                                                                          \
+#define DAISY_ARGS(fn, bad)                                                                         \
   do {                                                                                                \
     PATCH_ARGS(fn, bad);                                                                               \
     if (daisy_check_args(fn, patchSize, rad, radq, thq, histq, nrm_type)) return MODSX_ERR_ARG;      \

@@ -423,6 +423,8 @@ void ctx_destroy(modsx_ctx *c) {
   for (DevBuf &b : c->surfTab) b.release();
   for (DevBuf *b : {&c->sdInteg, &c->sdResp, &c->sdLap, &c->sdFlags, &c->sdCounts, &c->sdTab, &c->sdPoints, &c->sdExt}) b->release();
   c->sdHost.release(); c->sdBack.release();
+  for (DevBuf *b : {&c->claheTab, &c->clahePart, &c->claheLut, &c->claheDbg}) b->release();
+  c->claheHost.release();
   for (DevBuf &b : c->daisyTab) b.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();

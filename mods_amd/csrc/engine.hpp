@@ -466,6 +466,30 @@ void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef
 // SIFTnorm(std::vector<float>&) over [n][128] f32 rows (kernels_dsp.hip); out may be rows; 4-byte alignment suffices
 void launch_sift_norm_f32(hipStream_t s, const float *rows, int n, double maxBin, float *out);
 
+// ---- CLAHE (kernels_clahe.hip, engine_clahe.hip): cv::CLAHE::apply of OpenCV 2.4.9 on the gray f32 image ----
+constexpr int CLAHE_BINS = 256;
+constexpr int CLAHE_MAX_TILES = 256;      // MODSX_CLAHE_MAX_TILES: the image's LUT table (tiles x 256 B) is one workgroup's LDS, 64 KiB
+constexpr int CLAHE_STRIP_PX = 4096;      // a histogram workgroup takes whole tile rows up to this many pixels ...
+constexpr int CLAHE_MAX_STRIPS = 256;     // ... and a tile is never cut into more strips than this
+constexpr int CLAHE_APPLY_PX = 4096;      // consecutive pixels (row-major) one workgroup of k_clahe_apply maps
+// what the three launches need of one image; one entry per image of a batch, read from a device table
+struct ClaheImg {
+  const float *src;
+  float *dst;
+  long long partOfs;      // first [256]-int partial histogram of the image: (partOfs + tile * strips + strip) * 256
+  long long lutOfs;       // first tile of the image in the LUT table: (lutOfs + tile) * 256 bytes
+  int rows, cols, tileW, tileH;
+  int strips, stripRows;  // row strips per tile and the tile rows in each (the last one may be shorter)
+  int clipLimit, applyBlocks;
+  float lutScale;
+  int vec;                // src and dst are 16-byte aligned: quads of four consecutive pixels move as one access
+};
+void launch_clahe_hist(hipStream_t s, const ClaheImg *imgs, int n, int tx, int ty, int maxStrips, int *partials);
+// dbgHist (optional): [all tiles][256] the summed counts before clipping
+void launch_clahe_lut(hipStream_t s, const ClaheImg *imgs, int n, int tiles, int variant, const int *partials, unsigned char *lut,
+                      int *dbgHist);
+void launch_clahe_apply(hipStream_t s, const ClaheImg *imgs, int n, int tx, int ty, int variant, int maxBlocks, const unsigned char *lut);
+
 }  // namespace mx
 
 namespace mx {
@@ -583,6 +607,12 @@ struct modsx_ctx {
   // external affine adaptation (engine_detect.hip: affine_shape_batch), modsx_affshape_counters: calls, regions in, regions the
   // border test refused, regions launched, regions converged, launches
   long affshapeCounters[6] = {0, 0, 0, 0, 0, 0};
+  // CLAHE (engine_clahe.hip): the per-image table, the strip partials, the LUT table and the debug tap's summed histograms of one
+  // launch set; modsx_clahe_counters: calls, images, tiles, strips, pixels, launches
+  mx::DevBuf claheTab, clahePart, claheLut, claheDbg;
+  mx::PinBuf claheHost;
+  long claheCounters[6] = {0, 0, 0, 0, 0, 0};
+  double claheMs[3] = {0, 0, 0};   // under modsx_profile: event times of the last CLAHE call's three launches
   // float classes of stored representations (engine_reps_f32.hip): dense rows of a device extractor on their way into a slot, and
   // modsx_fginn32_group_counters: grouped launch sets, problems in them, queries sent to resolve, resolve launches
   mx::DevBuf repStage;

@@ -39,6 +39,15 @@ int affshape_check(const char *fn, const modsx_affshape_params &p);
 int affshape_jobs(const char *fn, const modsx_region *in, int n, int cols, int rows, float *ratio, int *res, unsigned char *border);
 int affine_shape_batch(modsx_ctx *c, const char *fn, const modsx_image *const *imgs, int nImgs, const modsx_region *in, const int *counts,
                        const modsx_affshape_params &p, int variant, std::vector<modsx_region> *out, const AffShapeReport *rep);
+// CLAHE (engine_clahe.hip).  clahe_check: the parameter refusals; clahe_geometry: tile and padded size, clipLimit, lutScale and the
+// work split of one image -- the function the launcher itself sizes its table and grids with (both need no device; fn names the
+// entry in the error text).  clahe_batch: n images of any sizes in one launch set on c->stream, out[i] may be in[i]; with out ==
+// nullptr the pixel pass is left out (modsx_debug_clahe) and dbgHist [tiles][256] / dbgLut [tiles][256] (host, n == 1) are filled.
+struct ClaheGeo { int tileW, tileH, padW, padH, clipLimit; float lutScale; int strips, stripRows, applyBlocks; };
+int clahe_check(const char *fn, const modsx_clahe_params &p);
+int clahe_geometry(const char *fn, int rows, int cols, const modsx_clahe_params &p, ClaheGeo &g);
+int clahe_batch(modsx_ctx *c, const char *fn, const modsx_image *const *in, modsx_image *const *out, int n, const modsx_clahe_params &p,
+                int *dbgHist, unsigned char *dbgLut);
 void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out);
 // reproj (optional, one entry per image): what the caller's reproject_regions will be called with.  A region that
 // reproject_certain_drop flags for it is treated like one at the view's border: no orientation job and no output entry,
