@@ -388,12 +388,15 @@ int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads);
 int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, int *ntiles_ub);
 /* what the description stage planned on this context since modsx_create, cumulative (measurement hook); the contexts that work on
  * its behalf (the peer of a lone multi-view pair, the chains of contexts that take parts of a view list) count with it.  Fills
- * out[0 .. min(n, 14) - 1] and returns 14.  In order: description calls; chunks (launch sets, cut where the window arena of
+ * out[0 .. min(n, 15) - 1] and returns 15.  In order: description calls; chunks (launch sets, cut where the window arena of
  * MODSX_ARENA_MB is full); the largest number of chunks in one call; chunks that began in the middle of an image's region list;
  * chunks that began at an image other than the call's first; regions; regions of the direct branch (no smoothed window); windows
  * whose sampling kernel also ran the column filter; row tiles and column tiles of the LDS filters; tiles of the global-memory
  * sampling kernel, of the global-memory row filter and of the global-memory column filter; windows whose LDS row tile was clamped
- * to 32 rows.  A call is counted when its planning begins and a chunk when its walk begins: a call refused for a window that is
+ * to 32 rows; and, last, ordered_workgroups: the k_describe workgroups (SIFT and raw-histogram forms; two regions each, DESIGN.md
+ * section 6.6) that took the ordered gather instead of the order-free one.  That one is counted on the device, which the planner
+ * cannot know: modsx_debug_describe_plan fills the first 14 only, and this call waits for the context's stream and copies
+ * the word (the description calls do neither for it).  A call is counted when its planning begins and a chunk when its walk begins: a call refused for a window that is
  * too large counts as one call and one chunk with no regions and leaves the largest-chunks value alone, and a call without any
  * region counts as a call with no chunk.  Read it while no call runs on the context; tests work with the difference of two
  * readings */

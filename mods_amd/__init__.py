@@ -171,6 +171,9 @@ EXCHANGE_ALL_GATHER, EXCHANGE_OWNER = 0, 1   # include/modsx.h: modsx_comm_set_e
 # include/modsx.h: modsx_describe_counters, in its order
 DESCRIBE_COUNTERS = ("calls", "chunks", "max_chunks", "chunks_mid_image", "chunks_later_image", "jobs", "direct_jobs", "fused_windows",
                      "lds_row_tiles", "lds_col_tiles", "sample_tiles", "global_row_tiles", "global_col_tiles", "clamped_windows")
+# ... and behind those, which the planner books (describe_plan gives them too), what only the device counts: k_describe
+# workgroups that took the ordered gather.  Context.describe_counters() has both
+DESCRIBE_DEVICE_COUNTERS = ("ordered_workgroups",)
 # include/modsx.h: modsx_detect_counters, in its order
 DETECT_COUNTERS = ("blur_th16", "blur_th32") + tuple("blur_r%d" % r for r in range(1, 9)) + (
     "hessian", "resize", "scan_per_octave", "scan_per_level", "nms_flushes", "last_jobs", "last_tiles", "last_accepted",
@@ -1366,8 +1369,9 @@ class Context(object):
         return self._counters("modsx_dsp_counters", DSP_COUNTERS)
 
     def describe_counters(self):
-        """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative)."""
-        return self._counters("modsx_describe_counters", DESCRIBE_COUNTERS)
+        """dict of DESCRIBE_COUNTERS: what the description stage planned on this context since it was created (cumulative), and
+        of DESCRIBE_DEVICE_COUNTERS: `ordered_workgroups`, read from the device (the call waits for the context's stream)."""
+        return self._counters("modsx_describe_counters", DESCRIBE_COUNTERS + DESCRIBE_DEVICE_COUNTERS)
 
     def detect_counters(self):
         """dict of DETECT_COUNTERS: what the pyramid and the extrema scan launched on this context since it was created (the
@@ -2110,8 +2114,8 @@ DEFAULT_ARENA_FLOATS = 192 << 18    # the window arena of a describe chunk witho
 def describe_plan(regs, mr_size, fast=0, arena_floats=DEFAULT_ARENA_FLOATS, max_cuts=4096):
     """modsx_debug_describe_plan: what the description stage plans for one call, on the host alone (no GPU, no context).
     regs: the region list of one image, or a list of them (one per image).  -> dict(rc, error, counters, cuts): rc 0 or the
-    refusal's code with its text in `error`; counters as Context.describe_counters() of a fresh context shows them after that
-    call; cuts: the flat index of the first region of every chunk after the first."""
+    refusal's code with its text in `error`; counters (DESCRIBE_COUNTERS: what the device counts is not among them) as
+    Context.describe_counters() of a fresh context shows them after that call; cuts: the flat index of the first region of every chunk after the first."""
     lists = [regs] if isinstance(regs, np.ndarray) else list(regs)
     counts = np.array([len(r) for r in lists], np.int32)
     flat = np.ascontiguousarray(np.concatenate([np.asarray(r).view(REGION) for r in lists]) if lists else np.zeros(0, REGION), REGION)

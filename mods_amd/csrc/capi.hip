@@ -522,13 +522,24 @@ int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
   if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_describe_counters: bad argument"); return MODSX_ERR_ARG; }
   // the contexts that describe on this one's behalf count with it: the peer (the second image of a lone multi-view pair) and the
   // chains of half contexts of both (the further parts of a view list, engine_views.hip)
-  long sum[mx::DC_N] = {0};
-  for (const modsx_ctx *head : {(const modsx_ctx *)ctx, (const modsx_ctx *)ctx->peer})
-    for (const modsx_ctx *c = head; c; c = c->half)
+  long sum[mx::DC_ALL] = {0};
+  for (modsx_ctx *head : {ctx, ctx->peer})
+    for (modsx_ctx *c = head; c; c = c->half) {
       for (int q = 0; q < mx::DC_N; q++)
         if (q == mx::DC_MAX_CHUNKS) sum[q] = std::max(sum[q], c->descCnt[q]); else sum[q] += c->descCnt[q];
-  for (int q = 0; q < n && q < mx::DC_N; q++) out[q] = sum[q];
-  return mx::DC_N;
+      // the device's word, read here and nowhere else: the description calls neither copy it nor wait for it
+      unsigned now = 0;
+      if (hipSetDevice(c->dev) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+          hipMemcpy(&now, c->dDescOrdered, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        mx::set_error("modsx_describe_counters: reading the device counter failed"); return MODSX_ERR_DEVICE;
+      }
+      c->descOrderedTotal += (long)(unsigned)(now - c->descOrderedSeen);
+      c->descOrderedSeen = now;
+      sum[mx::DC_ORDERED_WG] += c->descOrderedTotal;
+    }
+  hipSetDevice(ctx->dev);
+  for (int q = 0; q < n && q < mx::DC_ALL; q++) out[q] = sum[q];
+  return mx::DC_ALL;
 }
 
 int modsx_blur_geometry(const int *rows, const int *cols, int n, int *geometry) {

@@ -356,6 +356,8 @@ static int upload_tables(modsx_ctx *c) {
   }
   MX_HIP(hipMalloc(&c->dSiftBins, sizeof bins));
   MX_HIP(hipMemcpy(c->dSiftBins, bins, sizeof bins, hipMemcpyHostToDevice));
+  MX_HIP(hipMalloc(&c->dDescOrdered, 4));
+  MX_HIP(hipMemset(c->dDescOrdered, 0, 4));
   MX_HIP(hipMalloc(&c->dSiftW, sizeof w));
   MX_HIP(hipMemcpy(c->dSiftW, w, sizeof w, hipMemcpyHostToDevice));
   return MODSX_OK;
@@ -429,7 +431,7 @@ void ctx_destroy(modsx_ctx *c) {
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();
   hipFree(c->dSmmMask); hipFree(c->dOriMask); hipFree(c->dOriIdx); hipFree(c->dSiftMask); hipFree(c->dSiftMaskIdx); hipFree(c->dAtan); hipFree(c->dOriBinTab); hipFree(c->dSiftOTab); hipFree(c->dSiftBins);
-  hipFree(c->dSiftW);
+  hipFree(c->dSiftW); hipFree(c->dDescOrdered);
   for (int i = 0; i < 2; i++) hipEventDestroy(c->descEv[i]);
   c->hDescB.release(); c->hRefs.release();
   hipStreamDestroy(c->stream);
@@ -763,7 +765,7 @@ static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot
   ProfScope psd(c, K_DESCRIBE, (double)nj * 128 * ds.n);
   launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
                   c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
-                  c->dSiftBins, c->dSiftW, photoNorm, ds.packed(), ds.n, maxBin, outs);
+                  c->dSiftBins, c->dSiftW, photoNorm, ds.packed(), ds.n, maxBin, outs, c->dDescOrdered);
   return MODSX_OK;
 }
 

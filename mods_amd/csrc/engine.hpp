@@ -280,7 +280,8 @@ void launch_patch_blur(hipStream_t s, const DescJob *jobs, const int *tilePrefix
 void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
                      const int *needTab, const float *coordTab,
                      const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
-                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs);
+                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
+                     unsigned *orderedCnt);
 void launch_warp_affine(hipStream_t s, const WarpJob &jb);
 void launch_blur_pass(hipStream_t s, const float *src, float *dst, int rows, int cols, const float *taps, int n, int pass, int border = 0);
 void launch_sub(hipStream_t s, const float *a, const float *b, float *o, size_t n);
@@ -462,7 +463,7 @@ void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgR
 // or added in f32 to what is there (accumulate = 1)
 void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                          const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab,
-                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate);
+                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate, unsigned *orderedCnt);
 // SIFTnorm(std::vector<float>&) over [n][128] f32 rows (kernels_dsp.hip); out may be rows; 4-byte alignment suffices
 void launch_sift_norm_f32(hipStream_t s, const float *rows, int n, double maxBin, float *out);
 
@@ -519,7 +520,10 @@ namespace mx {
 // the order of include/modsx.h
 enum DescCounter { DC_CALLS = 0, DC_CHUNKS, DC_MAX_CHUNKS, DC_CHUNKS_MID_IMAGE, DC_CHUNKS_LATER_IMAGE, DC_JOBS, DC_DIRECT_JOBS,
                    DC_FUSED_WINDOWS, DC_LDS_ROW_TILES, DC_LDS_COL_TILES, DC_SAMPLE_TILES, DC_GLOBAL_ROW_TILES, DC_GLOBAL_COL_TILES,
-                   DC_CLAMPED_WINDOWS, DC_N };
+                   DC_CLAMPED_WINDOWS, DC_N,
+                   // behind the planner's: k_describe workgroups that took the ordered gather, counted on the device
+                   // (modsx_ctx::dDescOrdered) and read by modsx_describe_counters alone
+                   DC_ORDERED_WG = DC_N, DC_ALL };
 // measurement hook (modsx_detect_counters): what the scale-space front end launched on a context since modsx_create, in the order
 // of include/modsx.h.  Host-side increments next to the launches; DT_LAST_* describe the context's last scan / candidate set.
 enum DetectCounter { DT_BLUR_TH16 = 0, DT_BLUR_TH32, DT_BLUR_R1, DT_BLUR_R8 = DT_BLUR_R1 + 7, DT_HESSIAN, DT_RESIZE, DT_SCAN_OCTAVE,
@@ -573,6 +577,9 @@ struct modsx_ctx {
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
   const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
   long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
+  unsigned *dDescOrdered = nullptr;   // device word: k_describe workgroups (SIFT and raw forms) that took the ordered gather
+  unsigned descOrderedSeen = 0;       // its last reading, and the sum of the readings' differences (the word may wrap)
+  long descOrderedTotal = 0;
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
   double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search: packing, k_f32_topk + k_f32_merge

@@ -22,7 +22,8 @@ static int tail_raw(modsx_ctx *c, void *self, const DescJob *jobs, int n, const 
                     int photoNorm) {
   const RawTail *rt = (const RawTail *)self;
   launch_describe_raw(c->stream, jobs, n, (const ImgRef *)c->imgRefs.p, grid, needTab, coordTab, c->dSiftMask, c->dSiftMaskIdx,
-                      c->nSiftMask, c->dSiftOTab, c->dSiftBins, c->dSiftW, photoNorm, rt->out, rt->accumulate);
+                      c->nSiftMask, c->dSiftOTab, c->dSiftBins, c->dSiftW, photoNorm, rt->out, rt->accumulate,
+                      c->dDescOrdered);
   return MODSX_OK;
 }
 

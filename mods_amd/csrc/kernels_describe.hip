@@ -681,7 +681,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
                                                   const float *mask, const unsigned short *maskIdx,
                                                   const float *oTab, const int *binTab, const double *wTab,
                                                   SiftConst sc, int photoNorm, int descTypes, int nOut, double maxBin,
-                                                  DescOut outs, float *fOut, int fFlag) {
+                                                  DescOut outs, float *fOut, int fFlag, unsigned *orderedCnt) {
   const int tidw = threadIdx.x;                                    // thread of the workgroup
   const int reg = __builtin_amdgcn_readfirstlane(tidw >> 7);       // region of the workgroup (a wavefront is inside one region)
   const int tid = tidw & 127;                                      // thread of the region
@@ -930,7 +930,9 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   }
   const unsigned mxb = max(smax_[reg][0], smax_[reg][1]);
   const int E = (int)(mxb >> 23) - 126;                          // max val in [2^(E - 1), 2^E)
-  const bool scalable = mxb >= 0x00800000u && mxb < 0x7f800000u && E >= -60 && E <= 100;   // (a region of zeros: ordered, it is rare)
+  // E <= 64 is all a finite val allows: |grad| = sqrtf(xg^2 + yg^2) of a finite f32 sum is below 2^64 and the mask is at most 1
+  // (a region of zeros, or one whose largest val is below 2^-61: ordered, they are rare)
+  const bool scalable = mxb >= 0x00800000u && mxb < 0x7f800000u && E >= -60 && E <= 64;
   const float S = __uint_as_float((unsigned)(127 + 47 - (scalable ? E : 47)) << 23);
   __syncthreads();
   unsigned tmin = 0xffffffffu;     // (bits of the smallest nonzero scaled term) - 1: +0 wraps to the maximum and never wins
@@ -938,7 +940,10 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     int r = tid / PS, c = tid - r * PS;
 #pragma unroll
     for (int k = 0; k < PER_T; k++) {
-      const float val = vv[k] * S;   // exact: a power of two, no overflow, and scaling up makes no denormal
+      // exact: a power of two, no overflow, and no positive val becomes 0 or a denormal -- S >= 2^-17 (E <= 64), a nonzero val is
+      // above 2^-77 (a nonzero |grad| is at least 2^-74.5, a nonzero mask above 2^-2), so val * S > 2^-94 and its smallest term,
+      // times weights of at least 1/8, 1/8 and 2^-21, is above 2^-121 (tests/sift_gather_model.py)
+      const float val = vv[k] * S;
       if (val > 0) {                 // not: outside the mask's disc (a quarter of the pixels), flat, past the patch, NaN
         const float o = ov[k];
         const int bo0 = (int)o;
@@ -1000,6 +1005,9 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
 #endif
   const int ordered = __syncthreads_or(inexact);   // the regions of a workgroup share the barriers of the ordered gather
   if (ordered) {
+    // measurement hook (modsx_describe_counters: ordered_workgroups): one relaxed add per workgroup that comes here, nothing
+    // on the order-free path
+    if (tidw == 0) __hip_atomic_fetch_add(orderedCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int k = 0; k < PER_T; k++) {
       const int p = tid + 128 * k;
@@ -1192,13 +1200,14 @@ void launch_patch_blur(hipStream_t s, const DescJob *jobs, const int *tilePrefix
 }
 void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
                      const int *needTab, const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
-                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs) {
+                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
+                     unsigned *orderedCnt) {
   if (n <= 0) return;
   SiftConst sc;
   sc.nmask = nmask;
   MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<DM_SIFT>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
                      wts, sc,
-                     photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0);
+                     photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0, orderedCnt);
 }
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -1210,18 +1219,18 @@ void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgR
   memset(&none, 0, sizeof none);
   hipLaunchKernelGGL(k_describe<DM_PATCH>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab,
                      (const float *)nullptr, maskIdx, (const float *)nullptr, (const int *)nullptr, (const double *)nullptr, sc, photoNorm, 0, 0, 0.0,
-                     none, patchOut, patchByOutIdx);
+                     none, patchOut, patchByOutIdx, (unsigned *)nullptr);
 }
 void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                          const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab,
-                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate) {
+                         const int *bins, const double *wts, int photoNorm, float *raw, int accumulate, unsigned *orderedCnt) {
   if (n <= 0) return;
   SiftConst sc;
   sc.nmask = nmask;
   DescOut none;
   memset(&none, 0, sizeof none);
   hipLaunchKernelGGL(k_describe<DM_RAW>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx,
-                     oTab, bins, wts, sc, photoNorm, 0, 0, 0.0, none, raw, accumulate);
+                     oTab, bins, wts, sc, photoNorm, 0, 0, 0.0, none, raw, accumulate, orderedCnt);
 }
 
 }  // namespace mx
