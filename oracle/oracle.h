@@ -10,9 +10,12 @@
  * path; the only anchor is build/examples/cat.txt (the
  * ground-truth homography of the example pair).  OpenCV 2.4.9 (GaussianBlur,
  * resize, invert, flann) is an un-vendored dependency whose arithmetic is
- * restated here from its published algorithm.  => "parity unpinned" for the
- * detection/description stages; RANSAC is pinned against the reference's own
- * degensac sources compiled in place (oracle/_ref, see oracle/Makefile).
+ * restated here from its published algorithm.  => "parity unpinned" for what
+ * rests on it, for the pyramid scan and for the orientation functor.  Pinned
+ * against the reference's own sources compiled in place (oracle/_ref, see
+ * oracle/Makefile): RANSAC (degensac), MSER, and -- tests/test_ref_pin_cpu.py --
+ * interpolate, photometricallyNormalize, atan2LUTff, the masks, the 2x2 / 3x3
+ * helpers, SIFTDescriptor and AffineShape::findAffineShape.
  */
 #ifndef MODSX_ORACLE_H
 #define MODSX_ORACLE_H
@@ -157,6 +160,21 @@ void orc_describe_regions(const float *img, int rows, int cols, const orc_region
 void orc_describe_patch(float *patch41, int photoNorm, int rootsift, double maxBinValue, float *desc);
 void orc_extract_patch(const float *img, int rows, int cols, const orc_region *reg,
                        double mrSize, int patchSize, float *patch);
+
+/* parts of the above on their own, for the comparison with the reference's own sources (oracle/_ref/libhessaff_ref.so,
+ * tests/test_ref_pin_cpu.py): helpers.cpp's masks, photometricallyNormalize (mask NULL: the circular mask DescribeRegions builds),
+ * invSqrt, getEigenvalues, solveLinear3x3, rectifyAffineTransformationUpIsUp, computeGradient,
+ * computeGradientMagnitudeAndOrientation, and SIFTDescriptor's histogram before any norm */
+void orc_gauss_mask(int size, float *out);
+void orc_circular_gauss_mask(int rows, int cols, float sigma, float *out);
+void orc_photo_norm(float *patch, int rows, int cols, const float *mask, float *sum, float *var);
+void orc_inv_sqrt(float *abc /*3, in place*/, float *l12);
+int  orc_get_eigenvalues(float a, float b, float c, float d, float *l12);
+void orc_solve_linear3x3(float *A9, float *b3);
+void orc_rectify(double *a /*4, in place*/);
+void orc_compute_gradient(const float *img, int rows, int cols, float *gx, float *gy);
+void orc_grad_mag_ori(const float *img, int rows, int cols, float *mag, float *ori);
+void orc_sift_histogram(const float *patch41, double *raw /*128*/);
 
 /* matching: linear kNN (squared L2, ties by ascending index) + FGINN walk */
 int orc_match_fginn(const float *desc1, int n1, const float *desc2, int n2, int dim,

@@ -161,7 +161,7 @@ struct Sift {
    * (half[i*4+j] = vec[i*8+j] + vec[i*8+j+4]) and normalise the 64-vector; desc[64..127] are written 0.
    * NOTE: SIFTnorm's clip loop runs to the MEMBER vec.size() = 128 on the 64-element half vector
    * (siftdesc.cpp:250-254), an out-of-bounds read/write in the reference; the loop is restated over the 64 entries. */
-  void compute(const Img &patch, int type, float *desc) {
+  void compute(const Img &patch, int type, float *desc, double *raw = nullptr) {
     const bool rootsift = (type & 1) != 0, half = type >= 2;
     const int w = patch.cols, h = patch.rows;
     Img grad(h, w), ori(h, w);
@@ -179,6 +179,7 @@ struct Sift {
       }
     for (auto &x : vec) x = 0;
     sample_patch(grad, ori);
+    if (raw) memcpy(raw, vec.data(), 128 * sizeof(double));
     std::vector<double> full;
     if (half) {
       full = vec;
@@ -364,6 +365,19 @@ void orc_describe_patch(float *patch41, int photoNorm, int rootsift, double maxB
   if (photoNorm) photometrically_normalize(p, sift.mask);
   sift.compute(p, rootsift, desc);
   memcpy(patch41, p.v.data(), p.v.size() * 4);
+}
+
+/* the histogram before any norm (SIFTDescriptor::vec with doNorm = false) and computeGradientMagnitudeAndOrientation on their own */
+void orc_sift_histogram(const float *patch41, double *raw) {
+  float desc[128];
+  Sift sift(0.2);
+  sift.compute(Img(41, 41, patch41), 0, desc, raw);
+}
+void orc_grad_mag_ori(const float *img, int rows, int cols, float *mag, float *ori) {
+  Img m(rows, cols, img), g(rows, cols), o(rows, cols);
+  grad_mag_ori(m, g, o);
+  memcpy(mag, g.v.data(), g.v.size() * sizeof(float));
+  memcpy(ori, o.v.data(), o.v.size() * sizeof(float));
 }
 
 void orc_describe_regions(const float *img_, int rows, int cols, const orc_region *regs, int n, double mrSize,

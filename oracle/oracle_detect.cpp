@@ -506,6 +506,18 @@ int orc_interpolate_check_borders(int orig_w, int orig_h, float ofsx, float ofsy
   return interpolate_check_borders(orig_w, orig_h, ofsx, ofsy, a11, a12, a21, a22, res_w, res_h) ? 1 : 0;
 }
 
+/* the 2x2 / 3x3 helpers and computeGradient on their own (tests/test_ref_pin_cpu.py compares them with the reference's) */
+void orc_inv_sqrt(float *abc, float *l12) { inv_sqrt(abc[0], abc[1], abc[2], l12[0], l12[1]); }
+int orc_get_eigenvalues(float a, float b, float c, float d, float *l12) { return eigenvalues(a, b, c, d, l12[0], l12[1]) ? 1 : 0; }
+void orc_solve_linear3x3(float *A9, float *b3) { solve3(A9, b3); }
+void orc_rectify(double *a) { rectify(a[0], a[1], a[2], a[3]); }
+void orc_compute_gradient(const float *img, int rows, int cols, float *gx, float *gy) {
+  Img m(rows, cols, img), x(rows, cols), y(rows, cols);
+  gradient(m, x, y);
+  memcpy(gx, x.v.data(), x.v.size() * sizeof(float));
+  memcpy(gy, y.v.data(), y.v.size() * sizeof(float));
+}
+
 /* DetectAffineRegions<>, synth-detection.hpp:93-126 */
 int orc_detect_affine_regions(const orc_keypoint *kps, int n, int img_id, int det_type, orc_region *out) {
   for (int i = 0; i < n; i++) {

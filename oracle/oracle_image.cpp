@@ -347,7 +347,7 @@ void circular_gauss_mask(Img &mask, float sigma) {
 }
 
 /* photometricallyNormalize, detectors/helpers.cpp:666-715 */
-void photometrically_normalize(Img &image, const Img &mask) {
+void photometrically_normalize(Img &image, const Img &mask, float *sum_out, float *var_out) {
   const size_t n = image.v.size();
   float sum = 0, gsum = 0;
   for (size_t i = 0; i < n; i++)
@@ -357,6 +357,8 @@ void photometrically_normalize(Img &image, const Img &mask) {
   for (size_t i = 0; i < n; i++)
     if (mask.v[i] > 0) var += (sum - image.v[i]) * (sum - image.v[i]);
   var = sqrtf(var / gsum);
+  if (sum_out) *sum_out = sum;
+  if (var_out) *var_out = var;
   if (var < 0.0001) return;
   float fac = 50.0f / var;
   for (size_t i = 0; i < n; i++) {
@@ -410,5 +412,22 @@ int orc_interpolate(const float *im, int rows, int cols, float ofsx, float ofsy,
   return t ? 1 : 0;
 }
 float orc_atan2lut(float y, float x) { return atan2lut(y, x); }
+void orc_gauss_mask(int size, float *out) {
+  Img m(size, size);
+  gauss_mask(m);
+  memcpy(out, m.v.data(), m.v.size() * sizeof(float));
+}
+void orc_circular_gauss_mask(int rows, int cols, float sigma, float *out) {
+  Img m(rows, cols);
+  circular_gauss_mask(m, sigma);
+  memcpy(out, m.v.data(), m.v.size() * sizeof(float));
+}
+void orc_photo_norm(float *patch, int rows, int cols, const float *mask, float *sum, float *var) {
+  Img p(rows, cols, patch), m(rows, cols);
+  if (mask) m = Img(rows, cols, mask);
+  else circular_gauss_mask(m, 0);
+  photometrically_normalize(p, m, sum, var);
+  memcpy(patch, p.v.data(), p.v.size() * sizeof(float));
+}
 const double *orc_atan_lut(void) { return atan_lut(); }
 }

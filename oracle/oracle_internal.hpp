@@ -41,7 +41,7 @@ bool interpolate_check_borders(int orig_w, int orig_h, float ofsx, float ofsy, f
 bool interpolate(const Img &im, float ofsx, float ofsy, float a11, float a12, float a21, float a22, Img &res);
 void gauss_mask(Img &mask);
 void circular_gauss_mask(Img &mask, float sigma);
-void photometrically_normalize(Img &image, const Img &mask);
+void photometrically_normalize(Img &image, const Img &mask, float *sum_out = nullptr, float *var_out = nullptr);
 
 }  // namespace orc
 #endif

@@ -39,6 +39,7 @@ class View(C.Structure):
 
 
 _REF_MSER_SO = os.path.join(_HERE, "_ref", "libmser_ref.so")
+_REF_HESSAFF_SO = os.path.join(_HERE, "_ref", "libhessaff_ref.so")
 
 
 def build(force=False):
@@ -47,8 +48,10 @@ def build(force=False):
     stale = (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    # the reference's own degensac and MSER, compiled in place where its sources are (`make ref` builds what is missing of the two)
-    want = [(os.path.join(_HERE, "_ref", "libdegensac_ref.so"), "/root/reference/degensac"), (_REF_MSER_SO, "/root/reference/detectors/mser")]
+    # the reference's own degensac, MSER and helpers / SIFT / affine shape, compiled in place where its sources are (`make ref`
+    # builds what is missing of the three)
+    want = [(os.path.join(_HERE, "_ref", "libdegensac_ref.so"), "/root/reference/degensac"), (_REF_MSER_SO, "/root/reference/detectors/mser"),
+            (_REF_HESSAFF_SO, "/root/reference/detectors/affinedetectors")]
     if any(os.path.isdir(src) and (force or not os.path.exists(lib_)) for lib_, src in want):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     return so
@@ -232,6 +235,13 @@ def interpolate_check_borders(t):
     return np.array([f(int(r[0]), int(r[1]), r[2], r[3], r[4], r[5], r[6], r[7], int(r[8]), int(r[8])) for r in t.tolist()], bool)
 
 
+def interpolate_check_borders_wh(t):
+    """interpolateCheckBorders for an [n, 10] array of (cols, rows, ofsx, ofsy, a11, a12, a21, a22, res_w, res_h) -> bool [n]"""
+    f = lib().orc_interpolate_check_borders
+    f.argtypes = [C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_int, C.c_int]
+    return np.array([f(int(r[0]), int(r[1]), r[2], r[3], r[4], r[5], r[6], r[7], int(r[8]), int(r[9])) for r in np.asarray(t).tolist()], bool)
+
+
 def detect_affine_regions(kps, img_id=0, det_type=0):
     kps = np.ascontiguousarray(kps, KEYPOINT)
     out = np.zeros(len(kps), REGION)
@@ -402,6 +412,267 @@ def detect_msers_ref(img, min_size=30, max_area=0.05, min_margin=8.0, relative=0
     for i, f in enumerate(MSER_FIELDS):
         out[f] = out9[:n, i]
     return out
+
+
+# ---- the oracle's parts on their own (what tests/test_ref_pin_cpu.py compares with the reference's functions) ----
+def gauss_mask(size):
+    out = np.zeros((size, size), np.float32)
+    lib().orc_gauss_mask(int(size), _p(out))
+    return out
+
+
+def circular_gauss_mask(rows, cols, sigma=0.0):
+    out = np.zeros((rows, cols), np.float32)
+    lib().orc_circular_gauss_mask(int(rows), int(cols), C.c_float(sigma), _p(out))
+    return out
+
+
+def photo_norm(patch, mask=None):
+    """photometricallyNormalize -> (patch, sum, var); mask None: the circular mask DescribeRegions builds"""
+    p = _f32(patch).copy()
+    m = None if mask is None else _f32(mask)
+    s, v = C.c_float(), C.c_float()
+    lib().orc_photo_norm(_p(p), p.shape[0], p.shape[1], None if m is None else _p(m), C.byref(s), C.byref(v))
+    return p, np.float32(s.value), np.float32(v.value)
+
+
+def inv_sqrt(a, b, c):
+    """invSqrt -> (a, b, c, l1, l2) f32"""
+    abc, l = np.array([a, b, c], np.float32), np.zeros(2, np.float32)
+    lib().orc_inv_sqrt(_p(abc), _p(l))
+    return np.concatenate([abc, l])
+
+
+def get_eigenvalues(a, b, c, d):
+    """getEigenvalues -> (ok, l1, l2); l1, l2 are 0 when it returns false"""
+    l = np.zeros(2, np.float32)
+    ok = lib().orc_get_eigenvalues(C.c_float(a), C.c_float(b), C.c_float(c), C.c_float(d), _p(l))
+    return bool(ok), l
+
+
+def solve_linear3x3(A, b):
+    """solveLinear3x3 -> (A, b) as it leaves them"""
+    A, b = _f32(A).reshape(9).copy(), _f32(b).reshape(3).copy()
+    lib().orc_solve_linear3x3(_p(A), _p(b))
+    return A, b
+
+
+def rectify(a4):
+    a = np.array(a4, np.float64).reshape(4).copy()
+    lib().orc_rectify(_p(a))
+    return a
+
+
+def compute_gradient(img):
+    img = _f32(img)
+    gx, gy = np.zeros_like(img), np.zeros_like(img)
+    lib().orc_compute_gradient(_p(img), img.shape[0], img.shape[1], _p(gx), _p(gy))
+    return gx, gy
+
+
+def grad_mag_ori(img):
+    """computeGradientMagnitudeAndOrientation: interior pixels, the frame is 0"""
+    img = _f32(img)
+    mag, ori = np.zeros_like(img), np.zeros_like(img)
+    lib().orc_grad_mag_ori(_p(img), img.shape[0], img.shape[1], _p(mag), _p(ori))
+    return mag, ori
+
+
+def sift_histogram(patch):
+    """SIFTDescriptor's 128-bin histogram before any norm, f64"""
+    p = _f32(patch)
+    raw = np.zeros(128, np.float64)
+    lib().orc_sift_histogram(_p(p), _p(raw))
+    return raw
+
+
+# ---- the reference's own helpers.cpp / siftdesc.cpp / affine.cpp (oracle/_ref/libhessaff_ref.so, oracle/ref_hessaff_shim.cpp) ----
+# Every ref_* function below returns what the reference's function of that name computes; RefRefused is raised where the shim
+# refuses the call because the reference would read or write out of bounds, or reach a cv:: operation (see the shim's comment).
+class RefRefused(ValueError):
+    pass
+
+
+_ref_hessaff_lib = None
+_ref_hessaff_lock = threading.Lock()
+
+
+def ref_hessaff_available():
+    build()
+    return os.path.exists(_REF_HESSAFF_SO)
+
+
+def _rh():
+    global _ref_hessaff_lib
+    with _ref_hessaff_lock:
+        if _ref_hessaff_lib is None:
+            if not ref_hessaff_available():
+                raise RuntimeError("oracle/_ref/libhessaff_ref.so is not built: run `make -C oracle ref` where the reference is")
+            L = C.CDLL(_REF_HESSAFF_SO)
+            f, i, v = C.c_float, C.c_int, C.c_void_p
+            L.refhess_atan2lutff.restype = f
+            L.refhess_atan2lutff.argtypes = [f, f, v]
+            L.refhess_sift.argtypes = [v, i, C.c_double, i, v, v]
+            L.refhess_photo_norm.argtypes = [v, i, i, v, v, v]
+            L.refhess_circular_gauss_mask.argtypes = [i, i, f, v]
+            L.refhess_gauss_mask.argtypes = [i, v]
+            L.refhess_interpolate.argtypes = [v, i, i, f, f, f, f, f, f, v, i, i]
+            L.refhess_check_borders.argtypes = [i, i, f, f, f, f, f, f, i, i]
+            L.refhess_check_borders_mat.argtypes = [i, i, f, f, f, f, f, f, i, i]
+            L.refhess_inv_sqrt.argtypes = [v, v]
+            L.refhess_get_eigenvalues.argtypes = [f, f, f, f, v]
+            L.refhess_solve_linear3x3.argtypes = [v, v]
+            for n in ("refhess_rectify_f", "refhess_rectify_d", "refhess_rectify_dp"):
+                getattr(L, n).argtypes = [v]
+            L.refhess_compute_gradient.argtypes = [v, i, i, v, v]
+            L.refhess_grad_mag_ori.argtypes = [v, i, i, v, v]
+            L.refhess_find_affine_shape_batch.argtypes = [v, v, v, i, v, v, i, i, f, i, f, i, i, v, v, v]
+            _ref_hessaff_lib = L
+    return _ref_hessaff_lib
+
+
+def _refused(rc, what):
+    if rc < 0:
+        raise RefRefused("%s: the shim refuses this call (%d)" % (what, rc))
+    return rc
+
+
+def ref_atan2lutff(y, x):
+    """atan2LUTff(y, x) as f32; RefRefused where the reference would index outside ATAN_LUT"""
+    r = C.c_int()
+    out = _rh().refhess_atan2lutff(float(np.float32(y)), float(np.float32(x)), C.byref(r))
+    if r.value:
+        raise RefRefused("atan2LUTff(%r, %r) indexes outside the table" % (y, x))
+    return np.float32(out)
+
+
+def ref_sift(patch, desc_type=1, max_bin=0.2, route=None):
+    """SIFTDescriptor on a 41 x 41 patch -> (desc f32 [128], raw f64 [128]).  desc_type 0 SIFT, 1 RootSIFT, 2 HalfSIFT,
+    3 HalfRootSIFT (64 values, then zeros); raw = the public `vec` with doNorm = false.  route 0: operator() as DescribeRegions
+    calls it; route 1: the Half types through the public SIFTnorm / RootSIFTnorm (the shim's comment says why HalfSIFT must);
+    default: 1 for HalfSIFT, 0 otherwise."""
+    p = _f32(patch)
+    assert p.shape == (41, 41)
+    route = (1 if desc_type == 2 else 0) if route is None else route
+    desc, raw = np.zeros(128, np.float32), np.zeros(128, np.float64)
+    _refused(_rh().refhess_sift(_p(p), int(desc_type), float(max_bin), int(route), _p(desc), _p(raw)), "SIFTDescriptor")
+    return desc, raw
+
+
+def ref_photo_norm(patch, mask=None):
+    """photometricallyNormalize -> (patch, sum, var); mask None: computeCircularGaussMask(mask) of the patch's size"""
+    p = _f32(patch).copy()
+    m = None if mask is None else _f32(mask)
+    s, v = C.c_float(), C.c_float()
+    _refused(_rh().refhess_photo_norm(_p(p), p.shape[0], p.shape[1], None if m is None else _p(m), C.byref(s), C.byref(v)),
+             "photometricallyNormalize")
+    return p, np.float32(s.value), np.float32(v.value)
+
+
+def ref_describe_patch(patch, photo_norm=1, desc_type=1, max_bin=0.2, route=None):
+    """what DescribeRegions does with an extracted patch (synth-detection.hpp:225-229): photometricallyNormalize under the circular
+    mask when photoNorm, then the descriptor -> (desc, raw, patch as the descriptor saw it)"""
+    p = ref_photo_norm(patch)[0] if photo_norm else _f32(patch).copy()
+    desc, raw = ref_sift(p, desc_type, max_bin, route)
+    return desc, raw, p
+
+
+def ref_circular_gauss_mask(rows, cols, sigma=0.0):
+    out = np.zeros((rows, cols), np.float32)
+    _refused(_rh().refhess_circular_gauss_mask(int(rows), int(cols), float(sigma), _p(out)), "computeCircularGaussMask")
+    return out
+
+
+def ref_gauss_mask(size):
+    out = np.zeros((size, size), np.float32)
+    _refused(_rh().refhess_gauss_mask(int(size), _p(out)), "computeGaussMask")
+    return out
+
+
+def ref_interpolate(img, ofsx, ofsy, a11, a12, a21, a22, rrows, rcols):
+    img = _f32(img)
+    out = np.zeros((rrows, rcols), np.float32)
+    t = _refused(_rh().refhess_interpolate(_p(img), img.shape[0], img.shape[1], ofsx, ofsy, a11, a12, a21, a22, _p(out), rrows, rcols),
+                 "interpolate")
+    return out, bool(t)
+
+
+def ref_interpolate_check_borders(t, mat=False):
+    """interpolateCheckBorders for an [n, 10] array of (cols, rows, ofsx, ofsy, a11, a12, a21, a22, res_w, res_h) -> bool [n];
+    mat = True: the cv::Mat overload (image and result given as Mats of those sizes), else the int overload"""
+    L = _rh()
+    out = np.zeros(len(t), bool)
+    for k, r in enumerate(np.asarray(t, np.float64).tolist()):
+        if mat:
+            out[k] = L.refhess_check_borders_mat(int(r[1]), int(r[0]), r[2], r[3], r[4], r[5], r[6], r[7], int(r[9]), int(r[8]))
+        else:
+            out[k] = L.refhess_check_borders(int(r[0]), int(r[1]), r[2], r[3], r[4], r[5], r[6], r[7], int(r[8]), int(r[9]))
+    return out
+
+
+def ref_inv_sqrt(a, b, c):
+    abc, l = np.array([a, b, c], np.float32), np.zeros(2, np.float32)
+    _rh().refhess_inv_sqrt(_p(abc), _p(l))
+    return np.concatenate([abc, l])
+
+
+def ref_get_eigenvalues(a, b, c, d):
+    l = np.zeros(2, np.float32)
+    ok = _rh().refhess_get_eigenvalues(float(np.float32(a)), float(np.float32(b)), float(np.float32(c)), float(np.float32(d)), _p(l))
+    return bool(ok), l
+
+
+def ref_solve_linear3x3(A, b):
+    A, b = _f32(A).reshape(9).copy(), _f32(b).reshape(3).copy()
+    _rh().refhess_solve_linear3x3(_p(A), _p(b))
+    return A, b
+
+
+def ref_rectify(a4, overload="double"):
+    """rectifyAffineTransformationUpIsUp: overload "float" (float &), "double" (double &) or "pointer" (double *)"""
+    if overload == "float":
+        a = np.array(a4, np.float32).reshape(4).copy()
+        _rh().refhess_rectify_f(_p(a))
+    else:
+        a = np.array(a4, np.float64).reshape(4).copy()
+        (_rh().refhess_rectify_d if overload == "double" else _rh().refhess_rectify_dp)(_p(a))
+    return a
+
+
+def ref_compute_gradient(img):
+    img = _f32(img)
+    gx, gy = np.zeros_like(img), np.zeros_like(img)
+    _refused(_rh().refhess_compute_gradient(_p(img), img.shape[0], img.shape[1], _p(gx), _p(gy)), "computeGradient")
+    return gx, gy
+
+
+def ref_grad_mag_ori(img):
+    img = _f32(img)
+    mag, ori = np.zeros_like(img), np.zeros_like(img)
+    _refused(_rh().refhess_grad_mag_ori(_p(img), img.shape[0], img.shape[1], _p(mag), _p(ori)), "computeGradientMagnitudeAndOrientation")
+    return mag, ori
+
+
+def ref_find_affine_shape_batch(planes, plane_of, xyspd, params, method=0):
+    """AffineShape::findAffineShape through an AffineShapeCallback, over a job list laid out as for find_affine_shape_batch, with
+    maxIterations, convergenceThreshold, smmWindowSize, affInitialSigma and doBaumberg of `params` (a HessAffParams).
+    -> dict(hit [n] i32, u [n, 4] f32, iters [n] i32); u and iters are written for hits only (zeros / -1 elsewhere): the reference
+    reports nothing about a keypoint that did not converge.  method != 0 (AFF_BMBRG_HESSIAN) is refused."""
+    planes = [_f32(a) for a in planes]
+    plane_of = np.ascontiguousarray(plane_of, np.int32)
+    xyspd = np.ascontiguousarray(xyspd, np.float32).reshape(-1, 4)
+    n = len(plane_of)
+    assert len(xyspd) == n
+    ptrs = (C.c_void_p * max(1, len(planes)))(*[a.ctypes.data for a in planes])
+    rows = np.array([a.shape[0] for a in planes], np.int32)
+    cols = np.array([a.shape[1] for a in planes], np.int32)
+    hit, u, iters = np.zeros(n, np.int32), np.zeros((n, 4), np.float32), np.full(n, -1, np.int32)
+    rc = _rh().refhess_find_affine_shape_batch(ptrs, _p(rows), _p(cols), len(planes), _p(plane_of), _p(xyspd), n, int(params.maxIterations),
+                                               float(params.convergenceThreshold), int(params.smmWindowSize), float(params.affInitialSigma),
+                                               int(params.doBaumberg), int(method), _p(hit), _p(u), _p(iters))
+    _refused(rc, "findAffineShape")
+    assert rc == n, rc
+    return dict(hit=hit, u=u, iters=iters)
 
 
 MSER_FIELDS = ("x", "y", "a11", "a12", "a21", "a22", "s", "response", "sub_type")    # what DetectMSERs sets, in the shim's order

@@ -194,3 +194,11 @@ def need_mser_ref(oracle):
     /root/reference in place and carried to the GPU box with the snapshot).  The same rule as need_ref: where the comparison is
     expected, a missing build is an ERROR, not a skip -- a green run must mean that the comparisons were made."""
     assert oracle.ref_mser_available(), "oracle/_ref/libmser_ref.so is not built: run `make -C oracle ref` where /root/reference exists"
+
+
+def need_hessaff_ref(oracle):
+    """The comparisons with the reference's own helpers.cpp, siftdesc.cpp and affine.cpp are made against
+    oracle/_ref/libhessaff_ref.so (built from the reference's sources in place and carried to the GPU box with the snapshot).  The same rule
+    as need_ref and need_mser_ref: where the comparison is expected, a missing build is an ERROR, not a skip -- a green run must mean
+    that the comparisons were made."""
+    assert oracle.ref_hessaff_available(), "oracle/_ref/libhessaff_ref.so is not built: run `make -C oracle ref` where the reference's sources are"
