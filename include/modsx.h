@@ -706,6 +706,57 @@ int modsx_debug_fginn32_geometry(int n1, int n2, int dim, int splits, int *geome
  * finite d passes.  d0 finite and >= 0. */
 int modsx_debug_fginn32_dpass(const float *d0, const double *ratio, int n, float *dpass);
 
+/* FGINN matching under vector_dist = L1.  MatchFlannFGINN builds its index with GenFLANNIndex(keys2, par.vector_matcher,
+ * par.vector_dist, par.kd_trees) (matching/matching.cpp:388); vector_dist is a key of the [Matching] section of every config file
+ * and io_mods.cpp:528-548 reads L2, L1, Hamming, Mink, Hellinger, Chi_square, KL and Max.  For CV_32F rows a default OpenCV 2.4
+ * cv::flann::Index takes two of them, FLANN_DIST_L2 and FLANN_DIST_L1; these are the values of `dist` below, every other value is
+ * MODSX_ERR_ARG.  Every entry above is vector_dist = L2. */
+enum { MODSX_DIST_L2 = 0, MODSX_DIST_L1 = 1 };
+/* The f32 entries above with the distance as an argument.  dist = MODSX_DIST_L2 runs the very kernels of the entries above and
+ * returns the same bits.  dist = MODSX_DIST_L1: FLANN's L1<float> functor as the linear index calls it (no early exit), restated
+ * like L2 and, like every FLANN-dependent contract here, not pinned against a real OpenCV build:
+ *   distance  for each (query, train) one f32 chain over k = 0, 4, 8, ...: e_i = a[k+i] - b[k+i],
+ *             r = r + (((|e0| + |e1|) + |e2|) + |e3|), every operation rounded to f32, subnormals kept.
+ *   rows, limits, order, result, edges   those of modsx_match_fginn_f32: dim % 4 == 0, finite with |x| <= 1e17, nn in [2, 256],
+ *             ratio * ratio >= 1 (the "all points" branch) refused before any launch.
+ *   walk      UNCHANGED, including what looks like a quirk: the reference compares (double)(d_0 / d_j) with ratio^2 and records
+ *             ratio = sqrt(d_0 / d_j) although L1 distances are not squares (matching.cpp:437-451).  At match_ratio 0.8 the
+ *             first-to-second DISTANCE ratio that passes is therefore 0.64, not 0.8. */
+int modsx_match_fginn_f32_dist(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                               double ratio, double contradDist, int nn, int dist, modsx_tentative **out);
+int modsx_match_fginn_f32_dist_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim,
+                                      const double *pos2, double ratio, double contradDist, int nn, int dist, modsx_tentative **out);
+/* modsx_match_regions_f32 with the matcher above; the pair tail and modsx_pair_params are unchanged */
+int modsx_match_regions_f32_dist(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                                 const float *desc2, int n2, int dim, const modsx_pair_params *par, int dist, modsx_pair_result *res);
+/* modsx_debug_match_fginn_f32 with the distance: the same optional outputs */
+int modsx_debug_match_fginn_f32_dist(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim,
+                                     const double *pos2, double ratio, double contradDist, int nn, int dist, int splits, int stage_mask,
+                                     unsigned long long *top4, unsigned char *stage, int *geometry, int *counters,
+                                     modsx_tentative **out);
+/* L1 for the SIFT family: rows of 128 values that hold the integers 0..255, the domain of modsx_match_fginn, searched as bytes.
+ * On that domain every |e| is an integer <= 255, every group sum <= 1020 and every running sum <= 32640, all exact in f32: the
+ * integer sum of absolute differences, converted to f32, IS the chain's result, and the records are bit for bit those of
+ * modsx_match_fginn_f32_dist(..., 128, ..., MODSX_DIST_L1) on the same rows.
+ * desc*: [n][128] f32 holding integers 0..255; anything else is refused as modsx_match_fginn refuses it, and so are nn outside
+ * [2, 256], more than 2 000 000 rows on a side, a NaN ratio and, unlike there, ratio * ratio >= 1. */
+int modsx_match_fginn_l1(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2, double ratio,
+                         double contradDist, int nn, modsx_tentative **out);
+/* the same on dense [n][128] u8 rows that already live in HBM (any byte alignment), as modsx_match_fginn_device takes them */
+int modsx_match_fginn_l1_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2,
+                                const double *pos2, double ratio, double contradDist, int nn, modsx_tentative **out);
+/* modsx_match_regions_f32 with the matcher above.  desc*: [n][128] f32 holding the integers 0..255 (what
+ * modsx_describe_regions returns), from the host. */
+int modsx_match_regions_l1(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                           const float *desc2, int n2, const modsx_pair_params *par, modsx_pair_result *res);
+/* debug: modsx_match_fginn_l1 with forced `splits` and `stage_mask` and the optional outputs of modsx_debug_match_fginn_f32;
+ * geometry[3] is the row width in 32-bit words (32), geometry[2] the workgroups of k_l1_topk */
+int modsx_debug_match_fginn_l1(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2,
+                               double ratio, double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4,
+                               unsigned char *stage, int *geometry, int *counters, modsx_tentative **out);
+/* host only, no context: the geometry[6] modsx_debug_match_fginn_l1 would report for these sizes (one function of its arguments) */
+int modsx_debug_fginn_l1_geometry(int n1, int n2, int splits, int *geometry);
+
 /* One step of mods.cpp:229-415 with a ladder of synthesised views per image (same views for both images,
  * as in iters_mods_cviu.ini). */
 int modsx_match_pair_views(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2,

@@ -146,6 +146,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_detect_scalespace_batch", "modsx_debug_mser_front",
            "modsx_match_fginn_f32", "modsx_match_fginn_f32_device", "modsx_match_regions_f32", "modsx_debug_match_fginn_f32",
            "modsx_debug_fginn32_geometry", "modsx_debug_fginn32_dpass",
+           "modsx_match_fginn_f32_dist", "modsx_match_fginn_f32_dist_device", "modsx_match_regions_f32_dist",
+           "modsx_debug_match_fginn_f32_dist", "modsx_match_fginn_l1", "modsx_match_fginn_l1_device", "modsx_match_regions_l1",
+           "modsx_debug_match_fginn_l1", "modsx_debug_fginn_l1_geometry",
            "modsx_extract_patches", "modsx_extract_patches_device", "modsx_liop_patches", "modsx_liop_patches_device",
            "modsx_describe_regions_liop", "modsx_describe_regions_liop_device", "modsx_liop_tables", "modsx_debug_liop",
            "modsx_liop_counters",
@@ -199,6 +202,7 @@ DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, 
 # include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
 DESC_CAFFE, DESC_DAISY, DESC_LIOP, DESC_MROGH, DESC_SURF = 8, 9, 10, 11, 12
 REP_F32_FIRST_ROWS = 4096
+DIST_L2, DIST_L1 = 0, 1               # include/modsx.h: MODSX_DIST_L2, MODSX_DIST_L1 (vector_dist of the [Matching] section)
 # include/modsx.h: the binary descriptor classes of a stored representation, their own detector, the first capacity in rows
 DET_ORB = 4
 DESC_BRISK, DESC_FREAK, DESC_ORB = 16, 17, 18
@@ -345,6 +349,16 @@ def lib():
         L.modsx_debug_match_fginn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                                   C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
+        f32a, rega, dbga = (list(f.argtypes) for f in (L.modsx_match_fginn_f32, L.modsx_match_regions_f32, L.modsx_debug_match_fginn_f32))
+        L.modsx_match_fginn_f32_dist.argtypes = f32a[:10] + [C.c_int] + f32a[10:]            # dist behind nn
+        L.modsx_match_fginn_f32_dist_device.argtypes = L.modsx_match_fginn_f32_dist.argtypes
+        L.modsx_match_regions_f32_dist.argtypes = rega[:9] + [C.c_int] + rega[9:]            # dist behind par
+        L.modsx_debug_match_fginn_f32_dist.argtypes = dbga[:10] + [C.c_int] + dbga[10:]
+        L.modsx_match_fginn_l1.argtypes = f32a[:5] + f32a[6:]                                # no dim
+        L.modsx_match_fginn_l1_device.argtypes = L.modsx_match_fginn_l1.argtypes
+        L.modsx_match_regions_l1.argtypes = rega[:7] + rega[8:]
+        L.modsx_debug_match_fginn_l1.argtypes = dbga[:5] + dbga[6:]
+        L.modsx_debug_fginn_l1_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_fginn32_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.modsx_debug_fginn32_dpass.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.modsx_debug_fginn32_last_ms.argtypes = [C.c_void_p, C.c_void_p]
@@ -1572,58 +1586,117 @@ class Context(object):
                "match_regions_hamming")
         return _unpack_pair_result(res)
 
-    def match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
-        """MatchFlannFGINN on float rows of any width: [n][dim] float32, dim % 4 == 0, dim <= 256; pos2 [n2][2]."""
+    def match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50, dist=DIST_L2):
+        """MatchFlannFGINN on float rows of any width: [n][dim] float32, dim % 4 == 0, dim <= 256; pos2 [n2][2].  dist: DIST_L2 (the
+        default: the entry without a distance argument) or DIST_L1 (vector_dist = L1)."""
         d1, d2, dim = _f32_rows(d1, d2)
         pos2 = np.ascontiguousarray(pos2, np.float64)
         out = C.c_void_p()
-        n = _check(lib().modsx_match_fginn_f32(self._c(), _p(d1), len(d1), _p(d2), len(d2), dim, _p(pos2), C.c_double(ratio),
-                                               C.c_double(contrad_dist), int(nn), C.byref(out)), "match_fginn_f32")
+        head = (self._c(), _p(d1), len(d1), _p(d2), len(d2), dim, _p(pos2), C.c_double(ratio), C.c_double(contrad_dist), int(nn))
+        if dist == DIST_L2:
+            n = _check(lib().modsx_match_fginn_f32(*head, C.byref(out)), "match_fginn_f32")
+        else:
+            n = _check(lib().modsx_match_fginn_f32_dist(*head, int(dist), C.byref(out)), "match_fginn_f32_dist")
         return _take(out, n, TENT)
 
-    def match_fginn_f32_device(self, p1, n1, p2, n2, dim, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
+    def match_fginn_f32_device(self, p1, n1, p2, n2, dim, pos2, ratio=0.8, contrad_dist=30.0, nn=50, dist=DIST_L2):
         """The same on dense [n][dim] float32 rows in HBM (device pointers, 4-byte aligned)."""
         pos2 = np.ascontiguousarray(pos2, np.float64)
         out = C.c_void_p()
-        n = _check(lib().modsx_match_fginn_f32_device(self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), int(dim), _p(pos2),
-                                                      C.c_double(ratio), C.c_double(contrad_dist), int(nn), C.byref(out)),
-                   "match_fginn_f32_device")
+        head = (self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), int(dim), _p(pos2), C.c_double(ratio),
+                C.c_double(contrad_dist), int(nn))
+        if dist == DIST_L2:
+            n = _check(lib().modsx_match_fginn_f32_device(*head, C.byref(out)), "match_fginn_f32_device")
+        else:
+            n = _check(lib().modsx_match_fginn_f32_dist_device(*head, int(dist), C.byref(out)), "match_fginn_f32_dist_device")
         return _take(out, n, TENT)
 
-    def debug_match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50, splits=0, stage_mask=3):
+    def debug_match_fginn_f32(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50, splits=0, stage_mask=3, dist=DIST_L2):
         """dict(tentatives, top4 [n1][4] uint64 keys, stage [n1] (0 host walk, 1 resolve sweep, 2 its count: the nn ran out), geometry,
         resolve, by_count, records, flag) of the matcher with the train axis forced into `splits` parts (0 = production) and the
         stages of `stage_mask` (1 = top-4 search + host walk, 3 = + resolve sweep)."""
         d1, d2, dim = _f32_rows(d1, d2)
+        head = (self._c(), _p(d1), len(d1), _p(d2), len(d2), dim)
+        if dist == DIST_L2:
+            return self._debug_fginn(lib().modsx_debug_match_fginn_f32, "debug_match_fginn_f32", head, len(d1), pos2, ratio,
+                                     contrad_dist, (int(nn),), splits, stage_mask)
+        return self._debug_fginn(lib().modsx_debug_match_fginn_f32_dist, "debug_match_fginn_f32_dist", head, len(d1), pos2, ratio,
+                                 contrad_dist, (int(nn), int(dist)), splits, stage_mask)
+
+    def _debug_fginn(self, fn, name, head, n1, pos2, ratio, contrad_dist, nn_dist, splits, stage_mask):
         pos2 = np.ascontiguousarray(pos2, np.float64)
-        top4 = np.zeros((max(len(d1), 1), 4), np.uint64)
-        stage = np.zeros(max(len(d1), 1), np.uint8)
+        top4 = np.zeros((max(n1, 1), 4), np.uint64)
+        stage = np.zeros(max(n1, 1), np.uint8)
         geo, cnt = np.zeros(6, np.int32), np.zeros(4, np.int32)
         out = C.c_void_p()
-        n = _check(lib().modsx_debug_match_fginn_f32(self._c(), _p(d1), len(d1), _p(d2), len(d2), dim, _p(pos2), C.c_double(ratio),
-                                                     C.c_double(contrad_dist), int(nn), int(splits), int(stage_mask), _p(top4),
-                                                     _p(stage), _p(geo), _p(cnt), C.byref(out)), "debug_match_fginn_f32")
-        return dict(tentatives=_take(out, n, TENT), top4=top4[:len(d1)], stage=stage[:len(d1)],
+        n = _check(fn(*head, _p(pos2), C.c_double(ratio), C.c_double(contrad_dist), *nn_dist, int(splits), int(stage_mask), _p(top4),
+                      _p(stage), _p(geo), _p(cnt), C.byref(out)), name)
+        return dict(tentatives=_take(out, n, TENT), top4=top4[:n1], stage=stage[:n1],
                     geometry=dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo))), resolve=int(cnt[0]), by_count=int(cnt[1]),
                     records=int(cnt[2]), flag=int(cnt[3]))
 
+    def match_fginn_l1(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
+        """MatchFlannFGINN under vector_dist = L1 on [n][128] rows holding the integers 0..255 (the domain of match_fginn), searched
+        as bytes: the records of match_fginn_f32(dist=DIST_L1) on the same rows, bit for bit."""
+        d1, d2, dim = _f32_rows(d1, d2)
+        if dim != 128:
+            raise ValueError("match_fginn_l1: [n][128] rows are expected")
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_fginn_l1(self._c(), _p(d1), len(d1), _p(d2), len(d2), _p(pos2), C.c_double(ratio),
+                                              C.c_double(contrad_dist), int(nn), C.byref(out)), "match_fginn_l1")
+        return _take(out, n, TENT)
+
+    def match_fginn_l1_device(self, p1, n1, p2, n2, pos2, ratio=0.8, contrad_dist=30.0, nn=50):
+        """The same on dense [n][128] uint8 rows in HBM (device pointers, any alignment)."""
+        pos2 = np.ascontiguousarray(pos2, np.float64)
+        out = C.c_void_p()
+        n = _check(lib().modsx_match_fginn_l1_device(self._c(), C.c_void_p(p1), int(n1), C.c_void_p(p2), int(n2), _p(pos2),
+                                                     C.c_double(ratio), C.c_double(contrad_dist), int(nn), C.byref(out)),
+                   "match_fginn_l1_device")
+        return _take(out, n, TENT)
+
+    def debug_match_fginn_l1(self, d1, d2, pos2, ratio=0.8, contrad_dist=30.0, nn=50, splits=0, stage_mask=3):
+        """debug_match_fginn_f32 for match_fginn_l1; geometry["DK"] is the row width in 32-bit words."""
+        d1, d2, dim = _f32_rows(d1, d2)
+        if dim != 128:
+            raise ValueError("debug_match_fginn_l1: [n][128] rows are expected")
+        return self._debug_fginn(lib().modsx_debug_match_fginn_l1, "debug_match_fginn_l1", (self._c(), _p(d1), len(d1), _p(d2), len(d2)),
+                                 len(d1), pos2, ratio, contrad_dist, (int(nn),), splits, stage_mask)
+
     def fginn32_last_ms(self):
-        """(packing ms, search ms) of this context's last f32 FGINN search, HIP events; filled while profile() is on."""
+        """(packing ms, search ms) of this context's last f32 FGINN search or L1 search on byte rows, HIP events; filled while
+        profile() is on."""
         ms = np.zeros(2, np.float64)
         _check(lib().modsx_debug_fginn32_last_ms(self._c(), _p(ms)), "fginn32_last_ms")
         return float(ms[0]), float(ms[1])
 
-    def match_regions_f32(self, regs1, d1, regs2, d2, params):
+    def match_regions_f32(self, regs1, d1, regs2, d2, params, dist=DIST_L2):
         """One float-descriptor step on caller-supplied regions: MatchFlannFGINN (params.match_ratio, contradDist, nn; positions
-        = reproj_kp of regs2) + DuplicateFiltering + LO-RANSAC."""
+        = reproj_kp of regs2) + DuplicateFiltering + LO-RANSAC.  dist: DIST_L2 or DIST_L1."""
         regs1 = np.ascontiguousarray(regs1, REGION)
         regs2 = np.ascontiguousarray(regs2, REGION)
         d1, d2, dim = _f32_rows(d1, d2)
         if len(regs1) != len(d1) or len(regs2) != len(d2):
             raise ValueError("match_regions_f32: one descriptor row per region is expected")
         res = PairResult()
-        _check(lib().modsx_match_regions_f32(self._c(), _p(regs1), _p(d1), len(d1), _p(regs2), _p(d2), len(d2), dim,
-                                             C.byref(params), C.byref(res)), "match_regions_f32")
+        head = (self._c(), _p(regs1), _p(d1), len(d1), _p(regs2), _p(d2), len(d2), dim, C.byref(params))
+        if dist == DIST_L2:
+            _check(lib().modsx_match_regions_f32(*head, C.byref(res)), "match_regions_f32")
+        else:
+            _check(lib().modsx_match_regions_f32_dist(*head, int(dist), C.byref(res)), "match_regions_f32_dist")
+        return _unpack_pair_result(res)
+
+    def match_regions_l1(self, regs1, d1, regs2, d2, params):
+        """match_regions_f32 with match_fginn_l1 as the matcher: [n][128] rows holding the integers 0..255."""
+        regs1 = np.ascontiguousarray(regs1, REGION)
+        regs2 = np.ascontiguousarray(regs2, REGION)
+        d1, d2, dim = _f32_rows(d1, d2)
+        if dim != 128 or len(regs1) != len(d1) or len(regs2) != len(d2):
+            raise ValueError("match_regions_l1: one [128] descriptor row per region is expected")
+        res = PairResult()
+        _check(lib().modsx_match_regions_l1(self._c(), _p(regs1), _p(d1), len(d1), _p(regs2), _p(d2), len(d2), C.byref(params),
+                                            C.byref(res)), "match_regions_l1")
         return _unpack_pair_result(res)
 
     def rep_match_fginn(self, rep1, rep2, detector=0, desc_type=1, ratio=0.8, contrad_dist=30.0, nn=50):
@@ -1916,6 +1989,13 @@ def fginn32_geometry(n1, n2, dim, splits=0):
     GPU); splits = 0 is the production geometry, more splits than tiles are cut down to one per tile."""
     geo = np.zeros(6, np.int32)
     _check(lib().modsx_debug_fginn32_geometry(int(n1), int(n2), int(dim), int(splits), _p(geo)), "fginn32_geometry")
+    return dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo)))
+
+
+def fginn_l1_geometry(n1, n2, splits=0):
+    """fginn32_geometry for the L1 search on byte rows (match_fginn_l1): DK is the row width in 32-bit words (host only, no GPU)."""
+    geo = np.zeros(6, np.int32)
+    _check(lib().modsx_debug_fginn_l1_geometry(int(n1), int(n2), int(splits), _p(geo)), "fginn_l1_geometry")
     return dict(zip(FGINN32_GEOMETRY, (int(x) for x in geo)))
 
 

@@ -1388,55 +1388,138 @@ int modsx_match_regions_hamming(modsx_ctx *ctx, const modsx_region *regs1, const
 }
 
 // ---- MatchFlannFGINN on f32 rows of any width (engine_fginn32.hip) ----------------------------------------------------------------
-int modsx_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
-                          double ratio, double contradDist, int nn, modsx_tentative **out) {
+// the entries without `dist` are vector_dist = L2: the same calls with the default
+static int fginn_f32_host(const char *fn, modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                          double ratio, double contradDist, int nn, int dist, modsx_tentative **out) {
   NEED(ctx); NEED(out);
-  if ((n1 > 0 && !desc1) || (n2 > 0 && (!desc2 || !pos2))) { mx::set_error("modsx_match_fginn_f32: null rows or positions"); return MODSX_ERR_ARG; }
+  if ((n1 > 0 && !desc1) || (n2 > 0 && (!desc2 || !pos2))) { mx::set_error(std::string(fn) + ": null rows or positions"); return MODSX_ERR_ARG; }
   hipSetDevice(ctx->dev);
   std::vector<modsx_tentative> t;
-  int rc = match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t);
+  int rc = match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t, nullptr, dist);
   if (rc) return rc;
   *out = to_malloc(t);
   return (int)t.size();
 }
-int modsx_match_fginn_f32_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim, const double *pos2,
-                                 double ratio, double contradDist, int nn, modsx_tentative **out) {
+static int fginn_f32_device(const char *fn, modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim,
+                            const double *pos2, double ratio, double contradDist, int nn, int dist, modsx_tentative **out) {
   NEED(ctx); NEED(out);
-  int rc = fginn32_check_args("modsx_match_fginn_f32_device", n1, n2, dim, ratio, nn);
+  int rc = fginn32_check_args(fn, n1, n2, dim, ratio, nn);
   if (rc) return rc;
-  if ((n1 > 0 && !dev_desc1) || (n2 > 0 && (!dev_desc2 || !pos2))) { mx::set_error("modsx_match_fginn_f32_device: null rows or positions"); return MODSX_ERR_ARG; }
-  if (((uintptr_t)dev_desc1 | (uintptr_t)dev_desc2) & 3) { mx::set_error("modsx_match_fginn_f32_device: rows must be 4-byte aligned"); return MODSX_ERR_ARG; }
+  if ((rc = fginn32_check_dist(fn, dist))) return rc;
+  if ((n1 > 0 && !dev_desc1) || (n2 > 0 && (!dev_desc2 || !pos2))) { mx::set_error(std::string(fn) + ": null rows or positions"); return MODSX_ERR_ARG; }
+  if (((uintptr_t)dev_desc1 | (uintptr_t)dev_desc2) & 3) { mx::set_error(std::string(fn) + ": rows must be 4-byte aligned"); return MODSX_ERR_ARG; }
   std::vector<modsx_tentative> t;
   if (n1 > 0 && n2 > 0) {
     hipSetDevice(ctx->dev);
-    rc = match_fginn32_device(ctx, (const float *)dev_desc1, n1, (const float *)dev_desc2, n2, dim, pos2, ratio, contradDist, nn, t);
+    rc = match_fginn32_device(ctx, (const float *)dev_desc1, n1, (const float *)dev_desc2, n2, dim, pos2, ratio, contradDist, nn, t, nullptr, dist);
     if (rc) return rc;
   }
   *out = to_malloc(t);
   return (int)t.size();
 }
+int modsx_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                          double ratio, double contradDist, int nn, modsx_tentative **out) {
+  return fginn_f32_host("modsx_match_fginn_f32", ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, MODSX_DIST_L2, out);
+}
+int modsx_match_fginn_f32_dist(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                               double ratio, double contradDist, int nn, int dist, modsx_tentative **out) {
+  return fginn_f32_host("modsx_match_fginn_f32_dist", ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, dist, out);
+}
+int modsx_match_fginn_f32_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim, const double *pos2,
+                                 double ratio, double contradDist, int nn, modsx_tentative **out) {
+  return fginn_f32_device("modsx_match_fginn_f32_device", ctx, dev_desc1, n1, dev_desc2, n2, dim, pos2, ratio, contradDist, nn, MODSX_DIST_L2, out);
+}
+int modsx_match_fginn_f32_dist_device(modsx_ctx *ctx, const void *dev_desc1, int n1, const void *dev_desc2, int n2, int dim,
+                                      const double *pos2, double ratio, double contradDist, int nn, int dist, modsx_tentative **out) {
+  return fginn_f32_device("modsx_match_fginn_f32_dist_device", ctx, dev_desc1, n1, dev_desc2, n2, dim, pos2, ratio, contradDist, nn, dist, out);
+}
+static int fginn_regions(const char *fn, modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                         const float *desc2, int n2, int dim, const modsx_pair_params *par, int dist, bool bytes, modsx_pair_result *res) {
+  NEED(ctx); NEED(par); NEED(res);
+  if ((n1 > 0 && (!regs1 || !desc1)) || (n2 > 0 && (!regs2 || !desc2))) { mx::set_error(std::string(fn) + ": null regions or rows"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  return match_regions_f32(ctx, regs1, desc1, n1, regs2, desc2, n2, dim, *par, res, dist, bytes);
+}
 int modsx_match_regions_f32(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
                             const float *desc2, int n2, int dim, const modsx_pair_params *par, modsx_pair_result *res) {
-  NEED(ctx); NEED(par); NEED(res);
-  if ((n1 > 0 && (!regs1 || !desc1)) || (n2 > 0 && (!regs2 || !desc2))) { mx::set_error("modsx_match_regions_f32: null regions or rows"); return MODSX_ERR_ARG; }
-  hipSetDevice(ctx->dev);
-  return match_regions_f32(ctx, regs1, desc1, n1, regs2, desc2, n2, dim, *par, res);
+  return fginn_regions("modsx_match_regions_f32", ctx, regs1, desc1, n1, regs2, desc2, n2, dim, par, MODSX_DIST_L2, false, res);
 }
-int modsx_debug_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
-                                double ratio, double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4,
-                                unsigned char *stage, int *geometry, int *counters, modsx_tentative **out) {
+int modsx_match_regions_f32_dist(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                                 const float *desc2, int n2, int dim, const modsx_pair_params *par, int dist, modsx_pair_result *res) {
+  return fginn_regions("modsx_match_regions_f32_dist", ctx, regs1, desc1, n1, regs2, desc2, n2, dim, par, dist, false, res);
+}
+int modsx_match_regions_l1(modsx_ctx *ctx, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2,
+                           const float *desc2, int n2, const modsx_pair_params *par, modsx_pair_result *res) {
+  return fginn_regions("modsx_match_regions_l1", ctx, regs1, desc1, n1, regs2, desc2, n2, 128, par, MODSX_DIST_L1, true, res);
+}
+// bytes: the L1 search on byte rows (modsx_debug_match_fginn_l1)
+static int fginn_debug(const char *fn, modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                       double ratio, double contradDist, int nn, int dist, bool bytes, int splits, int stage_mask, unsigned long long *top4,
+                       unsigned char *stage, int *geometry, int *counters, modsx_tentative **out) {
   NEED(ctx); NEED(desc1); NEED(desc2); NEED(pos2);
   if (n1 < 1 || n2 < 1 || splits < 0 || (stage_mask != 1 && stage_mask != 3)) {
-    mx::set_error("modsx_debug_match_fginn_f32: needs n1 >= 1, n2 >= 1, splits >= 0 and a stage mask of 1 or 3");
+    mx::set_error(std::string(fn) + ": needs n1 >= 1, n2 >= 1, splits >= 0 and a stage mask of 1 or 3");
     return MODSX_ERR_ARG;
   }
   hipSetDevice(ctx->dev);
   const Fginn32Tap tap = {splits, stage_mask, top4, stage, geometry, counters};
   std::vector<modsx_tentative> t;
-  int rc = match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t, &tap);
+  int rc = bytes ? match_fginn_l1_host(ctx, desc1, n1, desc2, n2, pos2, ratio, contradDist, nn, t, &tap)
+                 : match_fginn32_host(ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, t, &tap, dist);
   if (rc) return rc;
   if (out) *out = to_malloc(t);
   return (int)t.size();
+}
+int modsx_debug_match_fginn_f32(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                                double ratio, double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4,
+                                unsigned char *stage, int *geometry, int *counters, modsx_tentative **out) {
+  return fginn_debug("modsx_debug_match_fginn_f32", ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, MODSX_DIST_L2, false, splits, stage_mask,
+                     top4, stage, geometry, counters, out);
+}
+int modsx_debug_match_fginn_f32_dist(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2,
+                                     double ratio, double contradDist, int nn, int dist, int splits, int stage_mask, unsigned long long *top4,
+                                     unsigned char *stage, int *geometry, int *counters, modsx_tentative **out) {
+  return fginn_debug("modsx_debug_match_fginn_f32_dist", ctx, desc1, n1, desc2, n2, dim, pos2, ratio, contradDist, nn, dist, false, splits, stage_mask, top4,
+                     stage, geometry, counters, out);
+}
+int modsx_debug_match_fginn_l1(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2, double ratio,
+                               double contradDist, int nn, int splits, int stage_mask, unsigned long long *top4, unsigned char *stage,
+                               int *geometry, int *counters, modsx_tentative **out) {
+  return fginn_debug("modsx_debug_match_fginn_l1", ctx, desc1, n1, desc2, n2, 128, pos2, ratio, contradDist, nn, MODSX_DIST_L1, true, splits, stage_mask, top4,
+                     stage, geometry, counters, out);
+}
+int modsx_match_fginn_l1(modsx_ctx *ctx, const float *desc1, int n1, const float *desc2, int n2, const double *pos2, double ratio,
+                         double contradDist, int nn, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  if ((n1 > 0 && !desc1) || (n2 > 0 && (!desc2 || !pos2))) { mx::set_error("modsx_match_fginn_l1: null rows or positions"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  std::vector<modsx_tentative> t;
+  int rc = match_fginn_l1_host(ctx, desc1, n1, desc2, n2, pos2, ratio, contradDist, nn, t);
+  if (rc) return rc;
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_match_fginn_l1_device(modsx_ctx *ctx, const void *dev_desc1_u8, int n1, const void *dev_desc2_u8, int n2, const double *pos2,
+                                double ratio, double contradDist, int nn, modsx_tentative **out) {
+  NEED(ctx); NEED(out);
+  int rc = fginn32_check_args("modsx_match_fginn_l1_device", n1, n2, 128, ratio, nn);
+  if (rc) return rc;
+  if ((n1 > 0 && !dev_desc1_u8) || (n2 > 0 && (!dev_desc2_u8 || !pos2))) { mx::set_error("modsx_match_fginn_l1_device: null rows or positions"); return MODSX_ERR_ARG; }
+  std::vector<modsx_tentative> t;
+  if (n1 > 0 && n2 > 0) {
+    hipSetDevice(ctx->dev);
+    rc = match_fginn_l1_device(ctx, (const uint8_t *)dev_desc1_u8, n1, (const uint8_t *)dev_desc2_u8, n2, pos2, ratio, contradDist, nn, t);
+    if (rc) return rc;
+  }
+  *out = to_malloc(t);
+  return (int)t.size();
+}
+int modsx_debug_fginn_l1_geometry(int n1, int n2, int splits, int *geometry) {
+  NEED(geometry);
+  int rc = fginn32_check_args("modsx_debug_fginn_l1_geometry", n1, n2, 128, 0.5, 2);
+  if (rc) return rc;
+  if (n1 < 1 || n2 < 1 || splits < 0) { mx::set_error("modsx_debug_fginn_l1_geometry: needs n1 >= 1, n2 >= 1, splits >= 0"); return MODSX_ERR_ARG; }
+  return fginn_l1_geometry_report(n1, n2, splits, geometry);
 }
 int modsx_debug_fginn32_geometry(int n1, int n2, int dim, int splits, int *geometry) {
   NEED(geometry);
@@ -1454,7 +1537,8 @@ int modsx_debug_fginn32_dpass(const float *d0, const double *ratio, int n, float
   return MODSX_OK;
 }
 // under modsx_profile(ctx, 1): HIP-event times in ms of the last f32 FGINN search of this context -- ms2[0] the two k_f32_pack
-// launches, ms2[1] k_f32_topk + k_f32_merge (tools/bench_fginn32.py)
+// launches, ms2[1] k_f32_topk + k_f32_merge (tools/bench_fginn32.py) -- or of its last L1 search on byte rows: the two k_l1_pack
+// launches, k_l1_topk + k_f32_merge (tools/bench_fginn_l1.py)
 extern "C" __attribute__((visibility("default"))) int modsx_debug_fginn32_last_ms(modsx_ctx *ctx, double *ms2) {
   NEED(ctx); NEED(ms2);
   ms2[0] = ctx->fginn32Ms[0]; ms2[1] = ctx->fginn32Ms[1];

@@ -376,12 +376,27 @@ struct Fginn32Geo { int dim, DK, tile, ntiles, tilesPerSplit, S, gx; };
 struct F32Open { unsigned long long klast; int q, t0; float dpass; int pad; };
 struct F32Closed { unsigned long long kterm; unsigned cnt, pad; };
 struct Fginn32Work { float *queries, *trains; unsigned long long *keys; F32Open *open; F32Closed *closed; };
+// the key of a (distance, train index): distances are >= +0 and never NaN, so the pattern orders like the value; all ones = no train
+constexpr unsigned long long F32_NONE = ~0ull;
+__device__ __forceinline__ unsigned long long f32_key(float d, int idx) {
+  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx;
+}
 Fginn32Geo fginn32_geometry(int n1, int n2, int dim, int splits);   // splits = 0: production; > 0: forced (at most one per tile)
+Fginn32Geo fginn32_geometry_rows(int n1, int n2, int dim, int DK, int tile, int splits);
 size_t fginn32_workspace_bytes(const Fginn32Geo &g, int n1);
 Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work);
 void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, int n1, const float *d2, int n2, void *work,
-                         void *flagAndTop4, hipEvent_t *ev = nullptr);
-void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work);
+                         void *flagAndTop4, hipEvent_t *ev = nullptr, int dist = MODSX_DIST_L2);
+void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work,
+                            int dist = MODSX_DIST_L2);
+void launch_fginn32_merge(hipStream_t s, const Fginn32Geo &g, const unsigned long long *keys, int n1, unsigned long long *top4);
+// The same search under L1 on rows of 128 bytes (kernels_fginn_l1.hip): the geometry, workspace layout, keys and records of the f32
+// search at a row of DK = 32 dwords and 128 trains per tile (fginn32_workspace_bytes / fginn32_work serve both).  d1 / d2: dense
+// [n][128] u8 rows in HBM of any alignment; flagAndTop4 as above (the flag word stays 0: every byte is a valid value)
+Fginn32Geo fginn_l1_geometry(int n1, int n2, int splits);
+void launch_fginn_l1_topk(hipStream_t s, const Fginn32Geo &g, const uint8_t *d1, int n1, const uint8_t *d2, int n2, void *work,
+                          void *flagAndTop4, hipEvent_t *ev = nullptr);
+void launch_fginn_l1_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work);
 // The grouped form: np <= MATCH_MAXB problems share one stored query side (rows of DK floats, padded to whole workgroups); problem p
 // has its own stored trains (zero rows up to a multiple of 256) and positions.  This is the whole table of the launch set, passed
 // to the kernels by value.  Train axis: problem p owns the splits [first[p], first[p + 1]) of tps[p] whole tiles each.  Resolve:
@@ -582,7 +597,7 @@ struct modsx_ctx {
   long descOrderedTotal = 0;
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context
   double hammingMs[2] = {0, 0};   // under modsx_profile: event times of the last Hamming search's packing and search launches
-  double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search: packing, k_f32_topk + k_f32_merge
+  double fginn32Ms[2] = {0, 0};   // the same for the last f32 FGINN search (or L1 search on byte rows): packing, top-4 sweep + k_f32_merge
   // the patch descriptors LIOP, SURF and DAISY (engine_patchdesc.hip): the patches of one sub-batch (at most 64 MiB), and the
   // descriptors (or the patches of modsx_extract_patches) on their way to a host caller.  Calls are serialised and copy their rows
   // out before they return, so one of each serves all of them

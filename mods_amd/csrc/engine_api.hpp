@@ -279,13 +279,22 @@ struct Fginn32Tap { int splits, stageMask; unsigned long long *top4; unsigned ch
 float fginn32_dpass(float d0, double rsq);
 bool fginn32_rows_ok(const float *f, size_t n);     // every value finite with |x| <= 1e17
 int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, int nn);
+int fginn32_check_dist(const char *fn, int dist);   // MODSX_DIST_L2 or MODSX_DIST_L1
 int fginn32_geometry_report(int n1, int n2, int dim, int splits, int *geo6);
+int fginn_l1_geometry_report(int n1, int n2, int splits, int *geo6);
+// dist: the chain of the sweep (MODSX_DIST_L2 / MODSX_DIST_L1; the host entries check it, the device entry's caller does)
 int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
-                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
+                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr, int dist = MODSX_DIST_L2);
 int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2, double ratioT,
-                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
+                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr, int dist = MODSX_DIST_L2);
 int match_regions_f32(modsx_ctx *c, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2, const float *desc2,
-                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res);
+                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res, int dist = MODSX_DIST_L2, bool bytes = false);
+// L1 on rows holding the integers 0..255 at 128 columns, searched as bytes (kernels_fginn_l1.hip): dense [n][128] u8 rows in HBM of
+// any alignment, or [n][128] f32 rows from the host (anything but those integers is refused)
+int match_fginn_l1_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2, double ratioT,
+                          double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
+int match_fginn_l1_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, const double *pos2, double ratioT,
+                        double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap = nullptr);
 DbSet *db_create(modsx_ctx *c, const void *rows, long n, int dtype);
 void db_free(DbSet *db);
 int db_nearest(modsx_ctx *c, const DbSet &db, const float *desc, int n, float *dmin);

@@ -4,6 +4,9 @@
 // A walk that is still open behind the fourth neighbour is closed by one more sweep (k_f32_resolve: the nearest train behind the
 // fourth that ends the walk, and how many trains do not end it).  That count gives the rank of a passing terminal train exactly, so
 // there is no further sweep (kernels_fginn32.hip).  No list of nn neighbours exists anywhere.
+// The distance (vector_dist of the [Matching] section: L2 or L1) is the chain of the sweep kernels and nothing else: the walk divides
+// and compares whatever distances it is handed, squares or not (matching.cpp:437-451).  Under L1, rows that hold the integers 0..255
+// at 128 columns have a search of their own on bytes (kernels_fginn_l1.hip) with the same keys, workspace and records.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -63,12 +66,21 @@ int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, i
   }
   return MODSX_OK;
 }
+int fginn32_check_dist(const char *fn, int dist) {
+  if (dist == MODSX_DIST_L2 || dist == MODSX_DIST_L1) return MODSX_OK;
+  set_error(std::string(fn) + ": dist must be MODSX_DIST_L2 or MODSX_DIST_L1 (the vector_dist values OpenCV's FLANN takes for float rows)");
+  return MODSX_ERR_ARG;
+}
 
 static void geo_out(const Fginn32Geo &g, int *geo) {
   geo[0] = g.tile; geo[1] = g.S; geo[2] = g.gx * g.S; geo[3] = g.DK; geo[4] = g.ntiles; geo[5] = g.tilesPerSplit;
 }
 int fginn32_geometry_report(int n1, int n2, int dim, int splits, int *geo6) {
   geo_out(fginn32_geometry(n1, n2, dim, splits), geo6);
+  return MODSX_OK;
+}
+int fginn_l1_geometry_report(int n1, int n2, int splits, int *geo6) {
+  geo_out(fginn_l1_geometry(n1, n2, splits), geo6);
   return MODSX_OK;
 }
 
@@ -80,14 +92,14 @@ static modsx_tentative make_record(int q, const unsigned long long *k, unsigned 
   return t;
 }
 
-// d1 / d2: dense [n][dim] f32 rows in HBM, pos2: [n2][2] f64 on the host.  n1 >= 1, n2 >= 1, arguments checked by the caller.
-// tap (optional): forced split count, stage mask, and what the stages did.
-int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
-                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+// d1 / d2: dense rows in HBM -- [n][dim] f32, or with bytes [n][128] u8 (dist is then L1); pos2: [n2][2] f64 on the host.  n1 >= 1,
+// n2 >= 1, arguments checked by the caller.  tap (optional): forced split count, stage mask, and what the stages did.
+static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n1, const void *d2, int n2, int dim, const double *pos2,
+                                 double ratioT, double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap, int dist) {
   out.clear();
   CtxBusy busy(c);
   const int stageMask = tap ? tap->stageMask : 3;
-  const Fginn32Geo g = fginn32_geometry(n1, n2, dim, tap ? tap->splits : 0);
+  const Fginn32Geo g = bytes ? fginn_l1_geometry(n1, n2, tap ? tap->splits : 0) : fginn32_geometry(n1, n2, dim, tap ? tap->splits : 0);
   if (tap && tap->geometry) geo_out(g, tap->geometry);
   const double rsq = ratioT * ratioT, cd2 = contradDist * contradDist;
   const size_t rowB = 16 + (size_t)n1 * 32;
@@ -95,7 +107,8 @@ int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2,
   hipEvent_t ev[3];
   const bool timed = c->prof.enabled;     // modsx_profile: the launches are timed into the context (tools/bench_fginn32.py)
   if (timed) for (int i = 0; i < 3; i++) MX_HIP(hipEventCreate(&ev[i]));
-  launch_fginn32_topk(c->stream, g, d1, n1, d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr);
+  if (bytes) launch_fginn_l1_topk(c->stream, g, (const uint8_t *)d1, n1, (const uint8_t *)d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr);
+  else launch_fginn32_topk(c->stream, g, (const float *)d1, n1, (const float *)d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr, dist);
   hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, rowB, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = ctx_sync(c);
   if (e == hipSuccess) e = hipGetLastError();
@@ -152,7 +165,8 @@ int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2,
     MX_HIP(hipMemcpyAsync(c->pos2.p, pos2, (size_t)n2 * 16, hipMemcpyHostToDevice, c->stream));
     MX_HIP(hipMemcpyAsync(w.open, open.data(), (size_t)nu * sizeof(F32Open), hipMemcpyHostToDevice, c->stream));
     MX_HIP(hipMemcpyAsync(w.closed, closed.data(), (size_t)nu * sizeof(F32Closed), hipMemcpyHostToDevice, c->stream));
-    launch_fginn32_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p);
+    if (bytes) launch_fginn_l1_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p);
+    else launch_fginn32_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p, dist);
     MX_HIP(hipMemcpyAsync(closed.data(), w.closed, (size_t)nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
     MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
     MX_HIP(hipGetLastError());
@@ -174,12 +188,23 @@ int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2,
   return MODSX_OK;
 }
 
+int match_fginn32_device(modsx_ctx *c, const float *d1, int n1, const float *d2, int n2, int dim, const double *pos2, double ratioT,
+                         double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap, int dist) {
+  return fginn_search_and_walk(c, false, d1, n1, d2, n2, dim, pos2, ratioT, contradDist, nn, out, tap, dist);
+}
+// the L1 search on dense [n][128] u8 rows in HBM (any alignment)
+int match_fginn_l1_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t *d2, int n2, const double *pos2, double ratioT,
+                          double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+  return fginn_search_and_walk(c, true, d1, n1, d2, n2, 128, pos2, ratioT, contradDist, nn, out, tap, MODSX_DIST_L1);
+}
+
 // rows from the host: checked here, uploaded, matched
 int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const double *pos2, double ratioT,
-                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+                       double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap, int dist) {
   out.clear();
   int rc = fginn32_check_args("modsx_match_fginn_f32", n1, n2, dim, ratioT, nn);
   if (rc) return rc;
+  if ((rc = fginn32_check_dist("modsx_match_fginn_f32", dist))) return rc;
   if (n1 == 0 || n2 == 0) return MODSX_OK;
   const size_t f1 = (size_t)n1 * dim, f2 = (size_t)n2 * dim;
   if (!fginn32_rows_ok(desc1, f1) || !fginn32_rows_ok(desc2, f2)) {
@@ -191,21 +216,46 @@ int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *de
   MX_HIP(hipMemcpyAsync(c->descF[0].p, desc1, f1 * 4, hipMemcpyHostToDevice, c->stream));
   MX_HIP(hipMemcpyAsync(c->descF[1].p, desc2, f2 * 4, hipMemcpyHostToDevice, c->stream));
   MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable
-  return match_fginn32_device(c, (const float *)c->descF[0].p, n1, (const float *)c->descF[1].p, n2, dim, pos2, ratioT, contradDist, nn, out, tap);
+  return match_fginn32_device(c, (const float *)c->descF[0].p, n1, (const float *)c->descF[1].p, n2, dim, pos2, ratioT, contradDist, nn, out, tap,
+                              dist);
+}
+
+// [n][128] f32 rows from the host that hold the integers 0..255 (the domain of modsx_match_fginn): narrowed to bytes, uploaded, matched
+int match_fginn_l1_host(modsx_ctx *c, const float *desc1, int n1, const float *desc2, int n2, const double *pos2, double ratioT,
+                        double contradDist, int nn, std::vector<modsx_tentative> &out, const Fginn32Tap *tap) {
+  out.clear();
+  int rc = fginn32_check_args("modsx_match_fginn_l1", n1, n2, 128, ratioT, nn);
+  if (rc) return rc;
+  if (n1 == 0 || n2 == 0) return MODSX_OK;
+  std::vector<uint8_t> u1((size_t)n1 * 128), u2((size_t)n2 * 128);
+  if (!desc_f32_to_u8(desc1, u1.size(), u1.data()) || !desc_f32_to_u8(desc2, u2.size(), u2.data())) {
+    set_error("modsx_match_fginn_l1: descriptors must hold the integers 0..255 (SIFT-family quantisation)");
+    return MODSX_ERR_ARG;
+  }
+  CtxBusy busy(c);
+  if (!c->descU8[0].ensure(u1.size()) || !c->descU8[1].ensure(u2.size())) return MODSX_ERR_NOMEM;
+  MX_HIP(hipMemcpyAsync(c->descU8[0].p, u1.data(), u1.size(), hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipMemcpyAsync(c->descU8[1].p, u2.data(), u2.size(), hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable
+  return match_fginn_l1_device(c, (const uint8_t *)c->descU8[0].p, n1, (const uint8_t *)c->descU8[1].p, n2, pos2, ratioT, contradDist, nn, out, tap);
 }
 
 // MatchFlannFGINN + DuplicateFiltering + LORANSACFiltering on caller-supplied regions: what match_pair leaves with the match stage
 // replaced.  pos2 = reproj_kp of the second list, as the reference takes it.  An empty side gives the zeroed result with H = -1.
+// bytes: the rows hold the integers 0..255 at dim = 128 and go through the L1 search on bytes (dist is then L1)
 int match_regions_f32(modsx_ctx *c, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2, const float *desc2,
-                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res) {
+                      int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res, int dist, bool bytes) {
   memset(res, 0, sizeof *res);
   for (int i = 0; i < 9; i++) res->H[i] = -1;
-  int rc = fginn32_check_args("modsx_match_regions_f32", n1, n2, dim, pp.match_ratio, pp.nn);
+  const char *fn = bytes ? "modsx_match_regions_l1" : "modsx_match_regions_f32";
+  int rc = fginn32_check_args(fn, n1, n2, dim, pp.match_ratio, pp.nn);
   if (rc) return rc;
+  if ((rc = fginn32_check_dist(fn, dist))) return rc;
   std::vector<double> pos2((size_t)n2 * 2);
   for (int i = 0; i < n2; i++) { pos2[2 * (size_t)i] = regs2[i].reproj_kp.x; pos2[2 * (size_t)i + 1] = regs2[i].reproj_kp.y; }
   std::vector<modsx_tentative> tents;
-  rc = match_fginn32_host(c, desc1, n1, desc2, n2, dim, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr);
+  rc = bytes ? match_fginn_l1_host(c, desc1, n1, desc2, n2, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr)
+             : match_fginn32_host(c, desc1, n1, desc2, n2, dim, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr, dist);
   if (rc) return rc;
   res->n_regions1 = n1; res->n_regions2 = n2;
   if (n1 == 0 || n2 == 0) return MODSX_OK;

@@ -60,6 +60,27 @@
 // Per (query, train) the sweep loop of k_f32_topk<DK> issues 100 / 195 / 387 / 551 / 744 vector instructions at DK = 32 / 64 / 128 /
 // 192 / 256 and DK / 4 ds_read_b128; at DK = 128 that is 96 v_sub_f32, 96 v_mul_f32, 103 v_add_f32, 28 v_pk_add_f32, 16 v_pk_mul_f32
 // and 48 for the key and its branch-free insertion (measured times 9.9).
+//
+// The distance is a template parameter of f32_chain / f32_sweep / k_f32_topk / k_f32_resolve (DIST = MODSX_DIST_L2 by default, or
+// MODSX_DIST_L1: vector_dist = L1, r = r + (((|e0| + |e1|) + |e2|) + |e3|), FLANN's L1<float>).  Everything else --
+// packing (a zero column adds +0 under L1 too), keys, merge, geometry, the host walk, d_pass and the resolve round trip -- is shared.
+// With the parameter in place the ISA of every L2 kernel of this file, k_f32_topk<128> and k_f32_resolve<128> among them, is
+// instruction for instruction what it was without it (--save-temps of both, compared per kernel; only the mangled names differ:
+// ...ILi128ELi0EE for ...ILi128EE), and the grouped k_f32g_* kernels compile to the same code too.  The L1 instantiations:
+//   kernel                VGPRs  SGPRs  LDS [B]  scratch  occupancy [waves/SIMD]
+//   k_f32_topk<32, L1>       82     24    16384        0      5
+//   k_f32_topk<64, L1>      113     24    16384        0      4
+//   k_f32_topk<128, L1>     174     24    16384        0      2
+//   k_f32_topk<192, L1>     144     26    28672        0      3
+//   k_f32_topk<256, L1>     180     27    32768        0      2
+//   k_f32_resolve<32, L1>    84     34    16384        0      5
+//   k_f32_resolve<64, L1>   114     34    16384        0      4
+//   k_f32_resolve<128, L1>  252     34    16384        0      2
+//   k_f32_resolve<192, L1>  146     38    28672        0      3
+//   k_f32_resolve<256, L1>  182     38    32768        0      2
+// Per (query, train) the sweep loop of k_f32_topk<DK, L1> issues 116 / 179 / 307 / 478 / 606 vector instructions, counted as above; at
+// DK = 128: 96 v_sub_f32, 103 v_add_f32 (72 of them with an |x| source modifier), 28 v_pk_add_f32 -- which has no such modifier, so
+// 32 v_and_b32 clear sign bits for it -- and 48 for the key and its insertion.  8.1 per group of four against the 8 of the source.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -67,18 +88,21 @@
 
 namespace mx {
 
-constexpr unsigned long long F32_NONE = ~0ull;
-
 int fginn32_kernel_width(int dim) { return dim <= 32 ? 32 : dim <= 64 ? 64 : dim <= 128 ? 128 : dim <= 192 ? 192 : 256; }
 static constexpr int f32_tile_trains(int DK) { return DK <= 32 ? 128 : DK <= 64 ? 64 : DK <= 128 ? 32 : 16; }
 
 // splits = 0: production (about 2048 workgroups: eight per CU, four rounds at the two that DK = 128 / 256 hold at a time, so that the
 // last round's tail stays short); splits > 0: that many, at most one per tile
 Fginn32Geo fginn32_geometry(int n1, int n2, int dim, int splits) {
+  const int DK = fginn32_kernel_width(dim);
+  return fginn32_geometry_rows(n1, n2, dim, DK, f32_tile_trains(DK), splits);
+}
+// the same rule for packed rows of DK dwords staged `tile` at a time (kernels_fginn_l1.hip: its byte rows)
+Fginn32Geo fginn32_geometry_rows(int n1, int n2, int dim, int DK, int tile, int splits) {
   Fginn32Geo g;
   g.dim = dim;
-  g.DK = fginn32_kernel_width(dim);
-  g.tile = f32_tile_trains(g.DK);
+  g.DK = DK;
+  g.tile = tile;
   g.ntiles = std::max(1, (n2 + g.tile - 1) / g.tile);
   g.gx = std::max(1, (n1 + 255) / 256);
   int S = splits > 0 ? splits : (2048 + g.gx - 1) / g.gx;
@@ -124,14 +148,16 @@ template <int DK> struct F32Cfg {
   static_assert(T * DK % 1024 == 0 && CH % 4 == 0 && CH * NCH == DK, "tile shape");
 };
 
-// the chain of one (query chunk, train chunk): r continues over CH floats
-template <int CH>
+// the chain of one (query chunk, train chunk): r continues over CH floats.  DIST = MODSX_DIST_L2: squares; MODSX_DIST_L1: magnitudes
+// (FLANN's L1<float>; the sign bit is dropped by a source modifier of the add, so a group costs 4 v_sub_f32 + 4 v_add_f32)
+template <int CH, int DIST = MODSX_DIST_L2>
 __device__ __forceinline__ float f32_chain(float r, const float (&a)[CH], const float *__restrict__ b) {
 #pragma unroll
   for (int k = 0; k < CH; k += 4) {
     const f32x4 v = *reinterpret_cast<const f32x4 *>(b + k);
     const float e0 = a[k] - v.x, e1 = a[k + 1] - v.y, e2 = a[k + 2] - v.z, e3 = a[k + 3] - v.w;
-    r = r + (((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3);
+    if constexpr (DIST == MODSX_DIST_L1) r = r + (((__builtin_fabsf(e0) + __builtin_fabsf(e1)) + __builtin_fabsf(e2)) + __builtin_fabsf(e3));
+    else r = r + (((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3);
   }
   return r;
 }
@@ -152,7 +178,7 @@ __device__ __forceinline__ void f32_load_chunk(float (&a)[CH], const float *__re
 
 // Sweeps the tiles [tBeg, tEnd) of `trains` (whole tiles; zero rows behind row n2 - 1 are never visited) for this lane's packed query
 // row (null: a lane without a query; it still takes part in the staging) and hands consume(distance, train index) every train.
-template <int DK, class F>
+template <int DK, int DIST = MODSX_DIST_L2, class F>
 __device__ __forceinline__ void f32_sweep(const float *__restrict__ qrow, const f32x4 *__restrict__ trains, int n2, int tBeg, int tEnd,
                                           float *__restrict__ tile, float *__restrict__ part, F &&consume) {
   using C = F32Cfg<DK>;
@@ -175,20 +201,16 @@ __device__ __forceinline__ void f32_sweep(const float *__restrict__ qrow, const 
     const int base = t * T, jn = min(T, n2 - base);
     if constexpr (C::NCH == 1) {
 #pragma unroll 1
-      for (int j = 0; j < jn; j++) consume(f32_chain<CH>(0.f, a, tile + j * DK), base + j);
+      for (int j = 0; j < jn; j++) consume(f32_chain<CH, DIST>(0.f, a, tile + j * DK), base + j);
     } else {
       f32_load_chunk<CH>(a, qrow);
 #pragma unroll 1
-      for (int j = 0; j < jn; j++) part[j * 256 + tid] = f32_chain<CH>(0.f, a, tile + j * DK);
+      for (int j = 0; j < jn; j++) part[j * 256 + tid] = f32_chain<CH, DIST>(0.f, a, tile + j * DK);
       f32_load_chunk<CH>(a, qrow ? qrow + CH : nullptr);
 #pragma unroll 1
-      for (int j = 0; j < jn; j++) consume(f32_chain<CH>(part[j * 256 + tid], a, tile + j * DK + CH), base + j);
+      for (int j = 0; j < jn; j++) consume(f32_chain<CH, DIST>(part[j * 256 + tid], a, tile + j * DK + CH), base + j);
     }
   }
-}
-
-__device__ __forceinline__ unsigned long long f32_key(float d, int idx) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx;
 }
 
 #define F32_SWEEP_LDS(DK)                                                      \
@@ -196,14 +218,14 @@ __device__ __forceinline__ unsigned long long f32_key(float d, int idx) {
   __shared__ float part[F32Cfg<DK>::PART]
 
 // keys: [S][n1][4].  Split blockIdx.y sweeps the tiles [y * tilesPerSplit, ...).
-template <int DK>
+template <int DK, int DIST = MODSX_DIST_L2>
 __global__ __launch_bounds__(256) void k_f32_topk(const float *__restrict__ queries, int n1, const float4 *__restrict__ trains, int n2,
                                                   int ntiles, int tilesPerSplit, unsigned long long *__restrict__ keys) {
   F32_SWEEP_LDS(DK);
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
   unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
-  f32_sweep<DK>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
+  f32_sweep<DK, DIST>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
     const unsigned long long key = f32_key(d, idx);
     if (key < k3) {
       k3 = min(k3, max(k2, key));
@@ -241,7 +263,7 @@ __global__ __launch_bounds__(256) void k_f32_merge(const unsigned long long *__r
 
 // open[u]: an undecided query; closed[u] (kterm = all ones, cnt = 0 on entry) receives over all splits the smallest key of a terminal
 // train and the count of non-terminal trains among the trains with key > klast.  pos: [n2][2] f64.
-template <int DK>
+template <int DK, int DIST = MODSX_DIST_L2>
 __global__ __launch_bounds__(256) void k_f32_resolve(const float *__restrict__ queries, const F32Open *__restrict__ open, int nu,
                                                      const float4 *__restrict__ trains, int n2, int ntiles, int tilesPerSplit,
                                                      const double *__restrict__ pos, double contrDistSq, F32Closed *__restrict__ closed) {
@@ -254,7 +276,7 @@ __global__ __launch_bounds__(256) void k_f32_resolve(const float *__restrict__ q
   const double px = pos[2 * (size_t)o.t0], py = pos[2 * (size_t)o.t0 + 1];
   unsigned long long kterm = F32_NONE;
   unsigned cnt = 0;
-  f32_sweep<DK>(u < nu ? queries + (size_t)o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
+  f32_sweep<DK, DIST>(u < nu ? queries + (size_t)o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
     const unsigned long long key = f32_key(d, idx);
     const double dx = px - pos[2 * (size_t)idx], dy = py - pos[2 * (size_t)idx + 1];
     const bool terminal = d >= o.dpass || dx * dx + dy * dy > contrDistSq;
@@ -269,6 +291,11 @@ __global__ __launch_bounds__(256) void k_f32_resolve(const float *__restrict__ q
   }
 }
 
+// the keys of every search in this format merge alike (kernels_fginn_l1.hip launches it too)
+void launch_fginn32_merge(hipStream_t s, const Fginn32Geo &g, const unsigned long long *keys, int n1, unsigned long long *top4) {
+  hipLaunchKernelGGL(k_f32_merge, dim3(g.gx), dim3(256), 0, s, keys, n1, g.S, top4);
+}
+
 Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work) {
   Fginn32Work w;
   char *p = (char *)work;
@@ -281,14 +308,15 @@ Fginn32Work fginn32_work(const Fginn32Geo &g, int n1, void *work) {
 }
 
 template <int DK>
-static void launch_topk(hipStream_t s, const Fginn32Geo &g, const Fginn32Work &w, int n1, int n2) {
-  hipLaunchKernelGGL(k_f32_topk<DK>, dim3(g.gx, g.S), dim3(256), 0, s, w.queries, n1, (const float4 *)w.trains, n2, g.ntiles,
-                     g.tilesPerSplit, w.keys);
+static void launch_topk(hipStream_t s, const Fginn32Geo &g, const Fginn32Work &w, int n1, int n2, int dist) {
+  const auto k = dist == MODSX_DIST_L1 ? k_f32_topk<DK, MODSX_DIST_L1> : k_f32_topk<DK>;
+  hipLaunchKernelGGL(k, dim3(g.gx, g.S), dim3(256), 0, s, w.queries, n1, (const float4 *)w.trains, n2, g.ntiles, g.tilesPerSplit, w.keys);
 }
 template <int DK>
-static void launch_resolve(hipStream_t s, const Fginn32Geo &g, const Fginn32Work &w, int nu, int n2, const double *pos, double cd2) {
-  hipLaunchKernelGGL(k_f32_resolve<DK>, dim3((nu + 255) / 256, g.S), dim3(256), 0, s, w.queries, w.open, nu, (const float4 *)w.trains, n2,
-                     g.ntiles, g.tilesPerSplit, pos, cd2, w.closed);
+static void launch_resolve(hipStream_t s, const Fginn32Geo &g, const Fginn32Work &w, int nu, int n2, const double *pos, double cd2, int dist) {
+  const auto k = dist == MODSX_DIST_L1 ? k_f32_resolve<DK, MODSX_DIST_L1> : k_f32_resolve<DK>;
+  hipLaunchKernelGGL(k, dim3((nu + 255) / 256, g.S), dim3(256), 0, s, w.queries, w.open, nu, (const float4 *)w.trains, n2, g.ntiles,
+                     g.tilesPerSplit, pos, cd2, w.closed);
 }
 #define F32_BY_WIDTH(g, fn, ...)               \
   switch ((g).DK) {                            \
@@ -301,9 +329,10 @@ static void launch_resolve(hipStream_t s, const Fginn32Geo &g, const Fginn32Work
 
 // d1 / d2: dense [n][dim] f32 rows in HBM (4-byte aligned); work: fginn32_workspace_bytes(g, n1), 256-byte aligned; flagAndTop4: 16
 // bytes (the validity flag word: bit 0 = queries, bit 1 = trains) followed by n1 x 4 keys.  n1 >= 1, n2 >= 1.  ev (optional): three
-// events -- before the packing, between the packing and the search (k_f32_topk + k_f32_merge), behind the search
+// events -- before the packing, between the packing and the search (k_f32_topk + k_f32_merge), behind the search.  dist: MODSX_DIST_L2
+// or MODSX_DIST_L1 (checked by the caller); it selects the chain of the sweep and nothing else
 void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, int n1, const float *d2, int n2, void *work,
-                         void *flagAndTop4, hipEvent_t *ev) {
+                         void *flagAndTop4, hipEvent_t *ev, int dist) {
   const Fginn32Work w = fginn32_work(g, n1, work);
   const int qRows = g.gx * 256, tRows = g.ntiles * g.tile, G = g.DK / 4;
   unsigned *flag = (unsigned *)flagAndTop4;
@@ -314,17 +343,18 @@ void launch_fginn32_topk(hipStream_t s, const Fginn32Geo &g, const float *d1, in
   hipLaunchKernelGGL(k_f32_pack, dim3((unsigned)(((size_t)tRows * G + 255) / 256)), dim3(256), 0, s, d2, n2, g.dim, g.DK, tRows,
                      (float4 *)w.trains, flag, 2u);
   if (ev) hipEventRecord(ev[1], s);
-  F32_BY_WIDTH(g, launch_topk, s, g, w, n1, n2);
-  hipLaunchKernelGGL(k_f32_merge, dim3(g.gx), dim3(256), 0, s, w.keys, n1, g.S, (unsigned long long *)((char *)flagAndTop4 + 16));
+  F32_BY_WIDTH(g, launch_topk, s, g, w, n1, n2, dist);
+  launch_fginn32_merge(s, g, w.keys, n1, (unsigned long long *)((char *)flagAndTop4 + 16));
   if (ev) hipEventRecord(ev[2], s);
 }
 
 // the packed rows of the last launch_fginn32_topk on this workspace are reused; the caller has set w.open[0 .. nu) and
 // w.closed[0 .. nu) = {all ones, 0}
-void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work) {
+void launch_fginn32_resolve(hipStream_t s, const Fginn32Geo &g, int n1, int nu, int n2, const double *pos, double contrDistSq, void *work,
+                            int dist) {
   const Fginn32Work w = fginn32_work(g, n1, work);
   static_assert(sizeof(F32Closed) == 16 && sizeof(F32Open) == 24, "record sizes");
-  F32_BY_WIDTH(g, launch_resolve, s, g, w, nu, n2, pos, contrDistSq);
+  F32_BY_WIDTH(g, launch_resolve, s, g, w, nu, n2, pos, contrDistSq, dist);
 }
 
 // ---- the grouped form: up to MATCH_MAXB problems, one stored query side, stored trains (engine_reps_f32.hip) ----------------------
