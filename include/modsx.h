@@ -1334,11 +1334,89 @@ int modsx_debug_clahe(modsx_ctx *ctx, const modsx_image *in, const modsx_clahe_p
  * launches.  Fills out[0 .. min(n, 6) - 1], returns 6. */
 int modsx_clahe_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- the learned-descriptor front end: CAFFE patches and row norms (engine_caffe.hip, kernels_caffe.hip) -------------------
+ * What the reference's "CAFFE" branch (imagerepresentation.cpp:1343-1534) does around its network: the input blob of the
+ * regions of one image, and L2normalize / L1normalize / RootNormalize (:181-217) on the network's output rows.  The network
+ * itself is the caller's (mods_amd/learned.py runs a torch module between the two on the same device).  Unlike
+ * DescribeRegions<> the branch samples the ORIGINAL image at the REPROJECTED frame, blurs nothing, normalises nothing
+ * photometrically, keeps colour, takes any odd patch size, rounds to bytes and subtracts a per-channel mean.
+ *   input     planes[c]: 1 or 3 modsx_image handles of equal size on the context's device.  Three are the B, G, R planes of
+ *             cv::split(OriginalImg) after convertTo(CV_32FC3), each uploaded with modsx_image_upload(.., channels = 1, ..);
+ *             one is a gray OriginalImg.  regs[n]: only reproj_kp is read (regions after modsx_reproject_regions).
+ *   frame     patchImageSize = 2 * (int)mrSize + 1; imageToPatchScale = (double)patchImageSize / (double)patchSize;
+ *             curr_sc = (float)(imageToPatchScale * reproj_kp.s), an f64 product rounded once; the arguments of interpolate are
+ *             (float)x, (float)y, (float)a11 * curr_sc, (float)a12 * curr_sc, (float)a21 * curr_sc, (float)a22 * curr_sc (f32
+ *             products) and a P x P result, P = patchSize.
+ *   samples   interpolate, detectors/helpers.cpp:551-626, on every plane: interpolateCheckBorders false -> the (int)
+ *             truncation branch, true -> floor + bounds test with 0 outside; the serial f32 running sums of the row starts
+ *             (rx += a12, ry += a22) and along a row (WX += a11, WY += a21), no multiplication by the index, no contraction.
+ *             The coordinates are the same for the three planes.
+ *   bytes     saturate_cast<uchar>(float): round to nearest, ties to even, clamp to 0 .. 255 (convertTo(CV_8UC3) / CV_8U).  A
+ *             gray input puts its one byte into all three channels (GRAY2BGR).
+ *   blob      out[i][c][h][w] = (float)byte - (float)(int)mean[c]: mean_px is a std::vector<int> assigned from doubles, so the
+ *             mean is truncated toward zero; the layout is CVMatToDatum's, channel-major f32 [n][3][P][P].
+ *   flags     optional, [n] u8 on the host: bit 0 = interpolateCheckBorders was true (the border branch ran); bit 1 = at least
+ *             one sample fell outside -- what interpolate returns and the branch ignores.
+ * Where the reference is broken: (1) the branch is #ifdef WITH_CAFFE and names CaffeDescParam.patchSize / .mrSize, which
+ * GetCaffePars writes but the struct holds in PEParam -- the contract is the text of the branch; (2) with an even patchSize
+ * interpolate writes (2 (P >> 1) + 1)^2 floats into a P x P Mat and overruns it -- refused; (3) blob_proto is never cleared
+ * between batches (:1475), so from its second batch on the reference feeds sums of patches -- not reproduced, every region
+ * gets what the reference gives a region of its FIRST batch; (4) neither OpenCV nor Caffe is linked: the rounding rule and the
+ * CHW layout are restated, not pinned, as CLAHE's.
+ * Defaults (modsx_default_caffe_params): mrSize 3 sqrt(3) and patchSize 41 (PatchExtractionParams), mean {104, 117, 123} in
+ * B, G, R order.  n is the caller's batch (the reference uses 256).  Both forms return after the work has finished.
+ * Refusals, MODSX_ERR_ARG with a message and before any launch: n < 0 or a null pointer; patchSize even or outside 1 ..
+ * MODSX_CAFFE_MAX_PATCH; mrSize not finite, negative or above 1e6; a mean that is not finite or outside +-2^30; a plane count
+ * other than 1 or 3; planes of different sizes or of another device; a device blob that is not 4-byte aligned.  n == 0
+ * succeeds and writes nothing.  Non-finite pixels and non-finite reproj_kp fields are outside the contract (every load stays
+ * inside the planes; a pixel whose rounded value leaves the int range clamps like any other).
+ * Not here: network inference; CAFFE in modsx_rep_describe_append, the ladder, modsx_rep_add_views or the sharded path; a
+ * 1-channel blob; even patch sizes; DoSIFTLikeOrientation at a patch size other than 41 (run modsx_detect_orientation and
+ * modsx_reproject_regions first); `Pooling`, which GetCaffePars reads and nothing uses. */
+#define MODSX_CAFFE_MAX_PATCH 255
+#define MODSX_CAFFE_MAX_DIM 4096
+enum { MODSX_CAFFE_NORM_L2 = 0, MODSX_CAFFE_NORM_L1 = 1, MODSX_CAFFE_NORM_ROOTL2 = 2, MODSX_CAFFE_NORM_NONE = 3 };
+typedef struct modsx_caffe_params {
+  double mrSize;                /* 3 sqrt(3) */
+  int patchSize;                /* 41 */
+  double mean[3];               /* 104, 117, 123: B, G, R */
+} modsx_caffe_params;
+void modsx_default_caffe_params(modsx_caffe_params *p);
+/* blob: [n][3][P][P] f32 on the host; flags: [n] u8 on the host or NULL.  Returns n. */
+int modsx_caffe_patches(modsx_ctx *ctx, const modsx_image *const *planes, int n_planes, const modsx_region *regs, int n,
+                        const modsx_caffe_params *par, float *blob, unsigned char *flags);
+/* the same with the blob in HBM: dev_blob is a dense [n][3][P][P] f32 device pointer, 4-byte aligned */
+int modsx_caffe_patches_device(modsx_ctx *ctx, const modsx_image *const *planes, int n_planes, const modsx_region *regs, int n,
+                               const modsx_caffe_params *par, void *dev_blob, unsigned char *flags);
+/* host only: what the launcher's job table holds for planes of rows x cols, from the function that fills it.  out [n][8] f32 =
+ * curr_sc, the six arguments of interpolate (x, y, a11, a12, a21, a22) and interpolateCheckBorders (0 or 1).  Returns n. */
+int modsx_caffe_jobs(const modsx_region *regs, int n, const modsx_caffe_params *par, int rows, int cols, float *out);
+/* host only: the work split of a launch over n regions at patchSize: out[0 .. 6] = workgroups, wavefronts per workgroup (one
+ * lane per patch row), column chunks per patch, columns per chunk (at most 64), LDS byte stride of a tile row, LDS bytes of a
+ * workgroup with one plane, the same with three.  Returns 7. */
+int modsx_debug_caffe_geometry(int n, int patchSize, int *out);
+/* The norms on [n][dim] f32 rows, 1 <= dim <= MODSX_CAFFE_MAX_DIM, exactly imagerepresentation.cpp:181-217.
+ *   L2      norm (f64) += (double)(x[i] * x[i]) with the product rounded to f32 first, i = 0 .. dim - 1 in that order; coef =
+ *           1.0 / sqrt(norm); out[i] = (float)floor(512.0 * coef * (double)x[i]), evaluated left to right
+ *   L1      norm += (double)x[i] -- the signed sum, the reference takes no absolute value; coef = 1.0 / norm; the same floor
+ *   ROOTL2  the L1 sum, out[i] = (float)sqrt(512.0 * coef * (double)x[i]) (the L2 pass RootNormalize runs first is overwritten)
+ *   NONE    a copy
+ * f64 division and square root are the IEEE ones.  A zero norm gives NaN / +-inf rows and a negative product NaN, as in the
+ * reference: they are returned as such and are outside the matcher's contract.  The device form takes 4-byte aligned dense rows;
+ * dev_out may be dev_rows.  MODSX_ERR_ARG before any launch: n < 0, a null pointer, dim or norm out of range, a misaligned
+ * device pointer; n == 0 succeeds and writes nothing.  Returns n. */
+int modsx_caffe_norm_rows(modsx_ctx *ctx, const float *rows, int n, int dim, int norm, float *out);
+int modsx_caffe_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, int dim, int norm, void *dev_out);
+/* Front-end work of this context since modsx_create, cumulative: patch calls, regions, regions on the border branch, launches
+ * (norm launches included).  Fills out[0 .. min(n, 4) - 1], returns 4. */
+int modsx_caffe_counters(modsx_ctx *ctx, long *out, int n);
+
 /* ---- float descriptor classes of a stored representation (engine_reps_f32.hip) -------------------------------------------
  * A modsx_rep also holds one class per (detector in {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF}) x (float descriptor
  * type MODSX_DESC_CAFFE .. MODSX_DESC_SURF), as RegionVectorMap[det][desc] does for any descriptor name.  Widths: CAFFE any
  * dim % 4 == 0 in [4, MODSX_FGINN32_MAX_DIM] (learned vectors), DAISY a width modsx_daisy_dim can return, LIOP 144, MROGH 192,
- * SURF 64; CAFFE and MROGH rows come from the caller only.  A class fixes its width at its first append; a later append of
+ * SURF 64; MROGH rows come from the caller only, CAFFE rows from the caller's network (modsx_caffe_patches in front of it,
+ * modsx_caffe_norm_rows and modsx_rep_append_f32_device behind it).  A class fixes its width at its first append; a later append of
  * another width is MODSX_ERR_ARG.
  *   Stored form.  A class keeps its rows in the row form of the f32 matcher (the kernel width DK floats per row, zero behind
  * dim, 16-byte aligned) padded with zero rows to a multiple of 256 rows, and the positions reproj_kp.x, y of its regions as
@@ -1353,6 +1431,11 @@ int modsx_clahe_counters(modsx_ctx *ctx, long *out, int n);
  * more than 2 000 000 regions in the class. */
 int modsx_rep_append_f32(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const float *rows,
                          int dim, int n);
+/* The same with the rows in HBM: dev_rows is a dense [n][dim] f32 device pointer, 4-byte aligned (rows a network or
+ * modsx_caffe_norm_rows_device left there).  The same checks, the same stored form and the same results as the host entry on
+ * the same values; the validity of the values is checked by the kernel that stores them. */
+int modsx_rep_append_f32_device(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs,
+                                const void *dev_rows, int dim, int n);
 /* Describes the caller's (oriented) regions of one view image with the class's extractor -- MODSX_DESC_SURF, MODSX_DESC_LIOP
  * or MODSX_DESC_DAISY (CAFFE and MROGH are refused) -- and appends regions and rows; the rows stay on the device from the
  * extractor's kernel to the class.  They are bit for bit what modsx_describe_regions_surf / _liop / _daisy return for the same

@@ -56,6 +56,11 @@ class ClaheParams(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("variant", C.c_int)]
 
 
+class CaffeParams(C.Structure):
+    """modsx_caffe_params: mrSize and patchSize of the reference's "CAFFE" branch and its per-channel mean (B, G, R)"""
+    _fields_ = [("mrSize", C.c_double), ("patchSize", C.c_int), ("mean", C.c_double * 3)]
+
+
 class MserParams(C.Structure):
     _fields_ = [("min_size", C.c_int), ("max_area", C.c_double), ("min_margin", C.c_double), ("relative", C.c_int),
                 ("mode", C.c_int), ("reg_number", C.c_int), ("rel_threshold", C.c_float), ("rel_reg_number", C.c_float)]
@@ -162,6 +167,9 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_debug_affine_shape", "modsx_affshape_jobs", "modsx_affshape_counters",
            "modsx_default_clahe_params", "modsx_image_clahe", "modsx_image_clahe_new", "modsx_image_clahe_batch",
            "modsx_clahe_geometry", "modsx_debug_clahe", "modsx_clahe_counters",
+           "modsx_default_caffe_params", "modsx_caffe_patches", "modsx_caffe_patches_device", "modsx_caffe_jobs",
+           "modsx_debug_caffe_geometry", "modsx_caffe_norm_rows", "modsx_caffe_norm_rows_device", "modsx_caffe_counters",
+           "modsx_rep_append_f32_device",
            "modsx_daisy_dim", "modsx_daisy_patches", "modsx_daisy_patches_device", "modsx_describe_regions_daisy",
            "modsx_describe_regions_daisy_device", "modsx_daisy_tables", "modsx_daisy_counters"]
 # include/modsx_degensac.h: the reference's own verification symbols (link-time drop-in for libdegensac)
@@ -197,6 +205,13 @@ AFFSHAPE_COUNTERS = ("calls", "regions", "border_refused", "launched", "converge
 CLAHE_COUNTERS = ("calls", "images", "tiles", "strips", "pixels", "launches")
 CLAHE_GEOMETRY = ("tile_w", "tile_h", "pad_cols", "pad_rows", "clip_limit", "lut_scale_bits", "strips", "strip_rows", "apply_blocks")
 CLAHE_MAX_TILES = 256                     # include/modsx.h: MODSX_CLAHE_MAX_TILES
+# include/modsx.h: modsx_caffe_counters, modsx_debug_caffe_geometry and modsx_caffe_jobs, in their order
+CAFFE_COUNTERS = ("calls", "regions", "border_regions", "launches")
+CAFFE_GEOMETRY = ("workgroups", "waves", "chunks", "chunk_cols", "lds_stride", "lds_bytes_gray", "lds_bytes_colour")
+CAFFE_JOB_FIELDS = ("curr_sc", "x", "y", "a11", "a12", "a21", "a22")
+CAFFE_MAX_PATCH, CAFFE_MAX_DIM = 255, 4096      # include/modsx.h: MODSX_CAFFE_MAX_PATCH, MODSX_CAFFE_MAX_DIM
+CAFFE_NORM_L2, CAFFE_NORM_L1, CAFFE_NORM_ROOTL2, CAFFE_NORM_NONE = 0, 1, 2, 3
+CAFFE_NORMS = {"L2": CAFFE_NORM_L2, "L1": CAFFE_NORM_L1, "RootL2": CAFFE_NORM_ROOTL2, "none": CAFFE_NORM_NONE}   # `Normalization=`
 DET_SURF, SURFDET_MAX_LAYERS = 6, 12      # include/modsx.h: MODSX_DET_SURF, MODSX_SURFDET_MAX_LAYERS
 DET_HESSIAN, DET_MSER = 0, 3              # include/modsx.h: MODSX_DET_HESSIAN, MODSX_DET_MSER
 # include/modsx.h: the float descriptor classes of a stored representation, and the first capacity of such a class in rows
@@ -416,6 +431,16 @@ def lib():
         L.modsx_debug_clahe.argtypes = [C.c_void_p] * 5
         L.modsx_clahe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_clahe_last_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.modsx_default_caffe_params.restype = None
+        L.modsx_default_caffe_params.argtypes = [C.c_void_p]
+        L.modsx_caffe_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_caffe_patches_device.argtypes = L.modsx_caffe_patches.argtypes
+        L.modsx_caffe_jobs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_debug_caffe_geometry.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.modsx_caffe_norm_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_caffe_norm_rows_device.argtypes = L.modsx_caffe_norm_rows.argtypes
+        L.modsx_caffe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_rep_append_f32_device.argtypes = L.modsx_rep_append_f32.argtypes
         L.modsx_synth_view.restype = C.c_void_p
         L.modsx_synth_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
@@ -607,6 +632,40 @@ def clahe_geometry(rows, cols, clip_limit=4.0, tiles=(8, 8), variant=0):
     g = dict(zip(CLAHE_GEOMETRY, (int(x) for x in out)))
     g["lut_scale"] = out[5:6].view(np.float32)[0]
     return g
+
+
+def caffe_params(mr_size=None, patch_size=None, mean=None):
+    """modsx_caffe_params; the defaults are the library's: mrSize 3 sqrt(3), patchSize 41, mean (104, 117, 123) in B, G, R order."""
+    p = CaffeParams()
+    lib().modsx_default_caffe_params(C.byref(p))
+    if mr_size is not None:
+        p.mrSize = float(mr_size)
+    if patch_size is not None:
+        p.patchSize = int(patch_size)
+    if mean is not None:
+        p.mean[0], p.mean[1], p.mean[2] = (float(m) for m in mean)
+    return p
+
+
+def caffe_jobs(regs, par, rows, cols):
+    """dict(curr_sc, x, y, a11, a12, a21, a22 [n] f32, border [n] bool): what the "CAFFE" branch calls interpolate with for every
+    region on planes of rows x cols, and interpolateCheckBorders for it -- from the function that fills the launcher's job table
+    (no device needed); raises for what the library refuses."""
+    regs = np.ascontiguousarray(regs, REGION)
+    n = len(regs)
+    out = np.zeros((max(n, 1), 8), np.float32)
+    _check(lib().modsx_caffe_jobs(_p(regs), n, C.byref(par), int(rows), int(cols), _p(out)), "caffe_jobs")
+    d = {k: out[:n, i].copy() for i, k in enumerate(CAFFE_JOB_FIELDS)}
+    d["border"] = out[:n, 7] != 0
+    return d
+
+
+def caffe_geometry(n, patch_size):
+    """dict of CAFFE_GEOMETRY: the work split the patch launcher uses for n regions at patch_size (no device needed)."""
+    out = np.zeros(len(CAFFE_GEOMETRY), np.int32)
+    got = _check(lib().modsx_debug_caffe_geometry(int(n), int(patch_size), _p(out)), "caffe_geometry")
+    assert got == len(CAFFE_GEOMETRY), got
+    return dict(zip(CAFFE_GEOMETRY, (int(x) for x in out)))
 
 
 def surfdet_normalise(params):
@@ -868,6 +927,12 @@ class Rep(object):
         return _check(lib().modsx_rep_append_f32((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs), _p(rows),
                                                  rows.shape[1], len(regs)), "rep_append_f32")
 
+    def append_f32_device(self, regs, rows_ptr, dim, detector=0, desc_type=DESC_CAFFE, ctx=None):
+        """append_f32 with the dense [n][dim] float32 rows in HBM (a 4-byte aligned device pointer).  Returns n."""
+        regs = np.ascontiguousarray(regs, REGION)
+        return _check(lib().modsx_rep_append_f32_device((ctx or self.ctx).h, self.h, int(detector), int(desc_type), _p(regs),
+                                                        C.c_void_p(rows_ptr), int(dim), len(regs)), "rep_append_f32_device")
+
     def describe_append(self, img, regs, detector=0, desc_type=DESC_SURF, mr_size=5.1962, patch_size=41, fast=0, photo_norm=1,
                         daisy_par=None, ctx=None):
         """Describes the (oriented) regions of one view image with the class's extractor (DESC_SURF, DESC_LIOP, DESC_DAISY) and
@@ -933,6 +998,7 @@ class Context(object):
     """One modsx_ctx (one HIP stream).  Raises if no gfx950 device is available."""
 
     def __init__(self, device=0):
+        self.device = int(device)
         self.h = lib().modsx_create(int(device))
         if not self.h:
             raise RuntimeError("modsx_create failed: " + _err())
@@ -1275,6 +1341,47 @@ class Context(object):
     def clahe_counters(self):
         """dict of CLAHE_COUNTERS: CLAHE work of this context since it was created (cumulative)."""
         return self._counters("modsx_clahe_counters", CLAHE_COUNTERS)
+
+    # ---- the learned-descriptor front end (engine_caffe.hip: the reference's "CAFFE" branch around its network) ----
+    def caffe_patches(self, planes, regs, par=None, out_ptr=None, want_flags=False):
+        """The network's input blob for the regions' reproj_kp on the ORIGINAL image: [n][3][P][P] float32, byte - mean.  planes:
+        one Image (gray) or three (B, G, R).  out_ptr: a device pointer that receives the blob instead (4-byte aligned); the blob
+        returned is then None.  want_flags: return (blob, flags [n] uint8: bit 0 border branch, bit 1 a sample outside)."""
+        planes = [planes] if isinstance(planes, Image) else list(planes)
+        par = par or caffe_params()
+        regs = np.ascontiguousarray(regs, REGION)
+        n, P = len(regs), par.patchSize
+        hs = (C.c_void_p * max(len(planes), 1))(*[im.h for im in planes])
+        flags = np.zeros(max(n, 1), np.uint8)
+        fp = _p(flags) if want_flags else None
+        blob = None
+        if out_ptr is not None:
+            _check(lib().modsx_caffe_patches_device(self._c(), hs, len(planes), _p(regs), n, C.byref(par), C.c_void_p(out_ptr), fp),
+                   "caffe_patches_device")
+        else:
+            blob = np.zeros((n, 3, max(P, 0), max(P, 0)), np.float32)
+            buf = blob if blob.size else np.zeros(1, np.float32)
+            _check(lib().modsx_caffe_patches(self._c(), hs, len(planes), _p(regs), n, C.byref(par), _p(buf), fp), "caffe_patches")
+        return (blob, flags[:n]) if want_flags else blob
+
+    def caffe_norm_rows(self, rows, norm=CAFFE_NORM_L2):
+        """L2normalize / L1normalize / RootNormalize / a copy (CAFFE_NORM_*) of [n][dim] float32 rows -> [n][dim] float32."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2:
+            raise ValueError("caffe_norm_rows: [n][dim] rows are expected")
+        out = np.zeros(rows.shape, np.float32)
+        a, b = (rows, out) if rows.size else (np.zeros(1, np.float32),) * 2
+        _check(lib().modsx_caffe_norm_rows(self._c(), _p(a), rows.shape[0], rows.shape[1], int(norm), _p(b)), "caffe_norm_rows")
+        return out
+
+    def caffe_norm_rows_device(self, rows_ptr, n, dim, norm=CAFFE_NORM_L2, out_ptr=None):
+        """the same on dense [n][dim] float32 rows in HBM (4-byte aligned); out_ptr = None: in place"""
+        _check(lib().modsx_caffe_norm_rows_device(self._c(), C.c_void_p(rows_ptr), int(n), int(dim), int(norm),
+                                                  C.c_void_p(rows_ptr if out_ptr is None else out_ptr)), "caffe_norm_rows_device")
+
+    def caffe_counters(self):
+        """dict of CAFFE_COUNTERS: front-end work of this context since it was created (cumulative)."""
+        return self._counters("modsx_caffe_counters", CAFFE_COUNTERS)
 
     def surfdet_counters(self):
         """dict of SURFDET_COUNTERS: SURF detector work of this context since it was created (cumulative)."""

@@ -2056,6 +2056,95 @@ int modsx_clahe_counters(modsx_ctx *ctx, long *out, int n) {
   return read_counters("modsx_clahe_counters", ctx->claheCounters, 6, out, n);
 }
 
+// ---- the learned-descriptor front end (engine_caffe.hip) ----
+void modsx_default_caffe_params(modsx_caffe_params *p) {
+  if (!p) return;
+  p->mrSize = 3.0 * sqrt(3.0);      // PatchExtractionParams
+  p->patchSize = 41;
+  p->mean[0] = 104; p->mean[1] = 117; p->mean[2] = 123;      // MeanB, MeanG, MeanR
+}
+// what both patch entries check before they look at the context
+static int caffe_args(const char *fn, const modsx_image *const *planes, int n_planes, const modsx_region *regs, int n,
+                      const modsx_caffe_params *par, const void *blob) {
+  if (!par) { mx::set_error(std::string(fn) + ": null argument: par"); return MODSX_ERR_ARG; }
+  const int rc = caffe_check(fn, *par);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!regs || !blob))) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  if (n_planes != 1 && n_planes != 3) { mx::set_error(std::string(fn) + ": 1 (gray) or 3 (B, G, R) planes"); return MODSX_ERR_ARG; }
+  if (!planes) { mx::set_error(std::string(fn) + ": null argument: planes"); return MODSX_ERR_ARG; }
+  for (int q = 0; q < n_planes; q++)
+    if (!planes[q]) { mx::set_error(std::string(fn) + ": null argument: a plane"); return MODSX_ERR_ARG; }
+  return MODSX_OK;
+}
+int modsx_caffe_patches(modsx_ctx *ctx, const modsx_image *const *planes, int n_planes, const modsx_region *regs, int n,
+                        const modsx_caffe_params *par, float *blob, unsigned char *flags) {
+  const char *fn = "modsx_caffe_patches";
+  const int rc = caffe_args(fn, planes, n_planes, regs, n, par, blob);
+  if (rc) return rc;
+  NEED(ctx);
+  RETURN_ROWS(caffe_patches(ctx, fn, planes, n_planes, regs, n, *par, blob, false, flags));
+}
+int modsx_caffe_patches_device(modsx_ctx *ctx, const modsx_image *const *planes, int n_planes, const modsx_region *regs, int n,
+                               const modsx_caffe_params *par, void *dev_blob, unsigned char *flags) {
+  const char *fn = "modsx_caffe_patches_device";
+  const int rc = caffe_args(fn, planes, n_planes, regs, n, par, dev_blob);
+  if (rc) return rc;
+  if ((uintptr_t)dev_blob & 3) { mx::set_error(std::string(fn) + ": the blob is not 4-byte aligned"); return MODSX_ERR_ARG; }
+  NEED(ctx);
+  RETURN_ROWS(caffe_patches(ctx, fn, planes, n_planes, regs, n, *par, (float *)dev_blob, true, flags));
+}
+int modsx_caffe_jobs(const modsx_region *regs, int n, const modsx_caffe_params *par, int rows, int cols, float *out) {
+  const char *fn = "modsx_caffe_jobs";
+  NEED(par);
+  const int rc = caffe_check(fn, *par);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!regs || !out)) || rows < 2 || cols < 2) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  std::vector<CaffeJob> jobs(n);
+  caffe_jobs(regs, n, *par, rows, cols, jobs.data());
+  for (int i = 0; i < n; i++) {
+    const CaffeJob &j = jobs[i];
+    const float v[8] = {j.sc, j.x, j.y, j.a11, j.a12, j.a21, j.a22, j.touch ? 1.f : 0.f};
+    memcpy(out + 8 * (size_t)i, v, sizeof v);
+  }
+  return n;
+}
+int modsx_debug_caffe_geometry(int n, int patchSize, int *out) {
+  NEED(out);
+  modsx_caffe_params p;
+  modsx_default_caffe_params(&p);
+  p.patchSize = patchSize;
+  const int rc = caffe_check("modsx_debug_caffe_geometry", p);
+  if (rc) return rc;
+  if (n < 0) { mx::set_error("modsx_debug_caffe_geometry: bad argument"); return MODSX_ERR_ARG; }
+  const CaffeGeo g = caffe_geometry(patchSize);
+  const int v[7] = {8 * ((n + 7) / 8), g.waves, g.chunks, g.chunkCols, g.stride, g.planeBytes, 3 * g.planeBytes};
+  memcpy(out, v, sizeof v);
+  return 7;
+}
+int modsx_caffe_norm_rows(modsx_ctx *ctx, const float *rows, int n, int dim, int norm, float *out) {
+  const char *fn = "modsx_caffe_norm_rows";
+  const int rc = caffe_norm_check(fn, n, dim, norm);
+  if (rc) return rc;
+  if (n > 0 && (!rows || !out)) { mx::set_error(std::string(fn) + ": bad argument"); return MODSX_ERR_ARG; }
+  NEED(ctx);
+  RETURN_ROWS(caffe_norm_rows(ctx, fn, rows, n, dim, norm, out, false));
+}
+int modsx_caffe_norm_rows_device(modsx_ctx *ctx, const void *dev_rows, int n, int dim, int norm, void *dev_out) {
+  const char *fn = "modsx_caffe_norm_rows_device";
+  const int rc = caffe_norm_check(fn, n, dim, norm);
+  if (rc) return rc;
+  if ((n > 0 && (!dev_rows || !dev_out)) || (((uintptr_t)dev_rows | (uintptr_t)dev_out) & 3)) {
+    mx::set_error(std::string(fn) + ": bad argument");
+    return MODSX_ERR_ARG;
+  }
+  NEED(ctx);
+  RETURN_ROWS(caffe_norm_rows(ctx, fn, (const float *)dev_rows, n, dim, norm, (float *)dev_out, true));
+}
+int modsx_caffe_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  return read_counters("modsx_caffe_counters", ctx->caffeCounters, 4, out, n);
+}
+
 // ---- DAISY (engine_daisy.hip) ----
 #define DAISY_ARGS(fn, bad)                                                                         \
   do {                                                                                                \

@@ -427,6 +427,7 @@ void ctx_destroy(modsx_ctx *c) {
   c->sdHost.release(); c->sdBack.release();
   for (DevBuf *b : {&c->claheTab, &c->clahePart, &c->claheLut, &c->claheDbg}) b->release();
   c->claheHost.release();
+  for (DevBuf *b : {&c->caffeJobs, &c->caffeFlags, &c->caffeOut}) b->release();
   for (DevBuf &b : c->daisyTab) b.release();
   PinBuf *pins[] = {&c->hCand, &c->hAff, &c->hOri, &c->hDesc, &c->hMisc, &c->hNms, &c->hMatch, &c->hViewTaps, &c->hViewJobs, &c->hMser};
   for (PinBuf *b : pins) b->release();

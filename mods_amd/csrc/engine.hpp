@@ -506,6 +506,36 @@ void launch_clahe_lut(hipStream_t s, const ClaheImg *imgs, int n, int tiles, int
                       int *dbgHist);
 void launch_clahe_apply(hipStream_t s, const ClaheImg *imgs, int n, int tx, int ty, int variant, int maxBlocks, const unsigned char *lut);
 
+// ---- the learned-descriptor front end (kernels_caffe.hip, engine_caffe.hip): the "CAFFE" branch, imagerepresentation.cpp:1343-1534 ----
+// one region: the f32 arguments interpolate() is called with (the products with curr_sc made), and whether
+// interpolateCheckBorders is true for them on the planes of the call
+struct CaffeJob { float x, y, a11, a12, a21, a22, sc; int touch; };
+static_assert(sizeof(CaffeJob) == 32, "caffe jobs are 32 bytes");
+constexpr int CAFFE_MAX_PATCH = 255;      // odd patch sizes 1 .. 255: one to four wavefronts of rows
+constexpr int CAFFE_COLS = 64;            // columns of the patch a workgroup samples before it stores them: one store row per wavefront
+constexpr int CAFFE_NORM_ROWS = 16;       // rows of a k_caffe_norm wavefront (one lane each sums a row) ...
+constexpr int CAFFE_NORM_COLS = 128;      // ... and the columns of the LDS tile they move through
+constexpr int CAFFE_MAX_DIM = 4096;
+// what a launch over P x P patches looks like (modsx_debug_caffe_geometry): wavefronts per workgroup (one lane per patch row),
+// column chunks, columns per chunk, LDS byte stride of a tile row (a multiple of 4, an odd number of dwords), LDS bytes per plane
+struct CaffeGeo { int waves, chunks, chunkCols, stride, planeBytes; };
+inline CaffeGeo caffe_geometry(int P) {
+  CaffeGeo g;
+  g.waves = (P + 63) / 64;
+  g.chunkCols = P < CAFFE_COLS ? P : CAFFE_COLS;
+  g.chunks = (P + g.chunkCols - 1) / g.chunkCols;
+  const int dw = (g.chunkCols + 3) / 4;
+  g.stride = 4 * (dw | 1);
+  g.planeBytes = g.stride * P;
+  return g;
+}
+// planes: 1 (gray, the byte goes to all three channels) or 3 (B, G, R) images of rows x cols; out [n][3][P][P] f32 (4-byte aligned);
+// flags [n] u8 (may be null): bit 0 = jobs[i].touch, bit 1 = a sample fell outside the plane
+void launch_caffe_patches(hipStream_t s, const CaffeJob *jobs, int n, const float *p0, const float *p1, const float *p2, int nplanes,
+                          int rows, int cols, int P, float m0, float m1, float m2, float *out, unsigned char *flags);
+// norm: MODSX_CAFFE_NORM_*; rows / out [n][dim] f32 (4-byte aligned), out may be rows
+void launch_caffe_norm(hipStream_t s, const float *rows, int n, int dim, int norm, float *out);
+
 }  // namespace mx
 
 namespace mx {
@@ -635,6 +665,10 @@ struct modsx_ctx {
   mx::PinBuf claheHost;
   long claheCounters[6] = {0, 0, 0, 0, 0, 0};
   double claheMs[3] = {0, 0, 0};   // under modsx_profile: event times of the last CLAHE call's three launches
+  // the learned-descriptor front end (engine_caffe.hip): the job table, the flags and, for a host caller, the blob or the rows of
+  // one call; modsx_caffe_counters: calls, regions, regions on the border branch, launches
+  mx::DevBuf caffeJobs, caffeFlags, caffeOut;
+  long caffeCounters[4] = {0, 0, 0, 0};
   // float classes of stored representations (engine_reps_f32.hip): dense rows of a device extractor on their way into a slot, and
   // modsx_fginn32_group_counters: grouped launch sets, problems in them, queries sent to resolve, resolve launches
   mx::DevBuf repStage;

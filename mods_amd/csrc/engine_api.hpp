@@ -48,6 +48,16 @@ int clahe_check(const char *fn, const modsx_clahe_params &p);
 int clahe_geometry(const char *fn, int rows, int cols, const modsx_clahe_params &p, ClaheGeo &g);
 int clahe_batch(modsx_ctx *c, const char *fn, const modsx_image *const *in, modsx_image *const *out, int n, const modsx_clahe_params &p,
                 int *dbgHist, unsigned char *dbgLut);
+// The learned-descriptor front end (engine_caffe.hip).  caffe_check / caffe_norm_check: the refusals that need no device (fn names
+// the entry in the error text); caffe_jobs: the per-region host work -- the function that fills the launcher's job table.
+// caffe_patches: blob [n][3][P][P] f32 on the host, or a device pointer (4-byte aligned) when onDevice; flags [n] u8 on the host or
+// null.  caffe_norm_rows: rows / out on the host, or device pointers when onDevice (out may be rows).  Both return after the work.
+int caffe_check(const char *fn, const modsx_caffe_params &p);
+int caffe_norm_check(const char *fn, int n, int dim, int norm);
+void caffe_jobs(const modsx_region *regs, int n, const modsx_caffe_params &p, int rows, int cols, CaffeJob *jobs);
+int caffe_patches(modsx_ctx *c, const char *fn, const modsx_image *const *planes, int nplanes, const modsx_region *regs, int n,
+                  const modsx_caffe_params &p, float *blob, bool onDevice, unsigned char *flags);
+int caffe_norm_rows(modsx_ctx *c, const char *fn, const float *rows, int n, int dim, int norm, float *out, bool onDevice);
 void detect_affine_regions(const modsx_keypoint *kps, int n, int img_id, int det_type, modsx_region *out);
 // reproj (optional, one entry per image): what the caller's reproject_regions will be called with.  A region that
 // reproject_certain_drop flags for it is treated like one at the view's border: no orientation job and no output entry,
@@ -395,7 +405,9 @@ int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const
 void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepClassList &classes, const RepTents &tents,
                       modsx_pair_result *res, int dev, VerifyTask &task);
 // float classes (engine_reps_f32.hip); det = the slot index rep_class_f32_ok gives
-int rep_append_f32(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const float *rows, int dim, int n);
+// rows: [n][dim] f32 on the host, or a device pointer (4-byte aligned) when onDevice
+int rep_append_f32(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const float *rows, int dim, int n,
+                   bool onDevice = false);
 int rep_describe_append(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_image *img, const modsx_region *regs, int n,
                         double mrSize, int patchSize, int fast, int photoNorm, const int *daisyPar);
 int rep_class_f32(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, float **rows, int *dim);

@@ -143,12 +143,17 @@ static int slot_store(const char *fn, modsx_ctx *c, RepSlotF &k, int dim, const 
   return MODSX_OK;
 }
 
-int rep_append_f32(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const float *rows, int dim, int n) {
+int rep_append_f32(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const float *rows, int dim, int n,
+                   bool onDevice) {
   CtxBusy busy(c);
   RepSlotF &k = fslot(rep, det, type);
-  int rc = append_args("modsx_rep_append_f32", c, rep, k, type, dim, n);
+  int rc = append_args(onDevice ? "modsx_rep_append_f32_device" : "modsx_rep_append_f32", c, rep, k, type, dim, n);
   if (rc) return rc;
   if (n == 0) return 0;
+  if (onDevice) {      // the rows are read where they lie; the pack kernel's flag word is the validity check
+    rc = slot_ingest("modsx_rep_append_f32_device", c, k, dim, regs, rows, n);
+    return rc ? rc : n;
+  }
   const size_t floats = (size_t)n * dim;
   if (!fginn32_rows_ok(rows, floats)) { set_error("modsx_rep_append_f32: rows must be finite with |x| <= 1e17"); return MODSX_ERR_ARG; }
   if (!c->repStage.ensure(floats * 4)) return MODSX_ERR_NOMEM;
@@ -364,6 +369,17 @@ int modsx_rep_append_f32(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_
   }
   hipSetDevice(ctx->dev);
   return rep_append_f32(ctx, rep, det, desc_type, regs, rows, dim, n);
+}
+
+int modsx_rep_append_f32_device(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const void *dev_rows,
+                                int dim, int n) {
+  int det;
+  if (!ctx || !rep || n < 0 || (n > 0 && (!regs || !dev_rows)) || ((uintptr_t)dev_rows & 3) || !rep_class_f32_ok(detector, desc_type, &det)) {
+    set_error("modsx_rep_append_f32_device: bad argument (detector HessianAffine / MSER / SURF, descriptor type MODSX_DESC_CAFFE .. MODSX_DESC_SURF, n >= 0 regions with 4-byte aligned [n][dim] device rows)");
+    return MODSX_ERR_ARG;
+  }
+  hipSetDevice(ctx->dev);
+  return rep_append_f32(ctx, rep, det, desc_type, regs, (const float *)dev_rows, dim, n, true);
 }
 
 int modsx_rep_describe_append(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_image *img, const modsx_region *regs,
