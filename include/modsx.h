@@ -379,8 +379,11 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
                             const modsx_image *const *imgs2, int n_pairs, const modsx_view *views, int n_views,
                             const modsx_pair_params *par, modsx_pair_result *results);
 
-/* host share of the last modsx_match_pairs / modsx_match_pairs_views call: wall time of DuplicateFiltering + LO-RANSAC summed over its pairs (ms),
- * the pairs verified and the helper threads that ran them (measurement hook) */
+/* host share of the process's last batch call: wall time of DuplicateFiltering + LO-RANSAC summed over its pairs (ms), the pairs
+ * verified and the contexts that worked on the call, min(n_ctx, groups), each with a helper thread (measurement hook).  Written by
+ * all four batch entries: modsx_match_pairs, modsx_match_pairs_views, modsx_match_reps, and modsx_match_one_to_many, which leaves
+ * the values of the last round of its ladder.  The same holds for modsx_debug_last_batch_verify_each and
+ * modsx_debug_last_batch_cpu.  A failed call leaves the values of the part that ran */
 int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads);
 /* shape of the process's most recent matcher launch, as used for its first problem: 32-query sets per wavefront (2 / 4), whole-CU
  * workgroups (0 / 1), splits of the train tiles, tiles per split, upper bound of the tile count (measurement hook).  The five

@@ -2027,7 +2027,8 @@ def last_batch_verify_each():
 
 
 def last_batch_verify():
-    """(summed ms of DuplicateFiltering + LO-RANSAC, pairs, helper threads) of the last match_pairs call."""
+    """(summed ms of DuplicateFiltering + LO-RANSAC, pairs verified, working contexts) of the last batch call: match_pairs,
+    match_pairs_views, match_reps, or the last round of match_one_to_many."""
     ms, n, t = C.c_double(), C.c_int(), C.c_int()
     lib().modsx_last_batch_verify(C.byref(ms), C.byref(n), C.byref(t))
     return ms.value, n.value, t.value
@@ -2425,14 +2426,16 @@ def _image_dims(handle):
     return st.rows, st.cols
 
 
+def _handles(objs):
+    """the handles (.h) of contexts, images or representations as a void* array; an empty list gives one unused entry"""
+    return (C.c_void_p * max(1, len(objs)))(*[o.h for o in objs])
+
+
 def match_pairs(ctxs, imgs1, imgs2, params):
     """modsx_match_pairs: a batch of pairs pipelined over several contexts (threads + streams)."""
     n = len(imgs1)
-    carr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    a1 = (C.c_void_p * n)(*[im.h for im in imgs1])
-    a2 = (C.c_void_p * n)(*[im.h for im in imgs2])
-    res = (PairResult * n)()
-    _check(lib().modsx_match_pairs(carr, len(ctxs), a1, a2, n, C.byref(params), res), "match_pairs")
+    res = (PairResult * max(1, n))()
+    _check(lib().modsx_match_pairs(_handles(ctxs), len(ctxs), _handles(imgs1), _handles(imgs2), n, C.byref(params), res), "match_pairs")
     return [_unpack_pair_result(res[i]) for i in range(n)]
 
 
@@ -2440,12 +2443,10 @@ def match_pairs_views(ctxs, imgs1, imgs2, views, params, arrays=True):
     """modsx_match_pairs_views: a batch of multi-view pairs over several contexts, verification on helper threads.
     arrays=False returns the counts and H only (the tentative / flag arrays are released without being copied out)."""
     n = len(imgs1)
-    carr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    a1 = (C.c_void_p * n)(*[im.h for im in imgs1])
-    a2 = (C.c_void_p * n)(*[im.h for im in imgs2])
     arr = _view_array(views)
-    res = (PairResult * n)()
-    _check(lib().modsx_match_pairs_views(carr, len(ctxs), a1, a2, n, arr, len(views), C.byref(params), res), "match_pairs_views")
+    res = (PairResult * max(1, n))()
+    _check(lib().modsx_match_pairs_views(_handles(ctxs), len(ctxs), _handles(imgs1), _handles(imgs2), n, arr, len(views), C.byref(params), res),
+           "match_pairs_views")
     return [_unpack_pair_result(res[i], arrays) for i in range(n)]
 
 
@@ -2455,14 +2456,12 @@ def match_reps(ctxs, rep1, reps2, params, classes=None, arrays=True):
     For a binary class (DESC_BRISK, DESC_FREAK, DESC_ORB) `ratio` is its DistanceThreshold; binary classes are matched only when
     they are listed."""
     n = len(reps2)
-    carr = (C.c_void_p * max(1, len(ctxs)))(*[c.h for c in ctxs])
-    rarr = (C.c_void_p * max(1, n))(*[r.h for r in reps2])
     classes = classes or []
     sel = (RepClassSel * max(1, len(classes)))()
     for i, (det, typ, ratio) in enumerate(classes):
         sel[i].detector, sel[i].desc_type, sel[i].ratio = int(det), int(typ), float(ratio)
     res = (PairResult * max(1, n))()
-    _check(lib().modsx_match_reps(carr, len(ctxs), rep1.h, rarr, n, sel, len(classes), C.addressof(params), res), "match_reps")
+    _check(lib().modsx_match_reps(_handles(ctxs), len(ctxs), rep1.h, _handles(reps2), n, sel, len(classes), C.addressof(params), res), "match_reps")
     return [_unpack_pair_result(res[i], arrays) for i in range(n)]
 
 
@@ -2471,31 +2470,28 @@ def match_one_to_many(ctxs, img1, imgs2, steps, params, min_matches=10, arrays=T
     Context.match_ladder); the loop ends after the first step in which any partner reached min_matches verified.
     Returns (list of per-partner results, steps executed)."""
     n = len(imgs2)
-    carr = (C.c_void_p * max(1, len(ctxs)))(*[c.h for c in ctxs])
-    a2 = (C.c_void_p * max(1, n))(*[im.h for im in imgs2])
     arr, keep = _ladder_steps(steps)
     res = (PairResult * max(1, n))()
     done = C.c_int(0)
-    _check(lib().modsx_match_one_to_many(carr, len(ctxs), img1.h, a2, n, arr, len(steps), int(min_matches), C.addressof(params),
-                                         res, C.byref(done)), "match_one_to_many")
+    _check(lib().modsx_match_one_to_many(_handles(ctxs), len(ctxs), img1.h, _handles(imgs2), n, arr, len(steps), int(min_matches),
+                                         C.addressof(params), res, C.byref(done)), "match_one_to_many")
     return [_unpack_pair_result(res[i], arrays) for i in range(n)], done.value
 
 
 def _unpack_pair_result(res, arrays=True):
-    if True:
-        T = res.n_unique if arrays else 0
-        out = dict(n_regions=(res.n_regions1, res.n_regions2), n_tentatives=res.n_tentatives, n_unique=res.n_unique,
-                   n_ransac_inliers=res.n_ransac_inliers, n_verified=res.n_verified,
-                   ransac_samples=res.ransac_samples, ransac_lo=res.ransac_lo,
-                   H=np.array(list(res.H)).reshape(3, 3))
-        if T > 0:
-            out["tentatives"] = np.frombuffer((C.c_char * (T * TENT.itemsize)).from_address(res.tentatives),
-                                              dtype=TENT, count=T).copy()
-            out["ransac_inlier"] = np.frombuffer((C.c_char * T).from_address(res.ransac_inlier), np.uint8, T).astype(bool)
-            out["verified"] = np.frombuffer((C.c_char * T).from_address(res.verified), np.uint8, T).astype(bool)
-        else:
-            out["tentatives"] = np.zeros(0, TENT)
-            out["ransac_inlier"] = np.zeros(0, bool)
-            out["verified"] = np.zeros(0, bool)
-        lib().modsx_pair_result_release(C.byref(res))
-        return out
+    T = res.n_unique if arrays else 0
+    out = dict(n_regions=(res.n_regions1, res.n_regions2), n_tentatives=res.n_tentatives, n_unique=res.n_unique,
+               n_ransac_inliers=res.n_ransac_inliers, n_verified=res.n_verified,
+               ransac_samples=res.ransac_samples, ransac_lo=res.ransac_lo,
+               H=np.array(list(res.H)).reshape(3, 3))
+    if T > 0:
+        out["tentatives"] = np.frombuffer((C.c_char * (T * TENT.itemsize)).from_address(res.tentatives),
+                                          dtype=TENT, count=T).copy()
+        out["ransac_inlier"] = np.frombuffer((C.c_char * T).from_address(res.ransac_inlier), np.uint8, T).astype(bool)
+        out["verified"] = np.frombuffer((C.c_char * T).from_address(res.verified), np.uint8, T).astype(bool)
+    else:
+        out["tentatives"] = np.zeros(0, TENT)
+        out["ransac_inlier"] = np.zeros(0, bool)
+        out["verified"] = np.zeros(0, bool)
+    lib().modsx_pair_result_release(C.byref(res))
+    return out

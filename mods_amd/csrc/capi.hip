@@ -5,9 +5,7 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
-#include <thread>
-#include <condition_variable>
-#include <deque>
+#include "batch_driver.hpp"
 #include "engine_api.hpp"
 #include "describe_plan.hpp"
 #include "views_plan.hpp"
@@ -27,22 +25,15 @@ static T *to_malloc(const std::vector<T> &v) {
   return p;
 }
 
-// host share of the last modsx_match_pairs call: summed wall time of DuplicateFiltering + LO-RANSAC over its pairs, and
-// the number of helper threads that ran them
-static std::atomic<long> g_verifyUs(0);
-static std::atomic<int> g_verifyThreads(0), g_verifyPairs(0);
-static std::mutex g_verifyEachMu;
-static std::vector<int> g_verifyEachUs;    // verification time of every pair of the last batch call, in completion order
-static void verify_timed(mx::VerifyTask &t, const modsx_pair_params &pp);
-// CPU time (not wall) of the last batch call, by kind of thread: the contexts' own threads and the verification helpers
-static std::atomic<long> g_cpuWorkerUs(0), g_cpuHelperUs(0);
-// helper threads of a batch call: one per working context unless MODSX_VERIFY_HELPERS says otherwise
-static int verify_helpers(int nw) {
+// The host share of the process's last batch call (modsx_match_pairs, modsx_match_pairs_views, modsx_match_reps; for
+// modsx_match_one_to_many the last round of its ladder): DuplicateFiltering + LO-RANSAC of its pairs are the tasks of run_batch
+// (batch_driver.hpp), which resets these statistics when a run starts.
+static mx::BatchStats g_batch;
+// helper threads of a batch call: one per working context unless MODSX_VERIFY_HELPERS gives a smaller number
+static int verify_helper_cap() {
   static const int cap = getenv("MODSX_VERIFY_HELPERS") ? atoi(getenv("MODSX_VERIFY_HELPERS")) : 0;
-  return cap > 0 ? (cap < nw ? cap : nw) : nw;
+  return cap;
 }
-static long thread_cpu_us() { timespec t; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t); return t.tv_sec * 1000000L + t.tv_nsec / 1000; }
-struct ThreadCpu { std::atomic<long> &acc; long t0; explicit ThreadCpu(std::atomic<long> &a) : acc(a), t0(thread_cpu_us()) {} ~ThreadCpu() { acc += thread_cpu_us() - t0; } };
 
 extern "C" {
 
@@ -726,21 +717,33 @@ int modsx_loransac_h_errtype(const double *pts, const double *laf1, const double
                     seed, H, Hraw, inl, keep, data_out, error_type);
 }
 
+// the consumer of the batch calls: DuplicateFiltering + LO-RANSAC of one matched pair, timed
 static void verify_timed(mx::VerifyTask &t, const modsx_pair_params &pp) {
+  hipSetDevice(t.dev);     // a new thread starts on device 0: the verifier's device-side loops belong on the producing context's GPU
   const auto v0 = std::chrono::steady_clock::now();
   mx::verify_tentatives(t.l1, t.l2, t.tents, pp, t.res);
-  const long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - v0).count();
-  g_verifyUs += us;
-  g_verifyPairs++;
-  std::lock_guard<std::mutex> lk(g_verifyEachMu);
-  g_verifyEachUs.push_back((int)us);
+  g_batch.add(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - v0).count());
 }
-// the caller's current HIP device is its own: worker(0) of the batch calls runs on the caller's thread and sets the contexts'
+// the caller's current HIP device is its own: worker 0 of the batch calls runs on the caller's thread and sets the contexts'.
+// Every public batch entry holds exactly one.
 struct DeviceGuard {
   int dev = -1;
   DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
   ~DeviceGuard() { if (dev >= 0) hipSetDevice(dev); }
 };
+// all contexts of a batch call search the same descriptor database, or none
+static int same_fginn_db(modsx_ctx *const *ctxs, int n_ctx, const char *who) {
+  for (int i = 1; i < n_ctx; i++)
+    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error(std::string(who) + ": all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
+  return MODSX_OK;
+}
+// the end of a batch call: n on success; a failed batch returns no results -- what the successful groups already own is released
+static int batch_return(const mx::BatchError &err, modsx_pair_result *results, int n) {
+  if (!err.rc) return n;
+  for (int i = 0; i < n; i++) modsx_pair_result_release(&results[i]);
+  mx::set_error(err.text);
+  return err.rc;
+}
 
 int modsx_match_pair(modsx_ctx *ctx, const modsx_image *img1, const modsx_image *img2, const modsx_pair_params *par,
                      modsx_pair_result *res) {
@@ -755,98 +758,21 @@ int modsx_match_pairs(modsx_ctx *const *ctxs, int n_ctx, const modsx_image *cons
   NEED(ctxs); NEED(par); NEED(results);
   if (n_ctx <= 0 || n_pairs < 0 || (n_pairs > 0 && (!imgs1 || !imgs2))) { mx::set_error("modsx_match_pairs: bad argument"); return MODSX_ERR_ARG; }
   for (int i = 0; i < n_ctx; i++) NEED(ctxs[i]);
-  for (int i = 1; i < n_ctx; i++)
-    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error("modsx_match_pairs: all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
+  { const int rc = same_fginn_db(ctxs, n_ctx, "modsx_match_pairs"); if (rc) return rc; }
   for (int i = 0; i < n_pairs; i++) memset(&results[i], 0, sizeof results[i]);   // no result owns arrays before its group ran
-  std::atomic<int> next(0), failed(0);
-  std::string firstErr;
-  std::mutex *mu = new std::mutex();
-  // every context takes up to MAXB / 2 pairs at a time and runs their 2g images as one batch; the group shrinks so
-  // that all contexts get work when the batch is small
-  int group = (n_pairs + n_ctx - 1) / n_ctx;
-  if (group > mx::PAIR_GROUP) group = mx::PAIR_GROUP;
-  if (group < 1) group = 1;
-  // Verification (DuplicateFiltering + LO-RANSAC, ~1.4 ms of host time per pair against ~0.9 ms of device time) runs on
-  // helper threads, one per working context: the context's own thread goes straight on to the next group, so its
-  // stream is idle only while the host prepares job tables, not while it runs RANSAC.
-  struct Queue {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<mx::VerifyTask> q;
-    bool done = false;
-  } vq;
   const modsx_pair_params pp = *par;
-  auto helper = [&]() {
-    ThreadCpu cpu(g_cpuHelperUs);
-    for (;;) {
-      mx::VerifyTask t;
-      {
-        std::unique_lock<std::mutex> lk(vq.m);
-        vq.cv.wait(lk, [&] { return vq.done || !vq.q.empty(); });
-        if (vq.q.empty()) return;
-        t = std::move(vq.q.front());
-        vq.q.pop_front();
-      }
-      hipSetDevice(t.dev);     // a new thread starts on device 0: the verifier's device-side loops belong on the producing context's GPU
-      verify_timed(t, pp);
-    }
-  };
-  auto worker = [&](int w) {
-    modsx_ctx *c = ctxs[w];
-    ThreadCpu cpu(g_cpuWorkerUs);
-    hipSetDevice(c->dev);
-    std::vector<mx::VerifyTask> tasks;
-    for (;;) {
-      if (failed.load()) break;   // another group failed: the batch is lost, stop feeding the stream
-      int i = next.fetch_add(group);
-      if (i >= n_pairs) break;
-      const int g = (n_pairs - i) < group ? (n_pairs - i) : group;
-      tasks.clear();
-      int rc = match_pair_group(c, imgs1 + i, imgs2 + i, g, pp, &results[i], &tasks);
-      if (rc) {
-        std::lock_guard<std::mutex> g(*mu);
-        if (!failed.exchange(rc)) firstErr = mx::last_error();
-      }
-      if (!tasks.empty()) {
-        { std::lock_guard<std::mutex> lk(vq.m); for (auto &t : tasks) vq.q.push_back(std::move(t)); }
-        vq.cv.notify_all();
-      }
-    }
-    // out of pairs: the context's thread helps the verification helpers with what is still queued (the tail of a batch call is
-    // the verification of its last pairs, with the device already idle)
-    for (;;) {
-      mx::VerifyTask t;
-      {
-        std::lock_guard<std::mutex> lk(vq.m);
-        if (vq.q.empty()) break;
-        t = std::move(vq.q.front());
-        vq.q.pop_front();
-      }
-      hipSetDevice(t.dev);
-      verify_timed(t, pp);
-    }
-  };
-  std::vector<std::thread> th, hth;
-  const int ngroups = (n_pairs + group - 1) / group;
-  const int nw = n_ctx < ngroups ? n_ctx : ngroups;
-  g_verifyUs = 0; g_verifyPairs = 0; g_verifyThreads = nw; g_cpuWorkerUs = 0; g_cpuHelperUs = 0;
-  { std::lock_guard<std::mutex> lk(g_verifyEachMu); g_verifyEachUs.clear(); }
   DeviceGuard restoreCallerDevice;
-  for (int w = 0; w < verify_helpers(nw); w++) hth.emplace_back(helper);
-  for (int w = 1; w < nw; w++) th.emplace_back(worker, w);
-  if (nw > 0) worker(0);
-  for (auto &t : th) t.join();
-  { std::lock_guard<std::mutex> lk(vq.m); vq.done = true; }
-  vq.cv.notify_all();
-  for (auto &t : hth) t.join();
-  delete mu;
-  if (failed.load()) {
-    // a failed batch returns no results: release what the successful groups already own
-    for (int i = 0; i < n_pairs; i++) modsx_pair_result_release(&results[i]);
-    mx::set_error(firstErr);
-    return failed.load();
-  }
-  return n_pairs;
+  // Every context takes up to PAIR_GROUP pairs at a time and runs their 2g images as one batch.  Verification (DuplicateFiltering +
+  // LO-RANSAC, ~1.4 ms of host time per pair against ~0.9 ms of device time) runs on helper threads: the context's own thread goes
+  // straight on to the next group, so its stream is idle only while the host prepares job tables, not while it runs RANSAC.
+  const mx::BatchError err = mx::run_batch<mx::VerifyTask>(
+      n_ctx, n_pairs, mx::PAIR_GROUP, verify_helper_cap(), g_batch,
+      [&](int w, int i, int g, std::vector<mx::VerifyTask> &tasks) {
+        hipSetDevice(ctxs[w]->dev);
+        return match_pair_group(ctxs[w], imgs1 + i, imgs2 + i, g, pp, &results[i], &tasks);
+      },
+      [&](mx::VerifyTask &t) { verify_timed(t, pp); }, mx::last_error);
+  return batch_return(err, results, n_pairs);
 }
 
 // modsx_match_pairs for multi-view pairs: every context takes one pair at a time (the pairs come off a shared counter), runs
@@ -862,167 +788,54 @@ int modsx_match_pairs_views(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
     return MODSX_ERR_ARG;
   }
   for (int i = 0; i < n_ctx; i++) NEED(ctxs[i]);
-  for (int i = 1; i < n_ctx; i++)
-    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error("modsx_match_pairs_views: all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
+  { const int rc = same_fginn_db(ctxs, n_ctx, "modsx_match_pairs_views"); if (rc) return rc; }
   for (int i = 0; i < n_pairs; i++) memset(&results[i], 0, sizeof results[i]);
-  std::atomic<int> next(0), failed(0);
-  std::string firstErr;
-  std::mutex mu;
-  struct Queue {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<mx::VerifyTask> q;
-    bool done = false;
-  } vq;
   const modsx_pair_params pp = *par;
-  auto helper = [&]() {
-    ThreadCpu cpu(g_cpuHelperUs);
-    for (;;) {
-      mx::VerifyTask t;
-      {
-        std::unique_lock<std::mutex> lk(vq.m);
-        vq.cv.wait(lk, [&] { return vq.done || !vq.q.empty(); });
-        if (vq.q.empty()) return;
-        t = std::move(vq.q.front());
-        vq.q.pop_front();
-      }
-      hipSetDevice(t.dev);     // a new thread starts on device 0: the verifier's device-side loops belong on the producing context's GPU
-      verify_timed(t, pp);
-    }
-  };
-  auto worker = [&](int w) {
-    modsx_ctx *c = ctxs[w];
-    ThreadCpu cpu(g_cpuWorkerUs);
-    hipSetDevice(c->dev);
-    for (;;) {
-      if (failed.load()) break;
-      const int i = next.fetch_add(1);
-      if (i >= n_pairs) break;
-      mx::VerifyTask task;
-      const int rc = mx::match_pair_views(c, imgs1[i], imgs2[i], views, n_views, pp, &results[i], &task);
-      if (rc) {
-        std::lock_guard<std::mutex> g(mu);
-        if (!failed.exchange(rc)) firstErr = mx::last_error();
-        continue;
-      }
-      { std::lock_guard<std::mutex> lk(vq.m); vq.q.push_back(std::move(task)); }
-      vq.cv.notify_one();
-    }
-    for (;;) {      // out of pairs: help with the verifications still queued (see modsx_match_pairs)
-      mx::VerifyTask t;
-      {
-        std::lock_guard<std::mutex> lk(vq.m);
-        if (vq.q.empty()) break;
-        t = std::move(vq.q.front());
-        vq.q.pop_front();
-      }
-      hipSetDevice(t.dev);
-      verify_timed(t, pp);
-    }
-  };
-  std::vector<std::thread> th, hth;
-  const int nw = n_ctx < n_pairs ? n_ctx : n_pairs;
-  g_verifyUs = 0; g_verifyPairs = 0; g_verifyThreads = nw; g_cpuWorkerUs = 0; g_cpuHelperUs = 0;
-  { std::lock_guard<std::mutex> lk(g_verifyEachMu); g_verifyEachUs.clear(); }
   DeviceGuard restoreCallerDevice;
-  for (int w = 0; w < verify_helpers(nw); w++) hth.emplace_back(helper);
-  for (int w = 1; w < nw; w++) th.emplace_back(worker, w);
-  if (nw > 0) worker(0);
-  for (auto &t : th) t.join();
-  { std::lock_guard<std::mutex> lk(vq.m); vq.done = true; }
-  vq.cv.notify_all();
-  for (auto &t : hth) t.join();
-  if (failed.load()) {
-    for (int i = 0; i < n_pairs; i++) modsx_pair_result_release(&results[i]);
-    mx::set_error(firstErr);
-    return failed.load();
-  }
-  return n_pairs;
+  const mx::BatchError err = mx::run_batch<mx::VerifyTask>(
+      n_ctx, n_pairs, 1, verify_helper_cap(), g_batch,
+      [&](int w, int i, int, std::vector<mx::VerifyTask> &tasks) {
+        hipSetDevice(ctxs[w]->dev);
+        tasks.emplace_back();
+        return mx::match_pair_views(ctxs[w], imgs1[i], imgs2[i], views, n_views, pp, &results[i], &tasks.back());
+      },
+      [&](mx::VerifyTask &t) { verify_timed(t, pp); }, mx::last_error);
+  return batch_return(err, results, n_pairs);
 }
 
 // ---- stored representations: one against many (engine_reps.hip) ---------------------------------------------------------------
 // One round of MatchImgReps + verification of rep1 against n partners: the contexts take groups of up to MATCH_MAXB partners off
 // a shared counter, a group costs one matcher launch set per class of sel; every partner's tentatives (tents[i], the classes of
 // sel replaced, the others kept) are verified over the ordered class list `present`, on helper threads while the contexts go on.
-// results[i] must own nothing or the arrays of an earlier round (released here).  The round is over when it returns.
-static int reps_round(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
-                      const modsx_rep_class_sel *sel, int nsel, const mx::RepClassList &present, const modsx_pair_params &pp, mx::RepTents *tents,
-                      modsx_pair_result *results) {
-  std::atomic<int> next(0), failed(0);
-  std::string firstErr;
-  std::mutex mu;
-  struct Queue {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<mx::VerifyTask> q;
-    bool done = false;
-  } vq;
-  int group = (n + n_ctx - 1) / n_ctx;       // the group shrinks so that all contexts get work when there are few partners
-  if (group > mx::MATCH_MAXB) group = mx::MATCH_MAXB;
-  if (group < 1) group = 1;
-  auto take = [&](mx::VerifyTask &t, bool wait) {
-    std::unique_lock<std::mutex> lk(vq.m);
-    if (wait) vq.cv.wait(lk, [&] { return vq.done || !vq.q.empty(); });
-    if (vq.q.empty()) return false;
-    t = std::move(vq.q.front());
-    vq.q.pop_front();
-    return true;
-  };
-  auto helper = [&]() {
-    ThreadCpu cpu(g_cpuHelperUs);
-    mx::VerifyTask t;
-    while (take(t, true)) { hipSetDevice(t.dev); verify_timed(t, pp); }
-  };
-  auto worker = [&](int w) {
-    modsx_ctx *c = ctxs[w];
-    ThreadCpu cpu(g_cpuWorkerUs);
-    hipSetDevice(c->dev);
-    for (;;) {
-      if (failed.load()) break;
-      const int i = next.fetch_add(group);
-      if (i >= n) break;
-      const int g = (n - i) < group ? (n - i) : group;
-      mx::RepTents *tp[mx::MATCH_MAXB];
-      for (int k = 0; k < g; k++) tp[k] = &tents[i + k];
-      const int rc = mx::reps_match_group(c, rep1, reps2 + i, g, sel, nsel, pp, tp);
-      if (rc) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!failed.exchange(rc)) firstErr = mx::last_error();
-        continue;
-      }
-      for (int k = 0; k < g; k++) {
-        mx::VerifyTask task;
-        modsx_pair_result_release(&results[i + k]);
-        mx::reps_verify_task(rep1, reps2[i + k], present, tents[i + k], &results[i + k], c->dev, task);
-        { std::lock_guard<std::mutex> lk(vq.m); vq.q.push_back(std::move(task)); }
-        vq.cv.notify_one();
-      }
-    }
-    mx::VerifyTask t;      // out of partners: help with the verifications still queued (see modsx_match_pairs)
-    while (take(t, false)) { hipSetDevice(t.dev); verify_timed(t, pp); }
-  };
-  std::vector<std::thread> th, hth;
-  const int ngroups = (n + group - 1) / group;
-  const int nw = n_ctx < ngroups ? n_ctx : ngroups;
-  g_verifyUs = 0; g_verifyPairs = 0; g_verifyThreads = nw; g_cpuWorkerUs = 0; g_cpuHelperUs = 0;
-  { std::lock_guard<std::mutex> lk(g_verifyEachMu); g_verifyEachUs.clear(); }
-  for (int w = 0; w < verify_helpers(nw); w++) hth.emplace_back(helper);
-  for (int w = 1; w < nw; w++) th.emplace_back(worker, w);
-  if (nw > 0) worker(0);
-  for (auto &t : th) t.join();
-  { std::lock_guard<std::mutex> lk(vq.m); vq.done = true; }
-  vq.cv.notify_all();
-  for (auto &t : hth) t.join();
-  if (failed.load()) { mx::set_error(firstErr); return failed.load(); }
-  return MODSX_OK;
+// results[i] must own nothing or the arrays of an earlier round (released here).  The round is over when it returns.  The caller
+// holds the DeviceGuard.
+static mx::BatchError reps_round(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, const modsx_rep *const *reps2, int n,
+                                 const modsx_rep_class_sel *sel, int nsel, const mx::RepClassList &present, const modsx_pair_params &pp,
+                                 mx::RepTents *tents, modsx_pair_result *results) {
+  return mx::run_batch<mx::VerifyTask>(
+      n_ctx, n, mx::MATCH_MAXB, verify_helper_cap(), g_batch,
+      [&](int w, int i, int g, std::vector<mx::VerifyTask> &tasks) {
+        modsx_ctx *c = ctxs[w];
+        hipSetDevice(c->dev);
+        mx::RepTents *tp[mx::MATCH_MAXB];
+        for (int k = 0; k < g; k++) tp[k] = &tents[i + k];
+        const int rc = mx::reps_match_group(c, rep1, reps2 + i, g, sel, nsel, pp, tp);
+        if (rc) return rc;
+        tasks.resize(g);
+        for (int k = 0; k < g; k++) {
+          modsx_pair_result_release(&results[i + k]);
+          mx::reps_verify_task(rep1, reps2[i + k], present, tents[i + k], &results[i + k], c->dev, tasks[k]);
+        }
+        return (int)MODSX_OK;
+      },
+      [&](mx::VerifyTask &t) { verify_timed(t, pp); }, mx::last_error);
 }
 static int reps_contexts_ok(modsx_ctx *const *ctxs, int n_ctx, const char *who) {
   if (!ctxs || n_ctx < 1) { mx::set_error(std::string(who) + ": at least one context is needed"); return MODSX_ERR_ARG; }
   for (int i = 0; i < n_ctx; i++) if (!ctxs[i]) { mx::set_error(std::string(who) + ": null context"); return MODSX_ERR_ARG; }
-  for (int i = 1; i < n_ctx; i++) {
-    if (ctxs[i]->fginnDb != ctxs[0]->fginnDb) { mx::set_error(std::string(who) + ": all contexts of a call must have the same descriptor database attached, or none"); return MODSX_ERR_ARG; }
+  { const int rc = same_fginn_db(ctxs, n_ctx, who); if (rc) return rc; }
+  for (int i = 1; i < n_ctx; i++)
     if (ctxs[i]->dev != ctxs[0]->dev) { mx::set_error(std::string(who) + ": the contexts must share one device (that of the representations)"); return MODSX_ERR_ARG; }
-  }
   return MODSX_OK;
 }
 
@@ -1076,9 +889,7 @@ int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, c
   if (n == 0) return 0;
   DeviceGuard restoreCallerDevice;
   std::vector<mx::RepTents> tents((size_t)n);
-  const int rc = reps_round(ctxs, n_ctx, rep1, reps2, n, sel, nsel, present, *par, tents.data(), results);
-  if (rc) { for (int i = 0; i < n; i++) modsx_pair_result_release(&results[i]); return rc; }
-  return n;
+  return batch_return(reps_round(ctxs, n_ctx, rep1, reps2, n, sel, nsel, present, *par, tents.data(), results), results, n);
 }
 
 int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image *img1, const modsx_image *const *imgs2, int n,
@@ -1100,46 +911,32 @@ int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
   std::vector<mx::RepTents> tents((size_t)n);
   mx::RepClassList u8Classes;      // the ladder carries the SIFT-family classes only
   mx::rep_classes_u8(u8Classes);
-  int rc = MODSX_OK, step = 0;
+  mx::BatchError err;
+  int step = 0;
   bool reached = false;
-  for (; step < nsteps && !reached && !rc; step++) {
+  for (; step < nsteps && !reached; step++) {
     // SynthDetectDescribeKeypoints + AddRegions of the step: the n + 1 images come off a shared counter
-    std::atomic<int> next(0), failed(0);
-    std::string firstErr;
-    std::mutex mu;
-    auto grow = [&](int w) {
-      hipSetDevice(ctxs[w]->dev);
-      for (;;) {
-        if (failed.load()) break;
-        const int i = next.fetch_add(1);
-        if (i > n) break;
-        const int ra = mx::rep_add_views(ctxs[w], reps[i], i ? imgs2[i - 1] : img1, steps[step], *par);
-        if (ra < 0) {
-          std::lock_guard<std::mutex> lk(mu);
-          if (!failed.exchange(ra)) firstErr = mx::last_error();
-        }
-      }
-    };
-    {
-      std::vector<std::thread> th;
-      const int nw = n_ctx < n + 1 ? n_ctx : n + 1;
-      for (int w = 1; w < nw; w++) th.emplace_back(grow, w);
-      grow(0);
-      for (auto &t : th) t.join();
-    }
-    if (failed.load()) { rc = failed.load(); mx::set_error(firstErr); break; }
+    err = mx::run_groups(
+        n_ctx, n + 1, 1,
+        [&](int w, int i, int) {
+          hipSetDevice(ctxs[w]->dev);
+          const int ra = mx::rep_add_views(ctxs[w], reps[i], i ? imgs2[i - 1] : img1, steps[step], *par);
+          return ra < 0 ? ra : 0;
+        },
+        mx::last_error, [](int) {});
+    if (err.rc) break;
     // MatchImgReps re-matches the classes of the step's detector with the step's ratios; the verified set comes from all classes
     mx::DescSet ds;
-    rc = mx::resolve_descs(*par, &steps[step], ds);
-    if (rc) break;
+    err.rc = mx::resolve_descs(*par, &steps[step], ds);
+    if (err.rc) { err.text = mx::last_error(); break; }
     modsx_rep_class_sel sel[MODSX_MAX_DESC];
     for (int j = 0; j < ds.n; j++) { sel[j].detector = steps[step].detector == MODSX_DET_MSER ? MODSX_DET_MSER : MODSX_DET_HESSIAN; sel[j].desc_type = ds.type[j]; sel[j].ratio = ds.ratio[j]; }
-    rc = reps_round(ctxs, n_ctx, reps[0], reps.data() + 1, n, sel, ds.n, u8Classes, *par, tents.data(), results);
-    if (rc) break;
+    err = reps_round(ctxs, n_ctx, reps[0], reps.data() + 1, n, sel, ds.n, u8Classes, *par, tents.data(), results);
+    if (err.rc) break;
     for (int i = 0; i < n; i++) reached = reached || results[i].n_verified >= min_matches;
   }
   for (auto &r : reps) modsx_rep_free(ctxs[0], r);
-  if (rc) { for (int i = 0; i < n; i++) modsx_pair_result_release(&results[i]); return rc; }
+  if (err.rc) return batch_return(err, results, n);
   if (steps_done) *steps_done = step;
   return n;
 }
@@ -1151,9 +948,9 @@ void modsx_pair_result_release(modsx_pair_result *res) {
 }
 
 int modsx_last_batch_verify(double *sum_ms, int *pairs, int *threads) {
-  if (sum_ms) *sum_ms = g_verifyUs.load() / 1000.0;
-  if (pairs) *pairs = g_verifyPairs.load();
-  if (threads) *threads = g_verifyThreads.load();
+  if (sum_ms) *sum_ms = g_batch.taskUs.load() / 1000.0;
+  if (pairs) *pairs = g_batch.tasks.load();
+  if (threads) *threads = g_batch.workers.load();
   return MODSX_OK;
 }
 
@@ -1162,18 +959,20 @@ int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, i
   return MODSX_OK;
 }
 
-// verification time (DuplicateFiltering + LO-RANSAC + the LAF checks, wall of the verifying thread) of every pair of the last batch call
+// verification time (DuplicateFiltering + LO-RANSAC + the LAF checks, wall of the verifying thread) of every pair of the last batch
+// call, in completion order.  Written by the four batch entries as modsx_last_batch_verify is (modsx.h).
 extern "C" __attribute__((visibility("default"))) int modsx_debug_last_batch_verify_each(double *ms, int cap) {
-  std::lock_guard<std::mutex> lk(g_verifyEachMu);
-  const int n = (int)g_verifyEachUs.size();
-  for (int i = 0; i < n && i < cap; i++) ms[i] = g_verifyEachUs[i] / 1000.0;
+  std::lock_guard<std::mutex> lk(g_batch.eachMu);
+  const int n = (int)g_batch.eachUs.size();
+  for (int i = 0; i < n && i < cap; i++) ms[i] = g_batch.eachUs[i] / 1000.0;
   return n;
 }
 
-// CPU seconds (thread CPU clocks, not wall) the last batch call spent in the contexts' own threads and in its verification helpers
+// CPU seconds (thread CPU clocks, not wall) the last batch call spent in the contexts' own threads (matching, and verifying once
+// they are out of pairs) and in its verification helpers.  Written by the four batch entries as modsx_last_batch_verify is.
 extern "C" __attribute__((visibility("default"))) int modsx_debug_last_batch_cpu(double *worker_s, double *helper_s) {
-  if (worker_s) *worker_s = g_cpuWorkerUs.load() / 1e6;
-  if (helper_s) *helper_s = g_cpuHelperUs.load() / 1e6;
+  if (worker_s) *worker_s = g_batch.cpuWorkerUs.load() / 1e6;
+  if (helper_s) *helper_s = g_batch.cpuHelperUs.load() / 1e6;
   return MODSX_OK;
 }
 

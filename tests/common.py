@@ -80,6 +80,16 @@ def grouped_pair_hosts(a, b):
     return [(a, b), (blank, b2), (a2, b2), (a3, b3), (b, a), (a2, b3[:200, :]), (a3, blank), (a, b), (b2, a2), (blank, blank)]
 
 
+def check_batch_statistics(modsx, n_ctx, n, group_cap):
+    """After a batch call over n items: every item was verified once and timed once, and the call worked with
+    min(n_ctx, ceil(n / group)) contexts, group = clamp(ceil(n / n_ctx), 1, group_cap) (PAIR_GROUP = MATCH_MAXB = 4, or 1 for the
+    per-pair entries)."""
+    group = max(1, min(-(-n // n_ctx), group_cap))
+    _, pairs, threads = modsx.last_batch_verify()
+    assert pairs == n and threads == min(n_ctx, -(-n // group)), (pairs, threads, n_ctx, n, group)
+    assert len(modsx.last_batch_verify_each()) == n
+
+
 def normH(H):
     H = np.asarray(H, float).reshape(3, 3)
     return H / H[2, 2]

@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from common import oracle_features, oracle_pair, laf_of, normH, same_records, need_ref, grouped_pair_hosts
+from common import oracle_features, oracle_pair, laf_of, normH, same_records, need_ref, grouped_pair_hosts, check_batch_statistics
 from tests.match_cases import tie_cases, all_points_case, clustered_cases
 
 pytestmark = pytest.mark.gpu
@@ -579,6 +579,7 @@ def test_grouped_pairs_equal_single_pairs(modsx, small_pair):
     singles = [ctxs[0].match_pair(x, y, par) for x, y in dev]
     for nctx in (1, 2):
         got = modsx.match_pairs(ctxs[:nctx], [x for x, _ in dev], [y for _, y in dev], par)
+        check_batch_statistics(modsx, nctx, len(dev), 4)
         assert len(got) == len(singles)
         for g, s in zip(got, singles):
             assert g["n_regions"] == s["n_regions"] and g["n_tentatives"] == s["n_tentatives"]

@@ -10,7 +10,7 @@ GPU -- nothing is retried."""
 import numpy as np
 import pytest
 
-from common import need_ref, normH, oracle_ladder, same_records
+from common import check_batch_statistics, need_ref, normH, oracle_ladder, same_records
 from tests import match_cases as MC
 
 pytestmark = pytest.mark.gpu
@@ -231,7 +231,9 @@ def test_match_reps_many_partners_equal_single_pairs(ctxs, modsx, dev):
             reps.append(r)
         assert reps[1].count() == 0
         got = modsx.match_reps(ctxs, ra, reps, par)
+        check_batch_statistics(modsx, 2, 6, 4)
         light = modsx.match_reps(ctxs, ra, reps, par, arrays=False)
+        check_batch_statistics(modsx, 2, 6, 4)
         assert len(got) == 6
         for i, nm in enumerate(names):
             ref = ctxs[0].match_pair_views(dev["a"], dev[nm], views, par)
@@ -333,6 +335,27 @@ def test_one_to_many_stops_when_any_partner_has_enough(ctxs, modsx, oracle, dev,
             assert any(g["n_verified"] >= min_matches for g in got)
         if partners == ("unrelated",):
             assert got[0]["n_verified"] == 0 and got[0]["n_tentatives"] == 42
+
+
+def test_a_refused_ladder_step_fails_the_whole_one_to_many_call(ctxs, modsx, dev, ladder):
+    """One ladder step whose second view the host planner refuses (views_plan.cpp, before any kernel of that view set is launched),
+    two partners over two contexts: the call raises the planner's error.  The same contexts then run the good ladder and give
+    what the per-pair ladder gives (b or b2 has ten matches after the first step: any_reaches_10 above)."""
+    with _Gpu():
+        par = modsx.default_pair_params(ransac_seed=SEED)
+        steps_m = ladder[1]
+        partners = ("b", "b2")
+        bad = [([steps_m[0][0][0], modsx.make_view(1e9, 0.0, 1.0, 0.2, 1)], 0.8)]
+        with pytest.raises(RuntimeError, match="degenerate"):
+            modsx.match_one_to_many(ctxs, dev["a"], [dev[nm] for nm in partners], bad, par, min_matches=10)
+        got, done = modsx.match_one_to_many(ctxs, dev["a"], [dev[nm] for nm in partners], steps_m, par, min_matches=10)
+        check_batch_statistics(modsx, 2, 2, 4)
+        assert done == 1 and len(got) == 2
+        for nm, g in zip(partners, got):
+            ref, n = ctxs[0].match_ladder(dev["a"], dev[nm], steps_m[:done], par, min_matches=10 ** 6)
+            assert n == done
+            _same_pair_result(g, ref)
+        assert any(g["n_verified"] >= 10 for g in got)
 
 
 # ---- 6. database -----------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ import os
 import numpy as np
 import pytest
 
-from common import laf_of, normH, oracle_ladder, same_records, need_ref
+from common import laf_of, normH, oracle_ladder, same_records, need_ref, check_batch_statistics
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -564,7 +564,9 @@ def test_match_pairs_views_equals_single_calls(modsx, small_pair):
     i1 = [ims[i % 2][0] for i in range(7)]
     i2 = [ims[i % 2][1] for i in range(7)]
     got = modsx.match_pairs_views(ctxs, i1, i2, views, par)
+    check_batch_statistics(modsx, 3, 7, 1)
     light = modsx.match_pairs_views(ctxs, i1, i2, views, par, arrays=False)
+    check_batch_statistics(modsx, 3, 7, 1)
     for i in range(7):
         ref = ctxs[0].match_pair_views(i1[i], i2[i], views, par)
         for k in ("n_regions", "n_tentatives", "n_unique", "n_ransac_inliers", "n_verified", "ransac_samples"):
@@ -574,4 +576,35 @@ def test_match_pairs_views_equals_single_calls(modsx, small_pair):
     assert modsx.match_pairs_views(ctxs, [], [], views, par) == []
     for x, y in ims:
         x.free(); y.free()
+
+
+def test_a_refused_pair_fails_the_whole_views_batch(modsx, small_pair):
+    """Three pairs over two contexts with a view list whose second view the host planner refuses (views_plan.cpp, before any
+    kernel of that view set is launched): the batch call raises the planner's error and returns nothing; the same contexts then
+    run the good list and give what modsx_match_pair_views gives pair by pair."""
+    a, b, _ = small_pair
+    ctxs = [modsx.Context(0) for _ in range(2)]
+    good = modsx.set_vs_pars([1.0], [1, 2, 3], 360.0, 0.2, 1, [])
+    assert len(good) >= 2
+    bad = list(good)
+    bad[1] = modsx.make_view(1e9, 0.0, 1.0, 0.2, 1)
+    with pytest.raises(RuntimeError, match="degenerate"):      # the refusal is the host's
+        modsx.view_plan(a.shape[0], a.shape[1], bad[1])
+    par = modsx.default_pair_params(ransac_seed=9)
+    ia, ib = ctxs[0].upload(a), ctxs[0].upload(b)
+    i1, i2 = [ia, ib, ia], [ib, ia, ib]
+    with pytest.raises(RuntimeError, match="degenerate"):
+        modsx.match_pairs_views(ctxs, i1, i2, bad, par)
+    got = modsx.match_pairs_views(ctxs, i1, i2, good, par)
+    check_batch_statistics(modsx, 2, 3, 1)
+    for i in range(3):
+        ref = ctxs[0].match_pair_views(i1[i], i2[i], good, par)
+        for k in ("n_regions", "n_tentatives", "n_unique", "n_ransac_inliers", "n_verified", "ransac_samples"):
+            assert got[i][k] == ref[k], k
+        assert np.array_equal(got[i]["H"], ref["H"]) and np.array_equal(got[i]["verified"], ref["verified"])
+        assert same_records(got[i]["tentatives"], ref["tentatives"])
+    assert got[0]["n_verified"] > 50
+    ia.free(); ib.free()
+    for c in ctxs:
+        c.close()
 
