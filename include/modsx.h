@@ -1230,10 +1230,97 @@ int modsx_debug_surfdet(modsx_ctx *ctx, const modsx_image *img, const modsx_surf
  * found, points accepted, regrows of the point buffer.  Fills out[0 .. min(n, 5) - 1], returns 5. */
 int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n);
 
+/* ---- The KAZE detector (AKAZE nonlinear scale space, Hessian extrema) -----------------------------------------------------
+ * The "KAZE" detector branch of the reference (imagerepresentation.cpp:678-681, 1132-1152): aka::AKAZE::
+ * Create_Nonlinear_Scale_Space and Feature_Detection (akaze/src/lib/AKAZE.cpp, nldiffusion_functions.cpp, fed.cpp) on the view
+ * / 255, bit for bit with what those three sources compute when compiled unmodified against tools/kaze_standin/, the one place
+ * where the arithmetic of the OpenCV calls they make is specified.  None of these rules is pinned against a real OpenCV:
+ *   input         pixels * 1.0 / 255.0 is each f32 pixel times (float)(1.0 / 255.0).
+ *   GaussianBlur  (f32, BORDER_REPLICATE) the library's gaussian_kernel(n, sigma) and two-pass order (modsx_gaussian_blur's), with
+ *                 AKAZE's size rule ceil(2 (1 + (sigma - 0.8) / 0.3)) made odd: 9 taps at sigma 1.6, 5 at sigma 1.
+ *   Scharr / sepFilter2D   f32, BORDER_REFLECT_101: a row pass into an f32 plane, then a column pass; taps in ascending index
+ *                 order, every product and every add rounded to f32, starting from the first product.  Kernels [-1, 0, 1] and
+ *                 [3, 10, 3] for Scharr, those of compute_derivative_kernels otherwise.  The kernels read only the three non-zero
+ *                 taps: a zero tap adds +-0, and -0 and +0 are not told apart anywhere downstream.
+ *   Mat expressions  element-wise f32 operations, each rounded: X / (k*k) is X * (float)(1.0 / (double)(k*k)), 1.0 + X an f32 add,
+ *                 1.0 / X an IEEE f32 division, L * n a multiply by (float)n, Ld + Lstep an f32 add.
+ *   resize        (INTER_AREA) (((a + b) + c) + d) * 0.25f with a, b the upper row where both ratios are exactly 2; otherwise the
+ *                 area table: per axis, scale = ssize / (double)dsize, fs1 = d * scale, fs2 = fs1 + scale, cell = min(scale, ssize -
+ *                 fs1), s2 = min(floor(fs2), ssize - 1), s1 = min(ceil(fs1), s2); a leading entry (s1 - 1, (float)((s1 - fs1) /
+ *                 cell)) if s1 - fs1 > 1e-3, entries (s, (float)(1.0 / cell)) for s1 <= s < s2, a trailing entry (s2,
+ *                 (float)(min(min(fs2 - s2, 1.0), cell) / cell)) if fs2 - s2 > 1e-3; per source row buf[dx] += S[sx] * alpha in
+ *                 table order in f32 from 0; per destination row sum = beta * buf for the first source row, sum += beta * buf after.
+ *   cv::solve     (2 x 2, DECOMP_LU) d = (double)a00 * a11 - (double)a01 * a10; if d != 0: x0 = (float)(((double)b0 * a11 -
+ *                 (double)b1 * a01) * (1 / d)), x1 = (float)(((double)b1 * a00 - (double)b0 * a10) * (1 / d)); if d == 0 the offsets
+ *                 keep what they held: zeros at first, the previous point's afterwards (the reference declares dst outside its loop).
+ * Everything else is the reference's own code, pinned by tests/golden/kaze_ref.npz: the level table and fed_tau_by_process_time with
+ * reordering, compute_k_percentile (its float counters as min(count, 2^24)), pm_g2, nld_step_scalar (0.5 * stepsize * (f32 sum) is
+ * an f64 product rounded on store; the corners of Lstep stay 0), Compute_Multiscale_Derivatives, Ldet = lxx * lyy - lxy * lxy
+ * without FMA, Find_Scale_Space_Extrema and Do_Subpixel_Refinement.  The 3 x 3 maxima are compacted on the device in (level, raster)
+ * order; the two filter passes and the refinement's erase loop are order-dependent and run on the host as written.
+ *   refusals  MODSX_ERR_ARG with a message, before any launch: a null pointer, n_imgs < 0, an image under 3 x 3, omax outside
+ *             1 .. 8, nsublevels < 1, more than MODSX_KAZE_MAX_LEVELS levels, soffset or derivative_factor not positive, a
+ *             derivative distance outside 1 .. 8 or more than MODSX_KAZE_MAX_TAU diffusion steps in a level (the defaults give 2 ..
+ *             4 and at most 14), kcontrast_nbins outside 1 .. 4096, descriptor outside 0 .. 5, and a diffusivity other than
+ *             PM_G2 (1): PM_G1, WEICKERT and CHARBONNIER call exp / pow / sqrt of OpenCV, whose arithmetic is not specified here.
+ *             n_imgs == 0 succeeds.  Pixels must be finite.  A flat image has k = 0: its planes hold NaN and it has no keypoint.
+ * No orientation is assigned (the branch calls no Compute_Main_Orientation) and no AKAZE descriptor (M-LDB, M-SURF) is computed.
+ * KAZE is no detector of the ladder, of modsx_rep_add_views, of stored representations or of the sharded path. */
+#define MODSX_DET_KAZE 9                 /* detector_type DET_KAZE, detectors/structures.hpp */
+#define MODSX_KAZE_MAX_LEVELS 32
+#define MODSX_KAZE_MAX_TAU 64
+typedef struct modsx_kaze_params {
+  int omax, nsublevels;                        /* AKAZEOptions: 4, 4 */
+  float soffset, derivative_factor;            /* 1.6, 1.5 */
+  float dthreshold, min_dthreshold;            /* 0.001, 0.00001 */
+  float kcontrast_percentile;                  /* 0.7 */
+  int kcontrast_nbins;                         /* 300 */
+  int descriptor;                              /* 5 (MLDB): only its class matters, smax = 10 sqrt(2) for 0, 1, 4, 5 and 12 sqrt(2) for 2, 3 */
+  int diffusivity;                             /* 1 (PM_G2), the only one built */
+} modsx_kaze_params;
+typedef struct modsx_kaze_point {              /* a cv::KeyPoint of the detector's lists */
+  float x, y, size, response;
+  int octave, class_id;                        /* class_id: the level */
+} modsx_kaze_point;
+void modsx_default_kaze_params(modsx_kaze_params *p);
+/* out: malloc'd (modsx_free) keypoints as the branch fills det_kp: x, y, response and s = size / 3.0 widened from the f32
+ * cv::KeyPoint, a11 = cos(0.0), a12 = sin(0.0), a21 = -sin(0.0), a22 = cos(0.0), octave_number = octave, every other field 0.
+ * Returns their number. */
+int modsx_detect_kaze(modsx_ctx *ctx, const modsx_image *img, const modsx_kaze_params *par, modsx_keypoint **out);
+/* The same for n_imgs images of any sizes with shared launches: out = the keypoints of image 0, then image 1, ...;
+ * counts[i] = the number of image i.  Returns the total.  Each image's list equals what modsx_detect_kaze gives for it. */
+int modsx_detect_kaze_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_kaze_params *par,
+                            modsx_keypoint **out, int *counts);
+/* host only: regions of KAZE keypoints as the branch leaves them -- type = MODSX_DET_KAZE, otherwise as modsx_surf_regions. */
+int modsx_kaze_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out);
+/* host only: the level table for a rows x cols image.  levels [MODSX_KAZE_MAX_LEVELS][8] = (octave, sublevel, rows, cols,
+ * sigma_size, derivative kernel size, derivative distance, FED steps); sigmas [.][2] = (esigma, etime); tau [.][MODSX_KAZE_MAX_TAU];
+ * tiles [4] = (width, height of a stencil tile, positions of a scan tile, the largest derivative distance); *omax = the octaves that
+ * survive the 80 x 40 rule.  Any output may be NULL.  Returns the number of levels, or MODSX_ERR_ARG as above. */
+int modsx_kaze_geometry(int rows, int cols, const modsx_kaze_params *par, int *levels, float *sigmas, float *tau, int *tiles, int *omax);
+/* Stage tap of one image.  kc [2] = (kcontrast, hmax); hist [kcontrast_nbins]; Lt, Lsmooth, Lflow, Ldet: the planes of every level,
+ * one after the other in level order (Lflow of level 0 is zeros, Lsmooth of level 0 is Lt); then the lists: raw [cap][3] = (level,
+ * row, col) with rawv [cap] the 3 x 3 maxima in scan order, aux after the same-level / lower-level pass, upper after the upper-level
+ * pass, fin after refinement (the first cap records of each).  counts [4] = their lengths (call again with a larger cap when one
+ * exceeds it).  Returns the number of levels. */
+int modsx_debug_kaze(modsx_ctx *ctx, const modsx_image *img, const modsx_kaze_params *par, float *kc, long *hist, float *Lt, float *Lsmooth,
+                     float *Lflow, float *Ldet, int *raw, float *rawv, modsx_kaze_point *aux, modsx_kaze_point *upper,
+                     modsx_kaze_point *fin, int cap, int *counts);
+/* The extrema scan, both filter passes and the refinement on caller-supplied Ldet planes (host memory, laid out as above for a rows
+ * x cols image); lists and counts as modsx_debug_kaze.  Returns the number of levels. */
+int modsx_debug_kaze_scan(modsx_ctx *ctx, int rows, int cols, const modsx_kaze_params *par, const float *ldet, int *raw, float *rawv,
+                          modsx_kaze_point *aux, modsx_kaze_point *upper, modsx_kaze_point *fin, int cap, int *counts);
+/* KAZE detector work of this context since modsx_create, cumulative (measurement hook): calls that launched, images, kernel
+ * launches, diffusion steps launched, waits of the host for the device, raw maxima, survivors of the filter passes, keypoints,
+ * microseconds the host spent in the filter passes and the refinement.  Fills out[0 .. min(n, 9) - 1], returns 9. */
+int modsx_kaze_counters(modsx_ctx *ctx, long *out, int n);
+
 /* ---- external affine adaptation: DetectAffineShape (synth-detection.cpp:922-1074) on a caller's regions ------------------
  * Baumberg iteration on the view image itself for a finished region list: what SynthDetectDescribeKeypoints runs
  * (imagerepresentation.cpp:1226-1236) in every detector branch that sets doExternalAffineAdaptation -- SURF with doBaumberg = 1
- * (imagerepresentation.cpp:1048), ORB, FAST, STAR, BRISK, KAZE, FOCI, SFOP, WAVE, WASH, TILDE-plugin.  Per region, bit for bit:
+ * (imagerepresentation.cpp:1048), ORB, FAST, STAR, BRISK, KAZE, FOCI, SFOP, WAVE, WASH, TILDE-plugin.  The
+ * library runs two of those detectors itself, SURF (modsx_detect_surf) and KAZE (modsx_detect_kaze: AKAZE's sources are in the
+ * reference tree, only the OpenCV routines they call are not); the regions of the others come from the caller.  Per region, bit for bit:
  *   lx, ly    (float)det_kp.x, (float)det_kp.y on img (no pyramid, no pixelDistance)
  *   ratio     (float)(det_kp.s / (double)1.6f): the function's own constant, formed on the host in f64; no parameter replaces it
  *   border    interpolateCheckBorders(cols, rows, lx, ly, (float)a11 .. (float)a22, res, res) with res = (int)(2 * 5.0 * ratio)

@@ -45,6 +45,29 @@ def surfdet_params(octaves=4, intervals=4, init_sample=2, thresh=0.0004):
     return SurfDetParams(int(octaves), int(intervals), int(init_sample), float(thresh))
 
 
+class KazeParams(C.Structure):
+    """modsx_kaze_params: AKAZEOptions as the reference's KAZE branch leaves them"""
+    _fields_ = [("omax", C.c_int), ("nsublevels", C.c_int), ("soffset", C.c_float), ("derivative_factor", C.c_float),
+                ("dthreshold", C.c_float), ("min_dthreshold", C.c_float), ("kcontrast_percentile", C.c_float),
+                ("kcontrast_nbins", C.c_int), ("descriptor", C.c_int), ("diffusivity", C.c_int)]
+
+
+def kaze_params(**kw):
+    """modsx_default_kaze_params with the given fields replaced"""
+    p = KazeParams()
+    lib().modsx_default_kaze_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(KazeParams._fields_):
+            raise TypeError("kaze_params: no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+# include/modsx.h: modsx_kaze_point
+KAZE_POINT = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("response", np.float32),
+                       ("octave", np.int32), ("class_id", np.int32)])
+
+
 class AffShapeParams(C.Structure):
     """modsx_affshape_params: the fields of AffineShapeParams that DetectAffineShape reads"""
     _fields_ = [("maxIterations", C.c_int), ("smmWindowSize", C.c_int), ("convergenceThreshold", C.c_float),
@@ -163,6 +186,8 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_surf_tables", "modsx_surf_counters",
            "modsx_detect_surf", "modsx_detect_surf_batch", "modsx_surf_regions", "modsx_surfdet_geometry", "modsx_surfdet_normalise",
            "modsx_debug_surfdet", "modsx_surfdet_counters",
+           "modsx_default_kaze_params", "modsx_detect_kaze", "modsx_detect_kaze_batch", "modsx_kaze_regions", "modsx_kaze_geometry",
+           "modsx_debug_kaze", "modsx_debug_kaze_scan", "modsx_kaze_counters",
            "modsx_default_affshape_params", "modsx_detect_affine_shape", "modsx_detect_affine_shape_batch",
            "modsx_debug_affine_shape", "modsx_affshape_jobs", "modsx_affshape_counters",
            "modsx_default_clahe_params", "modsx_image_clahe", "modsx_image_clahe_new", "modsx_image_clahe_batch",
@@ -199,6 +224,9 @@ SURF_COUNTERS = ("calls", "patches", "sub_batches")
 SURF_DIM = 64                         # include/modsx.h: MODSX_SURF_DIM
 # include/modsx.h: modsx_surfdet_counters, in its order
 SURFDET_COUNTERS = ("calls", "images", "extrema", "accepted", "regrows")
+# include/modsx.h: modsx_kaze_counters, in its order
+KAZE_COUNTERS = ("calls", "images", "launches", "fed_steps", "host_waits", "raw_maxima", "survivors", "keypoints", "filter_us")
+KAZE_MAX_LEVELS, KAZE_MAX_TAU, DET_KAZE = 32, 64, 9     # include/modsx.h: MODSX_KAZE_MAX_LEVELS, MODSX_KAZE_MAX_TAU, MODSX_DET_KAZE
 # include/modsx.h: modsx_affshape_counters, in its order
 AFFSHAPE_COUNTERS = ("calls", "regions", "border_refused", "launched", "converged", "launches")
 # include/modsx.h: modsx_clahe_counters and modsx_clahe_geometry, in their order
@@ -412,6 +440,15 @@ def lib():
         L.modsx_surfdet_normalise.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_debug_surfdet.argtypes = [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
         L.modsx_surfdet_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_default_kaze_params.argtypes = [C.c_void_p]
+        L.modsx_default_kaze_params.restype = None
+        L.modsx_detect_kaze.argtypes = [C.c_void_p] * 4
+        L.modsx_detect_kaze_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.modsx_kaze_regions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.modsx_kaze_geometry.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.modsx_debug_kaze.argtypes = [C.c_void_p] * 14 + [C.c_int, C.c_void_p]
+        L.modsx_debug_kaze_scan.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        L.modsx_kaze_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_daisy_tables.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9
         L.modsx_default_affshape_params.restype = None
         L.modsx_default_affshape_params.argtypes = [C.c_void_p]
@@ -682,6 +719,27 @@ def surfdet_geometry(rows, cols, params=None):
     layers = np.zeros((SURFDET_MAX_LAYERS, 4), np.int32)
     n = _check(lib().modsx_surfdet_geometry(int(rows), int(cols), C.byref(params), _p(layers)), "surfdet_geometry")
     return layers[:n].copy()
+
+
+def kaze_regions(kps, img_id=0):
+    """Regions of KAZE keypoints as the reference's KAZE branch leaves them: type DET_KAZE, det_kp as given (no device needed)."""
+    kps = np.ascontiguousarray(kps, KEYPOINT)
+    out = np.zeros(len(kps), REGION)
+    _check(lib().modsx_kaze_regions(_p(kps), len(kps), int(img_id), _p(out)), "kaze_regions")
+    return out
+
+
+def kaze_geometry(rows, cols, params=None):
+    """dict(levels [n][8] int32 (octave, sublevel, rows, cols, sigma_size, derivative kernel size, derivative distance, FED steps),
+    sigmas [n][2] f32 (esigma, etime), tau: a list of f32 arrays, tiles: dict(width, height, scan, max_distance), omax): the level
+    table the KAZE detector builds for a rows x cols image; raises where the library refuses (no device needed)."""
+    params = params or kaze_params()
+    levels, sig = np.zeros((KAZE_MAX_LEVELS, 8), np.int32), np.zeros((KAZE_MAX_LEVELS, 2), np.float32)
+    tau, tiles, omax = np.zeros((KAZE_MAX_LEVELS, KAZE_MAX_TAU), np.float32), np.zeros(4, np.int32), C.c_int(0)
+    n = _check(lib().modsx_kaze_geometry(int(rows), int(cols), C.byref(params), _p(levels), _p(sig), _p(tau), _p(tiles), C.byref(omax)),
+               "kaze_geometry")
+    return dict(levels=levels[:n].copy(), sigmas=sig[:n].copy(), tau=[tau[i, :levels[i, 7]].copy() for i in range(n)],
+                tiles=dict(zip(("width", "height", "scan", "max_distance"), (int(v) for v in tiles))), omax=omax.value)
 
 
 def reproject_regions(regs, H, w, h):
@@ -1247,6 +1305,76 @@ class Context(object):
         plane = lambda a, k: a[ofs[k]:ofs[k + 1]].reshape(layers[k, 1], layers[k, 0])      # noqa: E731
         return dict(layers=layers, integral=integral, resp=[plane(resp, k) for k in range(nl)], lap=[plane(lap, k) for k in range(nl)],
                     extrema=ext[:m], dD=dD[:m], H=H[:m], x=x[:m], accepted=acc[:m].astype(bool), laplacian=lp[:m])
+
+    # ---- the KAZE detector (engine_kaze.hip) ----
+    def detect_kaze(self, img, params=None):
+        """AKAZE's nonlinear scale space and Hessian extrema on the image: KEYPOINT records in the reference's order (x, y, s =
+        size / 3, response, octave_number and the frame of orientation 0)."""
+        params = params or kaze_params()
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_kaze(self._c(), C.c_void_p(img.h), C.byref(params), C.byref(out)), "detect_kaze")
+        return _take(out, n, KEYPOINT)
+
+    def detect_kaze_batch(self, imgs, params=None):
+        """detect_kaze of several images (any sizes) with shared launches: a list of KEYPOINT arrays."""
+        params = params or kaze_params()
+        ptrs = (C.c_void_p * max(1, len(imgs)))(*[im.h for im in imgs])
+        counts = np.zeros(max(1, len(imgs)), np.int32)
+        out = C.c_void_p()
+        n = _check(lib().modsx_detect_kaze_batch(self._c(), ptrs, len(imgs), C.byref(params), C.byref(out), _p(counts)),
+                   "detect_kaze_batch")
+        allk = _take(out, n, KEYPOINT)
+        ends = np.cumsum(counts[:len(imgs)])
+        return [allk[e - k:e].copy() for e, k in zip(ends, counts[:len(imgs)])]
+
+    @staticmethod
+    def _kaze_lists(call, cap=4096):
+        while True:
+            raw, rawv = np.zeros((cap, 3), np.int32), np.zeros(cap, np.float32)
+            aux, upper, fin = (np.zeros(cap, KAZE_POINT) for _ in range(3))
+            counts = np.zeros(4, np.int32)
+            nl = call(_p(raw), _p(rawv), _p(aux), _p(upper), _p(fin), cap, _p(counts))
+            if counts.max() <= cap:
+                break
+            cap = int(counts.max())
+        n = [int(v) for v in counts]
+        return nl, dict(raw=raw[:n[0]].copy(), rawv=rawv[:n[0]].copy(), aux=aux[:n[1]].copy(), upper=upper[:n[2]].copy(),
+                        final=fin[:n[3]].copy())
+
+    def debug_kaze(self, img, params=None):
+        """modsx_debug_kaze: dict(geometry, kcontrast, hmax, hist, Lt / Lsmooth / Lflow / Ldet: lists of planes, raw [m][3] (level,
+        row, col), rawv [m], aux, upper, final: KAZE_POINT arrays) -- the stages of detect_kaze for one image."""
+        params = params or kaze_params()
+        geo = kaze_geometry(img.rows, img.cols, params)
+        lv = geo["levels"]
+        sizes = lv[:, 2].astype(np.int64) * lv[:, 3]
+        kc, hist = np.zeros(2, np.float32), np.zeros(params.kcontrast_nbins, np.int64)
+        planes = [np.zeros(int(sizes.sum()), np.float32) for _ in range(4)]
+        nl, out = self._kaze_lists(lambda *a: _check(lib().modsx_debug_kaze(self._c(), C.c_void_p(img.h), C.byref(params), _p(kc), _p(hist),
+                                                                             *[_p(a_) for a_ in planes], *a), "debug_kaze"))
+        assert nl == len(lv)
+        ofs = np.concatenate([[0], np.cumsum(sizes)])
+        for name, a in zip(("Lt", "Lsmooth", "Lflow", "Ldet"), planes):
+            out[name] = [a[ofs[k]:ofs[k + 1]].reshape(lv[k, 2], lv[k, 3]) for k in range(nl)]
+        out.update(geometry=geo, kcontrast=kc[0], hmax=kc[1], hist=hist)
+        return out
+
+    def debug_kaze_scan(self, rows, cols, planes, params=None):
+        """modsx_debug_kaze_scan: the extrema scan, both filter passes and the refinement on the given Ldet planes (one per level
+        of a rows x cols image): dict(raw, rawv, aux, upper, final)."""
+        params = params or kaze_params()
+        lv = kaze_geometry(rows, cols, params)["levels"]
+        if len(planes) != len(lv) or any(np.shape(a) != (L[2], L[3]) for a, L in zip(planes, lv)):
+            raise ValueError("debug_kaze_scan: one plane per level, of the level's size")
+        flat = np.concatenate([np.ascontiguousarray(a, np.float32).reshape(-1) for a in planes])
+        nl, out = self._kaze_lists(lambda *a: _check(lib().modsx_debug_kaze_scan(self._c(), int(rows), int(cols), C.byref(params), _p(flat),
+                                                                                  *a), "debug_kaze_scan"))
+        assert nl == len(lv)
+        return out
+
+    def kaze_counters(self):
+        """dict of KAZE_COUNTERS: KAZE detector work of this context since it was created (cumulative)."""
+        return self._counters("modsx_kaze_counters", KAZE_COUNTERS)
 
     # ---- external affine adaptation (engine_detect.hip: DetectAffineShape) ----
     def detect_affine_shape(self, img, regs, params=None):

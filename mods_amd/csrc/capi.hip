@@ -1704,6 +1704,97 @@ int modsx_surfdet_counters(modsx_ctx *ctx, long *out, int n) {
   return read_counters("modsx_surfdet_counters", ctx->sdCounters, 5, out, n);
 }
 
+// ---- the KAZE detector (engine_kaze.hip) ----
+void modsx_default_kaze_params(modsx_kaze_params *p) {
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->omax = 4; p->nsublevels = 4; p->soffset = 1.6f; p->derivative_factor = 1.5f; p->dthreshold = 0.001f; p->min_dthreshold = 0.00001f;
+  p->kcontrast_percentile = 0.7f; p->kcontrast_nbins = 300; p->descriptor = 5; p->diffusivity = 1;
+}
+int modsx_kaze_geometry(int rows, int cols, const modsx_kaze_params *par, int *levels, float *sigmas, float *tau, int *tiles, int *omax) {
+  NEED(par);
+  std::vector<KazeLevel> lv;
+  const int n = kaze_geometry("modsx_kaze_geometry", rows, cols, *par, lv, omax);
+  if (n < 0) return n;
+  for (int i = 0; i < n; i++) {
+    const KazeLevel &L = lv[i];
+    if (levels) {
+      const int row[8] = {L.octave, L.sublevel, L.rows, L.cols, L.sigma_size, L.ksize, L.dsize, L.nsteps};
+      memcpy(levels + 8 * i, row, sizeof row);
+    }
+    if (sigmas) { sigmas[2 * i] = L.esigma; sigmas[2 * i + 1] = L.etime; }
+    if (tau)
+      for (int k = 0; k < MODSX_KAZE_MAX_TAU; k++) tau[(size_t)i * MODSX_KAZE_MAX_TAU + k] = k < L.nsteps ? L.tau[k] : 0.f;
+  }
+  if (tiles) { tiles[0] = KZ_TW; tiles[1] = KZ_TH; tiles[2] = KZ_TILE; tiles[3] = KZ_MAX_S; }
+  return n;
+}
+int modsx_kaze_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out) {
+  if (n < 0 || (n > 0 && (!kps || !out))) { mx::set_error("modsx_kaze_regions: bad argument"); return MODSX_ERR_ARG; }
+  kaze_regions(kps, n, img_id, out);
+  return n;
+}
+int modsx_detect_kaze_batch(modsx_ctx *ctx, const modsx_image *const *imgs, int n_imgs, const modsx_kaze_params *par,
+                            modsx_keypoint **out, int *counts) {
+  NEED(ctx); NEED(par); NEED(out);
+  if (n_imgs < 0 || (n_imgs > 0 && (!imgs || !counts))) { mx::set_error("modsx_detect_kaze_batch: bad argument"); return MODSX_ERR_ARG; }
+  for (int i = 0; i < n_imgs; i++) NEED(imgs[i]);
+  hipSetDevice(ctx->dev);
+  std::vector<std::vector<modsx_keypoint>> k(n_imgs);
+  const int rc = detect_kaze_batch(ctx, imgs, n_imgs, *par, k.data());
+  if (rc) return rc;
+  std::vector<modsx_keypoint> all;
+  for (int i = 0; i < n_imgs; i++) { counts[i] = (int)k[i].size(); all.insert(all.end(), k[i].begin(), k[i].end()); }
+  *out = to_malloc(all);
+  return (int)all.size();
+}
+int modsx_detect_kaze(modsx_ctx *ctx, const modsx_image *img, const modsx_kaze_params *par, modsx_keypoint **out) {
+  NEED(ctx); NEED(img); NEED(par); NEED(out);
+  int count = 0;
+  const modsx_image *imgs[1] = {img};
+  return modsx_detect_kaze_batch(ctx, imgs, 1, par, out, &count);
+}
+static void kaze_lists_out(const KazeLists &L, int *raw, float *rawv, modsx_kaze_point *aux, modsx_kaze_point *upper, modsx_kaze_point *fin,
+                           int cap, int *counts) {
+  counts[0] = (int)L.rawv.size(); counts[1] = (int)L.aux.size(); counts[2] = (int)L.upper.size(); counts[3] = (int)L.final.size();
+  const size_t c = (size_t)cap;
+  if (cap > 0) {
+    memcpy(raw, L.raw.data(), std::min(c, L.rawv.size()) * 3 * sizeof(int));
+    memcpy(rawv, L.rawv.data(), std::min(c, L.rawv.size()) * sizeof(float));
+    memcpy(aux, L.aux.data(), std::min(c, L.aux.size()) * sizeof(modsx_kaze_point));
+    memcpy(upper, L.upper.data(), std::min(c, L.upper.size()) * sizeof(modsx_kaze_point));
+    memcpy(fin, L.final.data(), std::min(c, L.final.size()) * sizeof(modsx_kaze_point));
+  }
+}
+int modsx_debug_kaze(modsx_ctx *ctx, const modsx_image *img, const modsx_kaze_params *par, float *kc, long *hist, float *Lt, float *Lsmooth,
+                     float *Lflow, float *Ldet, int *raw, float *rawv, modsx_kaze_point *aux, modsx_kaze_point *upper,
+                     modsx_kaze_point *fin, int cap, int *counts) {
+  NEED(ctx); NEED(img); NEED(par); NEED(kc); NEED(hist); NEED(Lt); NEED(Lsmooth); NEED(Lflow); NEED(Ldet); NEED(counts);
+  if (cap < 0 || (cap > 0 && (!raw || !rawv || !aux || !upper || !fin))) { mx::set_error("modsx_debug_kaze: bad argument"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  KazeLists L;
+  const KazeTap tap = {kc, hist, Lt, Lsmooth, Lflow, Ldet, &L};
+  const int rc = debug_kaze(ctx, img, *par, tap);
+  if (rc < 0) return rc;
+  kaze_lists_out(L, raw, rawv, aux, upper, fin, cap, counts);
+  return rc;
+}
+int modsx_debug_kaze_scan(modsx_ctx *ctx, int rows, int cols, const modsx_kaze_params *par, const float *ldet, int *raw, float *rawv,
+                          modsx_kaze_point *aux, modsx_kaze_point *upper, modsx_kaze_point *fin, int cap, int *counts) {
+  NEED(ctx); NEED(par); NEED(ldet); NEED(counts);
+  if (cap < 0 || (cap > 0 && (!raw || !rawv || !aux || !upper || !fin))) { mx::set_error("modsx_debug_kaze_scan: bad argument"); return MODSX_ERR_ARG; }
+  hipSetDevice(ctx->dev);
+  KazeLists L;
+  const int rc = debug_kaze_scan(ctx, rows, cols, *par, ldet, L);
+  if (rc < 0) return rc;
+  kaze_lists_out(L, raw, rawv, aux, upper, fin, cap, counts);
+  return rc;
+}
+int modsx_kaze_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  return read_counters("modsx_kaze_counters", ctx->kzCounters, 9, out, n);
+}
+
 // ---- external affine adaptation, DetectAffineShape (engine_detect.hip) ----
 void modsx_default_affshape_params(modsx_affshape_params *p) {
   if (!p) return;

@@ -425,6 +425,8 @@ void ctx_destroy(modsx_ctx *c) {
   for (DevBuf &b : c->surfTab) b.release();
   for (DevBuf *b : {&c->sdInteg, &c->sdResp, &c->sdLap, &c->sdFlags, &c->sdCounts, &c->sdTab, &c->sdPoints, &c->sdExt}) b->release();
   c->sdHost.release(); c->sdBack.release();
+  for (DevBuf *b : {&c->kzPlanes, &c->kzLdet, &c->kzTab, &c->kzHist, &c->kzFlags, &c->kzCounts, &c->kzRaw, &c->kzItems, &c->kzNine}) b->release();
+  c->kzHost.release(); c->kzBack.release();
   for (DevBuf *b : {&c->claheTab, &c->clahePart, &c->claheLut, &c->claheDbg}) b->release();
   c->claheHost.release();
   for (DevBuf *b : {&c->caffeJobs, &c->caffeFlags, &c->caffeOut}) b->release();

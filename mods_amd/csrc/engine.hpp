@@ -470,6 +470,36 @@ void launch_surfdet_scan(hipStream_t s, const SdJob *jobs, const SdSeg *segs, in
 void launch_surfdet_emit(hipStream_t s, const SdJob *jobs, const SdSeg *segs, int nsegs, int tiles, const float *resp,
                          const unsigned char *lap, const unsigned char *flags, const int *offs, SdPoint *points, int capPts, SdExt *ext,
                          int capExt);
+// The KAZE detector (kernels_kaze.hip; AKAZE's nonlinear scale space and Hessian extrema on a whole view).  Every kernel reads a run
+// of KzJob records in device memory, one per image and stage, and finds its image through the records' first workgroups, so a view
+// set is one launch per stage.  Stencil tiles are KZ_TW x KZ_TH outputs with a halo of at most KZ_MAX_S; the diffusion step and the
+// half-size resize take 64 x 4 pixels per workgroup; the scan takes KZ_TILE raster positions.
+constexpr int KZ_MAX_LEVELS = MODSX_KAZE_MAX_LEVELS, KZ_MAX_TAU = MODSX_KAZE_MAX_TAU, KZ_MAX_OCTAVES = 8, KZ_TW = 64, KZ_TH = 16,
+              KZ_MAX_S = 8, KZ_TILE = 256, KZ_MAX_BINS = 4096;
+enum { KZ_DERIV = 0, KZ_FLOW = 1, KZ_MAX = 2, KZ_HIST = 3 };      // the epilogues of k_kz_first
+struct KzJob {
+  const float *in0, *in1;      // the planes a stage reads (the diffusion step: Lt, Lflow; the second derivatives: Lx, Ly)
+  float *out0, *out1;
+  int rows, cols, srows, scols;   // of the output; of the source of the half-size resize
+  int s;                       // the derivative distance
+  float t0, t1, t2, scale;     // the smoothing taps; (float)(s * s)
+  int slot, octave, level;     // the image's index in the launch set
+  int blk0, tilesX;            // the first workgroup of the job and its tiles per row
+  int pad;
+};
+struct KzRaw { int slot, level, r, c; float value; };                 // one 3 x 3 maximum of an Ldet plane
+struct KzItem { unsigned long long ofs; int cols, y, x, pad; };       // k_kz_gather: the plane's offset in the Ldet arena
+void launch_kaze_scale(hipStream_t s, const KzJob *jobs, int njobs, int blocks);
+// hist [slots][nbins + 1]: the bits of hmax, then the bins; kinv [slots][KZ_MAX_OCTAVES] = (float)(1.0 / (double)(k * k)) per octave
+void launch_kaze_first(hipStream_t s, int mode, const KzJob *jobs, int njobs, int blocks, const float *kinv, unsigned *hist, int nbins);
+void launch_kaze_second(hipStream_t s, const KzJob *jobs, int njobs, int blocks);
+void launch_kaze_fed(hipStream_t s, const KzJob *jobs, int njobs, int blocks, float tau);
+void launch_kaze_half(hipStream_t s, const KzJob *jobs, int njobs, int blocks);
+// flags [tiles][KZ_TILE], counts [tiles], then the exclusive scan offs [tiles + 1] and slotStart [nslots + 1] = offs at tile0[slot]
+void launch_kaze_scan(hipStream_t s, const KzJob *jobs, int njobs, int tiles, float dthr, float minthr, unsigned char *flags, int *counts,
+                      int *offs, const int *tile0, int nslots, int *slotStart);
+void launch_kaze_emit(hipStream_t s, const KzJob *jobs, int njobs, int tiles, const unsigned char *flags, const int *offs, KzRaw *raw, int cap);
+void launch_kaze_gather(hipStream_t s, const KzItem *items, int n, const float *ldet, float *out);
 // the patch-out form of k_describe (kernels_describe.hip): [slot][1681] f32, slot = outIdx (patchByOutIdx) or the job's index
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -656,6 +686,13 @@ struct modsx_ctx {
   mx::DevBuf sdInteg, sdResp, sdLap, sdFlags, sdCounts, sdTab, sdPoints, sdExt;
   mx::PinBuf sdHost, sdBack;
   long sdCounters[5] = {0, 0, 0, 0, 0};  // modsx_surfdet_counters: calls, images, extrema found, points accepted, buffer regrows
+  // the KAZE detector (engine_kaze.hip): the per-level scratch planes and the Ldet planes of one launch set, the job tables, the
+  // histograms, the scan's flags / counts / offsets, the raw maxima and the gather's items and values
+  mx::DevBuf kzPlanes, kzLdet, kzTab, kzHist, kzFlags, kzCounts, kzRaw, kzItems, kzNine;
+  mx::PinBuf kzHost, kzBack;
+  // modsx_kaze_counters: calls, images, kernel launches, diffusion steps launched, host waits, raw maxima, survivors of the filter
+  // passes, keypoints, microseconds the host spent in the filter passes and the refinement
+  long kzCounters[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   // external affine adaptation (engine_detect.hip: affine_shape_batch), modsx_affshape_counters: calls, regions in, regions the
   // border test refused, regions launched, regions converged, launches
   long affshapeCounters[6] = {0, 0, 0, 0, 0, 0};

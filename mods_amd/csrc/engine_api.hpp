@@ -151,6 +151,17 @@ void surf_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *ou
 int detect_surf_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_surfdet_params &par, std::vector<modsx_keypoint> *out);
 int debug_surfdet(modsx_ctx *c, const modsx_image *img, const modsx_surfdet_params &par, float *integral, int *layers, float *resp,
                   unsigned char *lap, int *ext, double *dD, double *H, double *x, int *accepted, int *laplacian, int capExt, int *nExt);
+// The KAZE detector (engine_kaze.hip).  kaze_geometry: the level table of Allocate_Memory_Evolution with every tau list, and the
+// refusals that need no device (fn names the entry in the error text); returns the number of levels.  KazeTap: what modsx_debug_kaze
+// reads of one image; KazeLists: the lists of Find_Scale_Space_Extrema and Do_Subpixel_Refinement, records as modsx.h lays them out
+struct KazeLevel { int octave, sublevel, rows, cols, sigma_size, dsize, ksize, nsteps; float esigma, etime; std::vector<float> tau; };
+int kaze_geometry(const char *fn, int rows, int cols, const modsx_kaze_params &par, std::vector<KazeLevel> &lv, int *omax);
+void kaze_regions(const modsx_keypoint *kps, int n, int img_id, modsx_region *out);
+struct KazeLists { std::vector<int> raw; std::vector<float> rawv; std::vector<modsx_kaze_point> aux, upper, final; };
+struct KazeTap { float *kc; long *hist; float *Lt, *Lsmooth, *Lflow, *Ldet; KazeLists *lists; };
+int detect_kaze_batch(modsx_ctx *c, const modsx_image *const *imgs, int n, const modsx_kaze_params &par, std::vector<modsx_keypoint> *out);
+int debug_kaze(modsx_ctx *c, const modsx_image *img, const modsx_kaze_params &par, const KazeTap &tap);
+int debug_kaze_scan(modsx_ctx *c, int rows, int cols, const modsx_kaze_params &par, const float *ldet, KazeLists &lists);
 // DAISY (engine_daisy.hip).  patches [n][41][41] f32 / desc [n][(radq * thq + 1) * 8] f32: host pointers, or device pointers
 // (4-byte aligned) when onDevice.  daisy_check_args: the refusals that need no device (patchSize, rad, radq, thq, histq, nrmType),
 // made by the entries of capi.hip before they call in here; fn names the entry in the error text
