@@ -18,13 +18,6 @@ using namespace mx;
     if (!(c)) { mx::set_error("null argument: " #c); return MODSX_ERR_ARG; } \
   } while (0)
 
-template <typename T>
-static T *to_malloc(const std::vector<T> &v) {
-  T *p = (T *)malloc(sizeof(T) * (v.size() ? v.size() : 1));
-  if (p && !v.empty()) memcpy(p, v.data(), sizeof(T) * v.size());
-  return p;
-}
-
 // The host share of the process's last batch call (modsx_match_pairs, modsx_match_pairs_views, modsx_match_reps; for
 // modsx_match_one_to_many the last round of its ladder): DuplicateFiltering + LO-RANSAC of its pairs are the tasks of run_batch
 // (batch_driver.hpp), which resets these statistics when a run starts.
@@ -855,33 +848,29 @@ int modsx_match_reps(modsx_ctx *const *ctxs, int n_ctx, const modsx_rep *rep1, c
   mx::RepClassList present;      // the classes that are verified, in the order GetCorresponcesVector concatenates them
   if (n_classes > 0) {
     for (int k = 0; k < n_classes; k++) {
-      int det;
-      if (!mx::rep_class_ok(classes[k].detector, classes[k].desc_type, &det) && !mx::rep_class_f32_ok(classes[k].detector, classes[k].desc_type, &det) &&
-          !mx::rep_class_bin_ok(classes[k].detector, classes[k].desc_type, &det)) {
+      mx::RepClassId id;
+      if (!mx::rep_class_id(classes[k].detector, classes[k].desc_type, &id)) {
         mx::set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG;
       }
-      if (present.has(det, classes[k].desc_type)) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
-      if (classes[k].desc_type >= MODSX_DESC_BRISK) {
+      if (present.has(id)) { mx::set_error("modsx_match_reps: a class is listed twice"); return MODSX_ERR_ARG; }
+      if (id.kind == mx::REP_BIN) {
         // a binary class: `ratio` is its DistanceThreshold; every partner is checked before any group is launched
-        const int rc = mx::reps_bin_check("modsx_match_reps", ctxs[0], rep1, reps2, n, det, classes[k].desc_type, classes[k].ratio);
+        const int rc = mx::reps_bin_check("modsx_match_reps", ctxs[0], rep1, reps2, n, id.det, id.type, classes[k].ratio);
         if (rc) return rc;
       }
-      present.add(det, classes[k].desc_type);
+      present.add(id);
       sel[nsel++] = classes[k];
     }
   } else {
     mx::DescSet ds;
     { const int rd = mx::resolve_descs(*par, nullptr, ds); if (rd) return rd; }
-    static const int detOf[3] = {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_SURF};
-    mx::rep_classes_u8(present);
-    for (int t = MODSX_DESC_CAFFE; t <= MODSX_DESC_SURF; t++) for (int d = 0; d < 3; d++) present.add(d, t);
+    mx::rep_classes(present, 1u << mx::REP_U8 | 1u << mx::REP_F32);      // the binary classes are matched only when they are named
     for (int i = 0; i < present.n; i++) {
-      const int d = present.k[i].det, t = present.k[i].type;
-      const bool f32 = t >= MODSX_DESC_CAFFE;
-      if (f32 ? rep1->fslot[d][t - MODSX_DESC_CAFFE].regs.empty() : rep1->slot[d][t].regs.empty()) continue;   // no queries: no partner has tentatives in this class
+      const mx::RepClassId &id = present.k[i];
+      if (mx::rep_class_regions(rep1, id).empty()) continue;   // no queries: no partner has tentatives in this class
       double ratio = par->match_ratio;
-      for (int j = 0; j < ds.n && !f32; j++) if (ds.type[j] == t && ds.ratio[j] > 0) ratio = ds.ratio[j];
-      sel[nsel].detector = detOf[d]; sel[nsel].desc_type = t; sel[nsel].ratio = ratio;
+      for (int j = 0; j < ds.n && id.kind == mx::REP_U8; j++) if (ds.type[j] == id.type && ds.ratio[j] > 0) ratio = ds.ratio[j];
+      sel[nsel].detector = mx::rep_class_detector(id); sel[nsel].desc_type = id.type; sel[nsel].ratio = ratio;
       nsel++;
     }
   }
@@ -910,7 +899,7 @@ int modsx_match_one_to_many(modsx_ctx *const *ctxs, int n_ctx, const modsx_image
   for (auto &r : reps) r = modsx_rep_create(ctxs[0]);
   std::vector<mx::RepTents> tents((size_t)n);
   mx::RepClassList u8Classes;      // the ladder carries the SIFT-family classes only
-  mx::rep_classes_u8(u8Classes);
+  mx::rep_classes(u8Classes, 1u << mx::REP_U8);
   mx::BatchError err;
   int step = 0;
   bool reached = false;

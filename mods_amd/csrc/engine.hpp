@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/modsx.h"
 #include "kmath.hpp"
+#include "fginn_walk.hpp"
 
 namespace mx {
 
@@ -372,9 +373,7 @@ void launch_hamming_pack_rows(hipStream_t s, const uint8_t *src, int n, int nbyt
 // FGINN matching of f32 rows of any width (kernels_fginn32.hip).  DK = the kernel width dim rounds up to; tile = trains per LDS
 // tile; the train axis is cut into S splits of tilesPerSplit tiles; gx x S workgroups of k_f32_topk.
 struct Fginn32Geo { int dim, DK, tile, ntiles, tilesPerSplit, S, gx; };
-// an undecided query on its way to k_f32_resolve, and what comes back
-struct F32Open { unsigned long long klast; int q, t0; float dpass; int pad; };
-struct F32Closed { unsigned long long kterm; unsigned cnt, pad; };
+// F32Open / F32Closed, an undecided query on its way to k_f32_resolve and what comes back: fginn_walk.hpp, with the host's walk
 struct Fginn32Work { float *queries, *trains; unsigned long long *keys; F32Open *open; F32Closed *closed; };
 // the key of a (distance, train index): distances are >= +0 and never NaN, so the pattern orders like the value; all ones = no train
 constexpr unsigned long long F32_NONE = ~0ull;

@@ -1,7 +1,10 @@
 // engine_api.hpp -- functions shared between engine.hip, engine_detect.hip, engine_views.hip, engine_shard.hip, describe_plan.cpp,
-// ransac.cpp, filters.cpp and capi.hip.
+// ransac.cpp, filters.cpp and capi.hip.  Of the stored representations it holds the slot structures, the class identity
+// (RepClassId; the table behind it is engine_reps.hip), to_malloc and the group-geometry report; the host's FGINN walk on f32 keys
+// comes in through engine.hpp from fginn_walk.hpp.
 #pragma once
 #include <stdio.h>
+#include <algorithm>
 #include <chrono>
 #include <functional>
 #include <string>
@@ -232,6 +235,13 @@ struct HostMark {
 };
 inline double now_ms() { return HostMark::now(); }
 inline size_t align_up(size_t bytes, size_t a) { return (bytes + a - 1) & ~(a - 1); }   // a: a power of two
+// a list handed over the C ABI as a malloc'd array (never of size 0); the caller frees it
+template <typename T>
+inline T *to_malloc(const std::vector<T> &v) {
+  T *p = (T *)malloc(sizeof(T) * (v.size() ? v.size() : 1));
+  if (p && !v.empty()) memcpy(p, v.data(), sizeof(T) * v.size());
+  return p;
+}
 // Stable LSD radix sort of w by its bits loBit..hiBit, 11 bits per pass; a pass whose digit is the same in every word is left
 // out.  tmp is the second buffer of the passes (resized here; callers keep it to keep its memory).
 inline void host_radix_sort_u64(std::vector<uint64_t> &w, std::vector<uint64_t> &tmp, int loBit, int hiBit) {
@@ -291,13 +301,12 @@ int match_hamming_host(modsx_ctx *c, const void *desc1, int n1, const void *desc
                        std::vector<modsx_tentative> &out);
 int match_regions_hamming(modsx_ctx *c, const modsx_region *regs1, const void *desc1, int n1, const modsx_region *regs2, const void *desc2,
                           int n2, int nbytes, int dtype, double distanceThreshold, const modsx_pair_params &pp, modsx_pair_result *res);
-// ---- MatchFlannFGINN on f32 rows of any width (engine_fginn32.hip) ----
+// ---- MatchFlannFGINN on f32 rows of any width (engine_fginn32.hip; the host's walk, its records and fginn32_dpass: fginn_walk.hpp) ----
 // debug tap: splits forces the split count (0 = production); stageMask: 1 = top-4 + host walk (always run), 2 = k_f32_resolve
 // (a query that needs a stage that is masked off gives no record).  Outputs (each optional): top4 [n1][4] keys, stage [n1] = how
 // the query was closed (0 host walk, 1 resolve sweep, 2 resolve sweep and its count: the rank bound exceeded nn - 1), geometry [6],
 // counters [4] = {queries sent to resolve, of those closed by the count, records, validity flag}
 struct Fginn32Tap { int splits, stageMask; unsigned long long *top4; unsigned char *stage; int *geometry; int *counters; };
-float fginn32_dpass(float d0, double rsq);
 bool fginn32_rows_ok(const float *f, size_t n);     // every value finite with |x| <= 1e17
 int fginn32_check_args(const char *fn, int n1, int n2, int dim, double ratioT, int nn);
 int fginn32_check_dist(const char *fn, int dist);   // MODSX_DIST_L2 or MODSX_DIST_L1
@@ -371,45 +380,67 @@ struct RepSlot {
   size_t cap = (size_t)1 << 16;     // regions `desc` has room for (grows x4)
   DevBuf desc, pack;
 };
-// One float class of a stored representation (engine_reps_f32.hip): the host region list (and its positions), the rows in the matcher's form
-// (kernels_fginn32.hip: DK floats per row, zero columns behind dim, zero rows up to the capacity, which is a multiple of 256) and
-// the regions' reproj_kp as [n][2] f64.  dim is fixed by the first append that succeeds.
-constexpr size_t REP_F32_FIRST_ROWS = 4096;      // MODSX_REP_F32_FIRST_ROWS: the first capacity of a float slot (grows x4)
-struct RepSlotF {
+// What the float and the binary slot are (the store: engine_reps.hip slot_*): the host region list and the rows in their matcher's
+// form -- W 4-byte words per row, zero behind the row's own width, zero rows up to the capacity (4096 x 4^k rows: whole workgroups
+// of queries and whole tiles of trains at every tile length), so nothing is packed when a slot is matched and an append only
+// writes behind the old rows.  A class that holds regions has capW == its W, an empty one has no buffer.
+struct RepRows {
   std::vector<modsx_region> regs;
+  int W = 0;
+  size_t cap = 0;                // rows the buffers have room for, each of capW words
+  int capW = 0;
+  DevBuf rows, pos;              // pos: the regions' reproj_kp as [cap][2] f64, float slots only
+};
+// One float class (engine_reps_f32.hip): rows as kernels_fginn32.hip takes them, W = DK floats.  dim is fixed by the first append
+// that succeeds.  The first capacity is MODSX_REP_F32_FIRST_ROWS, that of a binary slot MODSX_REP_BIN_FIRST_ROWS.
+struct RepSlotF : RepRows {
   std::vector<double> hpos;      // reproj_kp.x, y of regs, dense: what the host's walk reads
-  int dim = 0, DK = 0;
-  size_t cap = 0;                // rows the buffers have room for, each of capDK floats
-  int capDK = 0;
-  DevBuf rows, pos;
+  int dim = 0;
 };
-// One binary class of a stored representation (engine_reps_bin.hip): the host region list and the rows exactly as k_hamming_pack
-// writes them (kernels_hamming.hip: WK dwords per row, zero behind nbytes, zero rows up to the capacity, which is a multiple of
-// 1024 rows: whole workgroups of queries and whole train tiles at every WK).  nbytes is fixed by the first append that succeeds.
-constexpr size_t REP_BIN_FIRST_ROWS = 4096;      // MODSX_REP_BIN_FIRST_ROWS: the first capacity of a binary slot (grows x4)
-struct RepSlotB {
-  std::vector<modsx_region> regs;
-  int nbytes = 0, WK = 0;
-  size_t cap = 0;                // rows the buffer has room for, each of capWK dwords
-  int capWK = 0;
-  DevBuf rows;
-};
-// the tentatives of every class's last match against one partner (CorrespondencesMapMap[desc][det])
-struct RepTents { std::vector<modsx_tentative> t[2][4], f[3][5], b[4][3]; };
-// A class by its slot; type = MODSX_DESC_*.  0..3: u8 slots, det 0 = HessianAffine, 1 = MSER; 8..12: float slots, det 2 = SURF as
-// well; 16..18: binary slots, det 0 = HessianAffine, 1 = MSER, 2 = ORB, 3 = SURF.  A RepClassList is sorted by rep_slot_order: the
-// order GetCorresponcesVector("All", "All") concatenates the classes in.
-struct RepClassId { int det, type; };
+// One binary class (engine_reps_bin.hip): rows exactly as k_hamming_pack writes them (kernels_hamming.hip), W = WK dwords.  nbytes
+// is fixed by the first append that succeeds.
+struct RepSlotB : RepRows { int nbytes = 0; };
+void slot_release(RepRows &k);
+// room for `rows` rows of W words: the old rows (and positions, isFloat) are copied once, everything behind them is zero
+int slot_reserve(modsx_ctx *c, RepRows &k, size_t rows, int W, bool isFloat);
+hipError_t slot_zero_again(modsx_ctx *c, RepRows &k, size_t base, int n);      // rows base .. base + n back to zero rows, waited for
+// modsx_rep_class_f32 / _bin: the regions and the rows as dense [n][widthBytes] (each optional), malloc'd; returns n
+int slot_download(modsx_ctx *c, const char *fn, const RepRows &k, size_t widthBytes, modsx_region **regs, void **rows);
+// The classes a representation can hold: what GetCorresponcesVector("All", "All") (correspondencebank.cpp:117-179) iterates over,
+// as the one table in engine_reps.hip.  kind: which slots hold the class; det: its slot index inside the kind (u8: HessianAffine,
+// MSER; float: HessianAffine, MSER, SURF; binary: HessianAffine, MSER, ORB, SURF); type = MODSX_DESC_*; order: its place in that
+// iteration, 4 * (place of the descriptor name) + (place of the detector name), both in std::map order.
+enum { REP_U8 = 0, REP_F32 = 1, REP_BIN = 2 };
+constexpr int REP_ORDERS = 12 * 4;
+struct RepClassId { int kind, det, type, order; };
+bool rep_class_id(int detector, int desc_type, RepClassId *id);      // false: the pair names no class
+int rep_class_detector(const RepClassId &k);                         // MODSX_DET_*
+inline bool rep_class_of_kind(int detector, int desc_type, int kind, int *det) {
+  RepClassId k;
+  if (!rep_class_id(detector, desc_type, &k) || k.kind != kind) return false;
+  *det = k.det;
+  return true;
+}
+inline bool rep_class_ok(int detector, int desc_type, int *det) { return rep_class_of_kind(detector, desc_type, REP_U8, det); }
+inline bool rep_class_f32_ok(int detector, int desc_type, int *det) { return rep_class_of_kind(detector, desc_type, REP_F32, det); }
+inline bool rep_class_bin_ok(int detector, int desc_type, int *det) { return rep_class_of_kind(detector, desc_type, REP_BIN, det); }
+// the tentatives of every class's last match against one partner (CorrespondencesMapMap[desc][det]), by RepClassId::order
+struct RepTents { std::vector<modsx_tentative> of[REP_ORDERS]; };
+const std::vector<modsx_region> &rep_class_regions(const modsx_rep *rep, const RepClassId &k);
+// sorted by order: the order GetCorresponcesVector("All", "All") concatenates the classes in
 struct RepClassList {
   int n = 0;
   RepClassId k[REP_CLASSES_MAX];
-  bool has(int det, int type) const { for (int i = 0; i < n; i++) if (k[i].det == det && k[i].type == type) return true; return false; }
-  void add(int det, int type);      // keeps the order
+  bool has(const RepClassId &c) const { for (int i = 0; i < n; i++) if (k[i].order == c.order) return true; return false; }
+  void add(const RepClassId &c) {
+    int at = n++;
+    for (; at > 0 && k[at - 1].order > c.order; at--) k[at] = k[at - 1];
+    k[at] = c;
+  }
 };
-int rep_class_rank(int detector, int desc_type);                 // -1: no such class
-bool rep_class_ok(int detector, int desc_type, int *det);        // a u8 class
-bool rep_class_f32_ok(int detector, int desc_type, int *det);    // a float class
-void rep_classes_u8(RepClassList &l);                            // the eight u8 classes
+void rep_classes(RepClassList &l, unsigned kinds);               // every class of the kinds in the mask (1 << REP_U8 | ...)
+int rep_class_rank(int detector, int desc_type);                 // modsx_rep_class_rank; -1: no such class
+int rep_class_order(int detector, int desc_type);                // modsx_rep_class_order; -1: no such class
 int rep_add_views(modsx_ctx *c, modsx_rep *rep, const modsx_image *img, const modsx_ladder_step &st, const modsx_pair_params &pp);
 int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, const modsx_rep_class_sel *sel, int nsel,
                      const modsx_pair_params &pp, RepTents *const *tents);
@@ -425,12 +456,7 @@ int rep_class_f32(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_r
 // MatchFlannFGINN of one float class for G <= MATCH_MAXB partners in one grouped launch set; outs[g]: partner g's records
 int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
                          double ratio, double contradDist, int nn, std::vector<modsx_tentative> *outs);
-void rep_free_f32(modsx_rep *rep);
 // binary classes (engine_reps_bin.hip); det = the slot index rep_class_bin_ok gives
-bool rep_class_bin_ok(int detector, int desc_type, int *det);    // a binary class
-int rep_class_order(int detector, int desc_type);                // over every class a representation can hold; -1: no such class
-int rep_slot_order(int det, int type);                           // the same by slot (RepClassId)
-const std::vector<modsx_region> &rep_slot_regions(const modsx_rep *rep, int det, int type);      // of any kind of class
 int rep_append_bin(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_region *regs, const uint8_t *rows, bool onDevice,
                    int nbytes, int n, const char *fn);
 int rep_class_bin(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, unsigned char **rows, int *nbytes);
@@ -441,7 +467,22 @@ int reps_bin_check(const char *fn, const modsx_ctx *c, const modsx_rep *rep1, co
 // MatchFLANNDistance of one binary class for G <= MATCH_MAXB partners in one grouped launch set; outs[g]: partner g's records
 int reps_bin_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
                          double distanceThreshold, std::vector<modsx_tentative> *outs);
-void rep_free_bin(modsx_rep *rep);
+// modsx_debug_fginn32_group_geometry / modsx_debug_hamming_group_geometry: the report of an F32Group or a HamGroup of kernel width W
+template <class Group>
+inline int group_geometry_report(const Group &g, int W, const int *prob, int G, int total, int *geometry, int *per_problem, int *splits,
+                                 int cap) {
+  geometry[0] = g.tile; geometry[1] = W; geometry[2] = g.gx; geometry[3] = total;
+  memset(per_problem, 0, sizeof(int) * 3 * G);
+  for (int p = 0; p < g.np; p++) {
+    int *o = per_problem + 3 * prob[p];
+    o[0] = g.ntiles[p]; o[1] = g.S[p]; o[2] = g.tps[p];
+    for (int s = 0; s < g.S[p] && g.first[p] + s < cap; s++) {
+      int *sp = splits + 3 * (g.first[p] + s);
+      sp[0] = prob[p]; sp[1] = s * g.tps[p]; sp[2] = std::min(g.ntiles[p], (s + 1) * g.tps[p]);
+    }
+  }
+  return total;
+}
 bool desc_f32_to_u8(const float *f, size_t n, uint8_t *u);   // false: a value that is not one of the integers 0..255
 int match_pair_group(modsx_ctx *c, const modsx_image *const *imgs1, const modsx_image *const *imgs2, int G,
                      const modsx_pair_params &pp, modsx_pair_result *res, std::vector<VerifyTask> *deferred = nullptr);

@@ -3,7 +3,8 @@
 // nearest keys of every query (32 bytes); the host walks j = 1..3 exactly as the reference does (its f32 division, its f64 positions).
 // A walk that is still open behind the fourth neighbour is closed by one more sweep (k_f32_resolve: the nearest train behind the
 // fourth that ends the walk, and how many trains do not end it).  That count gives the rank of a passing terminal train exactly, so
-// there is no further sweep (kernels_fginn32.hip).  No list of nn neighbours exists anywhere.
+// there is no further sweep (kernels_fginn32.hip).  No list of nn neighbours exists anywhere.  The walk itself -- keys, ratio test,
+// d_pass, the open / close / emit steps and the record -- is fginn_walk.hpp; this file holds the launches, copies and taps around it.
 // The distance (vector_dist of the [Matching] section: L2 or L1) is the chain of the sweep kernels and nothing else: the walk divides
 // and compares whatever distances it is handed, squares or not (matching.cpp:437-451).  Under L1, rows that hold the integers 0..255
 // at 128 columns have a search of their own on bytes (kernels_fginn_l1.hip) with the same keys, workspace and records.
@@ -15,33 +16,6 @@
 #include "engine_api.hpp"
 
 namespace mx {
-
-static inline float key_dist(unsigned long long k) { const uint32_t b = (uint32_t)(k >> 32); float f; memcpy(&f, &b, 4); return f; }
-static inline int key_idx(unsigned long long k) { return (int)(uint32_t)k; }
-constexpr unsigned long long KEY_NONE = ~0ull;
-
-// (double)(d0 / d) <= ratio^2 with the f32 division of matching.cpp:392: the ratio test of the walk
-static inline bool ratio_passes(float d0, float d, double rsq, double *ratio) {
-  const double r = d0 / d;
-  if (ratio) *ratio = r;
-  return r <= rsq;
-}
-
-// The smallest f32 d > 0 with (double)(d0 / d) <= rsq, by bisection over the bit patterns: the quotient does not grow with the
-// divisor (rounding is monotone), d0 / inf = 0 passes (rsq >= 0), so the patterns that pass are an upper range of [1, 0x7f800000].
-// d0 = 0 gives the smallest subnormal: 0 / d = 0 passes for every d > 0, 0 / 0 is NaN and passes nothing.  d0 >= 0 and finite.
-float fginn32_dpass(float d0, double rsq) {
-  uint32_t lo = 1, hi = 0x7f800000u;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    float d;
-    memcpy(&d, &mid, 4);
-    if (ratio_passes(d0, d, rsq, nullptr)) hi = mid; else lo = mid + 1;
-  }
-  float d;
-  memcpy(&d, &lo, 4);
-  return d;
-}
 
 bool fginn32_rows_ok(const float *f, size_t n) {
   bool ok = true;
@@ -84,14 +58,6 @@ int fginn_l1_geometry_report(int n1, int n2, int splits, int *geo6) {
   return MODSX_OK;
 }
 
-static modsx_tentative make_record(int q, const unsigned long long *k, unsigned long long kj, double ratio) {
-  modsx_tentative t;
-  t.q = q; t.t0 = key_idx(k[0]); t.tj = key_idx(kj); t.t1 = key_idx(k[1]);
-  t.d1 = key_dist(k[0]); t.d2 = key_dist(kj); t.d2by2ndcl = key_dist(k[1]);
-  t.ratio = sqrt(ratio);
-  return t;
-}
-
 // d1 / d2: dense rows in HBM -- [n][dim] f32, or with bytes [n][128] u8 (dist is then L1); pos2: [n2][2] f64 on the host.  n1 >= 1,
 // n2 >= 1, arguments checked by the caller.  tap (optional): forced split count, stage mask, and what the stages did.
 static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n1, const void *d2, int n2, int dim, const double *pos2,
@@ -132,31 +98,12 @@ static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n
   memcpy(top4.data(), (const char *)c->hMatch.p + 16, (size_t)n1 * 32);
   if (tap && tap->top4) memcpy(tap->top4, top4.data(), (size_t)n1 * 32);
 
-  std::vector<modsx_tentative> rec(n1);
-  std::vector<unsigned char> has(n1, 0), stage(n1, 0);
+  FginnWalk walk;
   std::vector<F32Open> open;
-  const int jTop = std::min(3, nn - 1);
-  for (int q = 0; q < n1; q++) {
-    const unsigned long long *k = &top4[(size_t)q * 4];
-    const float d0 = key_dist(k[0]);
-    bool ended = k[0] == KEY_NONE;
-    for (int j = 1; j <= jTop && !ended; j++) {
-      if (k[j] == KEY_NONE) { ended = true; break; }            // the trains ran out (the oracle's ir[j] < 0)
-      double ratio;
-      if (ratio_passes(d0, key_dist(k[j]), rsq, &ratio)) { rec[q] = make_record(q, k, k[j], ratio); has[q] = 1; ended = true; break; }
-      const int i0 = key_idx(k[0]), ij = key_idx(k[j]);
-      const double dx = pos2[2 * (size_t)i0] - pos2[2 * (size_t)ij], dy = pos2[2 * (size_t)i0 + 1] - pos2[2 * (size_t)ij + 1];
-      if (dx * dx + dy * dy > cd2) ended = true;
-    }
-    if (ended || nn - 1 <= 3) continue;
-    F32Open o;
-    o.klast = k[3]; o.q = q; o.t0 = key_idx(k[0]); o.dpass = fginn32_dpass(d0, rsq); o.pad = 0;
-    open.push_back(o);
-    stage[q] = 1;
-  }
+  fginn_walk_open(top4.data(), n1, pos2, rsq, cd2, nn, 0, walk, open);
 
   // the open queries go through one more sweep: open[] and the initial closed[] up, closed[] down
-  int nResolve = (int)open.size(), nByCount = 0;
+  int nByCount = 0;
   if (!open.empty() && (stageMask & 2)) {
     const Fginn32Work w = fginn32_work(g, n1, c->matchWork.p);
     const int nu = (int)open.size();
@@ -170,21 +117,11 @@ static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n
     MX_HIP(hipMemcpyAsync(closed.data(), w.closed, (size_t)nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
     MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
     MX_HIP(hipGetLastError());
-    for (int u = 0; u < nu; u++) {
-      const F32Open &o = open[u];
-      const unsigned long long kt = closed[u].kterm;
-      if (kt == KEY_NONE) continue;                             // nothing ends the walk before the trains or the nn run out
-      const unsigned long long *k = &top4[(size_t)o.q * 4];
-      double ratio;
-      if (!ratio_passes(key_dist(k[0]), key_dist(kt), rsq, &ratio)) continue;      // it ends the walk by contradiction, reached or not
-      // it passes, so d >= d_pass, and every non-terminal train (d < d_pass) comes before it: its rank is 3 + cnt + 1 exactly
-      if ((long)closed[u].cnt + 4 <= nn - 1) { rec[o.q] = make_record(o.q, k, kt, ratio); has[o.q] = 1; }
-      else { stage[o.q] = 2; nByCount++; }                      // the nn run out first
-    }
+    nByCount = fginn_walk_close(open, closed.data(), top4.data(), n1, rsq, nn, &walk);
   }
-  for (int q = 0; q < n1; q++) if (has[q]) out.push_back(rec[q]);
-  if (tap && tap->stage) memcpy(tap->stage, stage.data(), n1);
-  if (tap && tap->counters) { tap->counters[0] = nResolve; tap->counters[1] = nByCount; tap->counters[2] = (int)out.size(); }
+  fginn_walk_emit(walk, out);
+  if (tap && tap->stage) memcpy(tap->stage, walk.stage.data(), n1);
+  if (tap && tap->counters) { tap->counters[0] = (int)open.size(); tap->counters[1] = nByCount; tap->counters[2] = (int)out.size(); }
   return MODSX_OK;
 }
 

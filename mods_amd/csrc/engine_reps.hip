@@ -10,18 +10,121 @@
 // launch_match_pack_trains, MatchProblem::packed).  A representation is changed by one thread at a time; otherwise it is
 // read-only and any context of its device may match against it, also at the same time.  The float classes (SURF, LIOP, DAISY,
 // MROGH, learned vectors) and their grouped search are engine_reps_f32.hip, the binary classes (ORB, BRISK, FREAK) and theirs
-// engine_reps_bin.hip; reps_match_group and reps_verify_task take all three kinds.
+// engine_reps_bin.hip; reps_match_group and reps_verify_task take all three kinds.  What the kinds share is here in one copy: the
+// class table (which (detector, descriptor) pairs are classes, of which kind, in which slot and in which order) and the store of
+// the float and the binary slots (slot_release, slot_reserve, slot_zero_again, slot_download).
 #include <math.h>
 #include <algorithm>
 #include "engine_api.hpp"
 
 namespace mx {
 
-bool rep_class_ok(int detector, int desc_type, int *det) {
-  if (detector != MODSX_DET_HESSIAN && detector != MODSX_DET_MSER) return false;
-  if (desc_type < 0 || desc_type > 3) return false;
-  *det = detector == MODSX_DET_MSER ? 1 : 0;
+// ---- the class table: what GetCorresponcesVector("All", "All") (correspondencebank.cpp:117-179) iterates over ----
+// the twelve descriptor names in std::map order: BRISK, CAFFE, DAISY, FREAK, HalfRootSIFT, HalfSIFT, LIOP, MROGH, ORB, RootSIFT,
+// SIFT, SURF; the four detector names: HessianAffine, MSER, ORB, SURF
+static const int DESC_ORDER[12] = {MODSX_DESC_BRISK, MODSX_DESC_CAFFE, MODSX_DESC_DAISY, MODSX_DESC_FREAK, MODSX_DESC_HALF_ROOT_SIFT,
+                                   MODSX_DESC_HALF_SIFT, MODSX_DESC_LIOP, MODSX_DESC_MROGH, MODSX_DESC_ORB, MODSX_DESC_ROOT_SIFT,
+                                   MODSX_DESC_SIFT, MODSX_DESC_SURF};
+static const int DET_ORDER[4] = {MODSX_DET_HESSIAN, MODSX_DET_MSER, MODSX_DET_ORB, MODSX_DET_SURF};
+// per kind (REP_U8, REP_F32, REP_BIN) and detector place: the slot index inside the kind, -1: the kind has no class of that detector
+static const int SLOT_OF[3][4] = {{0, 1, -1, -1}, {0, 1, -1, 2}, {0, 1, 2, 3}};
+static int kind_of(int type) {
+  if (type >= MODSX_DESC_SIFT && type <= MODSX_DESC_HALF_ROOT_SIFT) return REP_U8;
+  if (type >= MODSX_DESC_CAFFE && type <= MODSX_DESC_SURF) return REP_F32;
+  return type >= MODSX_DESC_BRISK && type <= MODSX_DESC_ORB ? REP_BIN : -1;
+}
+static int place_in(const int *order, int n, int v) {
+  for (int i = 0; i < n; i++) if (order[i] == v) return i;
+  return -1;
+}
+
+bool rep_class_id(int detector, int desc_type, RepClassId *id) {
+  const int kind = kind_of(desc_type), dp = place_in(DET_ORDER, 4, detector);
+  if (kind < 0 || dp < 0 || SLOT_OF[kind][dp] < 0) return false;
+  *id = {kind, SLOT_OF[kind][dp], desc_type, place_in(DESC_ORDER, 12, desc_type) * 4 + dp};
   return true;
+}
+int rep_class_detector(const RepClassId &k) { return DET_ORDER[k.order % 4]; }
+void rep_classes(RepClassList &l, unsigned kinds) {
+  RepClassId k;
+  for (int o = 0; o < REP_ORDERS; o++)
+    if (rep_class_id(DET_ORDER[o % 4], DESC_ORDER[o / 4], &k) && (kinds >> k.kind & 1)) l.add(k);
+}
+int rep_class_order(int detector, int desc_type) {
+  RepClassId k;
+  return rep_class_id(detector, desc_type, &k) ? k.order : -1;
+}
+// the same order over the names that are not binary, with the float slots' three detectors for every one of them
+int rep_class_rank(int detector, int desc_type) {
+  const int kind = kind_of(desc_type), dp = place_in(DET_ORDER, 4, detector);
+  if (kind < 0 || kind == REP_BIN || dp < 0 || SLOT_OF[REP_F32][dp] < 0) return -1;
+  int names = 0;
+  for (int i = 0; DESC_ORDER[i] != desc_type; i++) names += kind_of(DESC_ORDER[i]) != REP_BIN;
+  return names * 3 + SLOT_OF[REP_F32][dp];
+}
+const std::vector<modsx_region> &rep_class_regions(const modsx_rep *rep, const RepClassId &k) {
+  if (k.kind == REP_BIN) return rep->bslot[k.det][k.type - MODSX_DESC_BRISK].regs;
+  if (k.kind == REP_F32) return rep->fslot[k.det][k.type - MODSX_DESC_CAFFE].regs;
+  return rep->slot[k.det][k.type].regs;
+}
+
+// ---- the store of the float and the binary slots (RepRows) ----
+void slot_release(RepRows &k) {
+  k.rows.release(); k.pos.release();
+  k.cap = 0; k.capW = 0;
+}
+
+int slot_reserve(modsx_ctx *c, RepRows &k, size_t rows, int W, bool isFloat) {
+  if (k.cap && k.capW != W) {
+    if (!k.regs.empty()) { set_error(std::string(isFloat ? "a float" : "a binary") + " class holds rows of another kernel width"); return MODSX_ERR_ARG; }
+    slot_release(k);
+  }
+  if (rows <= k.cap) return MODSX_OK;
+  size_t cap = k.cap ? k.cap : isFloat ? MODSX_REP_F32_FIRST_ROWS : MODSX_REP_BIN_FIRST_ROWS;
+  while (cap < rows) cap *= 4;
+  DevBuf nr, np;
+  if (!nr.ensure(cap * W * 4) || (isFloat && !np.ensure(cap * 16))) { nr.release(); np.release(); return MODSX_ERR_NOMEM; }
+  const size_t n = k.regs.size();
+  hipError_t e = hipMemsetAsync(nr.p, 0, cap * W * 4, c->stream);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(nr.p, k.rows.p, n * W * 4, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess && n && isFloat) e = hipMemcpyAsync(np.p, k.pos.p, n * 16, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { nr.release(); np.release(); }
+  MX_HIP(e);
+  k.rows.release(); k.pos.release();
+  k.rows = nr; k.pos = np; k.cap = cap; k.capW = W;
+  return MODSX_OK;
+}
+
+hipError_t slot_zero_again(modsx_ctx *c, RepRows &k, size_t base, int n) {
+  hipError_t e = hipMemsetAsync((uint32_t *)k.rows.p + base * k.capW, 0, (size_t)n * k.capW * 4, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  return e;
+}
+
+int slot_download(modsx_ctx *c, const char *fn, const RepRows &k, size_t widthBytes, modsx_region **regs, void **rows) {
+  CtxBusy busy(c);
+  const std::string f(fn);
+  const size_t n = k.regs.size();
+  if (regs) *regs = nullptr;
+  if (rows) {
+    *rows = malloc(std::max<size_t>(4, n * widthBytes));
+    if (!*rows) { set_error(f + ": out of memory"); return MODSX_ERR_NOMEM; }
+    if (n) {      // a row is its values in order, zero behind widthBytes
+      hipError_t e = hipMemcpy2DAsync(*rows, widthBytes, k.rows.p, (size_t)k.W * 4, widthBytes, n, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) { free(*rows); *rows = nullptr; set_error(f + ": row download failed"); return MODSX_ERR_DEVICE; }
+    }
+  }
+  if (regs) {
+    *regs = to_malloc(k.regs);
+    if (!*regs) {
+      if (rows) { free(*rows); *rows = nullptr; }
+      set_error(f + ": out of memory");
+      return MODSX_ERR_NOMEM;
+    }
+  }
+  return (int)n;
 }
 
 // the packed train form of a slot, rebuilt whole (the parity partition ranks a train among ALL trains of the slot) on c's stream
@@ -84,60 +187,50 @@ int rep_match_fginn(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *rep2, 
   return match_device_batch(c, 1, &d1, &n1, &d2, &n2, &pos, ratio, contradDist, nn, &out, nullptr, nullptr, nullptr, nullptr, &pack);
 }
 
-// MatchImgReps for the classes sel[0..nsel) of G <= MATCH_MAXB partners: one matcher launch set per class (problems with an
-// empty side are left out by match_device_batch), rep1 the queries, the partners' packs the trains.  tents[g]->t[det][type]
-// receives the class's tentatives of partner g; the other classes of tents[g] keep theirs.
+// one u8 class of G partners: one matcher launch set (problems with an empty side are left out by match_device_batch), rep1 the
+// queries, the partners' packs the trains
+static int reps_u8_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type, double ratio,
+                               const modsx_pair_params &pp, std::vector<modsx_tentative> *out) {
+  const RepSlot &q = rep1->slot[det][type];
+  const uint8_t *d1[MATCH_MAXB], *d2[MATCH_MAXB];
+  const double *pos[MATCH_MAXB];
+  const void *pack[MATCH_MAXB];
+  int n1[MATCH_MAXB], n2[MATCH_MAXB];
+  bool any = false;
+  for (int g = 0; g < G; g++) {
+    const RepSlot &t = reps2[g]->slot[det][type];
+    d1[g] = (const uint8_t *)q.desc.p; n1[g] = (int)q.regs.size();
+    d2[g] = (const uint8_t *)t.desc.p; n2[g] = (int)t.regs.size();
+    pos[g] = nullptr;
+    pack[g] = n2[g] ? t.pack.p : nullptr;
+    any = any || (n1[g] > 0 && n2[g] > 0);
+  }
+  if (!any) return MODSX_OK;
+  return match_device_batch(c, G, d1, n1, d2, n2, pos, ratio, pp.contradDist, pp.nn, out, nullptr, nullptr, fginn_db_for(c, type), nullptr, pack);
+}
+
+// MatchImgReps for the classes sel[0..nsel) of G <= MATCH_MAXB partners: one launch set per class -- the u8 matcher, the grouped
+// f32 matcher (engine_reps_f32.hip) or the grouped Hamming search (engine_reps_bin.hip; `ratio` is its DistanceThreshold).
+// tents[g]->of[the class's order] receives the class's tentatives of partner g; the other classes of tents[g] keep theirs.
 int reps_match_group(modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, const modsx_rep_class_sel *sel, int nsel,
                      const modsx_pair_params &pp, RepTents *const *tents) {
   CtxBusy busy(c);
   if (G < 1 || G > MATCH_MAXB) { set_error("reps_match_group: group size"); return MODSX_ERR_ARG; }
   for (int s = 0; s < nsel; s++) {
-    int det;
-    const int type = sel[s].desc_type;
-    if (rep_class_f32_ok(sel[s].detector, type, &det)) {
-      // a float class: one grouped launch set of the f32 matcher (engine_reps_f32.hip)
-      std::vector<modsx_tentative> out[MATCH_MAXB];
-      const int rc = reps_f32_match_group(c, "modsx_match_reps", rep1, reps2, G, det, type, sel[s].ratio, pp.contradDist, pp.nn, out);
-      if (rc) return rc;
-      for (int g = 0; g < G; g++) tents[g]->f[det][type - MODSX_DESC_CAFFE] = std::move(out[g]);
-      continue;
-    }
-    if (rep_class_bin_ok(sel[s].detector, type, &det)) {
-      // a binary class: one grouped launch set of the Hamming search (engine_reps_bin.hip); `ratio` is its DistanceThreshold
-      std::vector<modsx_tentative> out[MATCH_MAXB];
-      const int rc = reps_bin_match_group(c, "modsx_match_reps", rep1, reps2, G, det, type, sel[s].ratio, out);
-      if (rc) return rc;
-      for (int g = 0; g < G; g++) tents[g]->b[det][type - MODSX_DESC_BRISK] = std::move(out[g]);
-      continue;
-    }
-    if (!rep_class_ok(sel[s].detector, type, &det)) { set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
-    const RepSlot &q = rep1->slot[det][type];
-    const uint8_t *d1[MATCH_MAXB], *d2[MATCH_MAXB];
-    const double *pos[MATCH_MAXB];
-    const void *pack[MATCH_MAXB];
-    int n1[MATCH_MAXB], n2[MATCH_MAXB];
+    RepClassId k;
+    if (!rep_class_id(sel[s].detector, sel[s].desc_type, &k)) { set_error("modsx_match_reps: a class names a detector or descriptor type that does not exist"); return MODSX_ERR_ARG; }
     std::vector<modsx_tentative> out[MATCH_MAXB];
-    bool any = false;
-    for (int g = 0; g < G; g++) {
-      const RepSlot &t = reps2[g]->slot[det][type];
-      d1[g] = (const uint8_t *)q.desc.p; n1[g] = (int)q.regs.size();
-      d2[g] = (const uint8_t *)t.desc.p; n2[g] = (int)t.regs.size();
-      pos[g] = nullptr;
-      pack[g] = n2[g] ? t.pack.p : nullptr;
-      any = any || (n1[g] > 0 && n2[g] > 0);
-    }
-    if (any) {
-      const int rc = match_device_batch(c, G, d1, n1, d2, n2, pos, sel[s].ratio, pp.contradDist, pp.nn, out, nullptr, nullptr,
-                                        fginn_db_for(c, type), nullptr, pack);
-      if (rc) return rc;
-    }
-    for (int g = 0; g < G; g++) tents[g]->t[det][type] = std::move(out[g]);
+    const int rc = k.kind == REP_F32 ? reps_f32_match_group(c, "modsx_match_reps", rep1, reps2, G, k.det, k.type, sel[s].ratio, pp.contradDist, pp.nn, out)
+                 : k.kind == REP_BIN ? reps_bin_match_group(c, "modsx_match_reps", rep1, reps2, G, k.det, k.type, sel[s].ratio, out)
+                                     : reps_u8_match_group(c, rep1, reps2, G, k.det, k.type, sel[s].ratio, pp, out);
+    if (rc) return rc;
+    for (int g = 0; g < G; g++) tents[g]->of[k.order] = std::move(out[g]);
   }
   prof_collect(c);
   return MODSX_OK;
 }
 
-// GetCorresponcesVector("All", "All") over the classes of `classes` (in map order: rep_class_rank) that are non-empty in either
+// GetCorresponcesVector("All", "All") over the classes of `classes` (in map order: RepClassId::order) that are non-empty in either
 // representation: the region lists as segments of the representations' own vectors (which must outlive the task), the tentatives
 // re-based onto their concatenation.  res is reset to the zeroed result with H = -1.
 void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepClassList &classes, const RepTents &tents,
@@ -146,14 +239,12 @@ void reps_verify_task(const modsx_rep *rep1, const modsx_rep *rep2, const RepCla
   for (int i = 0; i < 9; i++) res->H[i] = -1;
   task.l1.clear(); task.l2.clear(); task.own.clear(); task.tents.clear();
   for (int i = 0; i < classes.n; i++) {
-    const int d = classes.k[i].det, t = classes.k[i].type;
-    const std::vector<modsx_region> &a = rep_slot_regions(rep1, d, t), &b = rep_slot_regions(rep2, d, t);
+    const RepClassId &k = classes.k[i];
+    const std::vector<modsx_region> &a = rep_class_regions(rep1, k), &b = rep_class_regions(rep2, k);
     if (a.empty() && b.empty()) continue;
     const int o1 = (int)task.l1.size(), o2 = (int)task.l2.size();
     task.l1.add(a); task.l2.add(b);
-    const std::vector<modsx_tentative> &mine = t >= MODSX_DESC_BRISK ? tents.b[d][t - MODSX_DESC_BRISK] :
-                                               t >= MODSX_DESC_CAFFE ? tents.f[d][t - MODSX_DESC_CAFFE] : tents.t[d][t];
-    for (modsx_tentative tt : mine) {
+    for (modsx_tentative tt : tents.of[k.order]) {
       tt.q += o1; tt.t0 += o2;
       if (tt.t1 >= 0) tt.t1 += o2;
       if (tt.tj >= 0) tt.tj += o2;
@@ -171,6 +262,9 @@ using namespace mx;
 
 extern "C" {
 
+int modsx_rep_class_rank(int detector, int desc_type) { return rep_class_rank(detector, desc_type); }
+int modsx_rep_class_order(int detector, int desc_type) { return rep_class_order(detector, desc_type); }
+
 modsx_rep *modsx_rep_create(modsx_ctx *ctx) {
   if (!ctx) { set_error("modsx_rep_create: null context"); return nullptr; }
   modsx_rep *rep = new modsx_rep();
@@ -182,8 +276,8 @@ void modsx_rep_free(modsx_ctx *ctx, modsx_rep *rep) {
   if (!rep) return;
   hipSetDevice(ctx ? ctx->dev : rep->dev);
   for (int d = 0; d < 2; d++) for (int t = 0; t < 4; t++) { rep->slot[d][t].desc.release(); rep->slot[d][t].pack.release(); }
-  rep_free_f32(rep);
-  rep_free_bin(rep);
+  for (auto &byDet : rep->fslot) for (RepSlotF &k : byDet) slot_release(k);
+  for (auto &byDet : rep->bslot) for (RepSlotB &k : byDet) slot_release(k);
   delete rep;
 }
 
@@ -222,10 +316,7 @@ int modsx_rep_class(modsx_ctx *ctx, const modsx_rep *rep, int detector, int desc
   if (!ctx || !rep || !rep_class_ok(detector, desc_type, &det)) { set_error("modsx_rep_class: bad argument"); return MODSX_ERR_ARG; }
   const RepSlot &k = rep->slot[det][desc_type];
   const size_t n = k.regs.size();
-  if (regs) {
-    *regs = (modsx_region *)malloc(sizeof(modsx_region) * std::max<size_t>(1, n));
-    if (n) memcpy(*regs, k.regs.data(), sizeof(modsx_region) * n);
-  }
+  if (regs) *regs = to_malloc(k.regs);
   if (desc_u8) {
     *desc_u8 = (unsigned char *)malloc(std::max<size_t>(1, n * 128));
     if (n) {
@@ -250,8 +341,7 @@ int modsx_rep_match_fginn(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_rep
   std::vector<modsx_tentative> t;
   const int rc = rep_match_fginn(ctx, rep1, rep2, det, desc_type, ratio, contradDist, nn, t);
   if (rc) return rc;
-  *out = (modsx_tentative *)malloc(sizeof(modsx_tentative) * std::max<size_t>(1, t.size()));
-  if (!t.empty()) memcpy(*out, t.data(), sizeof(modsx_tentative) * t.size());
+  *out = to_malloc(t);
   return (int)t.size();
 }
 

@@ -3,10 +3,11 @@
 //   ImageRepresentation::RegionVectorMap[det][desc]      any descriptor name                       (one RepSlotB per class)
 //   LoadRegions                                          imagerepresentation.cpp:2139-2215         (rep_append_bin)
 //   MatchImgReps: MatchFLANNDistance on a binary class   correspondencebank.cpp:291-347            (reps_bin_match_group)
-//   GetCorresponcesVector("All", "All")                  correspondencebank.cpp:117-179            (rep_class_order, RepClassList)
 // A slot keeps its rows exactly as k_hamming_pack writes them (kernels_hamming.hip: WK dwords per row, zero behind nbytes) with
 // zero rows up to its capacity, a multiple of 1024 rows: whole workgroups of queries and whole tiles of trains at every WK.  Nothing
-// is packed when a slot is matched, and an append only packs behind the old rows.  The search is the grouped launch set of
+// is packed when a slot is matched, and an append only packs behind the old rows.  The store itself (release, reserve, the
+// zero-again rollback, the class download) is the one the float slots use too and lives in engine_reps.hip with the class table;
+// here are the pack kernel, the width rule and the search.  The search is the grouped launch set of
 // kernels_hamming.hip; it has no walk and no resolve pass, so a group of partners costs one search launch, one merge launch and
 // ONE host round trip, where matching its partners one by one costs two pack launches, two search launches and a round trip each.
 // The record rule is the one copy in engine_hamming.hip (hamming_tentatives), applied per partner.
@@ -19,83 +20,23 @@
 
 namespace mx {
 
-// std::map order of the reference's descriptor names over every kind of class ...
-static const int DESC_ORDER[12] = {MODSX_DESC_BRISK, MODSX_DESC_CAFFE, MODSX_DESC_DAISY, MODSX_DESC_FREAK, MODSX_DESC_HALF_ROOT_SIFT,
-                                   MODSX_DESC_HALF_SIFT, MODSX_DESC_LIOP, MODSX_DESC_MROGH, MODSX_DESC_ORB, MODSX_DESC_ROOT_SIFT,
-                                   MODSX_DESC_SIFT, MODSX_DESC_SURF};
-// ... and of its detector names: HessianAffine, MSER, ORB, SURF
-static int det_name_place(int detector) {
-  return detector == MODSX_DET_HESSIAN ? 0 : detector == MODSX_DET_MSER ? 1 : detector == MODSX_DET_ORB ? 2 : detector == MODSX_DET_SURF ? 3 : -1;
-}
-static int order_of(int detPlace, int type) {
-  for (int i = 0; i < 12; i++) if (DESC_ORDER[i] == type) return i * 4 + detPlace;
-  return -1;
-}
-bool rep_class_bin_ok(int detector, int desc_type, int *det) {
-  *det = det_name_place(detector);
-  return *det >= 0 && desc_type >= MODSX_DESC_BRISK && desc_type <= MODSX_DESC_ORB;
-}
-int rep_class_order(int detector, int desc_type) {
-  int det;
-  if (!rep_class_ok(detector, desc_type, &det) && !rep_class_f32_ok(detector, desc_type, &det) && !rep_class_bin_ok(detector, desc_type, &det))
-    return -1;
-  return order_of(det_name_place(detector), desc_type);
-}
-// the u8 and float slots count HessianAffine, MSER, SURF as 0, 1, 2; the binary slots have ORB between MSER and SURF
-int rep_slot_order(int det, int type) { return order_of(type < MODSX_DESC_BRISK && det == 2 ? 3 : det, type); }
-
 static RepSlotB &bslot(modsx_rep *rep, int det, int type) { return rep->bslot[det][type - MODSX_DESC_BRISK]; }
 static const RepSlotB &bslot(const modsx_rep *rep, int det, int type) { return rep->bslot[det][type - MODSX_DESC_BRISK]; }
-
-const std::vector<modsx_region> &rep_slot_regions(const modsx_rep *rep, int det, int type) {
-  if (type >= MODSX_DESC_BRISK) return bslot(rep, det, type).regs;
-  if (type >= MODSX_DESC_CAFFE) return rep->fslot[det][type - MODSX_DESC_CAFFE].regs;
-  return rep->slot[det][type].regs;
-}
-
-static void slot_release(RepSlotB &k) {
-  k.rows.release();
-  k.cap = 0; k.capWK = 0;
-}
-
-// room for `rows` rows of WK dwords: the old rows are copied once, everything behind them is zero.  A class that holds regions
-// has capWK == its WK, an empty one has no buffer (rep_append_bin)
-static int slot_reserve(modsx_ctx *c, RepSlotB &k, size_t rows, int WK) {
-  if (k.cap && k.capWK != WK) {
-    if (!k.regs.empty()) { set_error("a binary class holds rows of another kernel width"); return MODSX_ERR_ARG; }
-    slot_release(k);
-  }
-  if (rows <= k.cap) return MODSX_OK;
-  size_t cap = k.cap ? k.cap : REP_BIN_FIRST_ROWS;
-  while (cap < rows) cap *= 4;
-  DevBuf nr;
-  if (!nr.ensure(cap * WK * 4)) { nr.release(); return MODSX_ERR_NOMEM; }
-  const size_t n = k.regs.size();
-  hipError_t e = hipMemsetAsync(nr.p, 0, cap * WK * 4, c->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(nr.p, k.rows.p, n * WK * 4, hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) nr.release();
-  MX_HIP(e);
-  k.rows.release();
-  k.rows = nr; k.cap = cap; k.capWK = WK;
-  return MODSX_OK;
-}
 
 // dense: [n][nbytes] u8 in HBM, any alignment.  The rows are packed behind the old ones; the count moves only when that is done
 static int slot_store(modsx_ctx *c, RepSlotB &k, int nbytes, const modsx_region *regs, const uint8_t *dense, int n) {
   const int WK = hamming_kernel_width((nbytes + 3) / 4);
   const size_t base = k.regs.size();
-  const int rc = slot_reserve(c, k, base + (size_t)n, WK);
+  const int rc = slot_reserve(c, k, base + (size_t)n, WK, false);
   if (rc) return rc;
-  uint32_t *dst = (uint32_t *)k.rows.p + base * WK;
-  launch_hamming_pack_rows(c->stream, dense, n, nbytes, WK, dst);
+  launch_hamming_pack_rows(c->stream, dense, n, nbytes, WK, (uint32_t *)k.rows.p + base * WK);
   hipError_t e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) {                                    // the padding behind the old rows is zero again, if the device still answers
-    if (hipMemsetAsync(dst, 0, (size_t)n * WK * 4, c->stream) == hipSuccess) hipStreamSynchronize(c->stream);
+    slot_zero_again(c, k, base, n);
     MX_HIP(e);
   }
-  k.nbytes = nbytes; k.WK = WK;
+  k.nbytes = nbytes; k.W = WK;
   k.regs.insert(k.regs.end(), regs, regs + n);
   c->hamGroupCounters[2] += n;
   return MODSX_OK;
@@ -129,35 +70,9 @@ int rep_append_bin(modsx_ctx *c, modsx_rep *rep, int det, int type, const modsx_
 }
 
 int rep_class_bin(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, unsigned char **rows, int *nbytes) {
-  CtxBusy busy(c);
   const RepSlotB &k = bslot(rep, det, type);
-  const size_t n = k.regs.size();
-  if (nbytes) *nbytes = n ? k.nbytes : 0;
-  if (regs) *regs = nullptr;
-  if (rows) {
-    *rows = (unsigned char *)malloc(std::max<size_t>(1, n * k.nbytes));
-    if (!*rows) { set_error("modsx_rep_class_bin: out of memory"); return MODSX_ERR_NOMEM; }
-    if (n) {
-      // a packed row is its bytes in order (little-endian dwords), zero behind nbytes
-      hipError_t e = hipMemcpy2DAsync(*rows, (size_t)k.nbytes, k.rows.p, (size_t)k.WK * 4, (size_t)k.nbytes, n, hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { free(*rows); *rows = nullptr; set_error("modsx_rep_class_bin: row download failed"); return MODSX_ERR_DEVICE; }
-    }
-  }
-  if (regs) {
-    *regs = (modsx_region *)malloc(sizeof(modsx_region) * std::max<size_t>(1, n));
-    if (!*regs) {
-      if (rows) { free(*rows); *rows = nullptr; }
-      set_error("modsx_rep_class_bin: out of memory");
-      return MODSX_ERR_NOMEM;
-    }
-    if (n) memcpy(*regs, k.regs.data(), sizeof(modsx_region) * n);
-  }
-  return (int)n;
-}
-
-void rep_free_bin(modsx_rep *rep) {
-  for (auto &byDet : rep->bslot) for (RepSlotB &k : byDet) slot_release(k);
+  if (nbytes) *nbytes = k.regs.empty() ? 0 : k.nbytes;
+  return slot_download(c, "modsx_rep_class_bin", k, (size_t)k.nbytes, regs, (void **)rows);      // a packed row is its bytes in order
 }
 
 int reps_bin_check(const char *fn, const modsx_ctx *c, const modsx_rep *rep1, const modsx_rep *const *reps2, int n, int det, int type,
@@ -214,14 +129,7 @@ int reps_bin_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
 
 using namespace mx;
 
-static void hand_over(const std::vector<modsx_tentative> &t, modsx_tentative **out) {
-  *out = (modsx_tentative *)malloc(sizeof(modsx_tentative) * std::max<size_t>(1, t.size()));
-  if (!t.empty()) memcpy(*out, t.data(), sizeof(modsx_tentative) * t.size());
-}
-
 extern "C" {
-
-int modsx_rep_class_order(int detector, int desc_type) { return rep_class_order(detector, desc_type); }
 
 int modsx_rep_append_bin(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const void *desc,
                          int nbytes, int dtype, int n) {
@@ -276,7 +184,7 @@ int modsx_rep_match_group_hamming(modsx_ctx *ctx, const modsx_rep *rep1, const m
   std::vector<modsx_tentative> t[MATCH_MAXB];
   const int rc = reps_bin_match_group(ctx, "modsx_rep_match_group_hamming", rep1, reps2, G, det, desc_type, distanceThreshold, t);
   if (rc) return rc;
-  for (int g = 0; g < G; g++) { hand_over(t[g], &outs[g]); counts[g] = (int)t[g].size(); }
+  for (int g = 0; g < G; g++) { outs[g] = to_malloc(t[g]); counts[g] = (int)t[g].size(); }
   return G;
 }
 
@@ -288,7 +196,7 @@ int modsx_rep_match_hamming(modsx_ctx *ctx, const modsx_rep *rep1, const modsx_r
   std::vector<modsx_tentative> t;
   const int rc = reps_bin_match_group(ctx, "modsx_rep_match_hamming", rep1, &rep2, 1, det, desc_type, distanceThreshold, &t);
   if (rc) return rc;
-  hand_over(t, out);
+  *out = to_malloc(t);
   return (int)t.size();
 }
 
@@ -304,17 +212,7 @@ int modsx_debug_hamming_group_geometry(int n1, const int *n2, int G, int nbytes,
   HamGroup g;
   int prob[MATCH_MAXB];
   const int total = hamming_group_geometry(n1, n2, G, (nbytes + 3) / 4, g, prob);
-  geometry[0] = g.tile; geometry[1] = g.WK; geometry[2] = g.gx; geometry[3] = total;
-  memset(per_problem, 0, sizeof(int) * 3 * G);
-  for (int p = 0; p < g.np; p++) {
-    int *o = per_problem + 3 * prob[p];
-    o[0] = g.ntiles[p]; o[1] = g.S[p]; o[2] = g.tps[p];
-    for (int s = 0; s < g.S[p] && g.first[p] + s < cap; s++) {
-      int *sp = splits + 3 * (g.first[p] + s);
-      sp[0] = prob[p]; sp[1] = s * g.tps[p]; sp[2] = std::min(g.ntiles[p], (s + 1) * g.tps[p]);
-    }
-  }
-  return total;
+  return group_geometry_report(g, g.WK, prob, G, total, geometry, per_problem, splits, cap);
 }
 
 int modsx_hamming_group_counters(modsx_ctx *ctx, long *out, int n) {

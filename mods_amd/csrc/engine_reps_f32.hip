@@ -4,13 +4,14 @@
 //   LoadRegions                                          imagerepresentation.cpp:2139-2215         (rep_append_f32)
 //   DescribeRegions<SURF / LIOP / DAISY>                 imagerepresentation.cpp:1829-1838, 1954-1963   (rep_describe_append)
 //   MatchImgReps: MatchFlannFGINN on every class         correspondencebank.cpp:291-347            (reps_f32_match_group)
-//   GetCorresponcesVector("All", "All")                  correspondencebank.cpp:117-179            (rep_class_rank, RepClassList)
 // A slot keeps its rows in the row form of the f32 matcher (kernels_fginn32.hip: DK floats per row, zero behind dim) with zero rows
 // up to its capacity, a multiple of 256: whole workgroups of queries and whole tiles of trains at every tile length.  Nothing is
-// packed when a slot is matched, and an append only writes behind the old rows.  The search is the grouped launch set of
-// kernels_fginn32.hip; the walk over the four nearest neighbours is that of engine_fginn32.hip (match_fginn32_device), run per
-// problem on the one copy of all problems' keys; the walks left open in any problem share one resolve launch.  So a group costs
-// two host round trips, where matching its partners one by one costs two each and packs both sides every time.
+// packed when a slot is matched, and an append only writes behind the old rows.  The store itself (release, reserve, the zero-again
+// rollback, the class download) is the one the binary slots use too and lives in engine_reps.hip with the class table; here are
+// the pack kernel, the flag word, the host positions and the width rules.  The search is the grouped launch set of
+// kernels_fginn32.hip; the walk over the four nearest neighbours is fginn_walk.hpp, the one the single call runs, opened per
+// problem on the one copy of all problems' keys; the walks left open in any problem share one resolve launch and one close step.
+// So a group costs two host round trips, where matching its partners one by one costs two each and packs both sides every time.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -20,35 +21,6 @@
 #include "engine_api.hpp"
 
 namespace mx {
-
-// std::map order of the reference's descriptor names: CAFFE, DAISY, HalfRootSIFT, HalfSIFT, LIOP, MROGH, RootSIFT, SIFT, SURF
-static const int DESC_ORDER[9] = {MODSX_DESC_CAFFE, MODSX_DESC_DAISY, MODSX_DESC_HALF_ROOT_SIFT, MODSX_DESC_HALF_SIFT, MODSX_DESC_LIOP,
-                                  MODSX_DESC_MROGH, MODSX_DESC_ROOT_SIFT, MODSX_DESC_SIFT, MODSX_DESC_SURF};
-// ... and of its detector names: HessianAffine, MSER, SURF
-static int det_slot(int detector) {
-  return detector == MODSX_DET_HESSIAN ? 0 : detector == MODSX_DET_MSER ? 1 : detector == MODSX_DET_SURF ? 2 : -1;
-}
-static int slot_rank(int det, int type) {
-  for (int i = 0; i < 9; i++) if (DESC_ORDER[i] == type) return i * 3 + det;
-  return -1;
-}
-int rep_class_rank(int detector, int desc_type) {
-  const int det = det_slot(detector);
-  return det < 0 ? -1 : slot_rank(det, desc_type);
-}
-bool rep_class_f32_ok(int detector, int desc_type, int *det) {
-  *det = det_slot(detector);
-  return *det >= 0 && desc_type >= MODSX_DESC_CAFFE && desc_type <= MODSX_DESC_SURF;
-}
-void RepClassList::add(int det, int type) {
-  int at = n;
-  while (at > 0 && rep_slot_order(k[at - 1].det, k[at - 1].type) > rep_slot_order(det, type)) { k[at] = k[at - 1]; at--; }
-  k[at] = {det, type};
-  n++;
-}
-void rep_classes_u8(RepClassList &l) {
-  for (int t = 0; t < 4; t++) for (int d = 0; d < 2; d++) l.add(d, t);
-}
 
 static RepSlotF &fslot(modsx_rep *rep, int det, int type) { return rep->fslot[det][type - MODSX_DESC_CAFFE]; }
 static const RepSlotF &fslot(const modsx_rep *rep, int det, int type) { return rep->fslot[det][type - MODSX_DESC_CAFFE]; }
@@ -77,35 +49,6 @@ static int append_args(const char *fn, modsx_ctx *c, const modsx_rep *rep, const
   return MODSX_OK;
 }
 
-static void slot_release(RepSlotF &k) {
-  k.rows.release(); k.pos.release();
-  k.cap = 0; k.capDK = 0;
-}
-
-// room for `rows` rows of DK floats: the old rows and positions are copied once, everything behind them is zero.  The capacity
-// counts rows of capDK floats; a class that holds regions has capDK == its DK, an empty one has no buffer (slot_ingest)
-static int slot_reserve(modsx_ctx *c, RepSlotF &k, size_t rows, int DK) {
-  if (k.cap && k.capDK != DK) {
-    if (!k.regs.empty()) { set_error("a float class holds rows of another kernel width"); return MODSX_ERR_ARG; }
-    slot_release(k);
-  }
-  if (rows <= k.cap) return MODSX_OK;
-  size_t cap = k.cap ? k.cap : REP_F32_FIRST_ROWS;
-  while (cap < rows) cap *= 4;
-  DevBuf nr, np;
-  if (!nr.ensure(cap * DK * 4) || !np.ensure(cap * 16)) { nr.release(); np.release(); return MODSX_ERR_NOMEM; }
-  const size_t n = k.regs.size();
-  hipError_t e = hipMemsetAsync(nr.p, 0, cap * DK * 4, c->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(nr.p, k.rows.p, n * DK * 4, hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(np.p, k.pos.p, n * 16, hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { nr.release(); np.release(); }
-  MX_HIP(e);
-  k.rows.release(); k.pos.release();
-  k.rows = nr; k.pos = np; k.cap = cap; k.capDK = DK;
-  return MODSX_OK;
-}
-
 // dense: [n][dim] f32 in HBM.  The rows enter the slot behind the old ones through the matcher's pack kernel, which also holds the
 // validity check; a row it flags takes the new rows out again (back to zero rows) and the slot is what it was.  A class that is
 // still empty when an append fails, for whatever reason, gives its buffers back: it has no width yet, so it keeps none.
@@ -118,7 +61,7 @@ static int slot_ingest(const char *fn, modsx_ctx *c, RepSlotF &k, int dim, const
 static int slot_store(const char *fn, modsx_ctx *c, RepSlotF &k, int dim, const modsx_region *regs, const float *dense, int n) {
   const int DK = fginn32_kernel_width(dim);
   const size_t base = k.regs.size();
-  int rc = slot_reserve(c, k, base + (size_t)n, DK);
+  int rc = slot_reserve(c, k, base + (size_t)n, DK, true);
   if (rc) return rc;
   if (!c->matchRows.ensure(16)) return MODSX_ERR_NOMEM;
   unsigned *flag = (unsigned *)c->matchRows.p, hflag = 0;
@@ -132,12 +75,11 @@ static int slot_store(const char *fn, modsx_ctx *c, RepSlotF &k, int dim, const 
   MX_HIP(hipStreamSynchronize(c->stream));
   MX_HIP(hipGetLastError());
   if (hflag) {
-    MX_HIP(hipMemsetAsync(dst, 0, (size_t)n * DK * 4, c->stream));
-    MX_HIP(hipStreamSynchronize(c->stream));
+    MX_HIP(slot_zero_again(c, k, base, n));
     set_error(std::string(fn) + ": rows must be finite with |x| <= 1e17");
     return MODSX_ERR_ARG;
   }
-  k.dim = dim; k.DK = DK;
+  k.dim = dim; k.W = DK;
   k.regs.insert(k.regs.end(), regs, regs + n);
   k.hpos.insert(k.hpos.end(), pos.begin(), pos.end());
   return MODSX_OK;
@@ -198,51 +140,9 @@ int rep_describe_append(modsx_ctx *c, modsx_rep *rep, int det, int type, const m
 }
 
 int rep_class_f32(modsx_ctx *c, const modsx_rep *rep, int det, int type, modsx_region **regs, float **rows, int *dim) {
-  CtxBusy busy(c);
   const RepSlotF &k = fslot(rep, det, type);
-  const size_t n = k.regs.size();
   if (dim) *dim = k.dim;
-  if (regs) *regs = nullptr;
-  if (rows) {
-    *rows = (float *)malloc(std::max<size_t>(4, n * k.dim * 4));
-    if (!*rows) { set_error("modsx_rep_class_f32: out of memory"); return MODSX_ERR_NOMEM; }
-    if (n) {
-      hipError_t e = hipMemcpy2DAsync(*rows, (size_t)k.dim * 4, k.rows.p, (size_t)k.DK * 4, (size_t)k.dim * 4, n, hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { free(*rows); *rows = nullptr; set_error("modsx_rep_class_f32: row download failed"); return MODSX_ERR_DEVICE; }
-    }
-  }
-  if (regs) {
-    *regs = (modsx_region *)malloc(sizeof(modsx_region) * std::max<size_t>(1, n));
-    if (!*regs) {
-      if (rows) { free(*rows); *rows = nullptr; }
-      set_error("modsx_rep_class_f32: out of memory");
-      return MODSX_ERR_NOMEM;
-    }
-    if (n) memcpy(*regs, k.regs.data(), sizeof(modsx_region) * n);
-  }
-  return (int)n;
-}
-
-void rep_free_f32(modsx_rep *rep) {
-  for (auto &byDet : rep->fslot) for (RepSlotF &k : byDet) slot_release(k);
-}
-
-// ---- the host's walk over a problem's four nearest keys: the rules of match_fginn32_device (engine_fginn32.hip), key for key ----
-static inline float key_dist(unsigned long long k) { const uint32_t b = (uint32_t)(k >> 32); float f; memcpy(&f, &b, 4); return f; }
-static inline int key_idx(unsigned long long k) { return (int)(uint32_t)k; }
-constexpr unsigned long long KEY_NONE = ~0ull;
-static inline bool ratio_passes(float d0, float d, double rsq, double *ratio) {
-  const double r = d0 / d;      // the f32 division of matching.cpp:392
-  *ratio = r;
-  return r <= rsq;
-}
-static modsx_tentative make_record(int q, const unsigned long long *k, unsigned long long kj, double ratio) {
-  modsx_tentative t;
-  t.q = q; t.t0 = key_idx(k[0]); t.tj = key_idx(kj); t.t1 = key_idx(k[1]);
-  t.d1 = key_dist(k[0]); t.d2 = key_dist(kj); t.d2by2ndcl = key_dist(k[1]);
-  t.ratio = sqrt(ratio);
-  return t;
+  return slot_download(c, "modsx_rep_class_f32", k, (size_t)k.dim * 4, regs, (void **)rows);
 }
 
 int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, const modsx_rep *const *reps2, int G, int det, int type,
@@ -284,38 +184,14 @@ int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
   if (e == hipSuccess) e = hipGetLastError();
   MX_HIP(e);
   c->f32GroupCounters[0]++; c->f32GroupCounters[1] += np;
-  // The keys are read where the copy left them (pinned host memory; nothing below writes there).  Records go straight to their
-  // partner's list in query order; an open walk leaves a place holder (q = -1) that the resolve sweep fills or that is dropped.
+  // The keys are read where the copy left them (pinned host memory; nothing below writes there): the walk of fginn_walk.hpp, one
+  // open step per problem, all problems' open entries in one list
   const unsigned long long *top4 = (const unsigned long long *)c->hMatch.p;
+  FginnWalk walks[MATCH_MAXB];
   std::vector<F32Open> open;
-  std::vector<size_t> place;        // per open entry: where its record goes in its partner's list
-  const int jTop = std::min(3, nn - 1);
   for (int p = 0; p < np; p++) {
-    const double *pos2 = t[prob[p]]->hpos.data();
-    std::vector<modsx_tentative> &out = outs[prob[p]];
     grp.ubeg[p] = (int)open.size();
-    for (int qi = 0; qi < n1; qi++) {
-      const unsigned long long *k = top4 + ((size_t)p * n1 + qi) * 4;
-      const float d0 = key_dist(k[0]);
-      bool ended = k[0] == KEY_NONE;
-      for (int j = 1; j <= jTop && !ended; j++) {
-        if (k[j] == KEY_NONE) { ended = true; break; }            // the trains ran out
-        double ratio;
-        if (ratio_passes(d0, key_dist(k[j]), rsq, &ratio)) { out.push_back(make_record(qi, k, k[j], ratio)); ended = true; break; }
-        const int i0 = key_idx(k[0]), ij = key_idx(k[j]);
-        const double dx = pos2[2 * (size_t)i0] - pos2[2 * (size_t)ij], dy = pos2[2 * (size_t)i0 + 1] - pos2[2 * (size_t)ij + 1];
-        if (dx * dx + dy * dy > cd2) ended = true;
-      }
-      if (ended || nn - 1 <= 3) continue;
-      F32Open o;
-      o.klast = k[3]; o.q = qi; o.t0 = key_idx(k[0]); o.dpass = fginn32_dpass(d0, rsq); o.pad = p;      // pad: the entry's problem
-      open.push_back(o);
-      place.push_back(out.size());
-      modsx_tentative hole;
-      memset(&hole, 0, sizeof hole);
-      hole.q = -1;
-      out.push_back(hole);
-    }
+    fginn_walk_open(top4 + (size_t)p * n1 * 4, n1, t[prob[p]]->hpos.data(), rsq, cd2, nn, p, walks[p], open);
     grp.uend[p] = (int)open.size();
   }
 
@@ -333,22 +209,9 @@ int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
     MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
     MX_HIP(hipGetLastError());
     c->f32GroupCounters[2] += nu; c->f32GroupCounters[3]++;
-    for (int u = 0; u < nu; u++) {
-      const F32Open &o = open[u];
-      const unsigned long long kt = closed[u].kterm;
-      if (kt == KEY_NONE) continue;                               // nothing ends the walk before the trains or the nn run out
-      const unsigned long long *k = top4 + ((size_t)o.pad * n1 + o.q) * 4;
-      double ratio;
-      if (!ratio_passes(key_dist(k[0]), key_dist(kt), rsq, &ratio)) continue;      // it ends the walk by contradiction
-      // it passes: every non-terminal train comes before it, its rank is 3 + cnt + 1 exactly (kernels_fginn32.hip)
-      if ((long)closed[u].cnt + 4 <= nn - 1) outs[prob[o.pad]][place[u]] = make_record(o.q, k, kt, ratio);
-    }
+    fginn_walk_close(open, closed.data(), top4, n1, rsq, nn, walks);
   }
-  if (!open.empty())
-    for (int p = 0; p < np; p++) {
-      std::vector<modsx_tentative> &out = outs[prob[p]];
-      out.erase(std::remove_if(out.begin(), out.end(), [](const modsx_tentative &r) { return r.q < 0; }), out.end());
-    }
+  for (int p = 0; p < np; p++) fginn_walk_emit(walks[p], outs[prob[p]]);
   return MODSX_OK;
 }
 
@@ -357,8 +220,6 @@ int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
 using namespace mx;
 
 extern "C" {
-
-int modsx_rep_class_rank(int detector, int desc_type) { return rep_class_rank(detector, desc_type); }
 
 int modsx_rep_append_f32(modsx_ctx *ctx, modsx_rep *rep, int detector, int desc_type, const modsx_region *regs, const float *rows, int dim,
                          int n) {
@@ -410,11 +271,7 @@ int modsx_rep_match_group_f32(modsx_ctx *ctx, const modsx_rep *rep1, const modsx
   std::vector<modsx_tentative> t[MATCH_MAXB];
   const int rc = reps_f32_match_group(ctx, "modsx_rep_match_group_f32", rep1, reps2, G, det, desc_type, ratio, contradDist, nn, t);
   if (rc) return rc;
-  for (int g = 0; g < G; g++) {
-    outs[g] = (modsx_tentative *)malloc(sizeof(modsx_tentative) * std::max<size_t>(1, t[g].size()));
-    if (!t[g].empty()) memcpy(outs[g], t[g].data(), sizeof(modsx_tentative) * t[g].size());
-    counts[g] = (int)t[g].size();
-  }
+  for (int g = 0; g < G; g++) { outs[g] = to_malloc(t[g]); counts[g] = (int)t[g].size(); }
   return G;
 }
 
@@ -426,8 +283,7 @@ int modsx_rep_match_fginn_f32(modsx_ctx *ctx, const modsx_rep *rep1, const modsx
   std::vector<modsx_tentative> t;
   const int rc = reps_f32_match_group(ctx, "modsx_rep_match_fginn_f32", rep1, &rep2, 1, det, desc_type, ratio, contradDist, nn, &t);
   if (rc) return rc;
-  *out = (modsx_tentative *)malloc(sizeof(modsx_tentative) * std::max<size_t>(1, t.size()));
-  if (!t.empty()) memcpy(*out, t.data(), sizeof(modsx_tentative) * t.size());
+  *out = to_malloc(t);
   return (int)t.size();
 }
 
@@ -441,17 +297,7 @@ int modsx_debug_fginn32_group_geometry(int n1, const int *n2, int G, int dim, in
   F32Group g;
   int prob[MATCH_MAXB];
   const int total = fginn32_group_geometry(n1, n2, G, dim, g, prob);
-  geometry[0] = g.tile; geometry[1] = g.DK; geometry[2] = g.gx; geometry[3] = total;
-  memset(per_problem, 0, sizeof(int) * 3 * G);
-  for (int p = 0; p < g.np; p++) {
-    int *o = per_problem + 3 * prob[p];
-    o[0] = g.ntiles[p]; o[1] = g.S[p]; o[2] = g.tps[p];
-    for (int s = 0; s < g.S[p] && g.first[p] + s < cap; s++) {
-      int *sp = splits + 3 * (g.first[p] + s);
-      sp[0] = prob[p]; sp[1] = s * g.tps[p]; sp[2] = std::min(g.ntiles[p], (s + 1) * g.tps[p]);
-    }
-  }
-  return total;
+  return group_geometry_report(g, g.DK, prob, G, total, geometry, per_problem, splits, cap);
 }
 
 int modsx_fginn32_group_counters(modsx_ctx *ctx, long *out, int n) {
