@@ -345,6 +345,19 @@ void launch_db_select(hipStream_t s, int nb, const MatchRow *const *rows, const 
                       int *const *dmin);
 void launch_dbnn_min(hipStream_t s, int nb, const uint8_t *const *d1, const int *n1, int *const *sel, int *cnt, int *const *dmin,
                      const DbSet &db);
+// The split rule of the exact searches (Hamming, f32 and byte-row FGINN, single and grouped): a train axis of ntiles >= 1 whole tiles
+// under gx blocks of 256 queries is cut into S splits of tilesPerSplit tiles.  splits = 0: production, about 2048 workgroups (eight
+// per CU; four rounds at the two that the widest f32 kernels hold at a time, so that the last round's tail stays short); splits > 0:
+// that many.  At most one split per tile, and no empty split.
+struct SplitCut { int tilesPerSplit, S; };
+inline SplitCut split_rule(int ntiles, int gx, int splits) {
+  int S = splits > 0 ? splits : (2048 + gx - 1) / gx;
+  S = std::max(1, std::min(S, ntiles));
+  SplitCut c;
+  c.tilesPerSplit = (ntiles + S - 1) / S;
+  c.S = (ntiles + c.tilesPerSplit - 1) / c.tilesPerSplit;
+  return c;
+}
 // The Hamming 2-NN search of MatchFLANNDistance (kernels_hamming.hip).  W = ceil(nbytes / 4) dwords per row, WK the kernel width
 // it rounds up to; tile = trains per LDS tile; the train axis is cut into S splits of tilesPerSplit tiles; gx x S workgroups.
 struct HammingGeo { int W, WK, tile, ntiles, tilesPerSplit, S, gx; };
@@ -375,11 +388,6 @@ void launch_hamming_pack_rows(hipStream_t s, const uint8_t *src, int n, int nbyt
 struct Fginn32Geo { int dim, DK, tile, ntiles, tilesPerSplit, S, gx; };
 // F32Open / F32Closed, an undecided query on its way to k_f32_resolve and what comes back: fginn_walk.hpp, with the host's walk
 struct Fginn32Work { float *queries, *trains; unsigned long long *keys; F32Open *open; F32Closed *closed; };
-// the key of a (distance, train index): distances are >= +0 and never NaN, so the pattern orders like the value; all ones = no train
-constexpr unsigned long long F32_NONE = ~0ull;
-__device__ __forceinline__ unsigned long long f32_key(float d, int idx) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx;
-}
 Fginn32Geo fginn32_geometry(int n1, int n2, int dim, int splits);   // splits = 0: production; > 0: forced (at most one per tile)
 Fginn32Geo fginn32_geometry_rows(int n1, int n2, int dim, int DK, int tile, int splits);
 size_t fginn32_workspace_bytes(const Fginn32Geo &g, int n1);
@@ -410,7 +418,7 @@ struct F32Group {
   int np, gx, DK, tile;
 };
 // n2[0..G): every problem's trains; problems with n2 == 0 are left out (prob[k] = the caller's index of table problem k).  Every
-// problem is cut as fginn32_geometry cuts it alone (about 2048 / gx splits, at most one per tile): its S and tps, whatever G is.
+// problem is cut as fginn32_geometry(n1, n2, dim, 0) cuts it alone: its S and tps, whatever G is.
 int fginn32_kernel_width(int dim);
 int fginn32_group_geometry(int n1, const int *n2, int G, int dim, F32Group &g, int *prob);
 // keys: [first[np]][n1][4]; top4: [np][n1][4]

@@ -355,6 +355,64 @@ void verify_tentatives(const std::vector<modsx_region> &r1, const std::vector<mo
                        const std::vector<modsx_tentative> &tents, const modsx_pair_params &pp, modsx_pair_result *res);
 void verify_tentatives_kp(const double *kp1, size_t n1, const double *kp2, size_t n2, const std::vector<modsx_tentative> &tents,
                           const modsx_pair_params &pp, modsx_pair_result *res);
+// ---- the host plumbing the exact searches share (Hamming, f32 / byte-row FGINN, single and grouped) ----
+// The search round trip: launch(ev) issues the search on c->stream (ev: three events to record before the packing, behind it and
+// behind the search, or null); `bytes` of its result come down from dev to the pinned host buffer.  ms (null: never timed) receives
+// the two event intervals under modsx_profile.  The events are destroyed on the error path too.
+template <class L>
+int search_download(modsx_ctx *c, L &&launch, const void *dev, void *host, size_t bytes, double *ms) {
+  hipEvent_t ev[3];
+  const bool timed = ms && c->prof.enabled;     // modsx_profile: the launches are timed into the context, no new kernel class
+  if (timed) for (int i = 0; i < 3; i++) MX_HIP(hipEventCreate(&ev[i]));
+  launch(timed ? ev : nullptr);
+  hipError_t e = ctx_copy(c, host, dev, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = ctx_sync(c);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (timed) {
+    float a = 0, b = 0;
+    if (e == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) {
+      ms[0] = a; ms[1] = b;
+    }
+    for (int i = 0; i < 3; i++) hipEventDestroy(ev[i]);
+  }
+  MX_HIP(e);
+  return MODSX_OK;
+}
+// The resolve round trip of the FGINN walk: open[] and the initial closed[] = {all ones, 0} up to dOpen / dClosed, launch() (the
+// resolve sweep on c->stream), closed[] down.  Pageable memory on both ends, so it ends with a stream synchronisation.
+template <class L>
+int resolve_round_trip(modsx_ctx *c, const std::vector<F32Open> &open, F32Open *dOpen, F32Closed *dClosed, std::vector<F32Closed> &closed,
+                       L &&launch) {
+  const size_t nu = open.size();
+  closed.assign(nu, F32Closed{KEY_NONE, 0u, 0u});
+  MX_HIP(hipMemcpyAsync(dOpen, open.data(), nu * sizeof(F32Open), hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipMemcpyAsync(dClosed, closed.data(), nu * sizeof(F32Closed), hipMemcpyHostToDevice, c->stream));
+  launch();
+  MX_HIP(hipMemcpyAsync(closed.data(), dClosed, nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));
+  MX_HIP(hipGetLastError());
+  return MODSX_OK;
+}
+// two pageable host row sets into a pair of context buffers; synchronised, so the sources may be temporaries (engine_hamming.hip)
+int upload_row_pair(modsx_ctx *c, DevBuf *buf2, const void *rows1, size_t bytes1, const void *rows2, size_t bytes2);
+// What the match_regions_* entries have in common: the zeroed result with H = -1 (all an empty side or an error leaves), then
+// match(tents) -- the caller's argument checks, before any work, and its search -- then DuplicateFiltering + LORANSACFiltering of
+// the tentatives on the two caller-supplied region lists.
+template <class M>
+int match_regions_with(const modsx_region *regs1, int n1, const modsx_region *regs2, int n2, const modsx_pair_params &pp,
+                       modsx_pair_result *res, M &&match) {
+  memset(res, 0, sizeof *res);
+  for (int i = 0; i < 9; i++) res->H[i] = -1;
+  std::vector<modsx_tentative> tents;
+  const int rc = match(tents);
+  if (rc) return rc;
+  res->n_regions1 = n1; res->n_regions2 = n2;
+  if (n1 == 0 || n2 == 0) return MODSX_OK;
+  RegList l1, l2;
+  l1.add(regs1, (size_t)n1); l2.add(regs2, (size_t)n2);
+  verify_tentatives(l1, l2, tents, pp, res);
+  return MODSX_OK;
+}
 // A pair whose tentatives are matched but not yet verified: modsx_match_pairs hands these to helper threads so that a
 // context's stream is fed the next group while the host runs DuplicateFiltering + LO-RANSAC of this one.  The task owns the
 // region vectors its two lists point into (moving a vector keeps its heap block, so the segments stay valid).

@@ -70,22 +70,11 @@ static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n
   const double rsq = ratioT * ratioT, cd2 = contradDist * contradDist;
   const size_t rowB = 16 + (size_t)n1 * 32;
   if (!c->matchWork.ensure(fginn32_workspace_bytes(g, n1)) || !c->matchRows.ensure(rowB) || !c->hMatch.ensure(rowB)) return MODSX_ERR_NOMEM;
-  hipEvent_t ev[3];
-  const bool timed = c->prof.enabled;     // modsx_profile: the launches are timed into the context (tools/bench_fginn32.py)
-  if (timed) for (int i = 0; i < 3; i++) MX_HIP(hipEventCreate(&ev[i]));
-  if (bytes) launch_fginn_l1_topk(c->stream, g, (const uint8_t *)d1, n1, (const uint8_t *)d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr);
-  else launch_fginn32_topk(c->stream, g, (const float *)d1, n1, (const float *)d2, n2, c->matchWork.p, c->matchRows.p, timed ? ev : nullptr, dist);
-  hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, rowB, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = ctx_sync(c);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (timed) {
-    float a = 0, b = 0;
-    if (e == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) {
-      c->fginn32Ms[0] = a; c->fginn32Ms[1] = b;
-    }
-    for (int i = 0; i < 3; i++) hipEventDestroy(ev[i]);
-  }
-  MX_HIP(e);
+  int rc = search_download(c, [&](hipEvent_t *ev) {      // timed under modsx_profile (tools/bench_fginn32.py)
+    if (bytes) launch_fginn_l1_topk(c->stream, g, (const uint8_t *)d1, n1, (const uint8_t *)d2, n2, c->matchWork.p, c->matchRows.p, ev);
+    else launch_fginn32_topk(c->stream, g, (const float *)d1, n1, (const float *)d2, n2, c->matchWork.p, c->matchRows.p, ev, dist);
+  }, c->matchRows.p, c->hMatch.p, rowB, c->fginn32Ms);
+  if (rc) return rc;
   const unsigned flag = *(const unsigned *)c->hMatch.p;
   if (tap && tap->counters) { tap->counters[0] = tap->counters[1] = tap->counters[2] = 0; tap->counters[3] = (int)flag; }
   if (flag) {
@@ -107,16 +96,14 @@ static int fginn_search_and_walk(modsx_ctx *c, bool bytes, const void *d1, int n
   if (!open.empty() && (stageMask & 2)) {
     const Fginn32Work w = fginn32_work(g, n1, c->matchWork.p);
     const int nu = (int)open.size();
-    std::vector<F32Closed> closed(nu, F32Closed{KEY_NONE, 0u, 0u});
+    std::vector<F32Closed> closed;
     if (!c->pos2.ensure((size_t)n2 * 16)) return MODSX_ERR_NOMEM;
     MX_HIP(hipMemcpyAsync(c->pos2.p, pos2, (size_t)n2 * 16, hipMemcpyHostToDevice, c->stream));
-    MX_HIP(hipMemcpyAsync(w.open, open.data(), (size_t)nu * sizeof(F32Open), hipMemcpyHostToDevice, c->stream));
-    MX_HIP(hipMemcpyAsync(w.closed, closed.data(), (size_t)nu * sizeof(F32Closed), hipMemcpyHostToDevice, c->stream));
-    if (bytes) launch_fginn_l1_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p);
-    else launch_fginn32_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p, dist);
-    MX_HIP(hipMemcpyAsync(closed.data(), w.closed, (size_t)nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
-    MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
-    MX_HIP(hipGetLastError());
+    rc = resolve_round_trip(c, open, w.open, w.closed, closed, [&] {
+      if (bytes) launch_fginn_l1_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p);
+      else launch_fginn32_resolve(c->stream, g, n1, nu, n2, (const double *)c->pos2.p, cd2, c->matchWork.p, dist);
+    });
+    if (rc) return rc;
     nByCount = fginn_walk_close(open, closed.data(), top4.data(), n1, rsq, nn, &walk);
   }
   fginn_walk_emit(walk, out);
@@ -149,10 +136,7 @@ int match_fginn32_host(modsx_ctx *c, const float *desc1, int n1, const float *de
     return MODSX_ERR_ARG;
   }
   CtxBusy busy(c);
-  if (!c->descF[0].ensure(f1 * 4) || !c->descF[1].ensure(f2 * 4)) return MODSX_ERR_NOMEM;
-  MX_HIP(hipMemcpyAsync(c->descF[0].p, desc1, f1 * 4, hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipMemcpyAsync(c->descF[1].p, desc2, f2 * 4, hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable
+  if ((rc = upload_row_pair(c, c->descF, desc1, f1 * 4, desc2, f2 * 4))) return rc;
   return match_fginn32_device(c, (const float *)c->descF[0].p, n1, (const float *)c->descF[1].p, n2, dim, pos2, ratioT, contradDist, nn, out, tap,
                               dist);
 }
@@ -170,10 +154,7 @@ int match_fginn_l1_host(modsx_ctx *c, const float *desc1, int n1, const float *d
     return MODSX_ERR_ARG;
   }
   CtxBusy busy(c);
-  if (!c->descU8[0].ensure(u1.size()) || !c->descU8[1].ensure(u2.size())) return MODSX_ERR_NOMEM;
-  MX_HIP(hipMemcpyAsync(c->descU8[0].p, u1.data(), u1.size(), hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipMemcpyAsync(c->descU8[1].p, u2.data(), u2.size(), hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable
+  if ((rc = upload_row_pair(c, c->descU8, u1.data(), u1.size(), u2.data(), u2.size()))) return rc;
   return match_fginn_l1_device(c, (const uint8_t *)c->descU8[0].p, n1, (const uint8_t *)c->descU8[1].p, n2, pos2, ratioT, contradDist, nn, out, tap);
 }
 
@@ -182,24 +163,16 @@ int match_fginn_l1_host(modsx_ctx *c, const float *desc1, int n1, const float *d
 // bytes: the rows hold the integers 0..255 at dim = 128 and go through the L1 search on bytes (dist is then L1)
 int match_regions_f32(modsx_ctx *c, const modsx_region *regs1, const float *desc1, int n1, const modsx_region *regs2, const float *desc2,
                       int n2, int dim, const modsx_pair_params &pp, modsx_pair_result *res, int dist, bool bytes) {
-  memset(res, 0, sizeof *res);
-  for (int i = 0; i < 9; i++) res->H[i] = -1;
-  const char *fn = bytes ? "modsx_match_regions_l1" : "modsx_match_regions_f32";
-  int rc = fginn32_check_args(fn, n1, n2, dim, pp.match_ratio, pp.nn);
-  if (rc) return rc;
-  if ((rc = fginn32_check_dist(fn, dist))) return rc;
-  std::vector<double> pos2((size_t)n2 * 2);
-  for (int i = 0; i < n2; i++) { pos2[2 * (size_t)i] = regs2[i].reproj_kp.x; pos2[2 * (size_t)i + 1] = regs2[i].reproj_kp.y; }
-  std::vector<modsx_tentative> tents;
-  rc = bytes ? match_fginn_l1_host(c, desc1, n1, desc2, n2, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr)
-             : match_fginn32_host(c, desc1, n1, desc2, n2, dim, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr, dist);
-  if (rc) return rc;
-  res->n_regions1 = n1; res->n_regions2 = n2;
-  if (n1 == 0 || n2 == 0) return MODSX_OK;
-  RegList l1, l2;
-  l1.add(regs1, (size_t)n1); l2.add(regs2, (size_t)n2);
-  verify_tentatives(l1, l2, tents, pp, res);
-  return MODSX_OK;
+  return match_regions_with(regs1, n1, regs2, n2, pp, res, [&](std::vector<modsx_tentative> &tents) {
+    const char *fn = bytes ? "modsx_match_regions_l1" : "modsx_match_regions_f32";
+    int rc = fginn32_check_args(fn, n1, n2, dim, pp.match_ratio, pp.nn);
+    if (rc) return rc;
+    if ((rc = fginn32_check_dist(fn, dist))) return rc;
+    std::vector<double> pos2((size_t)n2 * 2);
+    for (int i = 0; i < n2; i++) { pos2[2 * (size_t)i] = regs2[i].reproj_kp.x; pos2[2 * (size_t)i + 1] = regs2[i].reproj_kp.y; }
+    return bytes ? match_fginn_l1_host(c, desc1, n1, desc2, n2, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr)
+                 : match_fginn32_host(c, desc1, n1, desc2, n2, dim, pos2.data(), pp.match_ratio, pp.contradDist, pp.nn, tents, nullptr, dist);
+  });
 }
 
 }  // namespace mx

@@ -55,21 +55,10 @@ int hamming_search_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t
   if (geo4) { geo4[0] = g.tile; geo4[1] = g.S; geo4[2] = g.gx * g.S; geo4[3] = g.W; }
   const size_t rowB = (size_t)n1 * 16;
   if (!c->matchWork.ensure(hamming_workspace_bytes(g, n1)) || !c->matchRows.ensure(rowB) || !c->hMatch.ensure(rowB)) return MODSX_ERR_NOMEM;
-  hipEvent_t ev[3];
-  const bool timed = c->prof.enabled;     // modsx_profile: the launches are timed into the context (tools/bench_hamming.py), no new kernel class
-  if (timed) for (int i = 0; i < 3; i++) MX_HIP(hipEventCreate(&ev[i]));
-  launch_hamming(c->stream, g, d1, n1, d2, n2, nbytes, c->matchWork.p, (int *)c->matchRows.p, timed ? ev : nullptr);
-  hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, rowB, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = ctx_sync(c);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (timed) {
-    float a = 0, b = 0;
-    if (e == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) {
-      c->hammingMs[0] = a; c->hammingMs[1] = b;
-    }
-    for (int i = 0; i < 3; i++) hipEventDestroy(ev[i]);
-  }
-  MX_HIP(e);
+  const int rc = search_download(c, [&](hipEvent_t *ev) {      // timed under modsx_profile (tools/bench_hamming.py)
+    launch_hamming(c->stream, g, d1, n1, d2, n2, nbytes, c->matchWork.p, (int *)c->matchRows.p, ev);
+  }, c->matchRows.p, c->hMatch.p, rowB, c->hammingMs);
+  if (rc) return rc;
   c->hamGroupCounters[3] += 2;      // both sides were packed for this call (modsx_hamming_group_counters)
   memcpy(nn2, c->hMatch.p, rowB);
   return MODSX_OK;
@@ -86,6 +75,14 @@ int match_hamming_device(modsx_ctx *c, const uint8_t *d1, int n1, const uint8_t 
   rc = hamming_search_device(c, d1, n1, d2, n2, nbytes, 0, nn2.data(), nullptr);
   if (rc) return rc;
   return hamming_tentatives(nn2.data(), n1, distanceThreshold, out);
+}
+
+int upload_row_pair(modsx_ctx *c, DevBuf *buf2, const void *rows1, size_t bytes1, const void *rows2, size_t bytes2) {
+  if (!buf2[0].ensure(bytes1) || !buf2[1].ensure(bytes2)) return MODSX_ERR_NOMEM;
+  MX_HIP(hipMemcpyAsync(buf2[0].p, rows1, bytes1, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipMemcpyAsync(buf2[1].p, rows2, bytes2, hipMemcpyHostToDevice, c->stream));
+  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable and may be the caller's temporaries
+  return MODSX_OK;
 }
 
 // rows from the host: dtype 0 = u8, 1 = f32 holding the integers 0..255 (the rule of every other descriptor entry)
@@ -109,10 +106,7 @@ int match_hamming_host(modsx_ctx *c, const void *desc1, int n1, const void *desc
     p1 = u1.data(); p2 = u2.data();
   }
   CtxBusy busy(c);
-  if (!c->descU8[0].ensure(b1) || !c->descU8[1].ensure(b2)) return MODSX_ERR_NOMEM;
-  MX_HIP(hipMemcpyAsync(c->descU8[0].p, p1, b1, hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipMemcpyAsync(c->descU8[1].p, p2, b2, hipMemcpyHostToDevice, c->stream));
-  MX_HIP(hipStreamSynchronize(c->stream));      // the sources are pageable and may be the temporaries above
+  if ((rc = upload_row_pair(c, c->descU8, p1, b1, p2, b2))) return rc;
   return match_hamming_device(c, (const uint8_t *)c->descU8[0].p, n1, (const uint8_t *)c->descU8[1].p, n2, nbytes, distanceThreshold, out);
 }
 
@@ -120,19 +114,10 @@ int match_hamming_host(modsx_ctx *c, const void *desc1, int n1, const void *desc
 // stage replaced.  An empty side gives the zeroed result with H = -1 (as modsx_match_reps does for an empty partner).
 int match_regions_hamming(modsx_ctx *c, const modsx_region *regs1, const void *desc1, int n1, const modsx_region *regs2, const void *desc2,
                           int n2, int nbytes, int dtype, double distanceThreshold, const modsx_pair_params &pp, modsx_pair_result *res) {
-  memset(res, 0, sizeof *res);
-  for (int i = 0; i < 9; i++) res->H[i] = -1;
-  int rc = hamming_check_args("modsx_match_regions_hamming", n1, n2, nbytes);      // n2 == 1 included: before any work
-  if (rc) return rc;
-  std::vector<modsx_tentative> tents;
-  rc = match_hamming_host(c, desc1, n1, desc2, n2, nbytes, dtype, distanceThreshold, tents);
-  if (rc) return rc;
-  res->n_regions1 = n1; res->n_regions2 = n2;
-  if (n1 == 0 || n2 == 0) return MODSX_OK;
-  RegList l1, l2;
-  l1.add(regs1, (size_t)n1); l2.add(regs2, (size_t)n2);
-  verify_tentatives(l1, l2, tents, pp, res);
-  return MODSX_OK;
+  return match_regions_with(regs1, n1, regs2, n2, pp, res, [&](std::vector<modsx_tentative> &tents) {
+    const int rc = hamming_check_args("modsx_match_regions_hamming", n1, n2, nbytes);      // n2 == 1 included: before any work
+    return rc ? rc : match_hamming_host(c, desc1, n1, desc2, n2, nbytes, dtype, distanceThreshold, tents);
+  });
 }
 
 }  // namespace mx

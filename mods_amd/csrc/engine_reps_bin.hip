@@ -114,11 +114,10 @@ int reps_bin_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
   // workspace: the split keys [splits][n1][2]; the merged results [np][n1][4] travel through matchRows
   const size_t keyB = (size_t)grp.first[np] * n1 * 16, outB = (size_t)np * n1 * 16;
   if (!c->matchWork.ensure(keyB) || !c->matchRows.ensure(outB) || !c->hMatch.ensure(outB)) return MODSX_ERR_NOMEM;
-  launch_hamming_group(c->stream, grp, (const uint32_t *)q.rows.p, n1, (unsigned long long *)c->matchWork.p, (int *)c->matchRows.p);
-  hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, outB, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = ctx_sync(c);
-  if (e == hipSuccess) e = hipGetLastError();
-  MX_HIP(e);
+  rc = search_download(c, [&](hipEvent_t *) {
+    launch_hamming_group(c->stream, grp, (const uint32_t *)q.rows.p, n1, (unsigned long long *)c->matchWork.p, (int *)c->matchRows.p);
+  }, c->matchRows.p, c->hMatch.p, outB, nullptr);
+  if (rc) return rc;
   c->hamGroupCounters[0]++; c->hamGroupCounters[1] += np;
   const int *nn2 = (const int *)c->hMatch.p;
   for (int p = 0; p < np && !rc; p++) rc = hamming_tentatives(nn2 + (size_t)p * n1 * 4, n1, distanceThreshold, outs[prob[p]]);

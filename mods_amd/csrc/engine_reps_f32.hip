@@ -178,11 +178,10 @@ int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
   unsigned long long *keys = (unsigned long long *)c->matchWork.p;
   F32Open *dOpen = (F32Open *)((char *)c->matchWork.p + keyB);
   F32Closed *dClosed = (F32Closed *)((char *)dOpen + openB);
-  launch_fginn32_group_topk(c->stream, grp, (const float *)q.rows.p, n1, keys, (unsigned long long *)c->matchRows.p);
-  hipError_t e = ctx_copy(c, c->hMatch.p, c->matchRows.p, topB, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = ctx_sync(c);
-  if (e == hipSuccess) e = hipGetLastError();
-  MX_HIP(e);
+  rc = search_download(c, [&](hipEvent_t *) {
+    launch_fginn32_group_topk(c->stream, grp, (const float *)q.rows.p, n1, keys, (unsigned long long *)c->matchRows.p);
+  }, c->matchRows.p, c->hMatch.p, topB, nullptr);
+  if (rc) return rc;
   c->f32GroupCounters[0]++; c->f32GroupCounters[1] += np;
   // The keys are read where the copy left them (pinned host memory; nothing below writes there): the walk of fginn_walk.hpp, one
   // open step per problem, all problems' open entries in one list
@@ -201,13 +200,10 @@ int reps_f32_match_group(modsx_ctx *c, const char *fn, const modsx_rep *rep1, co
     int rfirst = 0;
     for (int p = 0; p < np; p++) { grp.rfirst[p] = rfirst; rfirst += (grp.uend[p] - grp.ubeg[p] + 255) / 256 * grp.S[p]; }
     for (int p = np; p <= MATCH_MAXB; p++) grp.rfirst[p] = rfirst;
-    std::vector<F32Closed> closed(nu, F32Closed{KEY_NONE, 0u, 0u});
-    MX_HIP(hipMemcpyAsync(dOpen, open.data(), (size_t)nu * sizeof(F32Open), hipMemcpyHostToDevice, c->stream));
-    MX_HIP(hipMemcpyAsync(dClosed, closed.data(), (size_t)nu * sizeof(F32Closed), hipMemcpyHostToDevice, c->stream));
-    launch_fginn32_group_resolve(c->stream, grp, (const float *)q.rows.p, dOpen, cd2, dClosed);
-    MX_HIP(hipMemcpyAsync(closed.data(), dClosed, (size_t)nu * sizeof(F32Closed), hipMemcpyDeviceToHost, c->stream));
-    MX_HIP(hipStreamSynchronize(c->stream));      // pageable memory on both ends
-    MX_HIP(hipGetLastError());
+    std::vector<F32Closed> closed;
+    rc = resolve_round_trip(c, open, dOpen, dClosed, closed,
+                            [&] { launch_fginn32_group_resolve(c->stream, grp, (const float *)q.rows.p, dOpen, cd2, dClosed); });
+    if (rc) return rc;
     c->f32GroupCounters[2] += nu; c->f32GroupCounters[3]++;
     fginn_walk_close(open, closed.data(), top4, n1, rsq, nn, walks);
   }

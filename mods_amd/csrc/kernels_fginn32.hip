@@ -27,9 +27,17 @@
 // There is no third, rank-counting sweep: it could never change a result.  A terminal train that passes the ratio test has
 // d >= d_pass, every non-terminal train has d < d_pass and so a smaller key: the terminal's rank is exactly 3 + count + 1.  A terminal
 // train that does not pass gives no record whether the walk reaches it or runs out of its nn first.
-// Geometry comes from fginn32_geometry(n1, n2, dim, splits) alone.
+// Geometry comes from fginn32_geometry(n1, n2, dim, splits) alone; the cut of the train axis is split_rule (engine.hpp), the one
+// rule of every exact search.
+// What these kernels have in common with each other and with kernels_fginn_l1.hip / kernels_hamming.hip is written once, in
+// search_dev.hpp: the key and Top4 (the four-deep insertion, guarded in the sweeps, unguarded in the merges, and the four-word
+// store), f32_merge_splits (the body of k_f32_merge and k_f32g_merge over a split range), F32Resolve (the default or loaded F32Open,
+// the anchor position, the per-train step with the terminal rule, the atomic commit: the body of every resolve kernel around its
+// own sweep call), group_pick / group_problem (the grouped kernels' table selection).  A kernel here keeps its way to its rows,
+// trains, tile range and output, and its sweep call.
 //
-// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
+// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; regenerated with the shared pieces in
+// place: every figure is what it was, and so is the ISA of every kernel but the two merges):
 //   kernel                VGPRs  SGPRs  LDS [B]  scratch  occupancy [waves/SIMD]
 //   k_f32_topk<32>           82     24    16384        0      5
 //   k_f32_topk<64>          113     24    16384        0      4
@@ -55,8 +63,8 @@
 //   k_f32g_resolve<256>     184     34    32768        0      2
 //   k_f32g_merge             26     25        0        0      8
 // The k_f32g_* kernels are the grouped form (stored representations, engine_reps_f32.hip): the same f32_sweep<DK> body, with the
-// problem of a workgroup, its trains and its tile range selected from a by-value table of at most four problems (F32Group).  The
-// selection is scalar compares on constant indices: it adds SGPRs, no VGPR at DK <= 128, and nothing inside the sweep loop.
+// problem of a workgroup, its trains and its tile range selected from a by-value table of at most four problems (F32Group) by
+// group_problem / group_pick.  The selection is scalar compares on constant indices: it adds SGPRs, no VGPR at DK <= 128, and nothing inside the sweep loop.
 // Per (query, train) the sweep loop of k_f32_topk<DK> issues 100 / 195 / 387 / 551 / 744 vector instructions at DK = 32 / 64 / 128 /
 // 192 / 256 and DK / 4 ds_read_b128; at DK = 128 that is 96 v_sub_f32, 96 v_mul_f32, 103 v_add_f32, 28 v_pk_add_f32, 16 v_pk_mul_f32
 // and 48 for the key and its branch-free insertion (measured times 9.9).
@@ -85,14 +93,14 @@
 #include <stdint.h>
 #include <algorithm>
 #include "engine.hpp"
+#include "search_dev.hpp"
 
 namespace mx {
 
 int fginn32_kernel_width(int dim) { return dim <= 32 ? 32 : dim <= 64 ? 64 : dim <= 128 ? 128 : dim <= 192 ? 192 : 256; }
 static constexpr int f32_tile_trains(int DK) { return DK <= 32 ? 128 : DK <= 64 ? 64 : DK <= 128 ? 32 : 16; }
 
-// splits = 0: production (about 2048 workgroups: eight per CU, four rounds at the two that DK = 128 / 256 hold at a time, so that the
-// last round's tail stays short); splits > 0: that many, at most one per tile
+// splits = 0: production; splits > 0: that many, at most one per tile (split_rule, engine.hpp)
 Fginn32Geo fginn32_geometry(int n1, int n2, int dim, int splits) {
   const int DK = fginn32_kernel_width(dim);
   return fginn32_geometry_rows(n1, n2, dim, DK, f32_tile_trains(DK), splits);
@@ -105,10 +113,9 @@ Fginn32Geo fginn32_geometry_rows(int n1, int n2, int dim, int DK, int tile, int 
   g.tile = tile;
   g.ntiles = std::max(1, (n2 + g.tile - 1) / g.tile);
   g.gx = std::max(1, (n1 + 255) / 256);
-  int S = splits > 0 ? splits : (2048 + g.gx - 1) / g.gx;
-  S = std::max(1, std::min(S, g.ntiles));
-  g.tilesPerSplit = (g.ntiles + S - 1) / S;
-  g.S = (g.ntiles + g.tilesPerSplit - 1) / g.tilesPerSplit;      // no empty split
+  const SplitCut cut = split_rule(g.ntiles, g.gx, splits);
+  g.tilesPerSplit = cut.tilesPerSplit;
+  g.S = cut.S;
   return g;
 }
 
@@ -224,20 +231,10 @@ __global__ __launch_bounds__(256) void k_f32_topk(const float *__restrict__ quer
   F32_SWEEP_LDS(DK);
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
-  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
-  f32_sweep<DK, DIST>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    if (key < k3) {
-      k3 = min(k3, max(k2, key));
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, max(k0, key));
-      k0 = min(k0, key);
-    }
-  });
-  if (q < n1) {
-    unsigned long long *o = keys + ((size_t)blockIdx.y * n1 + q) * 4;
-    o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
-  }
+  Top4 top;
+  f32_sweep<DK, DIST>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part,
+                      [&](float d, int idx) { top.put_below(f32_key(d, idx)); });
+  if (q < n1) top.store(keys + ((size_t)blockIdx.y * n1 + q) * 4);
 }
 
 // top4[q] = the four smallest of the 4 S keys of query q (all ones where there is none)
@@ -245,20 +242,7 @@ __global__ __launch_bounds__(256) void k_f32_merge(const unsigned long long *__r
                                                    unsigned long long *__restrict__ top4) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= n1) return;
-  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
-  for (int s = 0; s < S; s++) {
-    const unsigned long long *p = keys + ((size_t)s * n1 + q) * 4;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const unsigned long long key = p[e];
-      k3 = min(k3, max(k2, key));
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, max(k0, key));
-      k0 = min(k0, key);
-    }
-  }
-  unsigned long long *o = top4 + (size_t)q * 4;
-  o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
+  f32_merge_splits(keys, n1, q, 0, S, top4 + (size_t)q * 4);
 }
 
 // open[u]: an undecided query; closed[u] (kterm = all ones, cnt = 0 on entry) receives over all splits the smallest key of a terminal
@@ -270,25 +254,10 @@ __global__ __launch_bounds__(256) void k_f32_resolve(const float *__restrict__ q
   F32_SWEEP_LDS(DK);
   const int u = blockIdx.x * 256 + threadIdx.x;
   const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
-  F32Open o;
-  o.klast = F32_NONE; o.q = 0; o.t0 = 0; o.dpass = 0.f; o.pad = 0;
-  if (u < nu) o = open[u];
-  const double px = pos[2 * (size_t)o.t0], py = pos[2 * (size_t)o.t0 + 1];
-  unsigned long long kterm = F32_NONE;
-  unsigned cnt = 0;
-  f32_sweep<DK, DIST>(u < nu ? queries + (size_t)o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    const double dx = px - pos[2 * (size_t)idx], dy = py - pos[2 * (size_t)idx + 1];
-    const bool terminal = d >= o.dpass || dx * dx + dy * dy > contrDistSq;
-    if (key > o.klast) {
-      if (terminal) kterm = min(kterm, key);
-      else cnt++;
-    }
-  });
-  if (u < nu) {
-    if (kterm != F32_NONE) atomicMin(&closed[u].kterm, kterm);
-    if (cnt) atomicAdd(&closed[u].cnt, cnt);
-  }
+  F32Resolve r(open, u, u < nu, pos, contrDistSq);
+  f32_sweep<DK, DIST>(u < nu ? queries + (size_t)r.o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(trains), n2, t0, t1, tile, part,
+                      [&](float d, int idx) { r.step(d, idx); });
+  r.commit(closed, u, u < nu);
 }
 
 // the keys of every search in this format merge alike (kernels_fginn_l1.hip launches it too)
@@ -364,37 +333,19 @@ int fginn32_group_geometry(int n1, const int *n2, int G, int dim, F32Group &g, i
   g.DK = fginn32_kernel_width(dim);
   g.tile = f32_tile_trains(g.DK);
   g.gx = std::max(1, (n1 + 255) / 256);
+  int first = 0;
   for (int i = 0; i < G; i++) {
     if (n2[i] <= 0) continue;
+    const Fginn32Geo one = fginn32_geometry(n1, n2[i], dim, 0);      // every problem is cut as it would be alone
     const int p = g.np++;
     prob[p] = i;
-    g.n2[p] = n2[i];
-    g.ntiles[p] = (n2[i] + g.tile - 1) / g.tile;
-  }
-  const long total = (2048 + g.gx - 1) / g.gx;
-  int first = 0;
-  for (int p = 0; p < g.np; p++) {
-    // every problem is cut as it would be alone (fginn32_geometry): at most one split per tile; then no empty split
-    const int S = (int)std::min<long>(total, g.ntiles[p]);
-    g.tps[p] = (g.ntiles[p] + S - 1) / S;
-    g.S[p] = (g.ntiles[p] + g.tps[p] - 1) / g.tps[p];
+    g.n2[p] = n2[i]; g.ntiles[p] = one.ntiles; g.tps[p] = one.tilesPerSplit; g.S[p] = one.S;
     g.first[p] = first;
-    first += g.S[p];
+    first += one.S;
   }
   for (int p = g.np; p <= MATCH_MAXB; p++) g.first[p] = first;
   return first;
 }
-
-// element p of a by-value table: compares and selects on constant indices, so the table stays in scalar registers
-template <class T>
-__device__ __forceinline__ T f32g_pick(const T *a, int p) {
-  T v = a[0];
-  if (p == 1) v = a[1];
-  if (p == 2) v = a[2];
-  if (p == 3) v = a[3];
-  return v;
-}
-static_assert(MATCH_MAXB == 4, "f32g_pick and the problem search below are written for four problems");
 
 // keys: [splits][n1][4].  Workgroup (x, y) sweeps split y -- tiles of ONE problem -- for the queries of block x; train indices are
 // the problem's own
@@ -403,24 +354,13 @@ __global__ __launch_bounds__(256) void k_f32g_topk(const float *__restrict__ que
                                                    unsigned long long *__restrict__ keys) {
   F32_SWEEP_LDS(DK);
   const int q = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  const int p = (y >= g.first[1]) + (y >= g.first[2]) + (y >= g.first[3]);
-  const int tps = f32g_pick(g.tps, p), ntiles = f32g_pick(g.ntiles, p);
-  const int t0 = (y - f32g_pick(g.first, p)) * tps, t1 = min(ntiles, t0 + tps);
-  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
-  f32_sweep<DK>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(f32g_pick(g.trains, p)), f32g_pick(g.n2, p),
-                t0, t1, tile, part, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    if (key < k3) {
-      k3 = min(k3, max(k2, key));
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, max(k0, key));
-      k0 = min(k0, key);
-    }
-  });
-  if (q < n1) {
-    unsigned long long *o = keys + ((size_t)y * n1 + q) * 4;
-    o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
-  }
+  const int p = group_problem(g.first, y);
+  const int tps = group_pick(g.tps, p), ntiles = group_pick(g.ntiles, p);
+  const int t0 = (y - group_pick(g.first, p)) * tps, t1 = min(ntiles, t0 + tps);
+  Top4 top;
+  f32_sweep<DK>(q < n1 ? queries + (size_t)q * DK : nullptr, reinterpret_cast<const f32x4 *>(group_pick(g.trains, p)), group_pick(g.n2, p),
+                t0, t1, tile, part, [&](float d, int idx) { top.put_below(f32_key(d, idx)); });
+  if (q < n1) top.store(keys + ((size_t)y * n1 + q) * 4);
 }
 
 // top4[p][q] = the four smallest keys of query q over the splits of problem p = blockIdx.y
@@ -428,21 +368,8 @@ __global__ __launch_bounds__(256) void k_f32g_merge(const unsigned long long *__
                                                     unsigned long long *__restrict__ top4) {
   const int q = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
   if (q >= n1) return;
-  const int s0 = f32g_pick(g.first, p), s1 = s0 + f32g_pick(g.S, p);
-  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
-  for (int s = s0; s < s1; s++) {
-    const unsigned long long *k = keys + ((size_t)s * n1 + q) * 4;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const unsigned long long key = k[e];
-      k3 = min(k3, max(k2, key));
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, max(k0, key));
-      k0 = min(k0, key);
-    }
-  }
-  unsigned long long *o = top4 + ((size_t)p * n1 + q) * 4;
-  o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
+  const int s0 = group_pick(g.first, p);
+  f32_merge_splits(keys, n1, q, s0, s0 + group_pick(g.S, p), top4 + ((size_t)p * n1 + q) * 4);
 }
 
 // k_f32_resolve for the open walks of every problem at once: workgroup x belongs to one problem, one block of 256 of its open
@@ -452,33 +379,16 @@ __global__ __launch_bounds__(256) void k_f32g_resolve(const float *__restrict__ 
                                                       double contrDistSq, F32Closed *__restrict__ closed) {
   F32_SWEEP_LDS(DK);
   const int x = blockIdx.x;
-  const int p = (x >= g.rfirst[1]) + (x >= g.rfirst[2]) + (x >= g.rfirst[3]);
-  const int S = f32g_pick(g.S, p), local = x - f32g_pick(g.rfirst, p), ub = local / S, sp = local - ub * S;
-  const int tps = f32g_pick(g.tps, p), ntiles = f32g_pick(g.ntiles, p);
+  const int p = group_problem(g.rfirst, x);
+  const int S = group_pick(g.S, p), local = x - group_pick(g.rfirst, p), ub = local / S, sp = local - ub * S;
+  const int tps = group_pick(g.tps, p), ntiles = group_pick(g.ntiles, p);
   const int t0 = sp * tps, t1 = min(ntiles, t0 + tps);
-  const int u = f32g_pick(g.ubeg, p) + ub * 256 + threadIdx.x;
-  const bool live = u < f32g_pick(g.uend, p);
-  const double *__restrict__ pos = f32g_pick(g.pos, p);
-  F32Open o;
-  o.klast = F32_NONE; o.q = 0; o.t0 = 0; o.dpass = 0.f; o.pad = 0;
-  if (live) o = open[u];
-  const double px = pos[2 * (size_t)o.t0], py = pos[2 * (size_t)o.t0 + 1];
-  unsigned long long kterm = F32_NONE;
-  unsigned cnt = 0;
-  f32_sweep<DK>(live ? queries + (size_t)o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(f32g_pick(g.trains, p)), f32g_pick(g.n2, p),
-                t0, t1, tile, part, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    const double dx = px - pos[2 * (size_t)idx], dy = py - pos[2 * (size_t)idx + 1];
-    const bool terminal = d >= o.dpass || dx * dx + dy * dy > contrDistSq;
-    if (key > o.klast) {
-      if (terminal) kterm = min(kterm, key);
-      else cnt++;
-    }
-  });
-  if (live) {
-    if (kterm != F32_NONE) atomicMin(&closed[u].kterm, kterm);
-    if (cnt) atomicAdd(&closed[u].cnt, cnt);
-  }
+  const int u = group_pick(g.ubeg, p) + ub * 256 + threadIdx.x;
+  const bool live = u < group_pick(g.uend, p);
+  F32Resolve r(open, u, live, group_pick(g.pos, p), contrDistSq);
+  f32_sweep<DK>(live ? queries + (size_t)r.o.q * DK : nullptr, reinterpret_cast<const f32x4 *>(group_pick(g.trains, p)), group_pick(g.n2, p),
+                t0, t1, tile, part, [&](float d, int idx) { r.step(d, idx); });
+  r.commit(closed, u, live);
 }
 
 template <int DK>

@@ -7,16 +7,17 @@
 // chain's result, so the distance here is 32 v_sad_u8 (|a - b| over four bytes plus an accumulator, __builtin_amdgcn_sad_u8) and one
 // v_cvt_f32_u32.  L1 is no dot product: the matrix cores of kernels_match.hip cannot be used.
 //
-// Everything behind the distance is that of kernels_fginn32.hip: key = f32_key((float)sum, idx), the K = 4 smallest keys per query
-// and split (k_l1_topk), k_f32_merge itself, the host walk, the F32Open / F32Closed records and the resolve sweep (k_l1_resolve
-// compares (float)sum with d_pass exactly as k_f32_resolve compares its distance).  The geometry and the workspace are those of the
+// Everything behind the distance is that of kernels_fginn32.hip, by the same code (search_dev.hpp): key = f32_key((float)sum, idx),
+// the K = 4 smallest keys per query and split (k_l1_topk fills a Top4), k_f32_merge itself, the host walk, the F32Open / F32Closed
+// records and the resolve sweep (k_l1_resolve hands (float)sum to the F32Resolve that k_f32_resolve hands its distance to).  The geometry and the workspace are those of the
 // f32 search at a row of 32 dwords: fginn_l1_geometry = fginn32_geometry at DK = 32, 128 trains (16 KiB) per LDS tile.
 //
 // Layout.  k_l1_pack turns dense [n][128] u8 rows of any byte alignment into 16-byte-aligned rows of 8 uint4, the train side padded
 // with zero rows to whole tiles (never visited).  l1_sweep: one query per lane with its row in 32 VGPRs, 256-thread workgroups, the
 // next tile fetched into registers while this one is swept, every lane reads the same train words (broadcast ds_read_b128).
 //
-// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
+// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; regenerated with the shared pieces in
+// place: unchanged, and so is the ISA of all three kernels):
 //   kernel                VGPRs  SGPRs  LDS [B]  scratch  occupancy [waves/SIMD]
 //   k_l1_topk                86     25    16384        0      5
 //   k_l1_resolve             88     34    16384        0      5
@@ -30,6 +31,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "engine.hpp"
+#include "search_dev.hpp"
 
 namespace mx {
 
@@ -104,21 +106,10 @@ __global__ __launch_bounds__(256) void k_l1_topk(const uint4 *__restrict__ queri
   __shared__ __attribute__((aligned(16))) u32x4 tile[L1_TILE4];
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
-  unsigned long long k0 = F32_NONE, k1 = F32_NONE, k2 = F32_NONE, k3 = F32_NONE;
+  Top4 top;
   l1_sweep(q < n1 ? reinterpret_cast<const u32x4 *>(queries) + (size_t)q * (L1_W / 4) : nullptr, reinterpret_cast<const u32x4 *>(trains), n2,
-           t0, t1, tile, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    if (key < k3) {
-      k3 = min(k3, max(k2, key));
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, max(k0, key));
-      k0 = min(k0, key);
-    }
-  });
-  if (q < n1) {
-    unsigned long long *o = keys + ((size_t)blockIdx.y * n1 + q) * 4;
-    o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3;
-  }
+           t0, t1, tile, [&](float d, int idx) { top.put_below(f32_key(d, idx)); });
+  if (q < n1) top.store(keys + ((size_t)blockIdx.y * n1 + q) * 4);
 }
 
 // k_f32_resolve on byte rows: open[u] an undecided query; closed[u] (kterm = all ones, cnt = 0 on entry) receives over all splits the
@@ -129,26 +120,10 @@ __global__ __launch_bounds__(256) void k_l1_resolve(const uint4 *__restrict__ qu
   __shared__ __attribute__((aligned(16))) u32x4 tile[L1_TILE4];
   const int u = blockIdx.x * 256 + threadIdx.x;
   const int t0 = blockIdx.y * tilesPerSplit, t1 = min(ntiles, t0 + tilesPerSplit);
-  F32Open o;
-  o.klast = F32_NONE; o.q = 0; o.t0 = 0; o.dpass = 0.f; o.pad = 0;
-  if (u < nu) o = open[u];
-  const double px = pos[2 * (size_t)o.t0], py = pos[2 * (size_t)o.t0 + 1];
-  unsigned long long kterm = F32_NONE;
-  unsigned cnt = 0;
-  l1_sweep(u < nu ? reinterpret_cast<const u32x4 *>(queries) + (size_t)o.q * (L1_W / 4) : nullptr, reinterpret_cast<const u32x4 *>(trains), n2,
-           t0, t1, tile, [&](float d, int idx) {
-    const unsigned long long key = f32_key(d, idx);
-    const double dx = px - pos[2 * (size_t)idx], dy = py - pos[2 * (size_t)idx + 1];
-    const bool terminal = d >= o.dpass || dx * dx + dy * dy > contrDistSq;
-    if (key > o.klast) {
-      if (terminal) kterm = min(kterm, key);
-      else cnt++;
-    }
-  });
-  if (u < nu) {
-    if (kterm != F32_NONE) atomicMin(&closed[u].kterm, kterm);
-    if (cnt) atomicAdd(&closed[u].cnt, cnt);
-  }
+  F32Resolve r(open, u, u < nu, pos, contrDistSq);
+  l1_sweep(u < nu ? reinterpret_cast<const u32x4 *>(queries) + (size_t)r.o.q * (L1_W / 4) : nullptr, reinterpret_cast<const u32x4 *>(trains), n2,
+           t0, t1, tile, [&](float d, int idx) { r.step(d, idx); });
+  r.commit(closed, u, u < nu);
 }
 
 // work: fginn32_workspace_bytes(g, n1), 256-byte aligned.  n1 >= 1, n2 >= 1.  ev (optional): three events -- before the packing,

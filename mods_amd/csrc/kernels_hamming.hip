@@ -21,9 +21,11 @@
 // The train axis is cut into S splits (gridDim.y) of whole tiles; every split writes its two best per query as 64-bit keys
 // (distance << 32) | index (all ones = none).  k_hamming_merge takes the two smallest keys over the splits: integers only, the
 // keys are distinct, so the result is a pure function of the inputs -- not of S, the tile length or any launch order.
-// Geometry (tile length in trains, S, workgroups) comes from hamming_geometry(n1, n2, W, splits) alone.
+// Geometry (tile length in trains, S, workgroups) comes from hamming_geometry(n1, n2, W, splits) alone; the cut of the train axis
+// is split_rule (engine.hpp), the one rule of every exact search.
 //
-// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
+// Compiler figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; regenerated with the shared pieces in
+// place: every figure is what it was, and so is the ISA of every kernel but the two merges):
 //   kernel               VGPRs  SGPRs  LDS [B]  scratch  occupancy [waves/SIMD]
 //   k_hamming_2nn<1>        18     27     4096        0      8
 //   k_hamming_2nn<2>        22     27     4096        0      8
@@ -39,7 +41,8 @@
 //   k_hamg_2nn<16>          44     25     4096        0      8
 //   k_hamg_merge            14     19        0        0      8
 // k_hamg_* are the grouped form at the end of the file: up to four problems of one stored query side in one launch, the sweep
-// (ham_sweep) shared with k_hamming_2nn.  k_hamg_2nn asks for eight waves per SIMD in its launch bounds: without that the compiler
+// (ham_sweep) shared with k_hamming_2nn, the merge and its int4 decoding (ham_merge_splits) shared with k_hamming_merge, the
+// table selection (group_pick / group_problem) shared with the grouped f32 search: the last three live in search_dev.hpp.  k_hamg_2nn asks for eight waves per SIMD in its launch bounds: without that the compiler
 // gives the <16> instance 92 VGPRs (occupancy 5) where the same loop in k_hamming_2nn<16> takes 44.
 // i.e. eight workgroups of 256 per CU (the 32-wave cap), 32 KiB of the CU's 160 KiB LDS.  Per (query, train) k_hamming_2nn<8>
 // issues 2 WK + 3.75 vector instructions (WK v_xor_b32, WK v_bcnt_u32_b32, v_lshl_or_b32, v_max_u32, v_min_u32, half a v_min3_u32,
@@ -48,6 +51,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "engine.hpp"
+#include "search_dev.hpp"
 
 namespace mx {
 
@@ -58,6 +62,7 @@ constexpr unsigned HAM_NONE = 0xffffffffu;
 int hamming_kernel_width(int W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : 16; }
 
 // splits = 0: production (enough workgroups for every CU to hold its eight); splits > 0: that many, at most one per tile
+// (split_rule, engine.hpp)
 HammingGeo hamming_geometry(int n1, int n2, int W, int splits) {
   HammingGeo g;
   g.W = W;
@@ -65,10 +70,9 @@ HammingGeo hamming_geometry(int n1, int n2, int W, int splits) {
   g.tile = HAM_TILE_DWORDS / g.WK;
   g.ntiles = std::max(1, (n2 + g.tile - 1) / g.tile);
   g.gx = std::max(1, (n1 + 255) / 256);
-  int S = splits > 0 ? splits : (2048 + g.gx - 1) / g.gx;
-  S = std::max(1, std::min(S, g.ntiles));
-  g.tilesPerSplit = (g.ntiles + S - 1) / S;
-  g.S = (g.ntiles + g.tilesPerSplit - 1) / g.tilesPerSplit;      // no empty split
+  const SplitCut cut = split_rule(g.ntiles, g.gx, splits);
+  g.tilesPerSplit = cut.tilesPerSplit;
+  g.S = cut.S;
   return g;
 }
 
@@ -161,20 +165,7 @@ __global__ __launch_bounds__(256) void k_hamming_2nn(const uint32_t *__restrict_
 __global__ __launch_bounds__(256) void k_hamming_merge(const unsigned long long *__restrict__ part, int n1, int S, int4 *__restrict__ nn2) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= n1) return;
-  unsigned long long k1 = ~0ull, k2 = ~0ull;
-  for (int s = 0; s < S; s++) {
-    const unsigned long long *p = part + ((size_t)s * n1 + q) * 2;
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-      const unsigned long long k = p[e];
-      k2 = min(k2, max(k1, k));
-      k1 = min(k1, k);
-    }
-  }
-  int4 r;
-  r.x = k1 == ~0ull ? -1 : (int)(k1 & 0xffffffffu); r.y = k1 == ~0ull ? -1 : (int)(k1 >> 32);
-  r.z = k2 == ~0ull ? -1 : (int)(k2 & 0xffffffffu); r.w = k2 == ~0ull ? -1 : (int)(k2 >> 32);
-  nn2[q] = r;
+  ham_merge_splits(part, n1, q, 0, S, nn2 + q);
 }
 
 template <int WK>
@@ -229,17 +220,6 @@ int hamming_group_geometry(int n1, const int *n2, int G, int W, HamGroup &g, int
   return first;
 }
 
-// element p of a by-value table: compares and selects on constant indices, so the table stays in scalar registers
-template <class T>
-__device__ __forceinline__ T hamg_pick(const T *a, int p) {
-  T v = a[0];
-  if (p == 1) v = a[1];
-  if (p == 2) v = a[2];
-  if (p == 3) v = a[3];
-  return v;
-}
-static_assert(MATCH_MAXB == 4, "hamg_pick and the problem search below are written for four problems");
-
 // part: [splits of the group][n1][2] keys.  Workgroup (x, y) sweeps split y -- whole tiles of ONE problem -- for the queries of
 // block x; the keys carry the problem's own train index
 template <int WK>
@@ -247,11 +227,11 @@ __global__ __launch_bounds__(256, 8) void k_hamg_2nn(const uint32_t *__restrict_
                                                   unsigned long long *__restrict__ part) {
   __shared__ __attribute__((aligned(16))) uint32_t tile[HAM_TILE_DWORDS];
   const int q = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  const int p = (y >= g.first[1]) + (y >= g.first[2]) + (y >= g.first[3]);
-  const int tps = hamg_pick(g.tps, p);
-  const int t0 = (y - hamg_pick(g.first, p)) * tps, t1 = min(hamg_pick(g.ntiles, p), t0 + tps);
+  const int p = group_problem(g.first, y);
+  const int tps = group_pick(g.tps, p);
+  const int t0 = (y - group_pick(g.first, p)) * tps, t1 = min(group_pick(g.ntiles, p), t0 + tps);
   unsigned k1, k2;
-  ham_sweep<WK>(queries, q, n1, reinterpret_cast<const uint4 *>(hamg_pick(g.trains, p)), hamg_pick(g.n2, p), t0, t1, tile, k1, k2);
+  ham_sweep<WK>(queries, q, n1, reinterpret_cast<const uint4 *>(group_pick(g.trains, p)), group_pick(g.n2, p), t0, t1, tile, k1, k2);
   if (q < n1) {
     unsigned long long *o = part + ((size_t)y * n1 + q) * 2;
     o[0] = ham_key64(k1);
@@ -264,21 +244,8 @@ __global__ __launch_bounds__(256) void k_hamg_merge(const unsigned long long *__
                                                     int4 *__restrict__ nn2) {
   const int q = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
   if (q >= n1) return;
-  const int s0 = hamg_pick(g.first, p), s1 = s0 + hamg_pick(g.S, p);
-  unsigned long long k1 = ~0ull, k2 = ~0ull;
-  for (int s = s0; s < s1; s++) {
-    const unsigned long long *k = part + ((size_t)s * n1 + q) * 2;
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-      const unsigned long long key = k[e];
-      k2 = min(k2, max(k1, key));
-      k1 = min(k1, key);
-    }
-  }
-  int4 r;
-  r.x = k1 == ~0ull ? -1 : (int)(k1 & 0xffffffffu); r.y = k1 == ~0ull ? -1 : (int)(k1 >> 32);
-  r.z = k2 == ~0ull ? -1 : (int)(k2 & 0xffffffffu); r.w = k2 == ~0ull ? -1 : (int)(k2 >> 32);
-  nn2[(size_t)p * n1 + q] = r;
+  const int s0 = group_pick(g.first, p);
+  ham_merge_splits(part, n1, q, s0, s0 + group_pick(g.S, p), nn2 + ((size_t)p * n1 + q));
 }
 
 template <int WK>
