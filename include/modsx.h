@@ -404,6 +404,13 @@ int modsx_last_match_geometry(int *qs, int *fat, int *S, int *tiles_per_split, i
  * region counts as a call with no chunk.  Read it while no call runs on the context; tests work with the difference of two
  * readings */
 int modsx_describe_counters(modsx_ctx *ctx, long *out, int n);
+/* Measurement hook: which form of the SIFT describe kernel the launch sets of a context (and of those that describe on its behalf)
+ * took since modsx_create: out[0 .. min(n, 3) - 1], returns 3.  In order: launch sets that took the slim form (one LDS buffer per
+ * region) with its redo launch -- those without a direct-branch region, unless MODSX_DESCRIBE_SLIM=0 was set when the context was
+ * created --; launch sets that took the full kernel; and redo workgroups: the slim form's workgroups that needed the ordered
+ * gather and were run again by the redo launch (each also counts in ordered_workgroups).  The last is counted on the device:
+ * the call waits for the context's stream, like modsx_describe_counters */
+int modsx_describe_slim_counters(modsx_ctx *ctx, long *out, int n);
 /* Test entries and measurement hooks of the scale-space front end (ScaleSpaceDetector, affinedetectors/pyramid.cpp).
  * modsx_blur_geometry (host only): the tile rule of the pyramid's blur launch over n planes of rows[i] x cols[i] (1 <= n <= 32):
  * geometry[0] = rows of a 64-column tile, 32 when the launch has at least 2560 such tiles and 16 otherwise; geometry[1] = the
@@ -501,6 +508,10 @@ int modsx_debug_reproject_certain_drop(const modsx_region *regs, int n, const do
  * (MODSX_ERR_ARG and its modsx_last_error text) with the counters as the refused call leaves them */
 int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,
                               unsigned long long arena_floats, long *counters, int n, long *cuts, int cap_cuts, int *n_cuts);
+/* The same walk, reporting per chunk whether it may take the slim form of the describe kernel (no region of the direct branch):
+ * slim[0 .. min(*n_chunks, cap) - 1], *n_chunks the chunks planned.  Host only */
+int modsx_debug_describe_plan_slim(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,
+                                   unsigned long long arena_floats, unsigned char *slim, int cap, int *n_chunks);
 /* Test entries of the Baumberg stage (AffineShape::findAffineShape, affinedetectors/affine.cpp:26-169).
  * modsx_debug_baumberg_geometry (host only): what a launch of n keypoints at window W runs, geometry[4] = kernel (0 = the
  * two-slot stream kernel on static chunks, 1 = the one-keypoint kernel with the window size compiled in, 2 = the one-keypoint

@@ -156,7 +156,7 @@ EXPORTS = ["modsx_version", "modsx_last_error", "modsx_free", "modsx_create", "m
            "modsx_shard_owner_plan", "modsx_db_create", "modsx_db_free", "modsx_db_rows", "modsx_db_nearest",
            "modsx_match_fginn_db", "modsx_match_fginn_db_device", "modsx_set_fginn_db",
            "modsx_debug_orientation_counts", "modsx_debug_orientation_launches", "modsx_orientation_tables",
-           "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan",
+           "modsx_debug_reproject_certain_drop", "modsx_debug_describe_plan", "modsx_debug_describe_plan_slim", "modsx_describe_slim_counters",
            "modsx_debug_views_counters", "modsx_debug_view_plan", "modsx_debug_views_groups", "modsx_debug_synth_views",
            "modsx_debug_baumberg_geometry", "modsx_debug_baumberg_geometry_ctx", "modsx_debug_baumberg_variant",
            "modsx_debug_baumberg", "modsx_debug_check_borders", "modsx_debug_describe_lanes", "modsx_debug_describe_lane_map",
@@ -210,6 +210,8 @@ DESCRIBE_COUNTERS = ("calls", "chunks", "max_chunks", "chunks_mid_image", "chunk
 # ... and behind those, which the planner books (describe_plan gives them too), what only the device counts: k_describe
 # workgroups that took the ordered gather.  Context.describe_counters() has both
 DESCRIBE_DEVICE_COUNTERS = ("ordered_workgroups",)
+# include/modsx.h: modsx_describe_slim_counters, in its order
+DESCRIBE_SLIM_COUNTERS = ("slim_launches", "full_launches", "redo_workgroups")
 # include/modsx.h: modsx_detect_counters, in its order
 DETECT_COUNTERS = ("blur_th16", "blur_th32") + tuple("blur_r%d" % r for r in range(1, 9)) + (
     "hessian", "resize", "scan_per_octave", "scan_per_level", "nms_flushes", "last_jobs", "last_tiles", "last_accepted",
@@ -316,6 +318,9 @@ def lib():
         L.modsx_set_fginn_db.argtypes = [C.c_void_p, C.c_void_p]
         L.modsx_debug_reproject_certain_drop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.modsx_describe_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_describe_slim_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.modsx_debug_describe_plan_slim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p, C.c_int,
+                                                     C.c_void_p]
         L.modsx_debug_orientation_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_debug_orientation_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.modsx_orientation_tables.argtypes = [C.c_void_p] * 6
@@ -1622,6 +1627,11 @@ class Context(object):
         of DESCRIBE_DEVICE_COUNTERS: `ordered_workgroups`, read from the device (the call waits for the context's stream)."""
         return self._counters("modsx_describe_counters", DESCRIBE_COUNTERS + DESCRIBE_DEVICE_COUNTERS)
 
+    def describe_slim_counters(self):
+        """dict of DESCRIBE_SLIM_COUNTERS: SIFT launch sets of this context that took the slim form of the describe kernel / the
+        full kernel, and the slim form's workgroups that its redo launch ran again (the call waits for the context's stream)."""
+        return self._counters("modsx_describe_slim_counters", DESCRIBE_SLIM_COUNTERS)
+
     def detect_counters(self):
         """dict of DETECT_COUNTERS: what the pyramid and the extrema scan launched on this context since it was created (the
         last_* entries describe its last scan / candidate set)."""
@@ -2443,6 +2453,20 @@ def describe_plan(regs, mr_size, fast=0, arena_floats=DEFAULT_ARENA_FLOATS, max_
     assert ncuts.value <= max_cuts, "describe_plan: %d cuts, room for %d" % (ncuts.value, max_cuts)
     return dict(rc=rc, error=_err() if rc else "", counters=dict(zip(DESCRIBE_COUNTERS, (int(x) for x in cnt))),
                 cuts=[int(cuts[i]) for i in range(ncuts.value)])
+
+
+def describe_plan_slim(regs, mr_size, fast=0, arena_floats=DEFAULT_ARENA_FLOATS, max_chunks=4096):
+    """modsx_debug_describe_plan_slim: per chunk of describe_plan's walk, whether it holds no region of the direct branch (the
+    launch set may take the slim form of the describe kernel).  -> list of bool, one per chunk."""
+    lists = [regs] if isinstance(regs, np.ndarray) else list(regs)
+    counts = np.array([len(r) for r in lists], np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(r).view(REGION) for r in lists]) if lists else np.zeros(0, REGION), REGION)
+    slim = np.zeros(max(1, max_chunks), np.uint8)
+    nch = C.c_int(0)
+    _check(lib().modsx_debug_describe_plan_slim(_p(flat), _p(counts), len(lists), C.c_double(mr_size), int(fast), int(arena_floats),
+                                                _p(slim), max_chunks, C.byref(nch)), "debug_describe_plan_slim")
+    assert nch.value <= max_chunks, "describe_plan_slim: %d chunks, room for %d" % (nch.value, max_chunks)
+    return [bool(x) for x in slim[:nch.value]]
 
 
 def view_block_order(counts):

@@ -526,6 +526,26 @@ int modsx_describe_counters(modsx_ctx *ctx, long *out, int n) {
   return mx::DC_ALL;
 }
 
+int modsx_describe_slim_counters(modsx_ctx *ctx, long *out, int n) {
+  NEED(ctx);
+  if (n < 0 || (n > 0 && !out)) { mx::set_error("modsx_describe_slim_counters: bad argument"); return MODSX_ERR_ARG; }
+  long sum[3] = {0, 0, 0};   // the same contexts as modsx_describe_counters
+  for (modsx_ctx *head : {ctx, ctx->peer})
+    for (modsx_ctx *c = head; c; c = c->half) {
+      unsigned now = 0;
+      if (hipSetDevice(c->dev) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+          hipMemcpy(&now, c->dDescOrdered + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        mx::set_error("modsx_describe_slim_counters: reading the device counter failed"); return MODSX_ERR_DEVICE;
+      }
+      c->descRedoTotal += (long)(unsigned)(now - c->descRedoSeen);
+      c->descRedoSeen = now;
+      sum[0] += c->descSlimCnt[0]; sum[1] += c->descSlimCnt[1]; sum[2] += c->descRedoTotal;
+    }
+  hipSetDevice(ctx->dev);
+  for (int q = 0; q < n && q < 3; q++) out[q] = sum[q];
+  return 3;
+}
+
 int modsx_blur_geometry(const int *rows, const int *cols, int n, int *geometry) {
   NEED(rows); NEED(cols); NEED(geometry);
   if (n < 1 || n > mx::MAXB) { mx::set_error("modsx_blur_geometry: 1 .. 32 planes"); return MODSX_ERR_ARG; }
@@ -621,6 +641,33 @@ int modsx_debug_describe_plan(const modsx_region *regs, const int *counts, int n
   if (!rc) cnt[mx::DC_MAX_CHUNKS] = chunkNo;
   for (int q = 0; q < n && q < mx::DC_N; q++) counters[q] = cnt[q];
   return rc;
+}
+
+int modsx_debug_describe_plan_slim(const modsx_region *regs, const int *counts, int nimages, double mr_size, int fast_extraction,
+                                   unsigned long long arena_floats, unsigned char *slim, int cap, int *n_chunks) {
+  if (nimages < 0 || (nimages > 0 && !counts) || cap < 0 || (cap > 0 && !slim) || !n_chunks) {
+    mx::set_error("modsx_debug_describe_plan_slim: bad argument"); return MODSX_ERR_ARG;
+  }
+  if (nimages > mx::MAXB) { mx::set_error("describe batch too large"); return MODSX_ERR_ARG; }
+  std::vector<modsx_region> v[mx::MAXB];
+  size_t first = 0;
+  for (int i = 0; i < nimages; i++) {
+    if (counts[i] < 0 || (counts[i] > 0 && !regs)) { mx::set_error("modsx_debug_describe_plan_slim: bad argument"); return MODSX_ERR_ARG; }
+    v[i].assign(regs + first, regs + first + counts[i]);
+    first += (size_t)counts[i];
+  }
+  mx::HostMark hm;
+  mx::DescBatch batch;
+  batch.regs = v; batch.n = nimages; batch.mrSize = mr_size; batch.fast = fast_extraction;
+  *n_chunks = 0;
+  for (mx::DescCursor cur = mx::describe_windows(batch); cur.img < nimages; (*n_chunks)++) {
+    mx::DescChunkPlan cp;
+    const int rc = mx::describe_plan_chunk(batch, cur, (size_t)arena_floats, cp, hm);
+    if (rc) return rc;
+    if (*n_chunks < cap) slim[*n_chunks] = cp.slim ? 1 : 0;
+    cur = cp.next;
+  }
+  return MODSX_OK;
 }
 
 int modsx_describe_regions(modsx_ctx *ctx, const modsx_image *img, const modsx_region *regs, int n, double mrSize,

@@ -233,6 +233,7 @@ static void layout_chunk(DescChunkPlan &cp) {
     cp.cnt[DC_FUSED_WINDOWS] += j.P > 0 && j.ro1 == -1;
     cp.cnt[DC_CLAMPED_WINDOWS] += j.P > 0 && cp.sizes.find(j.P)->second.clamped;
   }
+  cp.slim = !cp.jobs.empty() && cp.cnt[DC_DIRECT_JOBS] == 0;
   cp.cnt[DC_JOBS] += (long)cp.jobs.size();
   cp.cnt[DC_LDS_ROW_TILES] += cp.pfxRowL.back();
   cp.cnt[DC_LDS_COL_TILES] += cp.pfxColL.back();
@@ -246,6 +247,7 @@ int describe_plan_chunk(const DescBatch &b, DescCursor from, size_t arenaFloats,
   for (std::vector<int> *p : {&cp.pfxSample, &cp.pfxRow, &cp.pfxCol, &cp.pfxRowL, &cp.pfxColL}) p->assign(1, 0);
   cp.arenaA = cp.arenaB = cp.arenaC = cp.rowStarts = 0;
   for (int q = 0; q < DC_N; q++) cp.cnt[q] = 0;
+  cp.slim = false;
   // a chunk is counted when its walk begins: a refusal leaves a chunk with no jobs
   cp.cnt[DC_CHUNKS] = 1;
   cp.cnt[DC_CHUNKS_MID_IMAGE] = from.reg > 0;
@@ -267,7 +269,9 @@ DescBlobLayout::DescBlobLayout(const DescChunkPlan &cp) {
   const size_t nj = cp.jobs.size();
   oJobs = 0; oPfx = align_up(nj * sizeof(DescJob), 16); pfxB = align_up((nj + 1) * 4, 16);
   oTaps = oPfx + 5 * pfxB; oNeed = oTaps + align_up(cp.taps.size() * 4, 16); oCoord = oNeed + align_up(cp.needTab.size() * 4, 16);
-  blobB = oCoord + align_up(cp.coordTab.size() * 4, 16) + 16;
+  oRedo = oCoord + align_up(cp.coordTab.size() * 4, 16) + 16;
+  blobB = oRedo + 16;
+  devB = blobB + align_up(((nj + 1) / 2) * 4, 16);
 }
 
 void describe_fill_blob(const DescChunkPlan &cp, const DescBlobLayout &L, char *hb) {
@@ -278,6 +282,7 @@ void describe_fill_blob(const DescChunkPlan &cp, const DescBlobLayout &L, char *
   if (!cp.taps.empty()) memcpy(hb + L.oTaps, cp.taps.data(), cp.taps.size() * 4);
   if (!cp.needTab.empty()) memcpy(hb + L.oNeed, cp.needTab.data(), cp.needTab.size() * 4);
   if (!cp.coordTab.empty()) memcpy(hb + L.oCoord, cp.coordTab.data(), cp.coordTab.size() * 4);
+  memset(hb + L.oRedo, 0, 16);
 }
 
 }  // namespace mx

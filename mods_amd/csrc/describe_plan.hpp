@@ -51,14 +51,17 @@ struct DescChunkPlan {
   size_t arenaA, arenaB, arenaC, rowStarts;                   // floats of the three arenas, float2 row starts of the fused windows
   size_t windowFloats;                                        // all P x P windows of the chunk: its size limit and its algorithmic bytes
   long cnt[DC_N];                                             // what this chunk adds to the counters (DC_CALLS, DC_MAX_CHUNKS: the caller's)
+  bool slim;                                                  // no job of the direct branch (P == 0): the SIFT launch may take k_describe's slim form
   DescCursor next;
 };
 // MODSX_ERR_ARG when a window of the chunk is refused: cnt then holds the chunk and no jobs.  hm: the host-phase marks.
 int describe_plan_chunk(const DescBatch &b, DescCursor from, size_t arenaFloats, DescChunkPlan &cp, HostMark &hm);
 
-// The staged blob of a chunk: the job table, the five tile prefixes and the three small tables, each 16-byte aligned.
+// The staged blob of a chunk: the job table, the five tile prefixes and the three small tables, each 16-byte aligned, and last the
+// count word of the slim form's redo list (16 bytes, staged as zeros: the blob's copy resets it for every launch set).  The list
+// itself (one entry per two jobs) lies behind the blob on the device alone: devB >= blobB bytes.
 struct DescBlobLayout {
-  size_t oJobs, oPfx, pfxB, oTaps, oNeed, oCoord, blobB;
+  size_t oJobs, oPfx, pfxB, oTaps, oNeed, oCoord, oRedo, blobB, devB;
   explicit DescBlobLayout(const DescChunkPlan &cp);
   size_t pfx(int q) const { return oPfx + q * pfxB; }         // q: sample, rows, columns, LDS rows, LDS columns
 };

@@ -356,8 +356,9 @@ static int upload_tables(modsx_ctx *c) {
   }
   MX_HIP(hipMalloc(&c->dSiftBins, sizeof bins));
   MX_HIP(hipMemcpy(c->dSiftBins, bins, sizeof bins, hipMemcpyHostToDevice));
-  MX_HIP(hipMalloc(&c->dDescOrdered, 4));
-  MX_HIP(hipMemset(c->dDescOrdered, 0, 4));
+  MX_HIP(hipMalloc(&c->dDescOrdered, 8));
+  MX_HIP(hipMemset(c->dDescOrdered, 0, 8));
+  { const char *e = getenv("MODSX_DESCRIBE_SLIM"); c->descSlim = !(e && atoi(e) == 0); }
   MX_HIP(hipMalloc(&c->dSiftW, sizeof w));
   MX_HIP(hipMemcpy(c->dSiftW, w, sizeof w, hipMemcpyHostToDevice));
   return MODSX_OK;
@@ -723,7 +724,7 @@ static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot
   const DescBlobLayout L(cp);
   PinBuf &hblob = slot ? c->hDescB : c->hDesc;
   if (c->descEvPending[slot]) { MX_HIP(c->descByEvent[slot] ? hipEventSynchronize(c->descEv[slot]) : ctx_wait_mark(c, c->descMark[slot])); c->descEvPending[slot] = false; }
-  if (!c->descJobs.ensure(L.blobB) || !hblob.ensure(L.blobB) ||
+  if (!c->descJobs.ensure(L.devB) || !hblob.ensure(L.blobB) ||
       !c->scratchA.ensure(std::max<size_t>(1, cp.arenaA) * 4) || !c->scratchB.ensure(std::max<size_t>(1, cp.arenaB) * 4) ||
       !c->scratchC.ensure(std::max<size_t>(1, cp.arenaC) * 4) || !c->rowStarts.ensure(std::max<size_t>(1, cp.rowStarts) * 8) ||
       !c->tileJob.ensure(((size_t)nS + nR + nC + 3) * 4))
@@ -766,9 +767,12 @@ static int launch_describe_chunk(modsx_ctx *c, const DescChunkPlan &cp, int slot
   // the patch-out callers (engine_liop.hip): the normalised patches of the chunk's jobs instead of their SIFT descriptors
   if (tail) return tail->run(c, tail->self, dj, (int)nj, (const float *)c->scratchC.p, dNeed, dCoord, photoNorm);
   ProfScope psd(c, K_DESCRIBE, (double)nj * 128 * ds.n);
-  launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
-                  c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
-                  c->dSiftBins, c->dSiftW, photoNorm, ds.packed(), ds.n, maxBin, outs, c->dDescOrdered);
+  // a chunk without a direct-branch job: the slim form, its redo list behind the blob (MODSX_DESCRIBE_SLIM=0: never)
+  unsigned *const redo = cp.slim && c->descSlim ? (unsigned *)(db + L.oRedo) : nullptr;
+  const int slim = launch_describe(s, dj, (int)nj, (ImgRef *)c->imgRefs.p, (float *)c->scratchC.p, dNeed, dCoord,
+                                   c->dSiftMask, c->dSiftMaskIdx, c->nSiftMask, c->dSiftOTab,
+                                   c->dSiftBins, c->dSiftW, photoNorm, ds.packed(), ds.n, maxBin, outs, c->dDescOrdered, redo);
+  c->descSlimCnt[slim ? 0 : 1]++;
   return MODSX_OK;
 }
 

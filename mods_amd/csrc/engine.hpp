@@ -278,11 +278,14 @@ void launch_patch_sample(hipStream_t s, const DescJob *jobs, const int *tilePref
                          const ImgRef *imgs, float *scratch);
 void launch_patch_blur(hipStream_t s, const DescJob *jobs, const int *tilePrefix, const int *tileJob, int nTiles,
                        const float *taps, const int *needTab, const float *src, float *dst, int pass);
-void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
-                     const int *needTab, const float *coordTab,
-                     const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
-                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
-                     unsigned *orderedCnt);
+// redo: null for today's kernel; else the launch set's redo list (a zero count word, 12 spare bytes, one entry per two jobs),
+// with which a launch whose jobs are all grid-branch ones takes the slim form and its redo launch.  orderedCnt: two words (the
+// ordered workgroups, the redo workgroups).  -> 1 when the slim form was launched, else 0
+int launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
+                    const int *needTab, const float *coordTab,
+                    const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
+                    const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
+                    unsigned *orderedCnt, unsigned *redo);
 void launch_warp_affine(hipStream_t s, const WarpJob &jb);
 void launch_blur_pass(hipStream_t s, const float *src, float *dst, int rows, int cols, const float *taps, int n, int pass, int border = 0);
 void launch_sub(hipStream_t s, const float *a, const float *b, float *o, size_t n);
@@ -659,7 +662,12 @@ struct modsx_ctx {
   size_t lastCandCount = 0;    // scale-space candidates of the context's last launch set (sizes the speculative download)
   const mx::DbSet *fginnDb = nullptr;   // modsx_set_fginn_db: the fused callers match their RootSIFT class against it (useDBforFGINN)
   long descCnt[mx::DC_N] = {0};   // modsx_describe_counters: what describe_batch planned on this context since modsx_create
-  unsigned *dDescOrdered = nullptr;   // device word: k_describe workgroups (SIFT and raw forms) that took the ordered gather
+  unsigned *dDescOrdered = nullptr;   // device words: k_describe workgroups (SIFT and raw forms) that took the ordered gather, and
+                                      // [1] those of them that the slim form handed to its redo launch
+  bool descSlim = true;               // MODSX_DESCRIBE_SLIM=0 (read when the context is created): today's kernel for every launch
+  long descSlimCnt[2] = {0, 0};       // modsx_describe_slim_counters: SIFT launch sets that took the slim form / the full kernel
+  unsigned descRedoSeen = 0;          // last reading of dDescOrdered[1] and the sum of the readings' differences
+  long descRedoTotal = 0;
   unsigned descOrderedSeen = 0;       // its last reading, and the sum of the readings' differences (the word may wrap)
   long descOrderedTotal = 0;
   long detCnt[mx::DT_N] = {0};    // modsx_detect_counters: what the pyramid and the extrema scan launched on this context

@@ -675,41 +675,81 @@ constexpr int DR = MODSX_DESCRIBE_REGIONS;
 // (The body is the kernel itself, not a function the kernels call: inlined from a function, k_describe<DM_SIFT> compiled to 71
 // VGPRs instead of 70.)
 enum { DM_SIFT = 0, DM_PATCH = 1, DM_RAW = 2 };
-template <int MODE>
-__global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
+// Three forms of the SIFT kernel (the other two modes have DF_FULL alone):
+//   DF_FULL  everything above, for any job.
+//   DF_SLIM  grid-branch jobs (P > 0) that end in the order-free gather, on ONE LDS buffer per region (below): 19.3 KB per
+//            workgroup instead of 32.5.  A workgroup that would need the ordered gather writes no descriptor: thread 0 counts it
+//            (orderedCnt[0], as DF_FULL does, and orderedCnt[1]: the redo workgroups) and appends blockIdx.x to the launch set's
+//            redo list -- redo[0] is the list's length, zeroed by the copy of the chunk's blob, redo[4 + i] its entries.
+//   DF_REDO  DF_FULL on the listed workgroups, launched behind DF_SLIM on the same stream: a small fixed grid whose workgroups
+//            stride over the list, an entry standing in for blockIdx.x.  It leaves orderedCnt alone (DF_SLIM has counted).
+enum { DF_FULL = 0, DF_SLIM = 1, DF_REDO = 2 };
+// Geometry of DF_SLIM, chosen by measurement: eight workgroups per CU, unpadded.  Padded to 7 / 6 / 5
+// workgroups per CU (-DMODSX_DESCRIBE_SLIM_PAD) the headline fell from 248.3 to 245.8 / 242.3 / 239.9 pairs/s (parent: 244.1).
+constexpr int DESC_SLIM_WAVES = 8;    // wavefronts per SIMD the slim form is compiled for: at most 64 VGPRs (it takes 60)
+constexpr int DESC_REDO_GRID = 64;    // workgroups of the redo launch at the most: a few microseconds when the list is empty
+constexpr int DESC_SLIM_PICKS = 10;   // masked pixels a thread of DF_SLIM keeps in registers: the form takes masks of <= 1280 pixels
+// DF_SLIM hides its thread index from the compiler at the head of every per-pixel phase: the (row, column) pairs of a thread's 14
+// pixels are then formed again where they are used -- kept from the sampling to the gather they were 28 long-lived VGPRs
+__device__ __forceinline__ int fresh_vgpr(int x) { asm volatile("" : "+v"(x)); return x; }
+// (the second launch bound: DESC_SLIM_WAVES for the slim form; 0 sets nothing, the other forms compile as they did)
+template <int MODE, int FORM = DF_FULL>
+__global__ __launch_bounds__(128 * DR, FORM == DF_SLIM ? DESC_SLIM_WAVES : 0) void k_describe(const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
                                                   const int *needTab, const float *coordTab,
                                                   const float *mask, const unsigned short *maskIdx,
                                                   const float *oTab, const int *binTab, const double *wTab,
                                                   SiftConst sc, int photoNorm, int descTypes, int nOut, double maxBin,
-                                                  DescOut outs, float *fOut, int fFlag, unsigned *orderedCnt) {
+                                                  DescOut outs, float *fOut, int fFlag, unsigned *orderedCnt, unsigned *redo) {
+  static_assert(FORM == DF_FULL || MODE == DM_SIFT, "the slim and redo forms are SIFT kernels");
+  constexpr bool SLIM = FORM == DF_SLIM;
   const int tidw = threadIdx.x;                                    // thread of the workgroup
   const int reg = __builtin_amdgcn_readfirstlane(tidw >> 7);       // region of the workgroup (a wavefront is inside one region)
   const int tid = tidw & 127;                                      // thread of the region
-  const int kreal = blockIdx.x * DR + reg;
+  unsigned li = blockIdx.x;
+  do {   // DF_REDO: once per list entry of this workgroup's stride (the body is not indented); the other forms: once
+  if (FORM == DF_REDO) {
+    if (li >= redo[0]) break;
+    if (li != blockIdx.x) __syncthreads();   // the tail of the last entry has read its LDS
+  }
+  const int wg = FORM == DF_REDO ? (int)redo[4 + li] : (int)blockIdx.x;
+  const int kreal = wg * DR + reg;
   const bool alive = kreal < n;                                    // a region past the end repeats the last one and stores nothing
   const int k = alive ? kreal : n - 1;
   // 15.8 KB of LDS per region (it was 19.7: four workgroups of two regions per CU; now five, and the kernel's time follows its
-  // residency -- its phases are chains of dependent LDS / global accesses, not issue-bound).  Two pixel arrays, both unpadded
-  // (index p = 41 r + c):
+  // residency -- its phases are chains of dependent LDS / global accesses, not issue-bound; DF_SLIM, at 9.5 KB per region and
+  // eight workgroups per CU, takes 174 us per launch on one stream where this form takes 233, section 9.26).  Two pixel arrays,
+  // both unpadded (index p = 41 r + c):
   //   bufO: the patch; after the gradients the pixel's orientation o = 8 (ori + 2 pi) / (2 pi) (staged in registers first) -- its
   //         bin and the two orientation weights are formed from it where they are used (the gather's forming step);
   //   bufA: WX (direct branch) / the resampling table (grid branch), the compacted masked values, later val = mask * |grad|.
+  // DF_SLIM: ONE buffer U of 9280 B per region, the size of the order-free gather's accumulators.  The patch lies in U[0, 6736)
+  // and the resampling table behind it (U's tail); every thread keeps its 14 raw samples in registers across the photometric
+  // normalisation, so the compacted masked values (bufA) may overwrite the patch from 0 -- the two one-lane chains read the
+  // same words in the same order -- and the normalised patch is written from the registers; the accumulators are U; vec /
+  // part reuse U[0, 2048) behind the merge's barrier.  The ordered gather (val beside o, sbs) is DF_REDO's.
   constexpr int NPXP = (NPX + 3) & ~3;
-  __shared__ __attribute__((aligned(16))) float buf_[DR][2][NPXP];   // [0] bufO, [1] bufA: contiguous (the order-free gather's
-                                                                     // accumulators span both)
-  float *const patch = buf_[reg][0], *const bufO = buf_[reg][0];
+  constexpr int ACS = 145, NAC = 8 * ACS;                      // the gather's copy stride and total in 8-byte words
+  constexpr int BUFW = SLIM ? 2 * NAC : 2 * NPXP;
+  __shared__ __attribute__((aligned(16))) float buf_[DR][BUFW];   // bufO, then bufA at NPXP: contiguous (the order-free gather's
+                                                                  // accumulators span both)
+  float *const patch = buf_[reg], *const bufO = buf_[reg];
   constexpr int PER_T = (NPX + 127) / 128;
-  float *const bufA = buf_[reg][1];
+  float *const bufA = buf_[reg] + (SLIM ? 0 : NPXP);
   __shared__ __attribute__((aligned(16))) double slut_[DR][256];   // the descriptor vector and its partial sums (2 KB)
   __shared__ __attribute__((aligned(16))) unsigned char sbs_[DR][4 * 64];   // gather: orientation bin bo0 % 8 of the step's 4 x 64 slots
   // precomputeBinsAndWeights (siftdesc.cpp:22-71) per row / column index i: {w0[i], w1[i], the smaller nonzero one of the two (1
   // if both are 0), bin0 | bin1 << 2 with the bins in 0..3}; one table for the workgroup
   __shared__ float4 stab[PS];
-  // the resampling table of the grid branch (smap, sfr) lies in bufA, which that branch does not use before the normalisation
-  int4 *const smap = reinterpret_cast<int4 *>(bufA);
-  float *const sfr = bufA + 168;
-  static_assert(PS * 16 <= 168 * 4 && (168 + PS) <= NPXP, "smap (41 x int4) and sfr (41 floats) fit in bufA");
-  double *const vec = slut_[reg], *const part = slut_[reg] + 128;
+  // the resampling table of the grid branch (smap, sfr) lies behind the patch: in bufA, which that branch does not use before the
+  // normalisation, or (DF_SLIM) in U's tail
+  int4 *const smap = reinterpret_cast<int4 *>(buf_[reg] + NPXP);
+  float *const sfr = buf_[reg] + NPXP + 168;
+  static_assert(PS * 16 <= 168 * 4 && NPXP + 168 + PS <= BUFW, "smap (41 x int4) and sfr (41 floats) fit behind the patch");
+  // region q's descriptor vector: its own 2 KB, or (DF_SLIM) the head of U
+  const auto vec_of = [&](int q) -> double * {
+    if constexpr (SLIM) return reinterpret_cast<double *>(buf_[q]); else return slut_[q];
+  };
+  double *const vec = vec_of(reg), *const part = vec + 128;
   __shared__ float sstat_[DR][2];
   float *const sstat = sstat_[reg];
   __shared__ double sfac_[DR];
@@ -718,6 +758,10 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   __shared__ volatile char spad_[MODSX_DESCRIBE_PAD];
   if (tidw == 0) spad_[MODSX_DESCRIBE_PAD - 1] = 1;
 #endif
+#ifdef MODSX_DESCRIBE_SLIM_PAD   // measurement build: the slim form alone padded to fewer workgroups per CU
+  __shared__ volatile char spads_[SLIM ? MODSX_DESCRIBE_SLIM_PAD : 1];
+  if (SLIM && tidw == 0) spads_[MODSX_DESCRIBE_SLIM_PAD - 1] = 1;
+#endif
   const DescJob jb = jobs[k];
   if (MODE != DM_PATCH && tidw < PS) {
     const float w0 = (float)wTab[tidw], w1 = (float)wTab[PS + tidw];   // const float wr0 = w0[r] (siftdesc.cpp:79-81)
@@ -725,7 +769,8 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     const float wm = w0 > 0 ? (w1 > 0 ? fminf(w0, w1) : w0) : (w1 > 0 ? w1 : 1.f);
     stab[tidw] = make_float4(w0, w1, wm, __int_as_float(b0 | (b1 << 2)));
   }
-  if (jb.P > 0) {
+  float sv[SLIM ? PER_T : 1];   // DF_SLIM: the thread's raw samples p = tid + 128 k
+  if (SLIM || jb.P > 0) {
     // interpolate(smoothed, P/2, P/2, i2p, 0, 0, i2p, patch) (synth-detection.hpp:211-212) on the compact blurred grid:
     // the host ran the coordinate recurrences once per window size; sample (j, i) blends grid rows idx(y0_j), idx(y0_j+1)
     // and columns idx(x0_i), idx(x0_i+1) with wx = WX_i - x0_i, wy = WY_j - y0_j -- the expression of helpers.cpp:575-577.
@@ -742,8 +787,9 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     __syncthreads();
     // two halves of seven samples: 28 grid values in flight per thread instead of 56 -- the registers of the second 28 were what
     // held the kernel at four wavefronts per SIMD (117 VGPRs) once its LDS allowed five workgroups per CU
-    constexpr int HALF_T = PER_T / 2;
-    static_assert(PER_T == 2 * HALF_T, "an even number of samples per thread");
+    // (DF_SLIM, compiled for 64 VGPRs and with its 14 samples kept: four batches of four, 16 grid values in flight)
+    constexpr int NH = SLIM ? 4 : 2, HALF_T = (PER_T + NH - 1) / NH;
+    static_assert(SLIM || PER_T == 2 * HALF_T, "an even number of samples per thread");
     // Addresses: 32-bit BYTE offsets from the region's (wave-uniform) grid base -- one 24-bit multiply per grid row and an
     // add + shift per load, the loads in the scalar base + vector offset form (the size_t row products this replaces were
     // quarter-rate 32-bit multiplies and 64-bit adds: two thirds of the issue slots of the sampling).  An entry that is not valid
@@ -754,11 +800,12 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     const unsigned NCu = (unsigned)NC;
     int rs = tid / PS, cs = tid - rs * PS;
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
+    for (int h = 0; h < NH; h++) {
       float g00[HALF_T], g01[HALF_T], g10[HALF_T], g11[HALF_T];
       int rr[HALF_T], cc[HALF_T];
 #pragma unroll
       for (int kk = 0; kk < HALF_T; kk++) {
+        if (h * HALF_T + kk >= PER_T) continue;
         const int r = rs < PS ? rs : PS - 1, c = rs < PS ? cs : PS - 1;   // p >= NPX: the last pixel again, not stored
         rr[kk] = r; cc[kk] = c;
         const int4 mr = smap[r], mc = smap[c];
@@ -768,9 +815,10 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
         cs += 128 - 3 * PS; rs += 3;     // p += 128
         if (cs >= PS) { cs -= PS; rs++; }
       }
-      if (h == 0) __syncthreads();   // (the direct branch of another region of the workgroup has a barrier here)
+      if (!SLIM && h == 0) __syncthreads();   // (the direct branch of another region of the workgroup has a barrier here)
 #pragma unroll
       for (int kk = 0; kk < HALF_T; kk++) {
+        if (h * HALF_T + kk >= PER_T) continue;
         const int p = tid + 128 * (h * HALF_T + kk);
         if (p < NPX) {
           const int r = rr[kk], c = cc[kk];
@@ -781,7 +829,8 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
             v = wyd * (wx * (g11[kk] - g10[kk]) + g10[kk] - I1) + I1;
           }
           patch[p] = v;
-        }
+          if constexpr (SLIM) sv[h * HALF_T + kk] = v;
+        } else if constexpr (SLIM) sv[h * HALF_T + kk] = 0.f;
       }
     }
   } else {
@@ -825,11 +874,19 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   // -- photometricallyNormalize (helpers.cpp:666-715): f32 running sums over the masked pixels
   if (photoNorm) {
     const int nm = sc.nmask, nm4 = (nm + 3) & ~3;
-    for (int i = tid; i < nm4; i += 128) bufA[i] = i < nm ? patch[maskIdx[i]] : 0.f;
+    if constexpr (SLIM) {
+      float mv[DESC_SLIM_PICKS];
+#pragma unroll
+      for (int k = 0; k < DESC_SLIM_PICKS; k++) { const int i = tid + 128 * k; mv[k] = i < nm ? patch[maskIdx[i]] : 0.f; }
+      __syncthreads();   // every masked value is in a register: the list may overwrite the patch
+#pragma unroll
+      for (int k = 0; k < DESC_SLIM_PICKS; k++) { const int i = tid + 128 * k; if (i < nm4) bufA[i] = mv[k]; }
+    } else
+      for (int i = tid; i < nm4; i += 128) bufA[i] = i < nm ? patch[maskIdx[i]] : 0.f;
     __syncthreads();
     if (tidw < DR) {   // lane q of wavefront 0 runs region q's chain
       float sum = 0.f;
-      const float *vals = buf_[tidw][1];
+      const float *vals = buf_[tidw] + (SLIM ? 0 : NPXP);
       const float4 *v4 = reinterpret_cast<const float4 *>(vals);
       const int full = nm >> 2;
 #pragma unroll 8
@@ -845,7 +902,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     __syncthreads();
     if (tidw < DR) {
       float var = 0.f;
-      const float *vals = buf_[tidw][1];
+      const float *vals = buf_[tidw] + (SLIM ? 0 : NPXP);
       const float4 *v4 = reinterpret_cast<const float4 *>(vals);
       const int full = nm >> 2;
 #pragma unroll 8
@@ -855,7 +912,22 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     }
     __syncthreads();
     const float var = sstat[1];
-    if (!((double)var < 0.0001)) {
+    if constexpr (SLIM) {   // the list lies where the patch was: every pixel is written again, from the registers
+      if (!((double)var < 0.0001)) {
+        const float fac = 50.0f / var;
+#pragma unroll
+        for (int k = 0; k < PER_T; k++) {
+          float v = 128.f + fac * (sv[k] - mean);
+          if (v > 255.f) v = 255.f;
+          if (v < 0.f) v = 0.f;
+          if (tid + 128 * k < NPX) patch[tid + 128 * k] = v;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < PER_T; k++)
+          if (tid + 128 * k < NPX) patch[tid + 128 * k] = sv[k];
+      }
+    } else if (!((double)var < 0.0001)) {
       const float fac = 50.0f / var;
       for (int i = tid; i < NPX; i += 128) {
         float v = 128.f + fac * (patch[i] - mean);
@@ -875,9 +947,10 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   }
   // -- gradients, orientation, per-pixel weights (siftdesc.cpp:346-379, 73-131)
   float ov[PER_T], vv[PER_T];   // o and val = mask * |grad| of the thread's pixels p = tid + 128 k
+  const int tidg = SLIM ? fresh_vgpr(tid) : tid;
 #pragma unroll
   for (int k = 0; k < PER_T; k++) {
-    const int p = tid + 128 * k;
+    const int p = tidg + 128 * k;
     ov[k] = 0.f; vv[k] = 0.f;
     if (p >= NPX) continue;
     const int r = p / PS, c = p - r * PS;
@@ -910,9 +983,8 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   // rate of f64 ones here: tools/ubench/lds_atomics.hip): 8 copies of the bins, one per column mod 8 and skewed by one 8-byte
   // bank (neighbouring pixels mostly share a bin), 9 orientation slots per cell so that bin b0 + 1 is always the next word
   // (slot 8 is slot 0's).  A quarter of the ordered gather's vector instructions, no barrier per step.
-  constexpr int ACS = 145, NAC = 8 * ACS;                      // copy stride and total in 8-byte words
-  static_assert(NAC * 2 <= 2 * NPXP, "8 skewed copies of 16 x 9 bins fit in bufO + bufA");
-  unsigned long long *const acc = reinterpret_cast<unsigned long long *>(buf_[reg][0]);
+  static_assert(NAC * 2 <= BUFW, "8 skewed copies of 16 x 9 bins fit in bufO + bufA");
+  unsigned long long *const acc = reinterpret_cast<unsigned long long *>(buf_[reg]);
   __shared__ unsigned smin_[DR][2], smax_[DR][2];
   {
     unsigned mb = 0;               // val >= +0: the bit patterns order like the values, and a NaN or an infinity (which end in
@@ -925,7 +997,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   }
   __syncthreads();   // all gradients taken: the patch and bufA are dead
   {
-    float4 *const z = reinterpret_cast<float4 *>(buf_[reg][0]);
+    float4 *const z = reinterpret_cast<float4 *>(buf_[reg]);
     for (int i = tid; i < (NAC * 2 + 3) / 4; i += 128) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   const unsigned mxb = max(smax_[reg][0], smax_[reg][1]);
@@ -937,7 +1009,8 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   __syncthreads();
   unsigned tmin = 0xffffffffu;     // (bits of the smallest nonzero scaled term) - 1: +0 wraps to the maximum and never wins
   {
-    int r = tid / PS, c = tid - r * PS;
+    const int tidq = SLIM ? fresh_vgpr(tid) : tid;
+    int r = tidq / PS, c = tidq - r * PS;
 #pragma unroll
     for (int k = 0; k < PER_T; k++) {
       // exact: a power of two, no overflow, and no positive val becomes 0 or a denormal -- S >= 2^-17 (E <= 64), a nonzero val is
@@ -1004,10 +1077,21 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   inexact = true;
 #endif
   const int ordered = __syncthreads_or(inexact);   // the regions of a workgroup share the barriers of the ordered gather
+  if constexpr (SLIM) {
+    if (ordered) {   // the redo launch's: counted as the full form counts it, listed, and nothing stored
+      if (tidw == 0) {
+        __hip_atomic_fetch_add(orderedCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(orderedCnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        redo[4 + __hip_atomic_fetch_add(redo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = blockIdx.x;
+      }
+      return;
+    }
+    vec[tid] = binT;   // behind the barrier: every accumulator word has been merged into registers
+  } else {
   if (ordered) {
     // measurement hook (modsx_describe_counters: ordered_workgroups): one relaxed add per workgroup that comes here, nothing
     // on the order-free path
-    if (tidw == 0) __hip_atomic_fetch_add(orderedCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (FORM != DF_REDO && tidw == 0) __hip_atomic_fetch_add(orderedCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int k = 0; k < PER_T; k++) {
       const int p = tid + 128 * k;
@@ -1080,6 +1164,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     if (gth) { vec[(rb * 4 + cb) * 8 + oa] = accA; vec[(rb * 4 + cb) * 8 + ob] = accB; }
   }
   } else vec[tid] = binT;
+  }
   __syncthreads();
   // The descriptors of one step share everything up to here (SIFTDescriptor::operator(), siftdesc.cpp:401-442: RootSIFT and
   // HalfRootSIFT run the same computeRootSiftDescriptor on the same patch and differ in the fold and the norm), so a step
@@ -1143,7 +1228,7 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
   __syncthreads();
   if (rootsift) {
     if (tidw < DR) {   // lane q of wavefront 0: the L1 norm of region q, in index order
-      const double *vq = slut_[tidw];
+      const double *vq = vec_of(tidw);
       double sum = 0.;
 #pragma unroll 16
       for (int i = 0; i < 128; i++) sum += fabs(vq[i]);
@@ -1167,6 +1252,8 @@ __global__ __launch_bounds__(128 * DR) void k_describe(const DescJob *jobs, int 
     }
   }
   }   // ot
+  li += gridDim.x;
+  } while (FORM == DF_REDO);
 }
 
 void launch_expand_tiles(hipStream_t s, const int *prefix, int nJobs, int *tileJob) {
@@ -1198,16 +1285,29 @@ void launch_patch_blur(hipStream_t s, const DescJob *jobs, const int *tilePrefix
   if (nTiles <= 0) return;
   hipLaunchKernelGGL(k_patch_blur, dim3(nTiles), dim3(256), 0, s, jobs, tilePrefix, tileJob, taps, needTab, src, dst, pass);
 }
-void launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
-                     const int *needTab, const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
-                     const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
-                     unsigned *orderedCnt) {
-  if (n <= 0) return;
+int launch_describe(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid,
+                    const int *needTab, const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab, const int *bins,
+                    const double *wts, int photoNorm, int descTypes, int nOut, double maxBin, const DescOut &outs,
+                    unsigned *orderedCnt, unsigned *redo) {
+  if (n <= 0) return 0;
   SiftConst sc;
   sc.nmask = nmask;
-  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<DM_SIFT>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
+  const int nwg = (n + DR - 1) / DR;
+  // the slim form and its redo launch: every job of the launch is a grid-branch one (the caller's promise when it hands over
+  // a redo list: redo[0] == 0, room for one entry per workgroup behind redo[4]) and a thread can hold its share of the mask
+  if (redo && ((nmask + 3) & ~3) <= 128 * DESC_SLIM_PICKS) {
+    // (not under MX_DUP: a second slim launch would list its workgroups again)
+    hipLaunchKernelGGL((k_describe<DM_SIFT, DF_SLIM>), dim3(nwg), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx,
+                       oTab, bins, wts, sc, photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0, orderedCnt, redo);
+    hipLaunchKernelGGL((k_describe<DM_SIFT, DF_REDO>), dim3(std::min(nwg, DESC_REDO_GRID)), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab,
+                       coordTab, mask, maskIdx, oTab, bins, wts, sc, photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0, orderedCnt,
+                       redo);
+    return 1;
+  }
+  MX_DUP(K_DESCRIBE) hipLaunchKernelGGL(k_describe<DM_SIFT>, dim3(nwg), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx, oTab, bins,
                      wts, sc,
-                     photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0, orderedCnt);
+                     photoNorm, descTypes, nOut, maxBin, outs, (float *)nullptr, 0, orderedCnt, (unsigned *)nullptr);
+  return 0;
 }
 void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                            const float *coordTab, const unsigned short *maskIdx, int nmask, int photoNorm, float *patchOut,
@@ -1219,7 +1319,7 @@ void launch_describe_patch(hipStream_t s, const DescJob *jobs, int n, const ImgR
   memset(&none, 0, sizeof none);
   hipLaunchKernelGGL(k_describe<DM_PATCH>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab,
                      (const float *)nullptr, maskIdx, (const float *)nullptr, (const int *)nullptr, (const double *)nullptr, sc, photoNorm, 0, 0, 0.0,
-                     none, patchOut, patchByOutIdx, (unsigned *)nullptr);
+                     none, patchOut, patchByOutIdx, (unsigned *)nullptr, (unsigned *)nullptr);
 }
 void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef *imgs, const float *grid, const int *needTab,
                          const float *coordTab, const float *mask, const unsigned short *maskIdx, int nmask, const float *oTab,
@@ -1230,7 +1330,7 @@ void launch_describe_raw(hipStream_t s, const DescJob *jobs, int n, const ImgRef
   DescOut none;
   memset(&none, 0, sizeof none);
   hipLaunchKernelGGL(k_describe<DM_RAW>, dim3((n + DR - 1) / DR), dim3(128 * DR), 0, s, jobs, n, imgs, grid, needTab, coordTab, mask, maskIdx,
-                     oTab, bins, wts, sc, photoNorm, 0, 0, 0.0, none, raw, accumulate, orderedCnt);
+                     oTab, bins, wts, sc, photoNorm, 0, 0, 0.0, none, raw, accumulate, orderedCnt, (unsigned *)nullptr);
 }
 
 }  // namespace mx
